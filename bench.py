@@ -16,7 +16,10 @@ Workloads (config.workload):
   crossbar_10nm_5pitch   the reference's 110 813-site crossbar (structures/crossbars/timing_10nm_5pitch), V = 1, current solve off
 
 Contract: python bench.py --gpus N --steps K --warmup W ; prints ONE JSON line on rank 0.  `--gpus N` with N > 1 and no rank environment
-starts the N ranks itself (devicekmc_amd/launch.py); a world that is not --gpus is refused.
+starts the N ranks itself (devicekmc_amd/launch.py); a world that is not --gpus is refused.  The line is kept to a few kB (result_line:
+the headline, config, split, rooflines, CPU baseline); the full record with every block below is written to --detail (bench_detail.json
+in the repository root by default) and the line names that file.  --dump-outputs DIR writes what the timed path computed in its last timed
+step as DIR/<name>.npy (dump_outputs).
 
 N = 1: `value` = steady-state steps/s of tile:10 at the library's defaults: CG tolerance 1e-6 (the snapshot's), the block-CG of width 16
 on the tiled X (csrc/xtb.hip), current solve started from the previous step's solution (dkmc_set_current_warm_start(1), the default since
@@ -38,8 +41,8 @@ N > 1 (the reference has no multi-GPU path): STRONG scaling of ONE simulation of
 lockstep, the tunnelling block of X is generated, stored and streamed in per-rank shares (csrc/xt.hip, csrc/xtb.hip, csrc/comm.hip);
 `value` = steps/s of that simulation, "scaling": "strong".  A `replicas` block (independent replicas of the 85 k-site device, aggregate
 steps/s, weak scaling) rides along.  A watchdog ends the run with a non-zero exit code if a rank hangs.
-If the requested K steps of a seconds-per-step workload would not fit the time budget (--budget, default 420 s), fewer steps are
-timed and `steps` says how many (`steps_requested` keeps K).
+The headline times exactly K steps.  Only with an explicit --budget S are fewer steps timed when K steps of a seconds-per-step workload
+would not fit S seconds; `steps` then says how many (`steps_requested` keeps K).
 """
 import argparse
 import json
@@ -537,7 +540,7 @@ def pmc_traffic(workload, kernel_prefix, x_format, cg_tol=None, x_block=None):
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--",
                sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
                "--scale-points", "none", "--no-alt", "--no-pmc", "--no-cpp-host", "--no-log-tolerance", "--no-device", "--no-reference-order",
-               "--x-format", str(x_format), "--x-block", str(x_block if x_block is not None else X_BLOCK)]
+               "--x-format", str(x_format), "--x-block", str(x_block if x_block is not None else X_BLOCK), "--detail", ""]
         if cg_tol is not None:      # bytes per launch do not depend on how many iterations the solve takes: a loose tolerance shortens the (serialised) counter run
             cmd += ["--cg-tol", repr(cg_tol)]
         try:
@@ -628,6 +631,58 @@ def crossbar_block(devname):
     return blk
 
 
+DUMP_CAP_BYTES = 64 * 10 ** 6
+# the site fields GPUBuffers.sync_GPUToHost hands back to the caller of a superstep
+DUMP_SITE_FIELDS = ("site_element", "site_charge", "site_potential_boundary", "site_potential_charge", "site_power", "site_temperature",
+                    "site_CB_edge")
+
+
+def save_outputs(outdir, sites, scalars, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """Write per-site arrays (all of one length) and scalars as float64 outdir/<name>.npy, at most cap_bytes in all.  Above the cap every
+    site array keeps the same fixed, seeded sample of sites, and the sample's indices are written as site_index.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    n = len(next(iter(sites.values())))
+    room = cap_bytes - 8 * len(scalars) - 128 * (len(sites) + len(scalars) + 1)      # 128 B: the header of a .npy file
+    if 8 * n * len(sites) > room:
+        idx = np.sort(np.random.default_rng(seed).choice(n, room // (8 * (len(sites) + 1)), replace=False))
+        sites = dict({name: a[idx] for name, a in sites.items()}, site_index=idx)
+    for name, a in list(sites.items()) + list(scalars.items()):
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64).reshape(-1))
+
+
+def dump_outputs(sim, outdir):
+    """--dump-outputs: what the caller of the timed superstep receives after the last timed step: the site fields of DUMP_SITE_FIELDS
+    and the step's dt [s], I_macro [A] and T_bg [K].  Copied from the device buffers, so the host mirror and the state that later
+    blocks step on are left as they are."""
+    import torch
+    torch.cuda.synchronize()
+    sites = {name: sim.gb.t[name].cpu().numpy() for name in DUMP_SITE_FIELDS}
+    dt, imacro, T_bg = sim.trace[-1]
+    save_outputs(outdir, sites, {"dt": dt, "I_macro": imacro, "T_bg": T_bg})
+
+
+# keys of the result line; the other blocks of the record (alternative runs, models, the 85 k-site device, scale points) are in --detail
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "steps_requested", "warmup", "ms_per_step", "higher_is_better", "scaling",
+             "vs_baseline", "dtype", "data", "error", "config", "split_ms", "per_step", "cold_step", "cpu_baseline", "gpu_over_cpu",
+             "roofline", "roofline_K_cg", "roofline_pair_sum", "x_poly_gain", "warm_start_gain", "block_cg_gain",
+             "strong_scaling_speedup", "sharding", "replicas", "single_gpu_reference")
+
+
+def result_line(out, detail=None):
+    """The JSON result line: LINE_KEYS of the full record, without the free-text notes (strings over 120 characters) and per-step lists of
+    its blocks.  A driver that keeps the tail of stdout must still hold the whole line."""
+    def short(v):
+        if not isinstance(v, dict):
+            return v
+        return {k: short(x) for k, x in v.items()
+                if not ((isinstance(x, str) and len(x) > 120) or (isinstance(x, list) and len(x) > 16))}
+    line = {k: short(out[k]) for k in LINE_KEYS if k in out}
+    if detail:
+        line["detail"] = detail
+    return line
+
+
 def arm_watchdog(seconds, rank, what):
     """A rank stuck in a collective cannot be unwound: report and leave with a non-zero exit code."""
     def fire():
@@ -666,8 +721,10 @@ def main():
     ap.add_argument("--k-blocked", type=int, default=1, help="dkmc_set_k_blocked: 1 = library default (K-CG on the blocked form up to 262 144 rows), 0 = CSR positions")
     ap.add_argument("--x-block", type=int, default=16, help="dkmc_set_x_block: 16 = library default (block-CG), 1 = the reference's single-vector CG on X")
     ap.add_argument("--cg-tol", type=float, default=None, help="override the CG tolerance (default: the reference's 1e-6)")
-    ap.add_argument("--budget", type=float, default=420.0, help="time budget [s] for the timed steps of seconds-per-step workloads")
+    ap.add_argument("--budget", type=float, default=None, help="time budget [s] for the timed steps of seconds-per-step workloads (default: none, exactly --steps steps)")
     ap.add_argument("--timeout", type=float, default=570.0, help="watchdog [s]: exit 3 if the run has not finished (a rank stuck in a collective cannot be unwound)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last timed step as DIR/<name>.npy (float64, <= 64 MB)")
+    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="file for the full record behind the result line ('' = none)")
     args = ap.parse_args()
 
     # ---- `python bench.py --gpus N` with N > 1 and no rank environment: start the N ranks ourselves (one process per GPU), BEFORE anything
@@ -709,6 +766,8 @@ def main():
         # ================= the headline: steady-state steps of the default workload at the library's defaults =================
         sim = Sim(name, devname, x_format=args.x_format, warm_start=args.warm_start, cg_tol=args.cg_tol)
         elapsed, n = sim.run(args.steps, args.warmup, budget_s=args.budget if sim.s.N > 150000 else None)
+        if args.dump_outputs:
+            dump_outputs(sim, args.dump_outputs)
         res = summary(sim, elapsed, n)
         roofs = rooflines(sim)
         out = {
@@ -949,6 +1008,8 @@ def main():
         if int(tn.item()) != n:
             raise SystemExit("ranks timed different step counts (%d vs %d): rerun with a smaller --steps" % (n, int(tn.item())))
         elapsed = parallel.max_over_ranks(elapsed, red_dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(sim, args.dump_outputs)
         res = summary(sim, elapsed, n)
         st = sim.host.get_stats()
         share = st["xt_local_subblocks"] / max(st["xt_subblocks"], 1)
@@ -1016,7 +1077,15 @@ def main():
 
     wd.cancel()
     if rank == 0:
-        print(json.dumps(out), flush=True)
+        detail = None
+        if args.detail:
+            try:
+                with open(args.detail, "w") as f:
+                    json.dump(out, f, indent=1)
+                detail = args.detail
+            except OSError as exc:
+                sys.stderr.write("bench.py: could not write %s: %r\n" % (args.detail, exc))
+        print(json.dumps(result_line(out, detail)), flush=True)
     parallel.finalize()
     if out is not None and out.get("error"):
         sys.exit(4)
