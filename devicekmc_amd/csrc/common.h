@@ -152,6 +152,7 @@ struct Engine {
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
     int x_apply_form = 0;          // tile x panel kernel of the block-CG: 0 = the product form, 1 = the round-4 form of its loop (same results; same-box comparisons, dkmc_set_x_apply_form)
+    int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_block = 16;              // block-CG width of the current solve on the tiled X (dkmc_set_x_block; xtb.hip): 16 by default, 1 = the reference's single-vector loop (its iterate sequence)
     int x_format = 1;              // 1: tiled X (xt.hip, default); 0: CSR X as the reference stores it (current.hip + cg.hip)
     int x_iter_hint = 0;           // iteration count of the previous CG solve of X (sizes the first launch batch)
@@ -193,6 +194,7 @@ enum {
     S_XTB_PANELS, S_XTB_QS, S_XTB_ROWPART, S_XTB_COLPART, S_XTB_GRAM, S_XTB_SMALL, S_XTB_XI,
     S_XTB_SLAB_BOX, S_XTB_SLAB_TAB, S_XTB_SLAB_OWNER, S_XTB_SLAB_LISTS, S_XTB_SLAB_SDST, S_XTB_SLAB_FLAG, S_XTB_SLAB_RLISTS, S_XTB_SLAB_GX, S_XTB_SLAB_S1, S_XTB_SLAB_S3, S_XTB_SLAB_R3,
     S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z,
+    S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,
     S_NSLOTS
 };

@@ -56,6 +56,8 @@ void dkmc_set_x_poly(int degree) { eng().x_poly = degree < 0 ? 0 : (degree > 16 
 int dkmc_get_x_poly(void) { return eng().x_poly; }
 void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }
 int dkmc_get_x_apply_form(void) { return eng().x_apply_form; }
+void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
+int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
 void dkmc_set_x_slab(int on) { eng().x_slab = on ? 1 : 0; }
 int dkmc_get_x_slab(void) { return eng().x_slab; }
 void dkmc_set_x_block(int s) { eng().x_block = s < 1 ? 1 : (s > 16 ? 16 : s); }

@@ -832,6 +832,90 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_nmul(int m, const xrp_t *__restri
     }
     if (ok) out[(size_t)row * XB_SP + v] = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
 }
+// N packed for the solve (dkmc_set_x_nmul_form(1), the default): sc and Xs do not change during a solve, so the 2 d N products of every sweep
+// read a copy with the column's scaling folded in.  Slice q = rows 4 q ... 4 q + 3 (one wave of k_xtb_nmulp); it is as wide as its longest row,
+// w_q slots; slot k of row 4 q + r at off[q] + 4 k + r (a wave's 16 slots x 4 rows are 64 contiguous entries).  Slot k of a row is its CSR
+// position rp[row] + k, so the sums run in the same order as k_xtb_nmul's; entries outside N (driver columns, the diagonal), the driver rows 0 / 1,
+// rows past m and the padding are zero weights on a column whose panel row is read anyway (the row itself): they add exactly +0.
+__global__ void k_xtb_npack_width(int m, const xrp_t *__restrict__ rp, int *__restrict__ cnt)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (m + 3) / 4) return;
+    int w = 0;
+    for (int r = 0; r < 4; ++r) { const int row = 4 * q + r; if (row >= 2 && row < m) w = max(w, (int)(rp[row + 1] - rp[row])); }
+    cnt[q] = 4 * w;
+}
+// one wave per slice; the weight is the product k_xtb_nmul forms in its register (val * sc[col], same rounding)
+__global__ __launch_bounds__(256) void k_xtb_npack(int m, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
+                                                   const double *__restrict__ sc, const long long *__restrict__ off, int *__restrict__ pcol, double *__restrict__ pw)
+{
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (q >= (m + 3) / 4) return;
+    const long long o0 = off[q], n = off[q + 1] - o0;
+    for (long long i = lane; i < n; i += 64) {
+        const int r = (int)(i & 3), k = (int)(i >> 2), row = 4 * q + r;
+        const bool atom = row >= 2 && row < m;
+        const xrp_t p0 = atom ? rp[row] : 0, len = atom ? rp[row + 1] - p0 : 0;
+        int c = k < len ? ci[p0 + k] : -1;
+        double w = 0.0;
+        if (c < 2 || c == row) c = row < m ? row : m - 1;
+        else w = val[p0 + k] * sc[c];
+        pcol[o0 + i] = c; pw[o0 + i] = w;
+    }
+}
+// out = ca * add + cb * (N in) on the packed N: the loop runs the slice's width, no row pointers, no scaling gather, no filter.  Entry e of a row goes
+// to accumulator e % 4 in increasing e, the result is formed as in k_xtb_nmul: the same bits.  QSF: also QS (as k_xtb_qs_from) from the rows in registers.
+template <bool QSF>
+__global__ __launch_bounds__(XT_NT) void k_xtb_nmulp(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
+                                                     const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
+                                                     double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS)
+{
+    if (ctrl->done) return;
+    const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3;
+    const int nb = (int)gridDim.x, b = (int)blockIdx.x;
+    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
+    const int q = (xc * xq + min(xc, xr) + (b >> 3)) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // XCD-contiguous row blocks (see k_xtb_neigh)
+    const int row = 4 * q + r;
+    if (q >= (m + 3) / 4) return;
+    const bool ok = row < m;
+    const long long o0 = off[q];
+    const int w = (int)((off[q + 1] - o0) >> 2);
+    const int *__restrict__ cq = pcol + o0 + r;
+    const double *__restrict__ wq = pw + o0 + r;
+    const double scr = ok ? sc[row] : 0.0;
+    const double av = ok ? add[(size_t)row * XB_SP + v] : 0.0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    // slots past the width (lanes of the last batch): weight 0 on column 0
+    int cn = v < w ? cq[4 * v] : 0;
+    double wn = v < w ? wq[4 * v] : 0.0;
+    for (int k0 = 0; k0 < w; k0 += 16) {
+        const int t = w - k0, cmb = cn, wlo = __double2loint(wn), whi = __double2hiint(wn);
+        if (t > 16) { const int k = k0 + 16 + v; cn = k < w ? cq[4 * k] : 0; wn = k < w ? wq[4 * k] : 0.0; }        // next batch in flight
+#define XN_BC(x_, u_) __builtin_amdgcn_update_dpp(0, (x_), 0x150 + (u_), 0xf, 0xf, false)
+#define XN_GATHER(u_) { const int cu_ = XN_BC(cmb, u_); \
+            x[u_] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(in) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v * 8))); }
+#define XN_W(u_) __hiloint2double(XN_BC(whi, u_), XN_BC(wlo, u_))
+#define XN_ACC(u_) { s0 += XN_W(u_) * x[u_]; s1 += XN_W(u_ + 1) * x[u_ + 1]; s2 += XN_W(u_ + 2) * x[u_ + 2]; s3 += XN_W(u_ + 3) * x[u_ + 3]; }
+        double x[16];
+        XN_GATHER(0) XN_GATHER(1) XN_GATHER(2) XN_GATHER(3)
+        if (t > 4) { XN_GATHER(4) XN_GATHER(5) XN_GATHER(6) XN_GATHER(7) }
+        if (t > 8) { XN_GATHER(8) XN_GATHER(9) XN_GATHER(10) XN_GATHER(11) }
+        if (t > 12) { XN_GATHER(12) XN_GATHER(13) XN_GATHER(14) XN_GATHER(15) }
+        XN_ACC(0)
+        if (t > 4) XN_ACC(4)
+        if (t > 8) XN_ACC(8)
+        if (t > 12) XN_ACC(12)
+#undef XN_BC
+#undef XN_GATHER
+#undef XN_W
+#undef XN_ACC
+    }
+    if (ok) {
+        const double o = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
+        out[(size_t)row * XB_SP + v] = o;
+        if (QSF) { const int sr = nsrank[row]; if (sr >= 0) QS[xtb_qs_pos(sr, v)] = sc[row] * o; }
+    }
+}
 // QS (the compact, interleaved copy of the S rows the tile kernel reads) of an arbitrary panel
 __global__ void k_xtb_qs_from(int m, const double *__restrict__ V, const double *__restrict__ sc, const int *__restrict__ nsrank, double *__restrict__ QS, const XCtrl *ctrl)
 {
@@ -1283,7 +1367,29 @@ static int xtb_aux_split(int mode, double tol2, bool warm, int s)
     if (!(tol2 >= 1e-16)) return 1;
     return warm ? std::max(1, s / 2) : 16;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used);
+// the packed N of one solve (k_xtb_npack): slice offsets, columns, weights
+struct XbNPack { const long long *off; const int *col; const double *w; };
+static int xtb_npack(const XtbArgs &A, XbNPack *np)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    const int m = A.m, nsl = (m + 3) / 4;
+    int *cnt = (int *)scratch(S_XTB_NPACK_CNT, (size_t)nsl * 4);
+    long long *off = (long long *)scratch(S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
+    if (!cnt || !off) return e.err_code;
+    hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, m, A.rp, cnt);
+    if (int rc = dkmc_exclusive_scan_i32_i64(cnt, off, nsl, off + nsl)) return rc;
+    long long nslot = 0;
+    HIPCHK(hipMemcpyAsync(&nslot, off + nsl, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int *col = (int *)scratch(S_XTB_NPACK_COL, (size_t)nslot * 4);
+    double *w = (double *)scratch(S_XTB_NPACK_W, (size_t)nslot * 8);
+    if (!col || !w) return e.err_code;
+    hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, m, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w);
+    KCHK();
+    np->off = off; np->col = col; np->w = w;
+    return 0;
+}
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
 int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
 {
@@ -1293,14 +1399,19 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     if (A.sharded && eng().x_slab && comm_nranks() > 1 && comm_nranks() <= XS_MAXR && A.ay && A.az)
         return xtb_cg_slab(A, comm_nranks(), comm_rank(), nullptr, -1, iters_out, rr_out);
     double rr0 = 0.0;
-    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used);
+    // the preconditioner's N packed once per solve (sc is known); the re-entry rounds below reuse it
+    XbNPack npk{};
+    const bool packed = !A.sharded && A.m > 2 && A.ns > 0 && eng().x_poly > 0 && eng().x_nmul_form == 1;
+    if (packed) { if (int rcp = xtb_npack(A, &npk)) return rcp; }
+    const XbNPack *np = packed ? &npk : nullptr;
+    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np);
     // split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
     // solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body).  A round that no longer reduces the
     // true residual by a factor of four has reached what the arithmetic gives (at tolerances of 1e-12 the recurrence residual the reference's test --
     // and the plain loop -- stop on goes below what the true one can reach): the solve ends there, as the plain loop's does.
     for (int round = 1; rc == DKMC_XTB_AGAIN && round < 6; ++round) {
         int it2 = 0; double rr1 = 0.0;
-        rc = xtb_cg_body(A, &it2, &rr1, &peer_used);
+        rc = xtb_cg_body(A, &it2, &rr1, &peer_used, np);
         if (iters_out) *iters_out += it2;
         if (rc == DKMC_XTB_AGAIN && !(rr1 < 0.25 * rr0)) rc = 0;
         rr0 = rr1;
@@ -1311,7 +1422,7 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     if (rc != 0 && rc != DKMC_XTB_BREAKDOWN && peer_used) comm_peer_drop();
     return rc;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used)
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     const int m = A.m, s = A.s, so = 4 * ((s + 3) / 4);                       // vector groups of four: the matrix instruction's width
@@ -1440,17 +1551,25 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         if (side) (void)hipStreamWaitEvent(st, g_xb_side.b[sl], 0);           // the sparse sums are in T before the row kernel reads them
         else hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
     };
-    // dst = L src (Horner: d sparse panel products); dst must be none of src, W1, W2
+    // dst = L src (Horner: d sparse panel products); dst must be none of src, W1, W2.  qs: QS of dst as well (the packed form writes it from the
+    // last step's registers, the CSR form by k_xtb_qs_from)
     const int nmb = (m + 15) / 16;
-    auto applyL = [&](const double *src, double *dst) {
+    auto applyL = [&](const double *src, double *dst, bool qs) {
         if (pd <= 0) return;
         const double *in = src;
         for (int i = 0; i < pd; ++i) {
             double *out = (i == pd - 1) ? dst : ((i & 1) ? W2 : W1);
             const int j = pd - 1 - i;                                         // out = c_j src + N (previous), the first step carries c_d
-            hipLaunchKernelGGL(k_xtb_nmul, dim3(nmb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, A.sc, in, src, pc[j], i == 0 ? pc[pd] : 1.0, out, (const XCtrl *)A.ctrl);
+            const double cb = i == 0 ? pc[pd] : 1.0;
+            if (!np) hipLaunchKernelGGL(k_xtb_nmul, dim3(nmb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl);
+            else if (qs && i == pd - 1)
+                hipLaunchKernelGGL(k_xtb_nmulp<true>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl, A.nsrank, QS);
+            else hipLaunchKernelGGL(k_xtb_nmulp<false>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl,
+                                    (const int *)nullptr, (double *)nullptr);
             in = out;
         }
+        if (qs && !np)
+            hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)dst, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
     };
     auto fold_rows = [&](double *Tt) {
         hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB,
@@ -1458,13 +1577,12 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     };
     // T = L A L P
     auto product_pre = [&](hipEvent_t e0, hipEvent_t e1) {
-        applyL((const double *)P, Vp);
-        hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)Vp, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
+        applyL((const double *)P, Vp, true);
         double *Pk = P, *Tk = T; P = Vp; T = Zp;                              // (the product reads P and QS, writes T)
         product(e0, e1);
         P = Pk; T = Tk;
         fold_rows(Zp);
-        applyL((const double *)Zp, T);
+        applyL((const double *)Zp, T, false);
     };
     const double *bsel = A.b;
 #define XB_ROWS_ARGS(IT_) A.ns, A.nK, A.nW, m, s, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB, A.srow, A.sS, A.nsrank, A.sc, \
@@ -1501,7 +1619,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         // the start vector goes into the right-hand side: column 0 solves L A L dh = L (b - A y0) from zero, the auxiliary columns keep their own
         fold_rows(T);                                                         // T = A Y0
         hipLaunchKernelGGL(k_xtb_pre_resid, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)T, A.b, Zp);
-        applyL((const double *)Zp, T);                                        // T(:, 0) = L (A y0 - b), the other columns 0
+        applyL((const double *)Zp, T, false);                                 // T(:, 0) = L (A y0 - b), the other columns 0
         bsel = bz;                                                            // R = T - [0 | auxiliary right-hand sides]
         HIPCHK(hipMemsetAsync(y0, 0, (size_t)m * 8, st));
     }
@@ -1556,7 +1674,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         // y = y0 + L dh, then the TRUE residual of column 0 in the unpreconditioned system: one more pass over the tiles
         HIPCHK(hipMemsetAsync(A.ctrl, 0, sizeof(XCtrl), st));                 // (the kernels below are gated by `done`)
         hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)y0, Zp);
-        applyL((const double *)Zp, Vp);
+        applyL((const double *)Zp, Vp, false);
         hipLaunchKernelGGL(k_xtb_pre_add, dim3((m + 255) / 256), dim3(256), 0, st, m, (const double *)Vp, A.y);
         if (!h.pad[0]) {
             hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, P);

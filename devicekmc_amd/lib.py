@@ -66,6 +66,8 @@ SYMBOLS = {
     "dkmc_set_x_items": (None, [_I]),
     "dkmc_set_x_poly": (None, [_I]),
     "dkmc_get_x_poly": (_I, []),
+    "dkmc_set_x_nmul_form": (None, [_I]),
+    "dkmc_get_x_nmul_form": (_I, []),
     "dkmc_set_x_apply_form": (None, [_I]),
     "dkmc_get_x_apply_form": (_I, []),
     "dkmc_set_x_slab": (None, [_I]),
