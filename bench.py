@@ -21,12 +21,18 @@ the headline, config, split, rooflines, CPU baseline); the full record with ever
 in the repository root by default) and the line names that file.  --dump-outputs DIR writes what the timed path computed in its last timed
 step as DIR/<name>.npy (dump_outputs).
 
+Such a plain run measures the headline alone: set-up, warm-up, the K timed steps and what is read off them (split, per-step counts,
+cold step, the rooflines of the HIP-event profile of the timed steps).  Every block below that runs or measures anything else (other
+configurations and workloads, CPU baselines, the reference's log, PMC child runs, models) runs only with --full; the --no-* options skip
+single blocks of a --full run.  A workload named by --scale-points is measured without --full too.
+
 N = 1: `value` = steady-state steps/s of tile:10 at the library's defaults: CG tolerance 1e-6 (the snapshot's), the block-CG of width 16
 on the tiled X (csrc/xtb.hip), current solve started from the previous step's solution (dkmc_set_current_warm_start(1), the default since
 round 5: tests/test_gpu_warm_start.py).  W >= 1 puts the cold step (coefficient cache, buffer sizing, zero start vector) into the warm-up; it is
 reported as `cold_step`.  The same line carries
   * `roofline`: the dominant kernel (k_xtb_apply: tile x panel product on the matrix cores) -- HIP-event time of sampled launches,
-    algorithmic bytes AND fp64 flops per launch, HBM `traffic` from two rocprofv3 --pmc child runs;
+    algorithmic bytes AND fp64 flops per launch; with --full HBM `traffic` from two rocprofv3 --pmc child runs;
+and with --full
   * `reference_order_cg`: the same workload with dkmc_set_x_block(1), the reference's single-vector CG (its iterate sequence) from the reference's start vector: cold + one
     steady step, sweeps per step, its own kernel roofline, and the strong-scaling model of the sharded solve built on it;
   * `reference_start_vector`: the same simulation with dkmc_set_current_warm_start(0), the reference code's start vector (the buffer it
@@ -39,8 +45,9 @@ reported as `cold_step`.  The same line carries
 
 N > 1 (the reference has no multi-GPU path): STRONG scaling of ONE simulation of tile:10: every rank advances the same simulation in
 lockstep, the tunnelling block of X is generated, stored and streamed in per-rank shares (csrc/xt.hip, csrc/xtb.hip, csrc/comm.hip);
-`value` = steps/s of that simulation, "scaling": "strong".  A `replicas` block (independent replicas of the 85 k-site device, aggregate
-steps/s, weak scaling) rides along.  A watchdog ends the run with a non-zero exit code if a rank hangs.
+`value` = steps/s of that simulation, "scaling": "strong".  With --full a `replicas` block (independent replicas of the 85 k-site device,
+aggregate steps/s, weak scaling) and the same simulation on one GPU (`single_gpu_reference`, `strong_scaling_speedup`) ride along.  A watchdog
+ends the run with a non-zero exit code if a rank hangs.
 The headline times exactly K steps.  Only with an explicit --budget S are fewer steps timed when K steps of a seconds-per-step workload
 would not fit S seconds; `steps` then says how many (`steps_requested` keeps K).
 """
@@ -521,7 +528,7 @@ def cpp_host_crosscheck(sim, steps, warmup):
 
 def pmc_traffic(workload, kernel_prefix, x_format, cg_tol=None, x_block=None):
     """HBM bytes per launch of the dominant kernel from the PMC counters, measured in this run: two rocprofv3 child runs of this
-    script on the same workload (one step), `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` in separate passes with the kernel trace only
+    script on the same workload (one step, plain run), `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` in separate passes with the kernel trace only
     (MI355X_MICROARCH.md, HBM / rocprofv3 sections); median over the kernel's working launches (the no-op launches behind the
     last iteration of a batch fetch next to nothing); gfx950 correction: FETCH_SIZE counts half of a wide coalesced streaming
     read, so bytes = (2 FETCH_SIZE + WRITE_SIZE) x 1024.  Returns (bytes or None, detail)."""
@@ -538,8 +545,7 @@ def pmc_traffic(workload, kernel_prefix, x_format, cg_tol=None, x_block=None):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="dkmc_pmc_", dir="/tmp")
         cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--",
-               sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-               "--scale-points", "none", "--no-alt", "--no-pmc", "--no-cpp-host", "--no-log-tolerance", "--no-device", "--no-reference-order",
+               sys.executable, os.path.abspath(__file__), "--workload", workload, "--steps", "1", "--warmup", "0",
                "--x-format", str(x_format), "--x-block", str(x_block if x_block is not None else X_BLOCK), "--detail", ""]
         if cg_tol is not None:      # bytes per launch do not depend on how many iterations the solve takes: a loose tolerance shortens the (serialised) counter run
             cmd += ["--cg-tol", repr(cg_tol)]
@@ -701,6 +707,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, help="default: tile:10 (configs[2])")
+    ap.add_argument("--full", action="store_true", help="also run every block beside the headline (docstring); without it the run measures the headline alone")
     ap.add_argument("--no-device", action="store_true", help="N = 1: skip the block on the reference's own 85 071-site device")
     ap.add_argument("--no-reference-order", action="store_true", help="N = 1: skip the runs with dkmc_set_x_block(1), the reference's single-vector CG")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -708,7 +715,8 @@ def main():
     ap.add_argument("--x-format", type=int, default=1, help="1: tiled X (default); 0: CSR X as the reference stores it")
     ap.add_argument("--mode", choices=["sharded", "replicas"], default="sharded",
                     help="N > 1: ONE simulation, X sharded over the ranks (strong scaling, default) or independent replicas (weak scaling)")
-    ap.add_argument("--scale-points", default=None, help="N = 1: comma list of extra workloads measured in the same run (default tile:5,crossbar_10nm_5pitch,tile:20:nocurrent; 'none')")
+    ap.add_argument("--scale-points", default=None, help="N = 1: comma list of extra workloads measured in the same run, with or without --full "
+                                                         "(default: with --full and no --workload tile:5,crossbar_10nm_5pitch,tile:20:nocurrent, else none; 'none')")
     ap.add_argument("--no-replicas", action="store_true", help="N > 1: skip the replicas block")
     ap.add_argument("--no-single-ref", action="store_true", help="N > 1: skip the single-GPU run of the same simulation (reference point of the speed-up)")
     ap.add_argument("--no-alt", action="store_true", help="skip the reference_start_vector block")
@@ -797,7 +805,7 @@ def main():
         # model below (the slab-distributed loop carries no preconditioner yet: the model compares plain loop with plain loop) ----
         res_plain = None
         pd_default = sim.L.dkmc_get_x_poly()
-        if sim.x_block > 1 and pd_default > 0 and not args.no_alt:
+        if args.full and sim.x_block > 1 and pd_default > 0 and not args.no_alt:
             sim.L.dkmc_set_x_poly(0)
             t0 = time.perf_counter(); itp = 0; npl = 2 if big else min(n, 5)
             for _ in range(npl):
@@ -809,13 +817,13 @@ def main():
                                        "note": "the next %d steps of the same simulation with dkmc_set_x_poly(0): the block-CG on the Jacobi-scaled X as in round 4" % npl}
             out["x_poly_gain"] = {"sweeps": round(itp / npl / max(res["per_step"]["cg_iters_X"], 1), 2), "steps_per_s": round(out["value"] / (npl / tp), 2),
                                   "note": "ratio of different steps of one trajectory (the sweeps of a step follow its events): tools/ab_x_poly.py compares the same steps"}
-        if big and sim.x_block > 1 and "roofline" in out and not args.no_scaling_model:
+        if args.full and big and sim.x_block > 1 and "roofline" in out and not args.no_scaling_model:
             out["strong_scaling_model"] = strong_scaling_model_slabs(sim, res_plain or res)
             if res_plain:
                 out["strong_scaling_model"]["baseline"] = ("the PLAIN block loop (plain_block_loop above): the slab-distributed loop has no split polynomial preconditioner "
                                                            "yet, so the model compares plain with plain -- the preconditioned single-GPU step of this line is faster than its N = 1 row")
         # ---- same simulation from the reference code's start vector (dkmc_set_current_warm_start(0)): what the default's warm start saves ----
-        if args.warm_start == 1 and not args.no_alt:
+        if args.full and args.warm_start == 1 and not args.no_alt:
             sim.warm_start = 0
             t0 = time.perf_counter(); it0 = 0; na = 2 if big else min(n, 5)
             for _ in range(na):
@@ -830,7 +838,7 @@ def main():
         sim.close()
         # ---- roofline.traffic: HBM bytes per launch of the dominant kernel from the PMC counters, measured now (the counter runs stop their
         # solves early on seconds-per-step workloads: the bytes one launch moves do not depend on the iteration count) ----
-        if not args.no_pmc and "roofline" in out:
+        if args.full and not args.no_pmc and "roofline" in out:
             tb, detail = pmc_traffic(name, out["roofline"]["kernel"], args.x_format, cg_tol=1e-3 if sites_main > 150000 else None, x_block=X_BLOCK)
             out["roofline"]["traffic"] = tb
             out["roofline"]["traffic_detail"] = detail
@@ -838,7 +846,7 @@ def main():
                 out["roofline"]["traffic_over_algorithmic"] = round(tb / out["roofline"]["algorithmic_bytes_per_launch"], 3)
         # ================= the same workload in the reference's iterate order (single-vector CG) =================
         ref_iters = None
-        if not args.no_reference_order and X_BLOCK > 1 and args.x_format:
+        if args.full and not args.no_reference_order and X_BLOCK > 1 and args.x_format:
             try:
                 sr = Sim(name, devname, x_format=args.x_format, x_block=1, warm_start=0)
                 elr, nr_ = sr.run(1 if big else min(n, 5), 1, budget_s=60.0)
@@ -857,7 +865,7 @@ def main():
             except Exception as exc:
                 out["reference_order_cg"] = {"error": repr(exc)[:300]}
         # ---- CPU leg: the oracle's CG iteration at this size x the reference algorithm's iteration count ----
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if sites_main > 150000:
                 # (needs the shape of X: a short-lived simulation, one step at a loose tolerance)
                 sc_ = Sim(name, devname, x_format=args.x_format, cg_tol=1e-2)
@@ -872,7 +880,7 @@ def main():
             if out["cpu_baseline"]:
                 out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         # ================= the reference's own 85 071-site device =================
-        if not args.no_device and name != "7.5nm":
+        if args.full and not args.no_device and name != "7.5nm":
             try:
                 d = Sim("7.5nm", devname, x_format=args.x_format)
                 eld, nd = d.run(20, 3)
@@ -907,7 +915,7 @@ def main():
             except Exception as exc:
                 out["device_7p5nm"] = {"error": repr(exc)[:300]}
         # ================= scale points =================
-        sp_names = (args.scale_points if args.scale_points is not None else ("tile:5,crossbar_10nm_5pitch,tile:20:nocurrent" if args.workload is None else "none"))
+        sp_names = (args.scale_points if args.scale_points is not None else ("tile:5,crossbar_10nm_5pitch,tile:20:nocurrent" if args.full and args.workload is None else "none"))
         points = {}
         for spn in [x for x in sp_names.split(",") if x and x != "none"]:
             try:
@@ -944,7 +952,7 @@ def main():
     else:
         name = args.workload or "tile:10"
         replicas = None
-        if args.mode == "sharded" and not args.no_replicas:
+        if args.full and args.mode == "sharded" and not args.no_replicas:
             # weak scaling on the side: independent replicas of the 85 k-site device (own KMC random streams), aggregate steps/s
             rs = Sim("7.5nm", devname, kmc_seed=parallel.replica_kmc_seed(1, rank))
             el, n = rs.run(5, 1, barrier=parallel.barrier)
@@ -953,7 +961,7 @@ def main():
                         "unit": "KMC steps/s (aggregate over %d independent replicas)" % world, "scaling": "weak", "ms_per_step": round(el / n * 1e3, 3)}
             rs.close()
         single = None
-        if args.mode == "sharded" and not args.no_single_ref:
+        if args.full and args.mode == "sharded" and not args.no_single_ref:
             # the same simulation on ONE GPU of this node (rank 0; the other ranks wait): the reference point of the strong scaling
             if rank == 0:
                 s1 = Sim(name, devname, x_format=1)
