@@ -60,6 +60,8 @@ void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
 void dkmc_set_x_slab(int on) { eng().x_slab = on ? 1 : 0; }
 int dkmc_get_x_slab(void) { return eng().x_slab; }
+void dkmc_set_x_slab_poly(int on) { eng().x_slab_poly = on ? 1 : 0; }
+int dkmc_get_x_slab_poly(void) { return eng().x_slab_poly; }
 void dkmc_set_x_block(int s) { eng().x_block = s < 1 ? 1 : (s > 16 ? 16 : s); }
 int dkmc_get_x_block(void) { return eng().x_block; }
 void dkmc_set_x_aux(int mode) { eng().x_aux = mode < 0 ? 0 : (mode > 3 ? 2 : mode); }

@@ -790,17 +790,22 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows(int ns, int nK, int nW, int 
 // preconditioned with An EXACTLY needs 8 iterations where A needs 666 (85 k sites, tools/precond_proto.py): the ill-conditioning of X lives in its
 // sparse part, and 2 d sparse panel products per sweep buy 2-3x fewer passes over the tiles (tools/precond_block_proto.py).  The loop's algebra
 // is untouched: it sees another SPD operator.  A start vector y0 enters as the right-hand side: A d = b - A y0, d = L dh, dh from zero.
-// out = ca * add + cb * (N in): 16 lanes per row as in k_xtb_neigh; rows 0 / 1 (driver nodes) and their columns take no part in N
+// out = ca * add + cb * (N in): 16 lanes per row as in k_xtb_neigh; rows 0 / 1 (driver nodes) and their columns take no part in N.
+// LIST (slab-distributed loop, xtb_slab.inc): the rows are the m entries of rowlist (a rank's two driver rows + the rows it owns); every row is
+// formed exactly as without the list: the same bits.
+template <bool LIST>
 __global__ __launch_bounds__(XT_NT) void k_xtb_nmul(int m, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
                                                     const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
-                                                    double ca, double cb, double *__restrict__ out, const XCtrl *ctrl)
+                                                    double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ rowlist)
 {
     if (ctrl->done) return;
     const int v = threadIdx.x & 15, g = threadIdx.x >> 4;
     const int nb = (int)gridDim.x, b = (int)blockIdx.x;
     const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int row = (xc * xq + min(xc, xr) + (b >> 3)) * 16 + g;               // XCD-contiguous row blocks (see k_xtb_neigh)
-    const bool ok = row < m, atom = ok && row >= 2;
+    const int li = (xc * xq + min(xc, xr) + (b >> 3)) * 16 + g;                // XCD-contiguous row blocks (see k_xtb_neigh)
+    const bool ok = li < m;
+    const int row = LIST ? (ok ? rowlist[li] : 0) : li;
+    const bool atom = ok && row >= 2;
     const xrp_t p0 = atom ? rp[row] : 0, p1 = atom ? rp[row + 1] : 0;
     const double scr = ok ? sc[row] : 0.0;
     const double av = ok ? add[(size_t)row * XB_SP + v] : 0.0;
@@ -837,47 +842,56 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_nmul(int m, const xrp_t *__restri
 // w_q slots; slot k of row 4 q + r at off[q] + 4 k + r (a wave's 16 slots x 4 rows are 64 contiguous entries).  Slot k of a row is its CSR
 // position rp[row] + k, so the sums run in the same order as k_xtb_nmul's; entries outside N (driver columns, the diagonal), the driver rows 0 / 1,
 // rows past m and the padding are zero weights on a column whose panel row is read anyway (the row itself): they add exactly +0.
-__global__ void k_xtb_npack_width(int m, const xrp_t *__restrict__ rp, int *__restrict__ cnt)
+// rowlist != nullptr (slab-distributed loop): slice q = list entries 4 q ... 4 q + 3 of the m entries of a rank's row list, same slots per row.
+__global__ void k_xtb_npack_width(int m, const xrp_t *__restrict__ rp, int *__restrict__ cnt, const int *__restrict__ rowlist = nullptr)
 {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= (m + 3) / 4) return;
     int w = 0;
-    for (int r = 0; r < 4; ++r) { const int row = 4 * q + r; if (row >= 2 && row < m) w = max(w, (int)(rp[row + 1] - rp[row])); }
+    for (int r = 0; r < 4; ++r) {
+        const int li = 4 * q + r; if (li >= m) continue;
+        const int row = rowlist ? rowlist[li] : li;
+        if (row >= 2) w = max(w, (int)(rp[row + 1] - rp[row]));
+    }
     cnt[q] = 4 * w;
 }
 // one wave per slice; the weight is the product k_xtb_nmul forms in its register (val * sc[col], same rounding)
 __global__ __launch_bounds__(256) void k_xtb_npack(int m, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
-                                                   const double *__restrict__ sc, const long long *__restrict__ off, int *__restrict__ pcol, double *__restrict__ pw)
+                                                   const double *__restrict__ sc, const long long *__restrict__ off, int *__restrict__ pcol, double *__restrict__ pw,
+                                                   const int *__restrict__ rowlist = nullptr)
 {
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (q >= (m + 3) / 4) return;
     const long long o0 = off[q], n = off[q + 1] - o0;
     for (long long i = lane; i < n; i += 64) {
-        const int r = (int)(i & 3), k = (int)(i >> 2), row = 4 * q + r;
-        const bool atom = row >= 2 && row < m;
+        const int r = (int)(i & 3), k = (int)(i >> 2), li = 4 * q + r;
+        const int row = rowlist ? rowlist[li < m ? li : m - 1] : li;
+        const bool atom = row >= 2 && li < m;
         const xrp_t p0 = atom ? rp[row] : 0, len = atom ? rp[row + 1] - p0 : 0;
         int c = k < len ? ci[p0 + k] : -1;
         double w = 0.0;
-        if (c < 2 || c == row) c = row < m ? row : m - 1;
+        if (c < 2 || c == row) c = rowlist ? row : (row < m ? row : m - 1);
         else w = val[p0 + k] * sc[c];
         pcol[o0 + i] = c; pw[o0 + i] = w;
     }
 }
 // out = ca * add + cb * (N in) on the packed N: the loop runs the slice's width, no row pointers, no scaling gather, no filter.  Entry e of a row goes
 // to accumulator e % 4 in increasing e, the result is formed as in k_xtb_nmul: the same bits.  QSF: also QS (as k_xtb_qs_from) from the rows in registers.
-template <bool QSF>
+// LIST (slab-distributed loop): N packed over the m entries of rowlist (k_xtb_npack with a row list); row = rowlist[4 q + r].
+template <bool QSF, bool LIST = false>
 __global__ __launch_bounds__(XT_NT) void k_xtb_nmulp(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
                                                      const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
-                                                     double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS)
+                                                     double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS,
+                                                     const int *__restrict__ rowlist = nullptr)
 {
     if (ctrl->done) return;
     const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3;
     const int nb = (int)gridDim.x, b = (int)blockIdx.x;
     const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
     const int q = (xc * xq + min(xc, xr) + (b >> 3)) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // XCD-contiguous row blocks (see k_xtb_neigh)
-    const int row = 4 * q + r;
     if (q >= (m + 3) / 4) return;
-    const bool ok = row < m;
+    const bool ok = 4 * q + r < m;
+    const int row = LIST ? (ok ? rowlist[4 * q + r] : 0) : 4 * q + r;
     const long long o0 = off[q];
     const int w = (int)((off[q + 1] - o0) >> 2);
     const int *__restrict__ cq = pcol + o0 + r;
@@ -1389,35 +1403,76 @@ static int xtb_npack(const XtbArgs &A, XbNPack *np)
     np->off = off; np->col = col; np->w = w;
     return 0;
 }
+// coefficients pc[0 ... pd] of the preconditioner L = p(N) (dkmc_set_x_poly; shared by the one-GPU and the slab-distributed loop)
+static void xtb_poly_coeffs(int pd, double *pc)
+{
+    // coefficients of L = p(N), p ~ (1 - x)^(-1/2): the Chebyshev interpolant of degree d on [-1, 1 - delta], delta = min(0.5, 1.6 / d^2), in the monomial
+    // basis (Horner).  Against the Taylor series of the same degree -- which is exact at 0 and weakest where it matters, towards x -> 1 (the largest
+    // eigenvalue of N is 0.99994 at 9.4 k sites) -- the block loop needs a third fewer sweeps (85 k sites, d = 4: 34 -> 24, 95 without preconditioner).
+    if (pd > 0) {
+        const int d = pd, n = d + 1;
+        const double a = -1.0, b = 1.0 - std::min(0.5, 1.6 / (double)(d * d));
+        double fx[XB_MAXPOLY + 1], c[XB_MAXPOLY + 1], pt[XB_MAXPOLY + 1] = {0}, Tm2[XB_MAXPOLY + 1] = {0}, Tm1[XB_MAXPOLY + 1] = {0};
+        for (int k = 0; k < n; ++k) { const double t = cos(M_PI * (k + 0.5) / n), x = 0.5 * (b - a) * t + 0.5 * (b + a); fx[k] = 1.0 / sqrt(1.0 - x); }
+        for (int j = 0; j < n; ++j) { double acc = 0.0; for (int k = 0; k < n; ++k) acc += fx[k] * cos(M_PI * j * (k + 0.5) / n); c[j] = acc * 2.0 / n; }
+        c[0] *= 0.5;
+        Tm2[0] = 1.0; Tm1[1] = 1.0;                                           // T_0, T_1 in powers of t
+        pt[0] += c[0]; pt[1] += c[1];
+        for (int j = 2; j <= d; ++j) {
+            double Tj[XB_MAXPOLY + 1];
+            for (int i = 0; i <= XB_MAXPOLY; ++i) Tj[i] = (i >= 1 ? 2.0 * Tm1[i - 1] : 0.0) - Tm2[i];
+            for (int i = 0; i <= XB_MAXPOLY; ++i) { pt[i] += c[j] * Tj[i]; Tm2[i] = Tm1[i]; Tm1[i] = Tj[i]; }
+        }
+        const double al = 2.0 / (b - a), be = -(a + b) / (b - a);             // t = al x + be
+        double res[XB_MAXPOLY + 2] = {0}; res[0] = pt[d]; int deg = 0;
+        for (int i = d - 1; i >= 0; --i) {
+            double nr[XB_MAXPOLY + 2] = {0};
+            for (int q = 0; q <= deg; ++q) { nr[q] += res[q] * be; nr[q + 1] += res[q] * al; }
+            ++deg; nr[0] += pt[i];
+            for (int q = 0; q <= XB_MAXPOLY + 1; ++q) res[q] = nr[q];
+        }
+        for (int q = 0; q <= d; ++q) pc[q] = res[q];
+    }
+}
 static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
-int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
+// split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
+// solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body / xtb_cg_slab).  A round that no longer
+// reduces the true residual by a factor of four has reached what the arithmetic gives (at tolerances of 1e-12 the recurrence residual the reference's
+// test -- and the plain loop -- stop on goes below what the true one can reach): the solve ends there, as the plain loop's does.  rc, rr0: the first
+// round's; body(&iters, &rr) runs one more round.
+template <class Body>
+static int xtb_reenter(int rc, double rr0, int *iters_out, double *rr_out, Body body)
 {
-    bool peer_used = false;
-    // more than one rank: the state of the solve is distributed by row slabs (xtb_slab.inc; dkmc_set_x_slab(0) keeps the all-gather variant
-    // below, which shards the tile stream only)
-    if (A.sharded && eng().x_slab && comm_nranks() > 1 && comm_nranks() <= XS_MAXR && A.ay && A.az)
-        return xtb_cg_slab(A, comm_nranks(), comm_rank(), nullptr, -1, iters_out, rr_out);
-    double rr0 = 0.0;
-    // the preconditioner's N packed once per solve (sc is known); the re-entry rounds below reuse it
-    XbNPack npk{};
-    const bool packed = !A.sharded && A.m > 2 && A.ns > 0 && eng().x_poly > 0 && eng().x_nmul_form == 1;
-    if (packed) { if (int rcp = xtb_npack(A, &npk)) return rcp; }
-    const XbNPack *np = packed ? &npk : nullptr;
-    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np);
-    // split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
-    // solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body).  A round that no longer reduces the
-    // true residual by a factor of four has reached what the arithmetic gives (at tolerances of 1e-12 the recurrence residual the reference's test --
-    // and the plain loop -- stop on goes below what the true one can reach): the solve ends there, as the plain loop's does.
     for (int round = 1; rc == DKMC_XTB_AGAIN && round < 6; ++round) {
         int it2 = 0; double rr1 = 0.0;
-        rc = xtb_cg_body(A, &it2, &rr1, &peer_used, np);
+        rc = body(&it2, &rr1);
         if (iters_out) *iters_out += it2;
         if (rc == DKMC_XTB_AGAIN && !(rr1 < 0.25 * rr0)) rc = 0;
         rr0 = rr1;
     }
     if (rc == DKMC_XTB_AGAIN) rc = 0;
     if (rr_out) *rr_out = rr0;
+    return rc;
+}
+int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
+{
+    bool peer_used = false;
+    double rr0 = 0.0;
+    // more than one rank: the state of the solve is distributed by row slabs (xtb_slab.inc; dkmc_set_x_slab(0) keeps the all-gather variant
+    // below, which shards the tile stream only)
+    if (A.sharded && eng().x_slab && comm_nranks() > 1 && comm_nranks() <= XS_MAXR && A.ay && A.az) {
+        const int nr = comm_nranks(), me = comm_rank();
+        const int rc = xtb_cg_slab(A, nr, me, nullptr, -1, iters_out, &rr0);
+        return xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { return xtb_cg_slab(A, nr, me, nullptr, -1, it, rr); });
+    }
+    // the preconditioner's N packed once per solve (sc is known); the re-entry rounds below reuse it
+    XbNPack npk{};
+    const bool packed = !A.sharded && A.m > 2 && A.ns > 0 && eng().x_poly > 0 && eng().x_nmul_form == 1;
+    if (packed) { if (int rcp = xtb_npack(A, &npk)) return rcp; }
+    const XbNPack *np = packed ? &npk : nullptr;
+    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np);
+    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { return xtb_cg_body(A, it, rr, &peer_used, np); });
     // a sharded solve that failed with the peer-write exchange in use: the ranks' sequence counters may have drifted (comm.hip)
     if (rc != 0 && rc != DKMC_XTB_BREAKDOWN && peer_used) comm_peer_drop();
     return rc;
@@ -1449,34 +1504,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         bz = Vp + pan;
         HIPCHK(hipMemsetAsync(bz, 0, (size_t)(m + 16) * 8, st));
     }
-    // coefficients of L = p(N), p ~ (1 - x)^(-1/2): the Chebyshev interpolant of degree d on [-1, 1 - delta], delta = min(0.5, 1.6 / d^2), in the monomial
-    // basis (Horner).  Against the Taylor series of the same degree -- which is exact at 0 and weakest where it matters, towards x -> 1 (the largest
-    // eigenvalue of N is 0.99994 at 9.4 k sites) -- the block loop needs a third fewer sweeps (85 k sites, d = 4: 34 -> 24, 95 without preconditioner).
     double pc[XB_MAXPOLY + 1] = {1.0};
-    if (pd > 0) {
-        const int d = pd, n = d + 1;
-        const double a = -1.0, b = 1.0 - std::min(0.5, 1.6 / (double)(d * d));
-        double fx[XB_MAXPOLY + 1], c[XB_MAXPOLY + 1], pt[XB_MAXPOLY + 1] = {0}, Tm2[XB_MAXPOLY + 1] = {0}, Tm1[XB_MAXPOLY + 1] = {0};
-        for (int k = 0; k < n; ++k) { const double t = cos(M_PI * (k + 0.5) / n), x = 0.5 * (b - a) * t + 0.5 * (b + a); fx[k] = 1.0 / sqrt(1.0 - x); }
-        for (int j = 0; j < n; ++j) { double acc = 0.0; for (int k = 0; k < n; ++k) acc += fx[k] * cos(M_PI * j * (k + 0.5) / n); c[j] = acc * 2.0 / n; }
-        c[0] *= 0.5;
-        Tm2[0] = 1.0; Tm1[1] = 1.0;                                           // T_0, T_1 in powers of t
-        pt[0] += c[0]; pt[1] += c[1];
-        for (int j = 2; j <= d; ++j) {
-            double Tj[XB_MAXPOLY + 1];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) Tj[i] = (i >= 1 ? 2.0 * Tm1[i - 1] : 0.0) - Tm2[i];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) { pt[i] += c[j] * Tj[i]; Tm2[i] = Tm1[i]; Tm1[i] = Tj[i]; }
-        }
-        const double al = 2.0 / (b - a), be = -(a + b) / (b - a);             // t = al x + be
-        double res[XB_MAXPOLY + 2] = {0}; res[0] = pt[d]; int deg = 0;
-        for (int i = d - 1; i >= 0; --i) {
-            double nr[XB_MAXPOLY + 2] = {0};
-            for (int q = 0; q <= deg; ++q) { nr[q] += res[q] * be; nr[q + 1] += res[q] * al; }
-            ++deg; nr[0] += pt[i];
-            for (int q = 0; q <= XB_MAXPOLY + 1; ++q) res[q] = nr[q];
-        }
-        for (int q = 0; q <= d; ++q) pc[q] = res[q];
-    }
+    xtb_poly_coeffs(pd, pc);
     const double tol2_loop = pd > 0 ? A.tol2 / 2.25 : A.tol2;                 // ||r|| <= 1.42 ||L r||: the loop stops a little early, the true residual is checked at the end
     HIPCHK(hipMemsetAsync(QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
     HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
@@ -1561,7 +1590,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             double *out = (i == pd - 1) ? dst : ((i & 1) ? W2 : W1);
             const int j = pd - 1 - i;                                         // out = c_j src + N (previous), the first step carries c_d
             const double cb = i == 0 ? pc[pd] : 1.0;
-            if (!np) hipLaunchKernelGGL(k_xtb_nmul, dim3(nmb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl);
+            if (!np) hipLaunchKernelGGL(k_xtb_nmul<false>, dim3(nmb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl,
+                                        (const int *)nullptr);
             else if (qs && i == pd - 1)
                 hipLaunchKernelGGL(k_xtb_nmulp<true>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl, A.nsrank, QS);
             else hipLaunchKernelGGL(k_xtb_nmulp<false>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl,
@@ -1707,11 +1737,25 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
 int xtb_cg_slab_emulate(const XtbArgs &A, int nr, const XShare *shares, int time_rank, int sweep_cap, int *iters_out, double *rr_out, double *times_us, long long *xdoubles)
 {
     g_slab_sweep_cap = sweep_cap;
-    const int rc = xtb_cg_slab(A, nr, 0, shares, time_rank, iters_out, rr_out);
+    double rr0 = 0.0;
+    int rc = xtb_cg_slab(A, nr, 0, shares, time_rank, iters_out, &rr0);
+    // re-entry rounds as xtb_cg runs them (preconditioned loop); the kernel times are those of the first round; a measurement run (sweep cap) has none
+    const double nmul_us = g_slab_last.nmul_us;
+    if (sweep_cap > 0) { if (rc == DKMC_XTB_AGAIN) rc = 0; if (rr_out) *rr_out = rr0; }
+    else rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { return xtb_cg_slab(A, nr, 0, shares, -1, it, rr); });
+    g_slab_last.nmul_us = nmul_us;
     g_slab_sweep_cap = 0;
     if (times_us) for (int c = 0; c < 8; ++c) times_us[c] = g_slab_times.us[c];
     if (xdoubles) for (int c = 0; c < 3; ++c) xdoubles[c] = g_slab_xbytes[c];
     return rc;
+}
+// measurement aid (devicekmc_hip_debug.h): exchanges per sweep, halo doubles per exchange and mean N x panel product time of the last slab solve
+extern "C" int dkmc_xtb_slab_last(int *exchanges_per_sweep, long long *halo_doubles_per_exchange, double *nmul_us)
+{
+    if (exchanges_per_sweep) *exchanges_per_sweep = g_slab_last.exchanges;
+    if (halo_doubles_per_exchange) *halo_doubles_per_exchange = g_slab_last.halo_doubles;
+    if (nmul_us) *nmul_us = g_slab_last.nmul_us;
+    return 0;
 }
 
 // ---- test aid (tests/test_gpu_block_cg.py; no counterpart in the reference) ---------------------------------------------------------------

@@ -84,7 +84,12 @@ __global__ void k_xtb_slab_tail(int nr, int so, SlabMeta M, const double *__rest
 __global__ void k_xtb_slab_gtail(const XCtrl *ctrl, double *__restrict__ gblock) { gblock[XB_NG * 256] = 0.0; gblock[XB_NG * 256 + 1] = ctrl->abort_local ? 1.0 : 0.0; }
 
 // ---- row kernel of a slab rank: recv1 = one piece per rank (rank order), each [nSme x so partial sums of MY S rows | XS_DRV driver partials | 2 control words]
-template <int INIT>
+// MODE (split polynomial preconditioner, dkmc_set_x_slab_poly): XS_FOLD -- the fold alone (the analogue of k_xtb_fold_rows): my S rows and the driver
+// rows of T completed from the partials, no Gram matrices; XS_NF -- T is final in every row (folded, then carried through L), the pass only forms R
+// (INIT) and the partial Gram matrices (the analogue of k_xtb_rows<..., NF = 1>)
+#define XS_FOLD 1
+#define XS_NF 2
+template <int INIT, int MODE = 0>
 __global__ __launch_bounds__(XT_NT) void k_xtb_rows_slab(int nSme, const int *__restrict__ slist, int nlist, const int *__restrict__ rowlist, int s, int so, int nr, int me,
                                                          const double *__restrict__ recv1, const int *__restrict__ srow, const double *__restrict__ sS,
                                                          const int *__restrict__ nsrank, const double *__restrict__ sc, double *__restrict__ T,
@@ -115,7 +120,7 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows_slab(int nSme, const int *__
     for (int kb = blockIdx.x; kb < nKb; kb += gridDim.x) {
         const int jA = XT_R * kb + r4, jB = jA + 16;
         double tA = 0.0, tB = 0.0;
-        if (v < so)
+        if (MODE != XS_NF && v < so)
             for (int r = 0; r < nr; ++r) {
                 if (jA < nSme) tA += recv1[r * piece + (size_t)jA * so + v];
                 if (jB < nSme) tB += recv1[r * piece + (size_t)jB * so + v];
@@ -123,14 +128,15 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows_slab(int nSme, const int *__
         double pA = 0.0, pB = 0.0, rA = 0.0, rB = 0.0;
         if (jA < nSme) {
             const int q = slist[jA], row = srow[q]; const size_t o = (size_t)row * XB_SP + v;
-            tA = sS[q] * (T[o] + tA); T[o] = tA;
-            if (INIT) { rA = tA - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = rA; } else { pA = P[o]; rA = R[o]; }
+            if (MODE == XS_NF) tA = T[o]; else { tA = sS[q] * (T[o] + tA); T[o] = tA; }
+            if (MODE != XS_FOLD) { if (INIT) { rA = tA - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = rA; } else { pA = P[o]; rA = R[o]; } }
         } else tA = 0.0;
         if (jB < nSme) {
             const int q = slist[jB], row = srow[q]; const size_t o = (size_t)row * XB_SP + v;
-            tB = sS[q] * (T[o] + tB); T[o] = tB;
-            if (INIT) { rB = tB - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = rB; } else { pB = P[o]; rB = R[o]; }
+            if (MODE == XS_NF) tB = T[o]; else { tB = sS[q] * (T[o] + tB); T[o] = tB; }
+            if (MODE != XS_FOLD) { if (INIT) { rB = tB - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = rB; } else { pB = P[o]; rB = R[o]; } }
         } else tB = 0.0;
+        if (MODE == XS_FOLD) continue;
         if (!INIT) {
             G[0] = XB_MFMA(pA, tA, G[0]); G[1] = XB_MFMA(pA, rA, G[1]); G[2] = XB_MFMA(tA, rA, G[2]); G[3] = XB_MFMA(tA, tA, G[3]); G[5] = XB_MFMA(pA, pA, G[5]);
             G[0] = XB_MFMA(pB, tB, G[0]); G[1] = XB_MFMA(pB, rB, G[1]); G[2] = XB_MFMA(tB, rB, G[2]); G[3] = XB_MFMA(tB, tB, G[3]); G[5] = XB_MFMA(pB, pB, G[5]);
@@ -143,15 +149,20 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows_slab(int nSme, const int *__
         double t_ = 0.0, p_ = 0.0, r_ = 0.0;
         if (r4 < 2) {
             const int row = r4; const size_t o = (size_t)row * XB_SP + v;
-            double sd = 0.0;
-            for (int r = 0; r < nr; ++r) sd += recv1[r * piece + (size_t)nSme * so + row * XB_SP + v];
-            t_ = sc[row] * sd; T[o] = t_;
-            if (INIT) { r_ = t_ - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = r_; } else { p_ = P[o]; r_ = R[o]; }
+            if (MODE == XS_NF) t_ = T[o];
+            else {
+                double sd = 0.0;
+                for (int r = 0; r < nr; ++r) sd += recv1[r * piece + (size_t)nSme * so + row * XB_SP + v];
+                t_ = sc[row] * sd; T[o] = t_;
+            }
+            if (MODE == XS_FOLD) {}
+            else if (INIT) { r_ = t_ - xtb_rhs(b, row, v, s, aux, ax, ay, az, sc); R[o] = r_; } else { p_ = P[o]; r_ = R[o]; }
             if (me != 0) { t_ = 0.0; p_ = 0.0; r_ = 0.0; }
         }
         if (!INIT) { G[0] = XB_MFMA(p_, t_, G[0]); G[1] = XB_MFMA(p_, r_, G[1]); G[2] = XB_MFMA(t_, r_, G[2]); G[3] = XB_MFMA(t_, t_, G[3]); G[5] = XB_MFMA(p_, p_, G[5]); }
         G[4] = XB_MFMA(r_, r_, G[4]);
     }
+    if (MODE == XS_FOLD) return;                                               // (uniform over the workgroup)
     // ---- my other rows (finished by k_xtb_neigh) ----
     if (nlist > 0) {
         const int chunk = ((nlist + (int)gridDim.x - 1) / (int)gridDim.x + 3) & ~3;
@@ -226,6 +237,37 @@ __global__ void k_xtb_unpack3(SlabMeta M, const int *__restrict__ S_by_owner, co
     }
     (void)ctrl;
 }
+// ---- halo exchange of one panel (preconditioned loop: the input of every N product): the rows of V each neighbour slab reads.  The pieces lie
+// in destination (source) order, as the halo lists do: position e of the buffer is entry e / 16 of the concatenated list ----
+__global__ void k_xtb_packH(long long n, const int *__restrict__ hsend, const double *__restrict__ V, double *__restrict__ sendH, const XCtrl *ctrl)
+{
+    if (ctrl->done) return;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+        sendH[e] = V[(size_t)hsend[e >> 4] * XB_SP + (int)(e & 15)];
+}
+__global__ void k_xtb_unpackH(long long n, const int *__restrict__ hrecv, const double *__restrict__ recvH, double *__restrict__ V, const XCtrl *ctrl)
+{
+    if (ctrl->done) return;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
+        V[(size_t)hrecv[e >> 4] * XB_SP + (int)(e & 15)] = recvH[e];
+}
+// this rank's part of ||T(:, 0) - b||^2 (the true residual of a preconditioned solve) over its list rows in one workgroup (fixed order); the two
+// driver rows (list entries 0 / 1) count on rank 0 only
+__global__ __launch_bounds__(1024) void k_xtb_pre_rr_list(int n, const int *__restrict__ rowlist, int me, const double *__restrict__ T, const double *__restrict__ b,
+                                                          double *__restrict__ out)
+{
+    __shared__ double red[1024];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        if (i < 2 && me != 0) continue;
+        const int row = rowlist[i]; const double d = T[(size_t)row * XB_SP] - b[row]; a += d * d;
+    }
+    red[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+
 // ---- the solution: every rank's rows of y0 to everybody (once per solve); piece for d != me = y0 of my rows, list order ----
 // w = 1: the vector y0; w = 16: a panel ([row][16], e.g. the block iterate whose auxiliary columns the next solve starts from)
 __global__ void k_xtb_pack4(SlabMeta M, const int *__restrict__ rows_by_owner, const double *__restrict__ y0, double *__restrict__ send4, int w)
@@ -261,10 +303,18 @@ struct SlabRank {
     XCtrl *ctrl = nullptr;
     SlabMeta M{};
     long long n1s = 0, n1r = 0, n3s = 0, n3r = 0;
+    // split polynomial preconditioner (dkmc_set_x_slab_poly): Vp = L P (+ m zeros: the right-hand side of column 0), Zp = A Vp, W1 / W2 the Horner
+    // steps; N packed over the rank's list rows (dkmc_set_x_nmul_form(1))
+    double *Vp = nullptr, *Zp = nullptr, *W1 = nullptr, *W2 = nullptr, *bz = nullptr;
+    XbNPack npk{};
 };
-struct SlabTimes { double us[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int n = 0; };      // apply, neigh, fold + tail, rows, gred, small, step, pack + unpack
+// apply, neigh, fold + tail, rows, gred, small, step, pack + unpack (preconditioned loop: rows includes the fold pass, pack + unpack the halo exchanges);
+// nmul_us: one N x panel product (mean over the launches)
+struct SlabTimes { double us[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int n = 0; double nmul_us = 0.0; };
 static SlabTimes g_slab_times;                       // filled by an emulation run with time_rank >= 0
 static long long g_slab_xbytes[3] = {0, 0, 0};       // doubles a rank receives per sweep in exchanges 1, 2, 3 (largest over the ranks)
+struct SlabLast { int exchanges = 0; long long halo_doubles = 0; double nmul_us = 0.0; };
+static SlabLast g_slab_last;                         // dkmc_xtb_slab_last: exchanges per sweep, doubles a rank receives per halo exchange (largest), nmul_us
 
 // Returns like xtb_cg.  emu_shares != nullptr: emulation -- nr virtual ranks in this process (X resident as after a single-GPU solve), the
 // exchanges as device copies; emu_shares[v] holds virtual rank v's share of the work items.  time_rank >= 0: every kernel of that virtual rank
@@ -357,6 +407,13 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     }
     KCHK();
 
+    // split polynomial preconditioner (dkmc_set_x_slab_poly; opt-in): the loop runs on L A L with the degree and coefficients of the one-GPU loop
+    const int pd = (e.x_slab_poly && m > 2 && ns > 0) ? std::min(e.x_poly, XB_MAXPOLY) : 0;
+    double pc[XB_MAXPOLY + 1] = {1.0};
+    xtb_poly_coeffs(pd, pc);
+    const double tol2_loop = pd > 0 ? A.tol2 / 2.25 : A.tol2;                  // as in xtb_cg_body: the true residual is checked at the end
+    const bool keep_aux = A.yaux != nullptr && pd == 0;                        // (no auxiliary columns are kept by a preconditioned solve, as on one GPU)
+
     // ---- per (virtual) rank: lists, panels, exchange buffers ----
     xrp_t drp[3] = {0, 0, 0};
     HIPCHK(hipMemcpy(drp, A.rp, sizeof(drp), hipMemcpyDeviceToHost));
@@ -365,12 +422,13 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     std::vector<SlabRank> RK((size_t)nv);
     // row-kernel workgroups = partial Gram matrices per rank: ~128 rows and one 32-row block of S per workgroup (170 workgroups for 8e4 rows took 63 us)
     const int ng = std::max(128, std::min(2048, (std::max(m / nr, 1) + 127) / 128 + (A.nK + nr - 1) / nr));
-    std::vector<long long> cnt1((size_t)nr * nr), cnt3((size_t)nr * nr), cnt4((size_t)nr * nr), cnt5((size_t)nr * nr);
+    std::vector<long long> cnt1((size_t)nr * nr), cnt3((size_t)nr * nr), cnt4((size_t)nr * nr), cnt5((size_t)nr * nr), cntH((size_t)nr * nr);
     for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) {
         cnt1[(size_t)a * nr + d] = (long long)nSr[d] * so + XS_DRV + 2;
         cnt3[(size_t)a * nr + d] = a == d ? 0 : ((long long)nSr[a] + hal[a * nr + d]) * XB_SP;
         cnt4[(size_t)a * nr + d] = a == d ? 0 : nown[a];
         cnt5[(size_t)a * nr + d] = a == d ? 0 : (long long)nown[a] * XB_SP;
+        cntH[(size_t)a * nr + d] = a == d ? 0 : (long long)hal[a * nr + d] * XB_SP;      // halo exchange (preconditioned loop): the halo part of exchange 3
     }
     for (int iv = 0; iv < nv; ++iv) {
         SlabRank &K = RK[iv]; const int v = emu ? iv : me0; K.v = v;
@@ -396,8 +454,12 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         K.gpart = (double *)salloc(iv, S_XTB_GRAM, (size_t)ng * XB_NG * 256 * 8);
         double *small = (double *)salloc(iv, S_XTB_SMALL, (size_t)(4 * 256 + 2 * XB_DSPLIT * XB_SP + XB_NG * 256) * 8);
         K.gx = (double *)salloc(iv, S_XTB_SLAB_GX, (size_t)nr * XS_GSTR * 8);
-        if (A.yaux) K.Ypanel = (double *)salloc(iv, S_XTB_YPANEL, pan * 8);
-        const size_t n4 = ((size_t)std::max<long long>((long long)(nr - 1) * K.n_own, (long long)(m - 2 - K.n_own)) + 8) * (A.yaux ? XB_SP : 1);
+        if (keep_aux) K.Ypanel = (double *)salloc(iv, S_XTB_YPANEL, pan * 8);
+        if (pd > 0) {
+            K.Vp = (double *)salloc(iv, S_XTB_PRE_V, (pan + m + 16) * 8); K.W1 = (double *)salloc(iv, S_XTB_PRE_W1, pan * 8);
+            K.W2 = (double *)salloc(iv, S_XTB_PRE_W2, pan * 8); K.Zp = (double *)salloc(iv, S_XTB_PRE_Z, pan * 8);
+        }
+        const size_t n4 = ((size_t)std::max<long long>((long long)(nr - 1) * K.n_own, (long long)(m - 2 - K.n_own)) + 8) * (keep_aux ? XB_SP : 1);
         K.send1 = (double *)salloc(iv, S_XTB_SLAB_S1, (size_t)std::max<long long>(K.n1s, (long long)n4) * 8);
         K.recv1 = (double *)salloc(iv, S_CG_XCHG, (size_t)std::max<long long>(K.n1r, (long long)n4) * 8);
         K.send3 = (double *)salloc(iv, S_XTB_SLAB_S3, (size_t)(K.n3s + 8) * 8);
@@ -440,6 +502,27 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         HIPCHK(hipMemsetAsync(K.ctrl, 0, sizeof(XCtrl), st));
         HIPCHK(hipMemsetAsync(K.send1, 0, (size_t)K.n1s * 8, st));
         HIPCHK(hipMemsetAsync(panels, 0, (pan * 3 + m + 16) * 8, st));
+        if (pd > 0) {
+            K.bz = K.Vp + pan;
+            HIPCHK(hipMemsetAsync(K.Vp, 0, (pan + m + 16) * 8, st));
+            HIPCHK(hipMemsetAsync(K.W1, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.W2, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.Zp, 0, pan * 8, st));
+            if (e.x_nmul_form == 1) {                    // N packed over the list rows (k_xtb_npack): slices of four list entries, the one-GPU slots per row
+                const int nl = K.n_own + 2, nsl = (nl + 3) / 4;
+                int *cnt = (int *)salloc(iv, S_XTB_NPACK_CNT, (size_t)nsl * 4);
+                long long *off = (long long *)salloc(iv, S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
+                if (fail) return fail;
+                hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, nl, A.rp, cnt, (const int *)K.steplist);
+                if (int rc = dkmc_exclusive_scan_i32_i64(cnt, off, nsl, off + nsl)) return rc;
+                long long nslot = 0;
+                HIPCHK(hipMemcpyAsync(&nslot, off + nsl, sizeof(long long), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                int *col = (int *)salloc(iv, S_XTB_NPACK_COL, (size_t)(nslot + 64) * 4);
+                double *w = (double *)salloc(iv, S_XTB_NPACK_W, (size_t)(nslot + 64) * 8);
+                if (fail) return fail;
+                hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, nl, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, (const int *)K.steplist);
+                K.npk.off = off; K.npk.col = col; K.npk.w = w;
+            }
+        }
     }
     KCHK();
     g_slab_xbytes[0] = g_slab_xbytes[1] = g_slab_xbytes[2] = 0;
@@ -450,11 +533,15 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     }
     g_slab_xbytes[1] = (long long)(nr - 1) * XS_GSTR;
     e.stats.comm_count_per_rank = g_slab_xbytes[0] + g_slab_xbytes[1] + g_slab_xbytes[2];
+    // preconditioned loop: exchange 3 carries QS + the halo of Vp; 2 d halo exchanges (P or Zp, then the Horner intermediates) are added per sweep
+    g_slab_last.exchanges = nr > 1 ? (pd > 0 ? 2 * pd + 3 : 3) : 2;
+    g_slab_last.halo_doubles = 0; g_slab_last.nmul_us = 0.0;
+    for (int v = 0; v < nr; ++v) { long long rh = 0; for (int a = 0; a < nr; ++a) rh += cntH[(size_t)a * nr + v]; g_slab_last.halo_doubles = std::max(g_slab_last.halo_doubles, rh); }
+    if (pd > 0 && nr > 1) e.stats.comm_count_per_rank += 2LL * pd * g_slab_last.halo_doubles;
 
     // smooth auxiliary columns (as in xtb_cg)
     XbAux *aux = nullptr;
     const int hs = xtb_aux_split(e.x_aux, A.tol2, A.yaux != nullptr, s);
-    const bool keep_aux = A.yaux != nullptr;
     if (A.ax && m > 2 && hs > 1) {
         aux = (XbAux *)scratch(S_XTB_XI, sizeof(XbAux));
         if (!aux) return e.err_code;
@@ -468,28 +555,34 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     e.stats.xb_aux = aux ? (hs >= s ? 1 : 2) : 0;
 
     // ---- exchanges: the communicator (one local rank) or device copies between the virtual ranks ----
-    auto xchg = [&](int which) -> int {                                      // 1, 3, 4: all-to-all-v; 2: all-gather of the Gram blocks
+    // 1, 3, 4, 5: all-to-all-v; 2: all-gather of the Gram blocks; 6: halo exchange (all-to-all-v in the buffers of exchange 3); 7: all-gather of one
+    // double per rank (gx[rank])
+    auto xchg = [&](int which) -> int {
         if (!emu) {
             SlabRank &K = RK[0];
             if (which == 1) return comm_alltoallv_f64(K.send1, K.recv1, cnt1.data());
             if (which == 3) return comm_alltoallv_f64(K.send3, K.recv3, cnt3.data());
             if (which == 4) return comm_alltoallv_f64(K.send1, K.recv1, cnt4.data());
             if (which == 5) return comm_alltoallv_f64(K.send1, K.recv1, cnt5.data());
+            if (which == 6) return comm_alltoallv_f64(K.send3, K.recv3, cntH.data());
+            if (which == 7) return comm_allgather_f64(K.gx, 1);
             return comm_allgather_f64(K.gx, (size_t)XS_GSTR);
         }
-        if (which == 2) {
+        if (which == 2 || which == 7) {
+            const size_t n = which == 2 ? (size_t)XS_GSTR : 1;
             for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d)
-                if (a != d) HIPCHK(hipMemcpyAsync(RK[d].gx + (size_t)a * XS_GSTR, RK[a].gx + (size_t)a * XS_GSTR, (size_t)XS_GSTR * 8, hipMemcpyDeviceToDevice, st));
+                if (a != d) HIPCHK(hipMemcpyAsync(RK[d].gx + (size_t)a * n, RK[a].gx + (size_t)a * n, n * 8, hipMemcpyDeviceToDevice, st));
             return 0;
         }
-        const std::vector<long long> &cnt = which == 1 ? cnt1 : (which == 3 ? cnt3 : (which == 4 ? cnt4 : cnt5));
+        const std::vector<long long> &cnt = which == 1 ? cnt1 : (which == 3 ? cnt3 : (which == 4 ? cnt4 : (which == 5 ? cnt5 : cntH)));
+        const bool b3 = which == 3 || which == 6;
         for (int a = 0; a < nr; ++a) {
             long long so_ = 0;
             for (int d = 0; d < nr; ++d) {
                 const long long n = cnt[(size_t)a * nr + d];
                 long long ro = 0; for (int a2 = 0; a2 < a; ++a2) ro += cnt[(size_t)a2 * nr + d];
-                const double *src = (which == 3 ? RK[a].send3 : RK[a].send1) + so_;
-                double *dst = (which == 3 ? RK[d].recv3 : RK[d].recv1) + ro;
+                const double *src = (b3 ? RK[a].send3 : RK[a].send1) + so_;
+                double *dst = (b3 ? RK[d].recv3 : RK[d].recv1) + ro;
                 if (n > 0) HIPCHK(hipMemcpyAsync(dst, src, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
                 so_ += n;
             }
@@ -518,7 +611,9 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     double prof_long_ms = 0.0, prof_short_ms = 0.0; int prof_long_n = 0, prof_short_n = 0;
     int local_fail = 0;
 
-    auto product = [&](bool on, hipEvent_t e0, hipEvent_t e1) -> int {
+    // panels of a rank by member: the preconditioned loop runs the same passes on Vp / Zp that the plain one runs on P / T
+    typedef double *SlabRank::*Pan;
+    auto product = [&](bool on, hipEvent_t e0, hipEvent_t e1, Pan pin = &SlabRank::P, Pan tout = &SlabRank::T) -> int {
         for (int iv = 0; iv < nv; ++iv) {
             SlabRank &K = RK[iv];
             const int ntb = (K.item_n + 3) / 4;
@@ -536,8 +631,8 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
                 }); if (rc) return rc;
             } else if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
             int rc = timed(iv, 1, on, [&]() {
-                hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb_of + (K.n_own + 15) / 16), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)K.P, A.sc, A.nsrank,
-                                   (const XCtrl *)K.ctrl, K.T, K.drvpart, (const int *)K.steplist + 2, K.n_own, (const int *)K.dlist, K.nd0, K.nd1);
+                hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb_of + (K.n_own + 15) / 16), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)(K.*pin), A.sc, A.nsrank,
+                                   (const XCtrl *)K.ctrl, K.*tout, K.drvpart, (const int *)K.steplist + 2, K.n_own, (const int *)K.dlist, K.nd0, K.nd1);
             }); if (rc) return rc;
             rc = timed(iv, 2, on, [&]() {
                 hipLaunchKernelGGL(k_xtb_fold_local, dim3(std::max(A.nK, 1)), dim3(XT_NT), 0, st, ns, A.nK, A.nW, so, A.wrange, K.nitem_w, (const double *)K.rowpartB,
@@ -547,21 +642,27 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         }
         return 0;
     };
-    auto rows = [&](bool init, int itn, bool on, hipEvent_t e2, hipEvent_t e3) -> int {
+    // exchange 1; a host-side failure of this rank between two collectives still joins, with the abort word set
+    auto xchg1 = [&]() -> int {
         if (!emu && (hipGetLastError() != hipSuccess || local_fail)) {
             if (!local_fail) local_fail = dkmc_fail(92, "block-CG: launch failed between two collectives", __FILE__, __LINE__);
             hipLaunchKernelGGL(k_xtb_abort_word, dim3(1), dim3(1), 0, st, RK[0].ctrl, RK[0].send1, (size_t)RK[0].M.soffs[1] * so + XS_DRV + 1);
             hipLaunchKernelGGL(k_xtb_slab_tail, dim3(nr), dim3(64), 0, st, nr, so, RK[0].M, (const double *)RK[0].drvpart, (const XCtrl *)RK[0].ctrl, RK[0].send1);
         }
-        if (int rcx = xchg(1)) return rcx;
+        return xchg(1);
+    };
+#define XS_ROWS_ARGS(T_, B_) K.nS, (const int *)S_by_owner + M0.soffs[K.v], K.n_own, (const int *)K.steplist + 2, s, so, nr, K.v, (const double *)K.recv1, A.srow, A.sS, \
+                     A.nsrank, A.sc, T_, (const double *)K.P, K.R, B_, K.gpart, K.ctrl, itn, (const XbAux *)aux, A.ax, A.ay, A.az
+    // the Gram pass (mode 0: with the fold; XS_NF: on the final T of the preconditioned loop, against the zero right-hand side of column 0), exchange 2
+    auto gram = [&](int mode, bool init, int itn, bool on, hipEvent_t e2, hipEvent_t e3) -> int {
         for (int iv = 0; iv < nv; ++iv) {
             SlabRank &K = RK[iv];
             int rc = timed(iv, 3, on, [&]() {
-#define XS_ROWS_ARGS K.nS, (const int *)S_by_owner + M0.soffs[K.v], K.n_own, (const int *)K.steplist + 2, s, so, nr, K.v, (const double *)K.recv1, A.srow, A.sS, A.nsrank, A.sc, \
-                     K.T, (const double *)K.P, K.R, A.b, K.gpart, K.ctrl, itn, (const XbAux *)aux, A.ax, A.ay, A.az
-                if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS);
-                else hipExtLaunchKernelGGL((k_xtb_rows_slab<0>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XS_ROWS_ARGS);
-#undef XS_ROWS_ARGS
+                if (mode == XS_NF) {
+                    if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1, XS_NF>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS(K.T, (const double *)K.bz));
+                    else hipExtLaunchKernelGGL((k_xtb_rows_slab<0, XS_NF>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XS_ROWS_ARGS(K.T, (const double *)K.bz));
+                } else if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS(K.T, A.b));
+                else hipExtLaunchKernelGGL((k_xtb_rows_slab<0>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XS_ROWS_ARGS(K.T, A.b));
             }); if (rc) return rc;
             rc = timed(iv, 4, on, [&]() {
                 hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)K.gpart, K.gx + (size_t)K.v * XS_GSTR, (const XCtrl *)K.ctrl);
@@ -570,35 +671,120 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         }
         return xchg(2);
     };
+    auto rows = [&](bool init, int itn, bool on, hipEvent_t e2, hipEvent_t e3) -> int {
+        if (int rcx = xchg1()) return rcx;
+        return gram(0, init, itn, on, e2, e3);
+    };
+    // the fold alone (preconditioned loop): my S rows and the driver rows of K.*tout from exchange 1
+    auto fold = [&](int itn, bool on, Pan tout) -> int {
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            int rc = timed(iv, 3, on, [&]() {
+                hipLaunchKernelGGL((k_xtb_rows_slab<0, XS_FOLD>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS(K.*tout, A.b));
+            }); if (rc) return rc;
+        }
+        return 0;
+    };
+#undef XS_ROWS_ARGS
+    // halo exchange of one panel: the rows of it that a neighbour slab reads
+    auto halo = [&](Pan pv, bool on) -> int {
+        if (nr < 2) return 0;
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            const long long n = (long long)K.M.hsoff[nr] * XB_SP;
+            if (n > 0) { int rc = timed(iv, 7, on, [&]() {
+                hipLaunchKernelGGL(k_xtb_packH, dim3((unsigned)std::min<long long>(1024, (n + 255) / 256)), dim3(256), 0, st, n, (const int *)K.hsend, (const double *)(K.*pv), K.send3,
+                                   (const XCtrl *)K.ctrl);
+            }); if (rc) return rc; }
+        }
+        if (int rcx = xchg(6)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            const long long n = (long long)K.M.hroff[nr] * XB_SP;
+            if (n > 0) { int rc = timed(iv, 7, on, [&]() {
+                hipLaunchKernelGGL(k_xtb_unpackH, dim3((unsigned)std::min<long long>(1024, (n + 255) / 256)), dim3(256), 0, st, n, (const int *)K.hrecv, (const double *)K.recv3, K.*pv,
+                                   (const XCtrl *)K.ctrl);
+            }); if (rc) return rc; }
+        }
+        return 0;
+    };
+    // dst = L src on every rank's list rows (Horner, d N products as in xtb_cg_body's applyL; the rows are formed as on one GPU: the same bits).  Before
+    // every product the halo of its input is exchanged, except src's when the caller has made it current.  qs: QS of dst's own S rows as well.
+    auto applyL = [&](Pan src, Pan dst, bool qs, bool src_halo, bool on) -> int {
+        Pan in = src;
+        for (int i = 0; i < pd; ++i) {
+            const Pan out = (i == pd - 1) ? dst : ((i & 1) ? &SlabRank::W2 : &SlabRank::W1);
+            const int j = pd - 1 - i;
+            const double cb = i == 0 ? pc[pd] : 1.0;
+            if (i > 0 || !src_halo) { if (int rcx = halo(in, on)) return rcx; }
+            for (int iv = 0; iv < nv; ++iv) {
+                SlabRank &K = RK[iv];
+                const int nl = K.n_own + 2, nmb = (nl + 15) / 16;
+                int rc = timed(iv, 8, on, [&]() {
+                    if (!K.npk.off) hipLaunchKernelGGL(k_xtb_nmul<true>, dim3(nmb), dim3(XT_NT), 0, st, nl, A.rp, A.ci, A.val, A.sc, (const double *)(K.*in), (const double *)(K.*src),
+                                                       pc[j], cb, K.*out, (const XCtrl *)K.ctrl, (const int *)K.steplist);
+                    else if (qs && i == pd - 1)
+                        hipLaunchKernelGGL((k_xtb_nmulp<true, true>), dim3(nmb), dim3(XT_NT), 0, st, nl, K.npk.off, K.npk.col, K.npk.w, A.sc, (const double *)(K.*in),
+                                           (const double *)(K.*src), pc[j], cb, K.*out, (const XCtrl *)K.ctrl, A.nsrank, K.QS, (const int *)K.steplist);
+                    else hipLaunchKernelGGL((k_xtb_nmulp<false, true>), dim3(nmb), dim3(XT_NT), 0, st, nl, K.npk.off, K.npk.col, K.npk.w, A.sc, (const double *)(K.*in),
+                                            (const double *)(K.*src), pc[j], cb, K.*out, (const XCtrl *)K.ctrl, (const int *)nullptr, (double *)nullptr, (const int *)K.steplist);
+                }); if (rc) return rc;
+            }
+            in = out;
+        }
+        if (qs && pd > 0)
+            for (int iv = 0; iv < nv; ++iv) {          // CSR form: QS from the panel (every S row; the other ranks' rows are overwritten by exchange 3)
+                SlabRank &K = RK[iv];
+                if (!K.npk.off) hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)(K.*dst), A.sc, A.nsrank, K.QS,
+                                                   (const XCtrl *)K.ctrl);
+            }
+        return 0;
+    };
+    // exchange 3: the own rows of QS to everybody + the halo of the panel the next product reads
+    auto xchg3 = [&](Pan pv, bool on) -> int {
+        if (nr < 2) return 0;
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            int rc = timed(iv, 7, on, [&]() {
+                hipLaunchKernelGGL(k_xtb_pack3, dim3((unsigned)std::max<long long>(1, std::min<long long>(256, (K.n3s / std::max(nr - 1, 1) + 255) / 256)), nr), dim3(256), 0, st,
+                                   K.M, (const int *)S_by_owner, (const int *)K.hsend, (const double *)K.QS, (const double *)(K.*pv), K.send3);
+            }); if (rc) return rc;
+        }
+        if (int rcx = xchg(3)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            int rc = timed(iv, 7, on, [&]() {
+                hipLaunchKernelGGL(k_xtb_unpack3, dim3((unsigned)std::max<long long>(1, std::min<long long>(256, (K.n3r / std::max(nr - 1, 1) + 255) / 256)), nr), dim3(256), 0, st,
+                                   K.M, (const int *)S_by_owner, (const int *)K.hrecv, (const double *)K.recv3, K.QS, K.*pv, (const XCtrl *)K.ctrl);
+            }); if (rc) return rc;
+        }
+        return 0;
+    };
     auto update = [&](int itn, bool on) -> int {
         for (int iv = 0; iv < nv; ++iv) {
             SlabRank &K = RK[iv];
             int rc = timed(iv, 5, on, [&]() {
-                hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, itn, s, (const double *)K.gx, K.mats, K.ctrl, A.tol2, nr, (int)XS_GSTR);
+                hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, itn, s, (const double *)K.gx, K.mats, K.ctrl, tol2_loop, nr, (int)XS_GSTR);
             }); if (rc) return rc;
             if (itn < 0) hipLaunchKernelGGL(k_xtb_zero, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, (long long)pan, K.P);
             rc = timed(iv, 6, on, [&]() {
                 hipLaunchKernelGGL(k_xtb_step, dim3(xt_grid((K.n_own + 2 + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, K.n_own + 2, itn, (const double *)K.mats, K.y0, K.R, K.P,
                                    (const double *)K.T, A.sc, A.nsrank, K.QS, (const XCtrl *)K.ctrl, (const int *)K.steplist, K.Ypanel);
             }); if (rc) return rc;
-            if (nr > 1) {
-                rc = timed(iv, 7, on, [&]() {
-                    hipLaunchKernelGGL(k_xtb_pack3, dim3((unsigned)std::max<long long>(1, std::min<long long>(256, (K.n3s / std::max(nr - 1, 1) + 255) / 256)), nr), dim3(256), 0, st,
-                                       K.M, (const int *)S_by_owner, (const int *)K.hsend, (const double *)K.QS, (const double *)K.P, K.send3);
-                }); if (rc) return rc;
-            }
         }
-        if (nr > 1) {
-            if (int rcx = xchg(3)) return rcx;
-            for (int iv = 0; iv < nv; ++iv) {
-                SlabRank &K = RK[iv];
-                int rc = timed(iv, 7, on, [&]() {
-                    hipLaunchKernelGGL(k_xtb_unpack3, dim3((unsigned)std::max<long long>(1, std::min<long long>(256, (K.n3r / std::max(nr - 1, 1) + 255) / 256)), nr), dim3(256), 0, st,
-                                       K.M, (const int *)S_by_owner, (const int *)K.hrecv, (const double *)K.recv3, K.QS, K.P, (const XCtrl *)K.ctrl);
-                }); if (rc) return rc;
-            }
-        }
-        return 0;
+        // preconditioned loop: the next product reads Vp, not P -- only the halo of P travels here (the first N product of the next sweep reads it)
+        return pd > 0 ? halo(&SlabRank::P, on) : xchg3(&SlabRank::P, on);
+    };
+    // one sweep of the preconditioned loop: T = L A L P (2 d + 3 exchanges with the two of the Gram pass and the update's halo of P)
+    auto sweep_pre = [&](int itn, bool on, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, hipEvent_t e3) -> int {
+        if (int rcx = applyL(&SlabRank::P, &SlabRank::Vp, true, true, on)) return rcx;
+        if (int rcx = xchg3(&SlabRank::Vp, on)) return rcx;
+        if (int rcx = product(on, e0, e1, &SlabRank::Vp, &SlabRank::Zp)) return rcx;
+        if (int rcx = xchg1()) return rcx;
+        if (int rcx = fold(itn, on, &SlabRank::Zp)) return rcx;
+        if (int rcx = applyL(&SlabRank::Zp, &SlabRank::T, false, false, on)) return rcx;
+        if (int rcx = gram(XS_NF, false, itn, on, e2, e3)) return rcx;
+        return update(itn, on);
     };
 
     // ---- R = A Y0 - B ; first directions ----
@@ -608,7 +794,16 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
                            (const double *)((keep_aux && A.yaux_valid) ? A.yaux : nullptr), hs, s, K.Ypanel);
     }
     if (int rcx = product(false, nullptr, nullptr)) return rcx;
-    if (int rcx = rows(true, -1, false, nullptr, nullptr)) return rcx;
+    if (pd > 0) {
+        // as xtb_cg_body: column 0 solves L A L dh = L (b - A y0) from zero -- T = A Y0 (fold), W = [T(:, 0) - b | 0], T = L W, R = T - [0 | auxiliary]
+        if (int rcx = xchg1()) return rcx;
+        if (int rcx = fold(-1, false, &SlabRank::T)) return rcx;
+        for (int iv = 0; iv < nv; ++iv)
+            hipLaunchKernelGGL(k_xtb_pre_resid, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)RK[iv].T, A.b, RK[iv].Zp);
+        if (int rcx = applyL(&SlabRank::Zp, &SlabRank::T, false, false, false)) return rcx;
+        if (int rcx = gram(XS_NF, true, -1, false, nullptr, nullptr)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) HIPCHK(hipMemsetAsync(RK[iv].y0, 0, (size_t)m * 8, st));
+    } else if (int rcx = rows(true, -1, false, nullptr, nullptr)) return rcx;
     if (int rcx = update(-1, false)) return rcx;
     KCHK();
     int it = 0, launched = 0, batch = 4;
@@ -635,9 +830,13 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             const int sl = bq / XT_PROF_STRIDE;
             const bool on = timing && it >= 2 && tphase < 24;            // sweeps 2 ... 25 of the emulation are timed, kernel by kernel
             if (g_xtb_fault_iter >= 0 && !emu && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
-            if (int rcx = product(on, pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr)) return rcx;
-            if (int rcx = rows(false, it, on, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
-            if (int rcx = update(it, on)) return rcx;
+            if (pd > 0) {
+                if (int rcx = sweep_pre(it, on, pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
+            } else {
+                if (int rcx = product(on, pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr)) return rcx;
+                if (int rcx = rows(false, it, on, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
+                if (int rcx = update(it, on)) return rcx;
+            }
             if (on) ++tphase;
         }
         launched = batch;
@@ -652,6 +851,20 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             XCtrl hv{};
             HIPCHK(hipMemcpy(&hv, RK[iv].ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost));
             if (hv.iters != h.iters || hv.done != h.done || hv.pad[0] != h.pad[0]) return dkmc_fail(13, "slab emulation: the virtual ranks left the loop at different sweeps", __FILE__, __LINE__);
+        }
+    }
+    if (pd > 0) {
+        // y = y0 + L dh on the own rows (y0 of every rank holds dh of its rows; L needs the halo of dh and of the Horner intermediates)
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            HIPCHK(hipMemsetAsync(K.ctrl, 0, sizeof(XCtrl), st));          // (the kernels below are gated by `done`)
+            hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)K.y0, K.Zp);
+        }
+        if (int rcx = applyL(&SlabRank::Zp, &SlabRank::Vp, false, false, false)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            HIPCHK(hipMemcpyAsync(K.y0, A.y, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_xtb_pre_add, dim3((m + 255) / 256), dim3(256), 0, st, m, (const double *)K.Vp, K.y0);
         }
     }
     // ---- the solution on every rank: own rows of y0 to everybody ----
@@ -683,6 +896,34 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     }
     HIPCHK(hipMemcpyAsync(A.y, RK[0].y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     if (keep_aux) hipLaunchKernelGGL(k_xtb_yaux_out, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const int *)nullptr, (const double *)RK[0].Ypanel, A.sc, A.yaux);
+    bool again = false;
+    if (pd > 0 && !h.pad[0]) {
+        // the TRUE residual of column 0: every rank holds all of y -- QS locally, one tile pass, exchange 1, the fold; the ranks' partials of
+        // ||A y - b||^2 over their rows are all-gathered and added in rank order: the same bits, the same re-entry decision on every rank
+        for (int iv = 0; iv < nv; ++iv) {
+            SlabRank &K = RK[iv];
+            hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)K.y0, K.P);
+            hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)K.P, A.sc, A.nsrank, K.QS, (const XCtrl *)K.ctrl);
+        }
+        if (int rcx = product(false, nullptr, nullptr)) return rcx;
+        if (int rcx = xchg1()) return rcx;
+        if (int rcx = fold(-1, false, &SlabRank::T)) return rcx;
+        for (int iv = 0; iv < nv; ++iv)
+            hipLaunchKernelGGL(k_xtb_pre_rr_list, dim3(1), dim3(1024), 0, st, RK[iv].n_own + 2, (const int *)RK[iv].steplist, RK[iv].v, (const double *)RK[iv].T, A.b,
+                               RK[iv].gx + RK[iv].v);
+        if (int rcx = xchg(7)) return rcx;
+        std::vector<double> part((size_t)nr);
+        HIPCHK(hipMemcpyAsync(part.data(), RK[0].gx, (size_t)nr * 8, hipMemcpyDeviceToHost, st));
+        XCtrl h2{};
+        HIPCHK(hipMemcpyAsync(&h2, RK[0].ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (local_fail) return local_fail;                                   // (the abort word of exchange 1 stops the peers here too: no rank re-enters)
+        if (h2.aborted) return dkmc_fail(46, "a peer rank aborted the sharded current solve", __FILE__, __LINE__);
+        double rr_true = 0.0;
+        for (int r = 0; r < nr; ++r) rr_true += part[r];
+        h.rr[h.iters & 1] = rr_true;
+        again = rr_true > A.tol2;
+    }
     HIPCHK(hipStreamSynchronize(st));
     if (!emu) e.x_iter_hint = h.iters;
     if (iters_out) *iters_out = h.iters;
@@ -692,10 +933,13 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         e.stats.spmv_long_launches = prof_long_n; e.stats.spmv_short_launches = prof_short_n;
     }
     if (timing) {
-        double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (auto &pr : tsamples) sum[pr.first] += pr.second;
+        double sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int nmul_n = 0;
+        for (auto &pr : tsamples) { sum[pr.first] += pr.second; if (pr.first == 8) ++nmul_n; }
         TM.n = tphase;
         for (int c = 0; c < 8; ++c) TM.us[c] = tphase ? sum[c] * 1e3 / tphase : 0.0;
+        TM.nmul_us = nmul_n ? sum[8] * 1e3 / nmul_n : 0.0;
+        g_slab_last.nmul_us = TM.nmul_us;
     }
-    return h.pad[0] ? DKMC_XTB_BREAKDOWN : 0;
+    if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
+    return again ? DKMC_XTB_AGAIN : 0;
 }

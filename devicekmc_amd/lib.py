@@ -72,6 +72,8 @@ SYMBOLS = {
     "dkmc_get_x_apply_form": (_I, []),
     "dkmc_set_x_slab": (None, [_I]),
     "dkmc_get_x_slab": (_I, []),
+    "dkmc_set_x_slab_poly": (None, [_I]),
+    "dkmc_get_x_slab_poly": (_I, []),
     "dkmc_set_x_aux_warm": (None, [_I]),
     "dkmc_get_x_aux_warm": (_I, []),
     "dkmc_set_x_aux": (None, [_I]),
@@ -125,6 +127,7 @@ SYMBOLS = {
     "dkmc_xtb_time_apply": (_I, [_I, _I, _I, c_dbl_p]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),
     "dkmc_xtb_emulate_slabs": (_I, [_I, _I, _D, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong), c_int_p]),
+    "dkmc_xtb_slab_last": (_I, [c_int_p, C.POINTER(C.c_longlong), c_dbl_p]),
     "dkmc_debug_inject_fault": (None, [_I, _I]),
     "dkmc_debug_step_stop_word": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dkmc_comm_unique_id": (_I, [C.c_char_p]),

@@ -149,11 +149,12 @@ int dkmc_get_x_block(void);
  * slab of the device: neighbour part, Gram pass and panel updates run on its rows only; per sweep the tile sums of the S rows go to their owners
  * (all-to-all-v), 6 x 256 Gram entries are all-gathered and added in rank order, the own rows of Q = S P and the halo rows of P go out
  * (all-to-all-v) (csrc/xtb_slab.inc).  0: the all-gather variant -- only the tile stream is sharded, everything else replicated. */
-/* Split polynomial preconditioner of the block-CG of the current solve (one GPU; csrc/xtb.hip): degree d > 0 runs the block loop on L A L with
- * L = p(N), p the degree-d Chebyshev interpolant of (1 - x)^(-1/2), N = I - (neighbour part + diagonal of the Jacobi-scaled X).  A sweep then costs
- * 2 d more sparse panel products and the loop needs 2-3x fewer sweeps (tools/precond_block_proto.py); the start vector enters through the right-hand
- * side L (b - A y0), the result meets the reference's stop test in the TRUE residual (checked, the loop is re-entered if it does not).  d in 0 ... 16
- * (clamped), 0 = off; default 8. */
+/* Split polynomial preconditioner of the block-CG of the current solve (csrc/xtb.hip): degree d > 0 runs the block loop on L A L with
+ * L = p(N), p the degree-d Chebyshev interpolant of (1 - x)^(-1/2) on [-1, 1 - min(0.5, 1.6 / d^2)], N = I - (neighbour part + diagonal of the
+ * Jacobi-scaled X).  A sweep then costs 2 d more sparse panel products and the loop needs 2-3x fewer sweeps (tools/precond_block_proto.py); the start
+ * vector enters through the right-hand side L (b - A y0), the result meets the reference's stop test in the TRUE residual (checked, the loop is
+ * re-entered if it does not).  d in 0 ... 16 (clamped), 0 = off; default 8.  Applies to the one-GPU loop; the slab-distributed loop of more than one
+ * rank carries it only with dkmc_set_x_slab_poly(1). */
 void dkmc_set_x_poly(int degree);
 int dkmc_get_x_poly(void);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
@@ -163,6 +164,14 @@ void dkmc_set_x_nmul_form(int form);
 int dkmc_get_x_nmul_form(void);
 void dkmc_set_x_slab(int on);
 int dkmc_get_x_slab(void);
+/* Opt-in: 1 runs the slab-distributed block-CG (dkmc_set_x_slab(1), more than one rank) on L A L with the degree and the coefficients of the one-GPU
+ * loop (dkmc_get_x_poly() > 0; 0 leaves it plain).  Every N product runs on the rank's own rows -- each row formed as on one GPU, bit for bit -- with
+ * one halo exchange of its input before it: 2 d + 3 exchanges per sweep instead of 3 (csrc/xtb_slab.inc).  Same solution to rounding, about the
+ * sweep count of the one-GPU preconditioned loop, the same bits on every rank; the true residual is checked at the end and the solve re-entered as
+ * on one GPU; no auxiliary columns are kept for the next solve.  Unchanged by it: the all-gather variant (dkmc_set_x_slab(0)) and a communicator
+ * of one rank (both run the plain loop).  Default 0. */
+void dkmc_set_x_slab_poly(int on);
+int dkmc_get_x_slab_poly(void);
 /* More than one rank, K system above the size of the blocked form (262 144 rows): 1 (default) distributes the CG on K (background potential, CB
  * edge) by the same lateral row slabs -- product, update and direction on the own rows, the two dot products of an iteration completed by
  * all-gathers of block partials added in one fixed order on every rank, the halo of the scaled direction by an all-to-all-v (csrc/kcg.hip;

@@ -59,6 +59,13 @@ int dkmc_debug_step_stop_word(int m, int it, int done_word, int *updated, int *d
 int dkmc_xtb_emulate_slabs(int nranks, int width, double tol, int time_rank, int sweep_cap, double *rel_diff, int *iters_slab, int *iters_ref,
                            double *times_us, long long *xdoubles, int *rows_min_max);
 
+/* Measurement aid: the last slab-distributed block-CG solve or emulation -- exchanges per sweep (3, or 2 d + 3 with dkmc_set_x_slab_poly(1); 2 with
+ * one rank), doubles a rank receives per halo exchange of the preconditioned loop (largest over the ranks; the halo share of exchange 3), and
+ * nmul_us: the mean duration of one N x panel product of the timed virtual rank (0 when untimed or unpreconditioned).  The times_us[8] classes of
+ * dkmc_xtb_emulate_slabs keep their meaning; with the switch on, "rows" includes the fold pass and "pack + unpack" the halo exchanges, and its
+ * one-GPU reference runs with dkmc_get_x_poly() instead of 0. */
+int dkmc_xtb_slab_last(int *exchanges_per_sweep, long long *halo_doubles_per_exchange, double *nmul_us);
+
 /* Test / measurement aid: the slab-distributed CG on K (csrc/kcg.hip) with nranks VIRTUAL ranks inside this process: the background-potential
  * system of the buffer's current state solved from the buffer's current potential by the one-GPU reference-order loop and by the distributed loop
  * (exchanges as device copies), into scratch copies.  max_abs_diff [V]; times_us[4]: product, update, direction, halo pack + unpack of virtual
