@@ -1381,27 +1381,185 @@ static int xtb_aux_split(int mode, double tol2, bool warm, int s)
     if (!(tol2 >= 1e-16)) return 1;
     return warm ? std::max(1, s / 2) : 16;
 }
+// bounding box of the atoms (k_xtb_box, from the empty box) and its modes (k_xtb_modes, which also decodes lo / hi) into d; h0: the other fields
+static int xtb_box_modes(XbAux *d, XbAux h0, const XtbArgs &A, int x_only, hipStream_t st)
+{
+    for (int k = 0; k < 3; ++k) { h0.mm[2 * k] = ~0ull; h0.mm[2 * k + 1] = 0ull; }
+    HIPCHK(hipMemcpyAsync(d, &h0, sizeof(XbAux), hipMemcpyHostToDevice, st));         // (pageable source: copied before the call returns)
+    hipLaunchKernelGGL(k_xtb_box, dim3(std::min((A.m - 2 + 255) / 256, 256)), dim3(256), 0, st, A.m - 2, A.ax, A.ay, A.az, d);
+    hipLaunchKernelGGL(k_xtb_modes, dim3(1), dim3(512), 0, st, d, x_only);
+    return 0;
+}
+// smooth auxiliary columns (see xtb_rhs): dkmc_set_x_aux 0 never, 1 always, 2 (default) at tolerances of 1e-8 and looser, 3 always with x modes only.
+// *hs: which auxiliary columns take which set, and which start from the previous solve's solutions (A.yaux, dkmc_set_x_aux_warm): see xtb_aux_split.
+// *aux: the smooth set's table, or null
+static int xtb_aux_setup(const XtbArgs &A, XbAux **aux, int *hs)
+{
+    Engine &e = eng();
+    *hs = xtb_aux_split(e.x_aux, A.tol2, A.yaux != nullptr, A.s);
+    *aux = nullptr;
+    if (A.ax && A.ay && A.az && A.m > 2 && *hs > 1) {
+        *aux = (XbAux *)scratch(S_XTB_XI, sizeof(XbAux));
+        if (!*aux) return e.err_code;
+        XbAux h0{};
+        h0.hs = *hs;
+        if (int rc = xtb_box_modes(*aux, h0, A, e.x_aux == 3 ? 1 : 0, e.stream)) return rc;
+    }
+    e.stats.xb_aux = *aux ? (*hs >= A.s ? 1 : 2) : 0;
+    return 0;
+}
 // the packed N of one solve (k_xtb_npack): slice offsets, columns, weights
 struct XbNPack { const long long *off; const int *col; const double *w; };
-static int xtb_npack(const XtbArgs &A, XbNPack *np)
+// N packed over n rows: rows 0 ... n - 1, or the entries of rowlist (a rank of the slab loop).  alloc(slot, bytes) provides the buffers (scratch, or a
+// virtual rank's own); pad: spare slots behind the packed ones
+template <class Alloc>
+static int xtb_npack(const XtbArgs &A, int n, const int *rowlist, Alloc alloc, long long pad, XbNPack *np)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
-    const int m = A.m, nsl = (m + 3) / 4;
-    int *cnt = (int *)scratch(S_XTB_NPACK_CNT, (size_t)nsl * 4);
-    long long *off = (long long *)scratch(S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
+    const int nsl = (n + 3) / 4;
+    int *cnt = (int *)alloc(S_XTB_NPACK_CNT, (size_t)nsl * 4);
+    long long *off = (long long *)alloc(S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
     if (!cnt || !off) return e.err_code;
-    hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, m, A.rp, cnt);
+    hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, n, A.rp, cnt, rowlist);
     if (int rc = dkmc_exclusive_scan_i32_i64(cnt, off, nsl, off + nsl)) return rc;
     long long nslot = 0;
     HIPCHK(hipMemcpyAsync(&nslot, off + nsl, sizeof(long long), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    int *col = (int *)scratch(S_XTB_NPACK_COL, (size_t)nslot * 4);
-    double *w = (double *)scratch(S_XTB_NPACK_W, (size_t)nslot * 8);
+    int *col = (int *)alloc(S_XTB_NPACK_COL, (size_t)(nslot + pad) * 4);
+    double *w = (double *)alloc(S_XTB_NPACK_W, (size_t)(nslot + pad) * 8);
     if (!col || !w) return e.err_code;
-    hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, m, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w);
+    hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, n, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, rowlist);
     KCHK();
     np->off = off; np->col = col; np->w = w;
     return 0;
+}
+// one rank's N for the preconditioner's products: n rows (rowlist: the entries of a rank's list, the slab loop), packed (np) or CSR (np null), the
+// rank's QS and control words
+struct XbNRank { int n; const int *rowlist; const XbNPack *np; double *QS; const XCtrl *ctrl; };
+// one Horner step out = ca add + cb (N in); qsf: QS of out as well, from the rows in registers (packed form)
+template <bool LIST>
+static void xtb_nstep(hipStream_t st, const XtbArgs &A, const XbNRank &R, const double *in, const double *add, double ca, double cb, double *out, bool qsf)
+{
+    const dim3 g((R.n + 15) / 16), b(XT_NT);
+    if (!R.np) hipLaunchKernelGGL(k_xtb_nmul<LIST>, g, b, 0, st, R.n, A.rp, A.ci, A.val, A.sc, in, add, ca, cb, out, R.ctrl, R.rowlist);
+    else if (qsf) hipLaunchKernelGGL((k_xtb_nmulp<true, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, A.nsrank, R.QS, R.rowlist);
+    else hipLaunchKernelGGL((k_xtb_nmulp<false, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, (const int *)nullptr,
+                            (double *)nullptr, R.rowlist);
+}
+// dst = L src (Horner: pd N products out = c_j src + N in, j = pd - 1 - i, the first step carries c_d); out rotates over w1 / w2 and is dst on the last
+// step, so dst must be none of src, w1, w2.  qs: QS of dst as well -- the packed form writes it from the last step's registers, the CSR form by
+// k_xtb_qs_from.  Panels are named by Pn: ranks(product, f) calls f(R, at) for every rank of the loop (one GPU: one), R its N and at(p) its panel p
+// (product: f issues an N product -- the slab loop times those); pre(i, in) runs before step i (the slab loop's halo exchange of the step's input).
+template <class Pn, class Pre, class Ranks>
+static int xtb_applyL(hipStream_t st, const XtbArgs &A, int pd, const double *pc, Pn src, Pn dst, Pn w1, Pn w2, bool qs, Pre pre, Ranks ranks)
+{
+    Pn in = src;
+    for (int i = 0; i < pd; ++i) {
+        const Pn out = (i == pd - 1) ? dst : ((i & 1) ? w2 : w1);
+        const int j = pd - 1 - i;
+        const double cb = i == 0 ? pc[pd] : 1.0;
+        if (int rc = pre(i, in)) return rc;
+        if (int rc = ranks(true, [&](const XbNRank &R, auto at) {
+                (R.rowlist ? xtb_nstep<true> : xtb_nstep<false>)(st, A, R, at(in), at(src), pc[j], cb, at(out), qs && i == pd - 1);
+            })) return rc;
+        in = out;
+    }
+    if (!qs || pd <= 0) return 0;
+    return ranks(false, [&](const XbNRank &R, auto at) {
+        if (!R.np) hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)(((size_t)A.m * XB_SP + 255) / 256)), dim3(256), 0, st, A.m, (const double *)at(dst), A.sc, A.nsrank,
+                                      R.QS, R.ctrl);
+    });
+}
+// the tile x panel kernel (one wave per tile run, four runs per workgroup) at NG = so / 4 vector groups: the product form, or the round-4 form
+// (dkmc_set_x_apply_form(1) = variant 8); variant != 0 (dkmc_xtb_time_apply in a DKMC_MEASURE_VARIANTS build): a measurement variant, where one exists
+struct XbApplyArgs { int n; const XItem *items; const XTile *tiles; int sub_base; const double *tval; const double *QS; int nW; double *rowpartB, *colpartB; const XCtrl *ctrl; };
+template <int NTL, int NG, int V>
+static void xtb_apply_v(const XbApplyArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+    hipExtLaunchKernelGGL((k_xtb_apply<NTL, NG, V>), dim3((a.n + 3) / 4), dim3(XT_NT), 0, st, e0, e1, 0, a.n, a.items, a.tiles, a.sub_base, a.tval, a.QS, a.nW,
+                          a.rowpartB, a.colpartB, a.ctrl);
+}
+template <int NTL, int NG>
+static void xtb_apply_ng(const XbApplyArgs &a, int variant, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+#ifdef DKMC_MEASURE_VARIANTS
+#define XB_V(v_) if (variant == (v_)) return xtb_apply_v<NTL, NG, v_>(a, st, e0, e1);
+    if constexpr (NTL == 1 && NG == 2) { XB_V(1) XB_V(2) }
+    if constexpr (NTL == 1 && NG == 4) { XB_V(1) XB_V(2) XB_V(3) XB_V(4) XB_V(7) XB_V(10) XB_V(12) }
+#undef XB_V
+#else
+    (void)variant;
+#endif
+    if (eng().x_apply_form == 1) xtb_apply_v<NTL, NG, 8>(a, st, e0, e1);
+    else xtb_apply_v<NTL, NG, 0>(a, st, e0, e1);
+}
+static void xtb_apply(const XbApplyArgs &a, bool ntl, int so, int variant, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
+{
+    static void (*const ng[2][4])(const XbApplyArgs &, int, hipStream_t, hipEvent_t, hipEvent_t) = {
+        {xtb_apply_ng<0, 1>, xtb_apply_ng<0, 2>, xtb_apply_ng<0, 3>, xtb_apply_ng<0, 4>}, {xtb_apply_ng<1, 1>, xtb_apply_ng<1, 2>, xtb_apply_ng<1, 3>, xtb_apply_ng<1, 4>}};
+    ng[ntl ? 1 : 0][so == 4 ? 0 : (so == 8 ? 1 : (so == 12 ? 2 : 3))](a, variant, st, e0, e1);
+}
+// the row kernels' first pass (INIT) launched plainly, a sweep's between the profiling events e0 / e1 (null: none)
+template <int SH, int NF, class... Args>
+static void xtb_rows_launch(bool init, int ng, hipStream_t st, hipEvent_t e0, hipEvent_t e1, Args... a)
+{
+    if (init) hipLaunchKernelGGL((k_xtb_rows<1, SH, NF>), dim3(ng), dim3(XT_NT), 0, st, a...);
+    else hipExtLaunchKernelGGL((k_xtb_rows<0, SH, NF>), dim3(ng), dim3(XT_NT), 0, st, e0, e1, 0, a...);
+}
+// profiling (dkmc_set_profiling): the tile and the row kernel of the first sweep of every XT_PROF_STRIDE of a batch (up to 8) between events of one set
+struct XbProf { double long_ms = 0.0, short_ms = 0.0; int long_n = 0, short_n = 0; };
+static hipEvent_t g_xb_evs[4 * 8]; static bool g_xb_evs_ready = false;
+static const hipEvent_t g_xb_noev[4] = {nullptr, nullptr, nullptr, nullptr};
+// Launch plan of a block loop: batches of sweeps, one read-back of the control words (into h) per batch.  The first batch covers three quarters of the
+// previous solve's sweeps -- with the warm start the count moves by +-30 per cent from step to step (9.4e5 sites: 268 ... 505), and a batch sized to the
+// previous count left up to a quarter of its launches as no-ops --, then batches of 8; without a hint batches of 4, 8, ... 64.
+// sweep(it, ev) issues sweep `it`; ev: its four events (tile kernel, row kernel) or none.  hint: plan from e.x_iter_hint; cap > 0: stop after cap sweeps;
+// prof: harvest the events into pf; fault: the test aid g_xtb_fault_iter applies (it fails this rank on the host side, local_fail).
+template <class Sweep>
+static int xtb_sweeps(const XCtrl *ctrl, XCtrl &h, bool hint, int cap, bool prof, bool fault, int &local_fail, XbProf &pf, Sweep sweep)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (prof && !g_xb_evs_ready) { for (auto &ev : g_xb_evs) HIPCHK(hipEventCreate(&ev)); g_xb_evs_ready = true; }
+    int it = 0, launched = 0, batch = 4;
+    if (hint && e.x_iter_hint > 12) batch = std::max(4, e.x_iter_hint * 3 / 4);
+    for (;;) {
+        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (prof && launched) {
+            for (int bq = 0; bq < 8 && bq * XT_PROF_STRIDE < launched; ++bq) {
+                if (it - launched + bq * XT_PROF_STRIDE >= h.iters) break;
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, g_xb_evs[4 * bq], g_xb_evs[4 * bq + 1])); pf.long_ms += ms; ++pf.long_n;
+                HIPCHK(hipEventElapsedTime(&ms, g_xb_evs[4 * bq + 2], g_xb_evs[4 * bq + 3])); pf.short_ms += ms; ++pf.short_n;
+            }
+        }
+        if (h.done) break;
+        if (cap > 0 && it >= cap) break;
+        if (it >= 200000) { dkmc_fail(4, "block-CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
+        for (int bq = 0; bq < batch; ++bq, ++it) {
+            const bool pb = prof && bq < 8 * XT_PROF_STRIDE && (bq % XT_PROF_STRIDE == 0);
+            if (fault && g_xtb_fault_iter >= 0 && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
+            if (int rc = sweep(it, pb ? g_xb_evs + 4 * (bq / XT_PROF_STRIDE) : g_xb_noev)) return rc;
+        }
+        launched = batch;
+        KCHK();
+        if (hint && e.x_iter_hint > 12) batch = 8; else if (batch < 64) batch *= 2;
+    }
+    return 0;
+}
+// end of a block loop: sweeps and residual to the caller, the profile to the stats; hint: the sweeps size the next solve's first batch
+static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, const XbProf &pf, int *iters_out, double *rr_out)
+{
+    Engine &e = eng();
+    if (hint) e.x_iter_hint = h.iters;
+    if (iters_out) *iters_out = h.iters;
+    if (rr_out) *rr_out = h.rr[h.iters & 1];
+    if (prof) {
+        e.stats.spmv_long_ms = pf.long_ms; e.stats.spmv_short_ms = pf.short_ms;
+        e.stats.spmv_long_launches = pf.long_n; e.stats.spmv_short_launches = pf.short_n;
+    }
+    if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
+    return again ? DKMC_XTB_AGAIN : 0;
 }
 // coefficients pc[0 ... pd] of the preconditioner L = p(N) (dkmc_set_x_poly; shared by the one-GPU and the slab-distributed loop)
 static void xtb_poly_coeffs(int pd, double *pc)
@@ -1469,7 +1627,7 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     // the preconditioner's N packed once per solve (sc is known); the re-entry rounds below reuse it
     XbNPack npk{};
     const bool packed = !A.sharded && A.m > 2 && A.ns > 0 && eng().x_poly > 0 && eng().x_nmul_form == 1;
-    if (packed) { if (int rcp = xtb_npack(A, &npk)) return rcp; }
+    if (packed) { if (int rcp = xtb_npack(A, A.m, nullptr, scratch, 0, &npk)) return rcp; }
     const XbNPack *np = packed ? &npk : nullptr;
     int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np);
     rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { return xtb_cg_body(A, it, rr, &peer_used, np); });
@@ -1526,24 +1684,11 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         if (!peer) { xbuf = (double *)scratch(S_CG_XCHG, xcount * nr * 8); if (!xbuf) return e.err_code; }
         hipLaunchKernelGGL(k_xtb_set_sharded, dim3(1), dim3(1), 0, st, A.ctrl);
     }
-    // smooth auxiliary columns (see xtb_rhs): dkmc_set_x_aux 0 never, 1 always, 2 (default) at tolerances of 1e-8 and looser, 3 always with x modes only
-    XbAux *aux = nullptr;
-    // which auxiliary columns take which set, and which start from the previous solve's solutions (A.yaux, dkmc_set_x_aux_warm): see xtb_aux_split
-    const int hs = xtb_aux_split(e.x_aux, A.tol2, A.yaux != nullptr, s);
     const bool keep_aux = A.yaux != nullptr && pd == 0;
     double *Ypanel = keep_aux ? (double *)scratch(S_XTB_YPANEL, pan * 8) : nullptr;
     if (keep_aux && !Ypanel) return e.err_code;
-    if (A.ax && A.ay && A.az && m > 2 && hs > 1) {
-        aux = (XbAux *)scratch(S_XTB_XI, sizeof(XbAux));
-        if (!aux) return e.err_code;
-        XbAux h0{};
-        h0.hs = hs;
-        for (int d = 0; d < 3; ++d) { h0.mm[2 * d] = ~0ull; h0.mm[2 * d + 1] = 0ull; }
-        HIPCHK(hipMemcpyAsync(aux, &h0, sizeof(XbAux), hipMemcpyHostToDevice, st));       // (pageable source: copied before the call returns)
-        hipLaunchKernelGGL(k_xtb_box, dim3(std::min((m - 2 + 255) / 256, 256)), dim3(256), 0, st, m - 2, A.ax, A.ay, A.az, aux);
-        hipLaunchKernelGGL(k_xtb_modes, dim3(1), dim3(512), 0, st, aux, e.x_aux == 3 ? 1 : 0);
-    }
-    e.stats.xb_aux = aux ? (hs >= s ? 1 : 2) : 0;
+    XbAux *aux = nullptr; int hs = 1;
+    if (int rc = xtb_aux_setup(A, &aux, &hs)) return rc;
     int local_fail = 0;
     hipLaunchKernelGGL(k_xtb_init, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, A.sc, A.nsrank, y0, P, QS,
                        (const double *)((keep_aux && A.yaux_valid) ? A.yaux : nullptr), hs, s, Ypanel);
@@ -1551,9 +1696,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     const int nnb = 2 * XB_DSPLIT + (std::max(m - 2, 1) + 15) / 16;
     const int gs = xt_grid((m + 15) / 16, 4, 2048);
     const bool prof = e.profiling != 0;
-    static hipEvent_t evs[4 * 8]; static bool evs_ready = false;
-    if (prof && !evs_ready) { for (auto &ev : evs) HIPCHK(hipEventCreate(&ev)); evs_ready = true; }
-    double prof_long_ms = 0.0, prof_short_ms = 0.0; int prof_long_n = 0, prof_short_n = 0;
+    XbProf pf;
     // neighbour part beside the tile kernel (see XbSide): only in a sharded solve, where a rank's tile pass is 1 / N of the sweep and the
     // (replicated) neighbour part would otherwise be a serial 0.3 ms behind it.  On ONE GPU the overlap was measured and does not pay: the two
     // kernels share the memory system, the tile pass slows by what the neighbour part takes (9.4e5 sites: 3.95 + 0 against 3.65 + 0.32 ms; 85 k sites,
@@ -1568,38 +1711,14 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, S.st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
             (void)hipEventRecord(S.b[sl], S.st);
         }
-        if (ntb > 0) {
-#define XB_APPLY_ARGS_ A.item_n, A.items, A.tiles, A.sub_base, A.tval, (const double *)QS, A.nW, rowpartB, colpartB, (const XCtrl *)A.ctrl
-#define XB_APPLY(NTL_, NG_) do { if (e.x_apply_form == 1) hipExtLaunchKernelGGL((k_xtb_apply<NTL_, NG_, 8>), dim3(ntb), dim3(XT_NT), 0, st, e0, e1, 0, XB_APPLY_ARGS_); \
-                                 else hipExtLaunchKernelGGL((k_xtb_apply<NTL_, NG_>), dim3(ntb), dim3(XT_NT), 0, st, e0, e1, 0, XB_APPLY_ARGS_); } while (0)
-            if (A.nt_loads) { if (so == 4) XB_APPLY(1, 1); else if (so == 8) XB_APPLY(1, 2); else if (so == 12) XB_APPLY(1, 3); else XB_APPLY(1, 4); }
-            else { if (so == 4) XB_APPLY(0, 1); else if (so == 8) XB_APPLY(0, 2); else if (so == 12) XB_APPLY(0, 3); else XB_APPLY(0, 4); }
-#undef XB_APPLY
-#undef XB_APPLY_ARGS_
-        }
+        if (ntb > 0) xtb_apply({A.item_n, A.items, A.tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl}, A.nt_loads, so, 0, st, e0, e1);
         if (side) (void)hipStreamWaitEvent(st, g_xb_side.b[sl], 0);           // the sparse sums are in T before the row kernel reads them
         else hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
     };
-    // dst = L src (Horner: d sparse panel products); dst must be none of src, W1, W2.  qs: QS of dst as well (the packed form writes it from the
-    // last step's registers, the CSR form by k_xtb_qs_from)
-    const int nmb = (m + 15) / 16;
-    auto applyL = [&](const double *src, double *dst, bool qs) {
-        if (pd <= 0) return;
-        const double *in = src;
-        for (int i = 0; i < pd; ++i) {
-            double *out = (i == pd - 1) ? dst : ((i & 1) ? W2 : W1);
-            const int j = pd - 1 - i;                                         // out = c_j src + N (previous), the first step carries c_d
-            const double cb = i == 0 ? pc[pd] : 1.0;
-            if (!np) hipLaunchKernelGGL(k_xtb_nmul<false>, dim3(nmb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl,
-                                        (const int *)nullptr);
-            else if (qs && i == pd - 1)
-                hipLaunchKernelGGL(k_xtb_nmulp<true>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl, A.nsrank, QS);
-            else hipLaunchKernelGGL(k_xtb_nmulp<false>, dim3(nmb), dim3(XT_NT), 0, st, m, np->off, np->col, np->w, A.sc, in, src, pc[j], cb, out, (const XCtrl *)A.ctrl,
-                                    (const int *)nullptr, (double *)nullptr);
-            in = out;
-        }
-        if (qs && !np)
-            hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)dst, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
+    // dst = L src (xtb_applyL)
+    const XbNRank nk{m, nullptr, np, QS, A.ctrl};
+    auto applyL = [&](double *src, double *dst, bool qs) {
+        xtb_applyL(st, A, pd, pc, src, dst, W1, W2, qs, [](int, double *) { return 0; }, [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; });
     };
     auto fold_rows = [&](double *Tt) {
         hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB,
@@ -1607,12 +1726,12 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     };
     // T = L A L P
     auto product_pre = [&](hipEvent_t e0, hipEvent_t e1) {
-        applyL((const double *)P, Vp, true);
+        applyL(P, Vp, true);
         double *Pk = P, *Tk = T; P = Vp; T = Zp;                              // (the product reads P and QS, writes T)
         product(e0, e1);
         P = Pk; T = Tk;
         fold_rows(Zp);
-        applyL((const double *)Zp, T, false);
+        applyL(Zp, T, false);
     };
     const double *bsel = A.b;
 #define XB_ROWS_ARGS(IT_) A.ns, A.nK, A.nW, m, s, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB, A.srow, A.sS, A.nsrank, A.sc, \
@@ -1632,15 +1751,9 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
                 if (int rcx = comm_peer_exchange(xpar, xcount, &A.ctrl->done, &A.ctrl->aborted, &A.ctrl->xchg_timeout, itn + 2)) return rcx;
                 xpar ^= 1;
             } else if (int rcx = comm_allgather_f64(xbuf, xcount)) return rcx;
-            if (init) hipLaunchKernelGGL((k_xtb_rows<1, 1>), dim3(ng), dim3(XT_NT), 0, st, XB_ROWS_ARGS(itn));
-            else hipExtLaunchKernelGGL((k_xtb_rows<0, 1>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XB_ROWS_ARGS(itn));
-        } else if (pd > 0) {
-            if (init) hipLaunchKernelGGL((k_xtb_rows<1, 0, 1>), dim3(ng), dim3(XT_NT), 0, st, XB_ROWS_ARGS(itn));
-            else hipExtLaunchKernelGGL((k_xtb_rows<0, 0, 1>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XB_ROWS_ARGS(itn));
-        } else {
-            if (init) hipLaunchKernelGGL((k_xtb_rows<1, 0>), dim3(ng), dim3(XT_NT), 0, st, XB_ROWS_ARGS(itn));
-            else hipExtLaunchKernelGGL((k_xtb_rows<0, 0>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XB_ROWS_ARGS(itn));
-        }
+            xtb_rows_launch<1, 0>(init, ng, st, e2, e3, XB_ROWS_ARGS(itn));
+        } else if (pd > 0) xtb_rows_launch<0, 1>(init, ng, st, e2, e3, XB_ROWS_ARGS(itn));
+        else xtb_rows_launch<0, 0>(init, ng, st, e2, e3, XB_ROWS_ARGS(itn));
         return 0;
     };
     // ---- R = A Y0 - B ; first directions ----
@@ -1649,7 +1762,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         // the start vector goes into the right-hand side: column 0 solves L A L dh = L (b - A y0) from zero, the auxiliary columns keep their own
         fold_rows(T);                                                         // T = A Y0
         hipLaunchKernelGGL(k_xtb_pre_resid, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)T, A.b, Zp);
-        applyL((const double *)Zp, T, false);                                 // T(:, 0) = L (A y0 - b), the other columns 0
+        applyL(Zp, T, false);                                                 // T(:, 0) = L (A y0 - b), the other columns 0
         bsel = bz;                                                            // R = T - [0 | auxiliary right-hand sides]
         HIPCHK(hipMemsetAsync(y0, 0, (size_t)m * 8, st));
     }
@@ -1660,40 +1773,17 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, -1, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
                        (const int *)nullptr, Ypanel);
     KCHK();
-    int it = 0, launched = 0, batch = 4;
-    // launch plan: the first batch covers three quarters of the previous solve's sweeps -- with the warm start the count moves by +-30 per cent from
-    // step to step (9.4e5 sites: 268 ... 505), and a batch sized to the previous count left up to a quarter of its launches as no-ops --, then batches of 8
-    if (e.x_iter_hint > 12) batch = std::max(4, e.x_iter_hint * 3 / 4);
     XCtrl h{};
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, A.ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (prof && launched && ntb > 0) {
-            for (int bq = 0; bq < 8 && bq * XT_PROF_STRIDE < launched; ++bq) {
-                if (it - launched + bq * XT_PROF_STRIDE >= h.iters) break;
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * bq], evs[4 * bq + 1])); prof_long_ms += ms; ++prof_long_n;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * bq + 2], evs[4 * bq + 3])); prof_short_ms += ms; ++prof_short_n;
-            }
-        }
-        if (h.done) break;
-        if (it >= 200000) { dkmc_fail(4, "block-CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int bq = 0; bq < batch; ++bq, ++it) {
-            const bool pb = prof && ntb > 0 && bq < 8 * XT_PROF_STRIDE && (bq % XT_PROF_STRIDE == 0);      // (no tile launch: its events would never be recorded)
-            const int sl = bq / XT_PROF_STRIDE;
-            if (g_xtb_fault_iter >= 0 && sharded && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
-            if (pd > 0) product_pre(pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr);
-            else product(pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr);
-            if (int rcx = rows(false, it, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
+    if (int rcx = xtb_sweeps(A.ctrl, h, true, 0, prof && ntb > 0, sharded, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {     // (no tile launch: no events)
+            if (pd > 0) product_pre(ev[0], ev[1]);
+            else product(ev[0], ev[1]);
+            if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
             hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, gfin, (const XCtrl *)A.ctrl);
             hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, it, s, (const double *)gfin, mats, A.ctrl, tol2_loop);
             hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
                                (const int *)nullptr, Ypanel);
-        }
-        launched = batch;
-        KCHK();
-        if (e.x_iter_hint > 12) batch = 8; else if (batch < 64) batch *= 2;
-    }
+            return 0;
+        })) return rcx;
 #undef XB_ROWS_ARGS
     if (local_fail) return local_fail;                                         // the peers were told (abort word)
     if (h.xchg_timeout) return dkmc_fail(48, "block-CG: the peer-write exchange timed out waiting for a peer's slot", __FILE__, __LINE__);
@@ -1704,7 +1794,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         // y = y0 + L dh, then the TRUE residual of column 0 in the unpreconditioned system: one more pass over the tiles
         HIPCHK(hipMemsetAsync(A.ctrl, 0, sizeof(XCtrl), st));                 // (the kernels below are gated by `done`)
         hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)y0, Zp);
-        applyL((const double *)Zp, Vp, false);
+        applyL(Zp, Vp, false);
         hipLaunchKernelGGL(k_xtb_pre_add, dim3((m + 255) / 256), dim3(256), 0, st, m, (const double *)Vp, A.y);
         if (!h.pad[0]) {
             hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, P);
@@ -1721,15 +1811,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     } else
     HIPCHK(hipMemcpyAsync(A.y, y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     if (keep_aux) hipLaunchKernelGGL(k_xtb_yaux_out, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const int *)nullptr, (const double *)Ypanel, A.sc, A.yaux);
-    e.x_iter_hint = h.iters;
-    if (iters_out) *iters_out = h.iters;
-    if (rr_out) *rr_out = h.rr[h.iters & 1];
-    if (prof) {
-        e.stats.spmv_long_ms = prof_long_ms; e.stats.spmv_short_ms = prof_short_ms;
-        e.stats.spmv_long_launches = prof_long_n; e.stats.spmv_short_launches = prof_short_n;
-    }
-    if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
-    return again ? DKMC_XTB_AGAIN : 0;
+    return xtb_finish(h, true, again, prof, pf, iters_out, rr_out);
 }
 
 #include "xtb_slab.inc"
@@ -1812,11 +1894,9 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(nrec + 1) * XT_C * so * 8, st));
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((ns * XB_SP + 255) / 256), dim3(256), 0, st, ns, QS);
-#define XB_APPLY_ARGS_ X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, (const double *)QS, X.nW, rowpartB, colpartB, (const XCtrl *)ctrl
-#define XB_APPLY(NG_) do { if (e.x_apply_form == 1) hipLaunchKernelGGL((k_xtb_apply<1, NG_, 8>), dim3((X.item_n + 3) / 4), dim3(XT_NT), 0, st, XB_APPLY_ARGS_); \
-                           else hipLaunchKernelGGL((k_xtb_apply<1, NG_>), dim3((X.item_n + 3) / 4), dim3(XT_NT), 0, st, XB_APPLY_ARGS_); } while (0)
-    if (so == 4) XB_APPLY(1); else if (so == 8) XB_APPLY(2); else if (so == 12) XB_APPLY(3); else XB_APPLY(4);
-#undef XB_APPLY
+    const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
+                         colpartB, ctrl};
+    xtb_apply(xa, true, so, 0, st);
     hipLaunchKernelGGL((k_xtb_rows<1, 0>), dim3(ng), dim3(XT_NT), 0, st, ns, X.nK, X.nW, m, s, so, (const int2 *)g_xb.wrange, (const int *)g_xb.nitem_w, (const double *)rowpartB,
                        (const double *)colpartB, (const int *)g_xb.srow, (const double *)sS, (const int *)g_xb.nsrank, (const double *)sc, (const double *)drvpart, T,
                        (const double *)P, R, (const double *)rhs, gpart, ctrl, (const double *)nullptr, -1, 1, (const XbAux *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr);
@@ -1857,21 +1937,12 @@ extern "C" int dkmc_xtb_time_apply(int width, int variant, int reps, double *us)
     if (!QS || !rowpartB || !colpartB || !ctrl) return e.err_code;
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((X.ns * XB_SP + 255) / 256), dim3(256), 0, st, X.ns, QS);
+    const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
+                         colpartB, ctrl};
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     for (int r = -1; r < reps; ++r) {
         if (r == 0) HIPCHK(hipEventRecord(e0, st));
-#define XB_APPLY(NG_, V_) do { if (e.x_apply_form == 1 && (V_) == 0) hipLaunchKernelGGL((k_xtb_apply<1, NG_, 8>), dim3((X.item_n + 3) / 4), dim3(XT_NT), 0, st, XB_APPLY_ARGS_); \
-                               else hipLaunchKernelGGL((k_xtb_apply<1, NG_, V_>), dim3((X.item_n + 3) / 4), dim3(XT_NT), 0, st, XB_APPLY_ARGS_); } while (0)
-#ifdef DKMC_MEASURE_VARIANTS
-        if (so == 4) XB_APPLY(1, 0);
-        else if (so == 8) { if (variant == 1) XB_APPLY(2, 1); else if (variant == 2) XB_APPLY(2, 2); else XB_APPLY(2, 0); }
-        else if (so == 12) XB_APPLY(3, 0);
-        else { if (variant == 1) XB_APPLY(4, 1); else if (variant == 2) XB_APPLY(4, 2); else if (variant == 3) XB_APPLY(4, 3); else if (variant == 4) XB_APPLY(4, 4); else if (variant == 7) XB_APPLY(4, 7); else if (variant == 10) XB_APPLY(4, 10); else if (variant == 12) XB_APPLY(4, 12); else XB_APPLY(4, 0); }
-#else
-        // (the library as shipped carries the product kernel and the round-4 form only; DKMC_MEASURE_VARIANTS=1 python __graft_entry__.py builds the rest)
-        if (so == 4) XB_APPLY(1, 0); else if (so == 8) XB_APPLY(2, 0); else if (so == 12) XB_APPLY(3, 0); else XB_APPLY(4, 0);
-#endif
-#undef XB_APPLY
+        xtb_apply(xa, true, so, variant, st);
     }
     HIPCHK(hipEventRecord(e1, st));
     HIPCHK(hipEventSynchronize(e1));

@@ -207,6 +207,13 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows_slab(int nSme, const int *__
         }
     }
 }
+// k_xtb_rows_slab's first pass (INIT) launched plainly, a sweep's between the profiling events e0 / e1 (null: none)
+template <int MODE, class... Args>
+static void xtb_rows_slab_launch(bool init, int ng, hipStream_t st, hipEvent_t e0, hipEvent_t e1, Args... a)
+{
+    if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1, MODE>), dim3(ng), dim3(XT_NT), 0, st, a...);
+    else hipExtLaunchKernelGGL((k_xtb_rows_slab<0, MODE>), dim3(ng), dim3(XT_NT), 0, st, e0, e1, 0, a...);
+}
 
 // ---- exchange 3: piece for d != me = [QS of my S rows (nS[me] x 16, list order) | the P rows d reads (halo, 16 each)] ----
 __global__ void k_xtb_pack3(SlabMeta M, const int *__restrict__ S_by_owner, const int *__restrict__ hsend, const double *__restrict__ QS, const double *__restrict__ P,
@@ -355,10 +362,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     int *pos = flag + m + 8;
     {
         XbAux h0{};
-        for (int d = 0; d < 3; ++d) { h0.mm[2 * d] = ~0ull; h0.mm[2 * d + 1] = 0ull; }
-        HIPCHK(hipMemcpyAsync(box, &h0, sizeof(XbAux), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_xtb_box, dim3(std::min((m - 2 + 255) / 256, 256)), dim3(256), 0, st, m - 2, A.ax, A.ay, A.az, box);
-        hipLaunchKernelGGL(k_xtb_modes, dim3(1), dim3(512), 0, st, box, 0);      // (decodes lo / hi)
+        if (int rc = xtb_box_modes(box, h0, A, 0, st)) return rc;
         HIPCHK(hipMemcpyAsync(&h0, box, sizeof(XbAux), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         // Which lateral axis: the rows are balanced along either, the S rows (inner-contact metals, vacancies) need not be -- the inner-contact
@@ -506,22 +510,9 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             K.bz = K.Vp + pan;
             HIPCHK(hipMemsetAsync(K.Vp, 0, (pan + m + 16) * 8, st));
             HIPCHK(hipMemsetAsync(K.W1, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.W2, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.Zp, 0, pan * 8, st));
-            if (e.x_nmul_form == 1) {                    // N packed over the list rows (k_xtb_npack): slices of four list entries, the one-GPU slots per row
-                const int nl = K.n_own + 2, nsl = (nl + 3) / 4;
-                int *cnt = (int *)salloc(iv, S_XTB_NPACK_CNT, (size_t)nsl * 4);
-                long long *off = (long long *)salloc(iv, S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
-                if (fail) return fail;
-                hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, nl, A.rp, cnt, (const int *)K.steplist);
-                if (int rc = dkmc_exclusive_scan_i32_i64(cnt, off, nsl, off + nsl)) return rc;
-                long long nslot = 0;
-                HIPCHK(hipMemcpyAsync(&nslot, off + nsl, sizeof(long long), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                int *col = (int *)salloc(iv, S_XTB_NPACK_COL, (size_t)(nslot + 64) * 4);
-                double *w = (double *)salloc(iv, S_XTB_NPACK_W, (size_t)(nslot + 64) * 8);
-                if (fail) return fail;
-                hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, nl, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, (const int *)K.steplist);
-                K.npk.off = off; K.npk.col = col; K.npk.w = w;
-            }
+            // N packed over the list rows (dkmc_set_x_nmul_form(1)): slices of four list entries, the one-GPU slots per row
+            if (e.x_nmul_form == 1)
+                if (int rc = xtb_npack(A, K.n_own + 2, K.steplist, [&](int slot, size_t bytes) { return salloc(iv, slot, bytes); }, 64, &K.npk)) return rc;
         }
     }
     KCHK();
@@ -540,19 +531,8 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     if (pd > 0 && nr > 1) e.stats.comm_count_per_rank += 2LL * pd * g_slab_last.halo_doubles;
 
     // smooth auxiliary columns (as in xtb_cg)
-    XbAux *aux = nullptr;
-    const int hs = xtb_aux_split(e.x_aux, A.tol2, A.yaux != nullptr, s);
-    if (A.ax && m > 2 && hs > 1) {
-        aux = (XbAux *)scratch(S_XTB_XI, sizeof(XbAux));
-        if (!aux) return e.err_code;
-        XbAux h0{};
-        h0.hs = hs;
-        for (int d = 0; d < 3; ++d) { h0.mm[2 * d] = ~0ull; h0.mm[2 * d + 1] = 0ull; }
-        HIPCHK(hipMemcpyAsync(aux, &h0, sizeof(XbAux), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_xtb_box, dim3(std::min((m - 2 + 255) / 256, 256)), dim3(256), 0, st, m - 2, A.ax, A.ay, A.az, aux);
-        hipLaunchKernelGGL(k_xtb_modes, dim3(1), dim3(512), 0, st, aux, e.x_aux == 3 ? 1 : 0);
-    }
-    e.stats.xb_aux = aux ? (hs >= s ? 1 : 2) : 0;
+    XbAux *aux = nullptr; int hs = 1;
+    if (int rc = xtb_aux_setup(A, &aux, &hs)) return rc;
 
     // ---- exchanges: the communicator (one local rank) or device copies between the virtual ranks ----
     // 1, 3, 4, 5: all-to-all-v; 2: all-gather of the Gram blocks; 6: halo exchange (all-to-all-v in the buffers of exchange 3); 7: all-gather of one
@@ -606,9 +586,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     };
     const int nnb_of = 2 * XB_DSPLIT;
     const bool prof = e.profiling != 0 && !emu;
-    static hipEvent_t evs[4 * 8]; static bool evs_ready = false;
-    if (prof && !evs_ready) { for (auto &ev : evs) HIPCHK(hipEventCreate(&ev)); evs_ready = true; }
-    double prof_long_ms = 0.0, prof_short_ms = 0.0; int prof_long_n = 0, prof_short_n = 0;
+    XbProf pf;
     int local_fail = 0;
 
     // panels of a rank by member: the preconditioned loop runs the same passes on Vp / Zp that the plain one runs on P / T
@@ -617,17 +595,9 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         for (int iv = 0; iv < nv; ++iv) {
             SlabRank &K = RK[iv];
             const int ntb = (K.item_n + 3) / 4;
-            if (emu && iv > 0) {          // (virtual ranks share nothing, but a boundary window's cells of the grid-indexed arrays belong to two ranks: each has its own arrays)
-            }
             if (ntb > 0) {
                 int rc = timed(iv, 0, on, [&]() {
-#define XB_APPLY_ARGS_ K.item_n, K.items, A.tiles, K.sub_base, A.tval, (const double *)K.QS, A.nW, K.rowpartB, K.colpartB, (const XCtrl *)K.ctrl
-#define XB_APPLY(NTL_, NG_) do { if (e.x_apply_form == 1) hipExtLaunchKernelGGL((k_xtb_apply<NTL_, NG_, 8>), dim3(ntb), dim3(XT_NT), 0, st, e0, e1, 0, XB_APPLY_ARGS_); \
-                                 else hipExtLaunchKernelGGL((k_xtb_apply<NTL_, NG_>), dim3(ntb), dim3(XT_NT), 0, st, e0, e1, 0, XB_APPLY_ARGS_); } while (0)
-                    if (A.nt_loads) { if (so == 4) XB_APPLY(1, 1); else if (so == 8) XB_APPLY(1, 2); else if (so == 12) XB_APPLY(1, 3); else XB_APPLY(1, 4); }
-                    else { if (so == 4) XB_APPLY(0, 1); else if (so == 8) XB_APPLY(0, 2); else if (so == 12) XB_APPLY(0, 3); else XB_APPLY(0, 4); }
-#undef XB_APPLY
-#undef XB_APPLY_ARGS_
+                    xtb_apply({K.item_n, K.items, A.tiles, K.sub_base, A.tval, K.QS, A.nW, K.rowpartB, K.colpartB, K.ctrl}, A.nt_loads, so, 0, st, e0, e1);
                 }); if (rc) return rc;
             } else if (e0) { HIPCHK(hipEventRecord(e0, st)); HIPCHK(hipEventRecord(e1, st)); }
             int rc = timed(iv, 1, on, [&]() {
@@ -658,11 +628,8 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         for (int iv = 0; iv < nv; ++iv) {
             SlabRank &K = RK[iv];
             int rc = timed(iv, 3, on, [&]() {
-                if (mode == XS_NF) {
-                    if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1, XS_NF>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS(K.T, (const double *)K.bz));
-                    else hipExtLaunchKernelGGL((k_xtb_rows_slab<0, XS_NF>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XS_ROWS_ARGS(K.T, (const double *)K.bz));
-                } else if (init) hipLaunchKernelGGL((k_xtb_rows_slab<1>), dim3(ng), dim3(XT_NT), 0, st, XS_ROWS_ARGS(K.T, A.b));
-                else hipExtLaunchKernelGGL((k_xtb_rows_slab<0>), dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, XS_ROWS_ARGS(K.T, A.b));
+                if (mode == XS_NF) xtb_rows_slab_launch<XS_NF>(init, ng, st, e2, e3, XS_ROWS_ARGS(K.T, (const double *)K.bz));
+                else xtb_rows_slab_launch<0>(init, ng, st, e2, e3, XS_ROWS_ARGS(K.T, A.b));
             }); if (rc) return rc;
             rc = timed(iv, 4, on, [&]() {
                 hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)K.gpart, K.gx + (size_t)K.v * XS_GSTR, (const XCtrl *)K.ctrl);
@@ -708,37 +675,21 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         }
         return 0;
     };
-    // dst = L src on every rank's list rows (Horner, d N products as in xtb_cg_body's applyL; the rows are formed as on one GPU: the same bits).  Before
-    // every product the halo of its input is exchanged, except src's when the caller has made it current.  qs: QS of dst's own S rows as well.
+    // dst = L src on every rank's list rows (xtb_applyL; the rows are formed as on one GPU: the same bits).  Before every product the halo of its input
+    // is exchanged, except src's when the caller has made it current.  qs: QS of dst's own S rows as well (CSR form: of every S row; the other ranks'
+    // rows are overwritten by exchange 3).
     auto applyL = [&](Pan src, Pan dst, bool qs, bool src_halo, bool on) -> int {
-        Pan in = src;
-        for (int i = 0; i < pd; ++i) {
-            const Pan out = (i == pd - 1) ? dst : ((i & 1) ? &SlabRank::W2 : &SlabRank::W1);
-            const int j = pd - 1 - i;
-            const double cb = i == 0 ? pc[pd] : 1.0;
-            if (i > 0 || !src_halo) { if (int rcx = halo(in, on)) return rcx; }
-            for (int iv = 0; iv < nv; ++iv) {
-                SlabRank &K = RK[iv];
-                const int nl = K.n_own + 2, nmb = (nl + 15) / 16;
-                int rc = timed(iv, 8, on, [&]() {
-                    if (!K.npk.off) hipLaunchKernelGGL(k_xtb_nmul<true>, dim3(nmb), dim3(XT_NT), 0, st, nl, A.rp, A.ci, A.val, A.sc, (const double *)(K.*in), (const double *)(K.*src),
-                                                       pc[j], cb, K.*out, (const XCtrl *)K.ctrl, (const int *)K.steplist);
-                    else if (qs && i == pd - 1)
-                        hipLaunchKernelGGL((k_xtb_nmulp<true, true>), dim3(nmb), dim3(XT_NT), 0, st, nl, K.npk.off, K.npk.col, K.npk.w, A.sc, (const double *)(K.*in),
-                                           (const double *)(K.*src), pc[j], cb, K.*out, (const XCtrl *)K.ctrl, A.nsrank, K.QS, (const int *)K.steplist);
-                    else hipLaunchKernelGGL((k_xtb_nmulp<false, true>), dim3(nmb), dim3(XT_NT), 0, st, nl, K.npk.off, K.npk.col, K.npk.w, A.sc, (const double *)(K.*in),
-                                            (const double *)(K.*src), pc[j], cb, K.*out, (const XCtrl *)K.ctrl, (const int *)nullptr, (double *)nullptr, (const int *)K.steplist);
-                }); if (rc) return rc;
-            }
-            in = out;
-        }
-        if (qs && pd > 0)
-            for (int iv = 0; iv < nv; ++iv) {          // CSR form: QS from the panel (every S row; the other ranks' rows are overwritten by exchange 3)
-                SlabRank &K = RK[iv];
-                if (!K.npk.off) hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)(K.*dst), A.sc, A.nsrank, K.QS,
-                                                   (const XCtrl *)K.ctrl);
-            }
-        return 0;
+        return xtb_applyL(st, A, pd, pc, src, dst, &SlabRank::W1, &SlabRank::W2, qs, [&](int i, Pan in) { return (i > 0 || !src_halo) ? halo(in, on) : 0; },
+                          [&](bool nprod, auto f) -> int {
+                              for (int iv = 0; iv < nv; ++iv) {
+                                  SlabRank &K = RK[iv];
+                                  const XbNRank R{K.n_own + 2, K.steplist, K.npk.off ? &K.npk : nullptr, K.QS, K.ctrl};
+                                  auto at = [&K](Pan p) { return K.*p; };
+                                  if (!nprod) f(R, at);
+                                  else if (int rc = timed(iv, 8, on, [&]() { f(R, at); })) return rc;
+                              }
+                              return 0;
+                          });
     };
     // exchange 3: the own rows of QS to everybody + the halo of the panel the next product reads
     auto xchg3 = [&](Pan pv, bool on) -> int {
@@ -806,43 +757,20 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     } else if (int rcx = rows(true, -1, false, nullptr, nullptr)) return rcx;
     if (int rcx = update(-1, false)) return rcx;
     KCHK();
-    int it = 0, launched = 0, batch = 4;
-    // launch plan: the first batch covers three quarters of the previous solve's sweeps -- with the warm start the count moves by +-30 per cent from
-    // step to step (9.4e5 sites: 268 ... 505), and a batch sized to the previous count left up to a quarter of its launches as no-ops --, then batches of 8
-    if (e.x_iter_hint > 12 && !emu) batch = std::max(4, e.x_iter_hint * 3 / 4);
+    // the launch plan of xtb_cg_body; an emulation starts without the hint and leaves it unset
     XCtrl h{};
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, RK[0].ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (prof && launched) {
-            for (int bq = 0; bq < 8 && bq * XT_PROF_STRIDE < launched; ++bq) {
-                if (it - launched + bq * XT_PROF_STRIDE >= h.iters) break;
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * bq], evs[4 * bq + 1])); prof_long_ms += ms; ++prof_long_n;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * bq + 2], evs[4 * bq + 3])); prof_short_ms += ms; ++prof_short_n;
-            }
-        }
-        if (h.done) break;
-        if (emu && g_slab_sweep_cap > 0 && it >= g_slab_sweep_cap) break;
-        if (it >= 200000) { dkmc_fail(4, "block-CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int bq = 0; bq < batch; ++bq, ++it) {
-            const bool pb = prof && bq < 8 * XT_PROF_STRIDE && (bq % XT_PROF_STRIDE == 0);
-            const int sl = bq / XT_PROF_STRIDE;
+    if (int rcx = xtb_sweeps(RK[0].ctrl, h, !emu, emu ? g_slab_sweep_cap : 0, prof, !emu, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {
             const bool on = timing && it >= 2 && tphase < 24;            // sweeps 2 ... 25 of the emulation are timed, kernel by kernel
-            if (g_xtb_fault_iter >= 0 && !emu && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
             if (pd > 0) {
-                if (int rcx = sweep_pre(it, on, pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
+                if (int rcx = sweep_pre(it, on, ev[0], ev[1], ev[2], ev[3])) return rcx;
             } else {
-                if (int rcx = product(on, pb ? evs[4 * sl] : nullptr, pb ? evs[4 * sl + 1] : nullptr)) return rcx;
-                if (int rcx = rows(false, it, on, pb ? evs[4 * sl + 2] : nullptr, pb ? evs[4 * sl + 3] : nullptr)) return rcx;
+                if (int rcx = product(on, ev[0], ev[1])) return rcx;
+                if (int rcx = rows(false, it, on, ev[2], ev[3])) return rcx;
                 if (int rcx = update(it, on)) return rcx;
             }
             if (on) ++tphase;
-        }
-        launched = batch;
-        KCHK();
-        if (e.x_iter_hint > 12 && !emu) batch = 8; else if (batch < 64) batch *= 2;
-    }
+            return 0;
+        })) return rcx;
     if (local_fail) return local_fail;
     if (h.aborted) return dkmc_fail(46, "a peer rank aborted the sharded current solve", __FILE__, __LINE__);
     if (e.err_code) return e.err_code;
@@ -925,13 +853,6 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         again = rr_true > A.tol2;
     }
     HIPCHK(hipStreamSynchronize(st));
-    if (!emu) e.x_iter_hint = h.iters;
-    if (iters_out) *iters_out = h.iters;
-    if (rr_out) *rr_out = h.rr[h.iters & 1];
-    if (prof) {
-        e.stats.spmv_long_ms = prof_long_ms; e.stats.spmv_short_ms = prof_short_ms;
-        e.stats.spmv_long_launches = prof_long_n; e.stats.spmv_short_launches = prof_short_n;
-    }
     if (timing) {
         double sum[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; int nmul_n = 0;
         for (auto &pr : tsamples) { sum[pr.first] += pr.second; if (pr.first == 8) ++nmul_n; }
@@ -940,6 +861,5 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         TM.nmul_us = nmul_n ? sum[8] * 1e3 / nmul_n : 0.0;
         g_slab_last.nmul_us = TM.nmul_us;
     }
-    if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
-    return again ? DKMC_XTB_AGAIN : 0;
+    return xtb_finish(h, !emu, again, prof, pf, iters_out, rr_out);
 }
