@@ -133,6 +133,13 @@ struct KBlocked {
     int *perm;          // [m] row of the blocked order -> row of the pattern
     int *pcol;          // [total] columns in the blocked order, rows padded to 64 / 32 entries with the row itself, diagonal left out
     int4 *blk;          // [nb] {first column of the window, columns in the window, first int of the block in pcol, rows padded to 64}
+    // form 2: the windowed form above KB_MAXROWS rows (dkmc_set_k_blocked_large): pcol holds LDS offsets into the block's window, blk is
+    // {window doubles, LDS offset of the block's first row, first int of the block in pcol, rows padded to 64}, and the window is copied
+    // from the segments seg[KBW_MAXSEG * b ...] {LDS offset, length, first row in the blocked order, 0}
+    int form = 1;
+    int maxseg = 0;     // segments of the most fragmented window
+    long long segsum = 0;
+    int4 *seg = nullptr;
 };
 // ---- host side ---------------------------------------------------------------------------------
 struct Engine {
@@ -145,6 +152,7 @@ struct Engine {
     long long tcache_budget = -1;  // bytes the tunnelling-coefficient cache may take; -1 = a third of the free device memory, 8-128 GiB (dkmc_set_tcache_budget)
     double pair_cut = 6.5;         // screening cut-off of the pair sum in units of sigma sqrt 2 (dkmc_set_pair_cutoff; 0 = all pairs like the reference)
     int k_blocked = 1;             // build the blocked form of K patterns (dkmc_set_k_blocked; kcg.hip)
+    int k_blocked_large = 0;       // 1: above KB_MAXROWS rows build the windowed blocked form instead (dkmc_set_k_blocked_large; kcg.hip)
     int x_aux = 2;                 // auxiliary columns of the block-CG (dkmc_set_x_aux; xtb.hip): 0 hash set, 1 smooth set, 2 smooth at tolerances >= 1e-8
     int x_slab = 1;                // > 1 rank: distribute the STATE of the block-CG by row slabs (xtb_slab.inc; dkmc_set_x_slab); 0: all-gather variant (tile stream sharded only)
     int k_slab = 1;                // > 1 rank, system above the size of the blocked form: CG on K distributed by row slabs (kcg.hip; dkmc_set_k_slab); 0: replicated

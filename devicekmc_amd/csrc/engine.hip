@@ -68,6 +68,8 @@ void dkmc_set_x_aux(int mode) { eng().x_aux = mode < 0 ? 0 : (mode > 3 ? 2 : mod
 int dkmc_get_x_aux(void) { return eng().x_aux; }
 void dkmc_set_k_blocked(int on) { eng().k_blocked = on ? 1 : 0; }
 int dkmc_get_k_blocked(void) { return eng().k_blocked; }
+void dkmc_set_k_blocked_large(int on) { eng().k_blocked_large = on ? 1 : 0; }
+int dkmc_get_k_blocked_large(void) { return eng().k_blocked_large; }
 void dkmc_set_cb_edge_domain(int atoms_only) { eng().cb_edge_domain = atoms_only ? 1 : 0; }
 
 int dkmc_get_gpu_info(char *gpu_string, int capacity, int dev)

@@ -12,6 +12,7 @@
 // Bytes per iteration: 4 nnz + 4 (m + 1) + 15 vector touches of 8 m  (CSR formulation, SURVEY 8d: 12 nnz + 4 (m + 1) + 96 m).
 #include "common.h"
 #include "slab.h"
+#include "kbw_plan.h"
 #include <algorithm>
 #include <functional>
 #include <vector>
@@ -322,6 +323,151 @@ __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__
     }
 }
 
+// ---- the windowed blocked form of K (above KB_MAXROWS rows, opt-in: dkmc_set_k_blocked_large) --------------------------------------------
+// Above 2.6e5 rows one x-sorted window per block no longer fits the LDS: a block of x-sorted rows is a thin slice through the whole lateral
+// plane.  kbw_build (kbw_plan.h) orders the rows spatially instead -- lateral columns of one neighbour distance, walked in serpentine order,
+// rows of a column in x -- and cuts them into blocks of R rows whose window (every row the block reads) is a short list of contiguous
+// segments of that order (at most KBW_MAXSEG), copied one after the other into one LDS image; the stored columns are offsets into that image.
+// Same storage of the rows (no row pointers; > 32 entries first, padded to 64, the others to 32; padding = the row's own offset), same
+// pairwise row sums and fused partials as k_kb_apply; more blocks than CUs run as a grid, several workgroups per CU one after the other.
+// The iteration keeps the reference-order three launches (product, k_kc_update, k_kc_direction; see k_kc_update for why beta is summed directly).
+// LDS budget KB_MAXWIN doubles (112 KiB of the 160 KiB per CU): one 1024-thread workgroup per CU, 16 waves = 4 per SIMD.
+// k_kbw_apply<0>: 113 VGPR, 79 SGPR, no scratch (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; <1>: 107 VGPR): registers and LDS window
+// both allow 4 waves per SIMD, the occupancy it runs at (one workgroup of 16 waves per CU at a time).  tile:20 (3.64e6 rows, 1 143 blocks of
+// 3 189 rows, windows 3.4 x the rows, 7.2 segments per window): 173 us per launch against 304 us for k_kc_apply in the same run, 783 MB
+// per launch (4 B per stored entry, 36.8 per row with the padding; window copies; 5 vector touches) = 4.5 TB/s
+// (profiles/kcg_forms_tile20_product_launches.txt, kcg_forms_tile20_tile10.jsonl).
+__device__ __forceinline__ int kbw_row(const int4 *sg, int off)
+{
+    int g = 0;
+#pragma unroll
+    for (int s = 0; s < KBW_MAXSEG; ++s) { const int4 v = sg[s]; if (off >= v.x) g = v.z + (off - v.x); }      // (unused entries: x = INT_MAX)
+    return g;
+}
+// (R >= KC_NT / 16: the 16 rows of a workgroup lie in at most two blocks, whose segment tables it keeps in LDS)
+template <int CB>
+__global__ __launch_bounds__(KC_NT) void k_kbw_assemble(int m, int N_left, int R, int nb, const int4 *__restrict__ blk, const int4 *__restrict__ seg,
+                                                        const int *__restrict__ perm, const int *__restrict__ pcol, const int *__restrict__ element,
+                                                        const int *__restrict__ charge, MetalSet ms, double high_G, double low_G,
+                                                        const int *__restrict__ lrp, const int *__restrict__ lci,
+                                                        const int *__restrict__ rrp, const int *__restrict__ rci,
+                                                        double VL, double VR, int *__restrict__ cf, double *__restrict__ diag, double *__restrict__ rhs)
+{
+    const int LPR = 16;
+    __shared__ int4 ssg[2][KBW_MAXSEG];
+    const int g = threadIdx.x / LPR, l = threadIdx.x % LPR;
+    const int rb = blockIdx.x * (KC_NT / LPR) + g;           // row in the blocked order
+    const int bb0 = blockIdx.x * (KC_NT / LPR) / R;
+    if (threadIdx.x < 2 * KBW_MAXSEG && bb0 + (int)threadIdx.x / KBW_MAXSEG < nb)
+        ssg[threadIdx.x / KBW_MAXSEG][threadIdx.x % KBW_MAXSEG] = seg[(size_t)bb0 * KBW_MAXSEG + threadIdx.x];
+    __syncthreads();
+    if (rb >= m) return;
+    const int bb = rb / R;
+    const int4 bi = blk[bb];
+    const int4 *sg = ssg[bb - bb0];
+    int width;
+    const int base = kb_row_base(bi, rb - bb * R, &width);
+    const int self = bi.y + (rb - bb * R);                   // the row's own offset in the window
+    const int r = perm[rb], i = N_left + r;
+    const int ei = element[i], qi = charge[i];
+    double off = 0.0, kl = 0.0, kr = 0.0;
+    for (int k = l; k < width; k += LPR) {
+        const int c = pcol[base + k];
+        if (c == self) { cf[base + k] = self; continue; }    // padding
+        const int j = N_left + perm[kbw_row(sg, c)];
+        const int ej = element[j];
+        if (CB == 2 && (k_interstitial(ei) || k_interstitial(ej))) { cf[base + k] = self; continue; }      // no link: stored like padding
+        const bool hi = k_high<CB>(ei, ej, qi, charge[j], ms);
+        cf[base + k] = hi ? (c | (int)0x80000000) : c;
+        off += hi ? high_G : low_G;
+    }
+    const bool cut = CB == 2 && k_interstitial(ei);
+    for (int p = lrp[r] + l; p < lrp[r + 1] && !cut; p += LPR) { const int j = lci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kl += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
+    for (int p = rrp[r] + l; p < rrp[r + 1] && !cut; p += LPR) { const int j = N_left + m + rci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kr += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
+    { off = group_sum<LPR>(off); kl = group_sum<LPR>(kl); kr = group_sum<LPR>(kr); }
+    if (l == 0) {
+        double d = off;
+        d += kl;
+        d += kr;
+        if (CB == 2 && d == 0.0) d = 1.0;
+        diag[rb] = d;
+        rhs[rb] = kl * VL + kr * VR;
+    }
+}
+template <int MODE>
+__global__ __launch_bounds__(KB_NT) void k_kbw_apply(int m, int R, const int4 *__restrict__ blk, const int4 *__restrict__ seg, const int *__restrict__ cf,
+                                                     const double *__restrict__ diag, const double *__restrict__ s, const double *__restrict__ q,
+                                                     double high_G, double low_G, const double *__restrict__ pv, double *__restrict__ t,
+                                                     double *__restrict__ part, const KCtrl *ctrl, const double *__restrict__ b,
+                                                     double *__restrict__ r, double *__restrict__ p)
+{
+    extern __shared__ double win[];
+    __shared__ double red[3][KB_NT / 64];
+    if (MODE == 0 && ctrl->done) return;                    // (a launch after the stop test: one scalar load, not a window copy)
+    const int4 bi = blk[blockIdx.x];
+    const int wn = bi.x, self0 = bi.y;
+    const int r0 = blockIdx.x * R, nrows = min(R, m - r0);
+    const int g = threadIdx.x >> 2, l = threadIdx.x & 3;
+    // the segments of the window, copied into one LDS image: every load is issued before anything is waited for
+    const int4 *sg = seg + (size_t)blockIdx.x * KBW_MAXSEG;
+    int slo[KBW_MAXSEG], sbase[KBW_MAXSEG];
+#pragma unroll
+    for (int j = 0; j < KBW_MAXSEG; ++j) { const int4 v = sg[j]; slo[j] = v.x; sbase[j] = v.z - v.x; }
+    double wv[KB_WREG];
+#pragma unroll
+    for (int j = 0; j < KB_WREG; ++j) {
+        const int idx = threadIdx.x + j * KB_NT;
+        int gb = 0;
+#pragma unroll
+        for (int u = 0; u < KBW_MAXSEG; ++u) gb = idx >= slo[u] ? sbase[u] : gb;
+        wv[j] = idx < wn ? q[gb + idx] : 0.0;
+    }
+    int4 cc[4];
+    bool lg;
+    int k = g;
+    kb_load_row(cf, bi, k, l, k < nrows, cc, &lg);
+#pragma unroll
+    for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; if (idx < wn) win[idx] = wv[j]; }
+    __syncthreads();
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (; k < nrows; k += KB_NT / 4) {
+        const int row = r0 + k, self = self0 + k;
+        const double qr = win[self], dg = diag[row], sv = s[row];
+        const double a1 = MODE == 0 ? pv[row] : b[row], a2 = MODE == 0 ? r[row] : 0.0;
+        int c[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[4 * j] = cc[j].x; c[4 * j + 1] = cc[j].y; c[4 * j + 2] = cc[j].z; c[4 * j + 3] = cc[j].w; }
+        const bool lgc = lg;
+        double x[16];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = win[c[u] & 0x7fffffff];
+        if (lgc) {
+#pragma unroll
+            for (int u = 8; u < 16; ++u) x[u] = win[c[u] & 0x7fffffff];
+        }
+        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cc, &lg);      // next pass
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
+        double sum = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
+        if (lgc) {
+#pragma unroll
+            for (int u = 8; u < 16; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
+            sum += ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
+        }
+        sum = group_sum<4>(sum);
+        if (l == 0) {
+            const double tv = sv * (dg * qr - sum);
+            if (MODE == 0) { t[row] = tv; acc[0] += a1 * tv; acc[1] += a2 * tv; acc[2] += tv * tv; }
+            else { const double rv = -a1 + tv; r[row] = rv; p[row] = -rv; acc[0] += rv * rv; }
+        }
+    }
+    block_sum_n<KB_NT, 3>(acc, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = acc[0];
+        if (MODE == 0) { part[KC_NPA + blockIdx.x] = acc[1]; part[2 * KC_NPA + blockIdx.x] = acc[2]; }
+    }
+}
+
 __global__ __launch_bounds__(KC_NT) void k_kc_check0(double *part, KCtrl *ctrl, double tol2)
 {
     __shared__ double red[KC_NT / 64];
@@ -516,7 +662,49 @@ void kblocked_free(KBlocked *kb)
     if (kb->perm) (void)hipFree(kb->perm);
     if (kb->pcol) (void)hipFree(kb->pcol);
     if (kb->blk) (void)hipFree(kb->blk);
+    if (kb->seg) (void)hipFree(kb->seg);
     delete kb;
+}
+
+// Builds the windowed blocked form of a K pattern above KB_MAXROWS rows (kbw_plan.h; host side, once per pattern; nullptr when a row has more
+// than 64 off-diagonal entries or no block size gives windows within KB_MAXWIN doubles and g_kbw_segcap segments: the solve then uses the CSR
+// positions).  x, y, z: device pointers to the coordinates of the pattern's rows.
+static int g_kbw_segcap = KBW_MAXSEG;       // dkmc_debug_kbw_segment_cap (test aid)
+extern "C" void dkmc_debug_kbw_segment_cap(int cap) { g_kbw_segcap = (cap < 1 || cap > KBW_MAXSEG) ? KBW_MAXSEG : cap; }
+static KBlocked *kbw_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st)
+{
+    std::vector<int> rp(m + 1), ci(nnz);
+    std::vector<double> x(m), y(m), z(m);
+    if (hipMemcpyAsync(rp.data(), rp_d, (size_t)(m + 1) * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
+    if (hipMemcpyAsync(ci.data(), ci_d, (size_t)nnz * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
+    if (hipMemcpyAsync(x.data(), x_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
+    if (hipMemcpyAsync(y.data(), y_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
+    if (hipMemcpyAsync(z.data(), z_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
+    if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
+    KbwPlan P;
+    if (kbw_plan(m, rp.data(), ci.data(), x.data(), y.data(), z.data(), ncu, KB_MAXWIN, g_kbw_segcap, KC_NPA, P) || P.R < KC_NT / 16) return nullptr;
+    KBlocked *kb = new KBlocked{m, P.R, P.nb, P.total, P.maxwin, P.maxints, P.winsum, nullptr, nullptr, nullptr};
+    kb->form = 2; kb->maxseg = P.maxseg; kb->segsum = P.segsum;
+    static_assert(sizeof(KbwI4) == sizeof(int4), "segment table layout");
+    bool ok = hipMalloc((void **)&kb->perm, (size_t)m * 4) == hipSuccess && hipMalloc((void **)&kb->pcol, (size_t)P.total * 4) == hipSuccess &&
+              hipMalloc((void **)&kb->blk, (size_t)P.nb * sizeof(int4)) == hipSuccess &&
+              hipMalloc((void **)&kb->seg, (size_t)P.nb * KBW_MAXSEG * sizeof(int4)) == hipSuccess;
+    ok = ok && hipMemcpy(kb->perm, P.perm.data(), (size_t)m * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(kb->pcol, P.pcol.data(), (size_t)P.total * 4, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(kb->blk, P.blk.data(), (size_t)P.nb * sizeof(int4), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(kb->seg, P.seg.data(), (size_t)P.nb * KBW_MAXSEG * sizeof(int4), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { kblocked_free(kb); (void)hipGetLastError(); return nullptr; }
+    return kb;
+}
+// The form initialize_sparsity keeps for a K pattern: the windowed form above KB_MAXROWS rows when dkmc_set_k_blocked_large(1), else the
+// blocked form (nullptr above KB_MAXROWS).
+KBlocked *kpattern_form_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st)
+{
+    const Engine &e = eng();
+    if (e.k_blocked && e.k_blocked_large && m > KB_MAXROWS && nnz >= 1) return kbw_build(rp_d, ci_d, m, nnz, x_d, y_d, z_d, st);
+    return kblocked_build(rp_d, ci_d, m, nnz, x_d, st);
 }
 
 // Assemble K for the current elements / charges and solve K y = rhs in place in y (warm start = y on entry).
@@ -533,6 +721,9 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     Engine &e = eng(); hipStream_t st = e.stream;
     if (m <= 0) { if (iters_out) *iters_out = 0; if (rr_out) *rr_out = 0; return 0; }
     if (kb && kb->m != m) return dkmc_fail(6, "K-CG: the blocked form belongs to another pattern", __FILE__, __LINE__);
+    // the windowed form runs on one GPU only: more than one rank (or the emulation of it) keeps the slab-distributed loop on the CSR positions
+    if (kb && kb->form == 2 && row_y && row_z && (emu_nr > 0 || (e.k_slab && comm_attached() && comm_nranks() > 1 && comm_nranks() <= XS_MAXR))) kb = nullptr;
+    const bool kbw = kb && kb->form == 2;
     int *cf = (int *)scratch(S_K_DATA, kb ? (size_t)kb->total * 4 : (size_t)nnz * 4);
     double *rhs = (double *)scratch(S_K_RHS, (size_t)m * 8 * 3);
     double *s = (double *)scratch(S_CG_S, (size_t)m * 8), *r = (double *)scratch(S_CG_R, (size_t)m * 8);
@@ -545,7 +736,19 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const double tol2 = e.cg_tol * e.cg_tol;
     const int ab = (m + 15) / 16, vb = (m + 255) / 256;
     const size_t lds = kb ? (size_t)kb->maxwin * 8 : 0;
-    if (kb) {
+    if (kbw) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            HIPCHK(hipFuncSetAttribute((const void *)k_kbw_apply<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
+            HIPCHK(hipFuncSetAttribute((const void *)k_kbw_apply<1>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
+            attr_set = true;
+        }
+#define KBW_ASM(CBV) hipLaunchKernelGGL((k_kbw_assemble<CBV>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm, \
+                                        (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs)
+        if (cb == 2) KBW_ASM(2); else if (cb) KBW_ASM(1); else KBW_ASM(0);
+#undef KBW_ASM
+        hipLaunchKernelGGL(k_kb_scale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)diag, s, rhs, (const double *)y_site, y, q);
+    } else if (kb) {
         static bool attr_set = false;
         if (!attr_set) {
             HIPCHK(hipFuncSetAttribute((const void *)k_kb_apply<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
@@ -571,7 +774,8 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const int npa = (ga + KC_NT - 1) / KC_NT * KC_NT;
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(KCtrl), st));
     HIPCHK(hipMemsetAsync(part, 0, (size_t)KC_PART_DOUBLES * 8, st));       // the slots beyond either grid stay zero
-#define KC_APPLY(MODE, ...) do { if (kb) hipLaunchKernelGGL((k_kb_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, __VA_ARGS__); \
+#define KC_APPLY(MODE, ...) do { if (kbw) hipLaunchKernelGGL((k_kbw_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
+                                 else if (kb) hipLaunchKernelGGL((k_kb_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, __VA_ARGS__); \
                                  else hipLaunchKernelGGL((k_kc_apply<MODE>), dim3(ga), dim3(KC_NT), 0, st, m, rp, __VA_ARGS__); } while (0)
     // more than one rank (or the emulation of it) on a system above the size of the blocked form: the loop distributed by row slabs
     const bool slab = !kb && row_y && row_z && (emu_nr > 0 || (e.k_slab && comm_attached() && comm_nranks() > 1 && comm_nranks() <= XS_MAXR));
@@ -603,7 +807,7 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
         for (int b = 0; b < batch; ++b, ++it) {
             KC_APPLY(0, (const int *)cf, (const double *)diag, (const double *)s, (const double *)q, high_G, low_G,
                      (const double *)p, t, part, (const KCtrl *)ctrl, (const double *)nullptr, r, (double *)nullptr);
-            if (kb) hipLaunchKernelGGL(k_kc_step, dim3(gv), dim3(KC_NT), 0, st, m, it, part, p, (const double *)t, y, r, (const double *)s, q, ctrl, tol2, npa);
+            if (kb && !kbw) hipLaunchKernelGGL(k_kc_step, dim3(gv), dim3(KC_NT), 0, st, m, it, part, p, (const double *)t, y, r, (const double *)s, q, ctrl, tol2, npa);
             else {
                 hipLaunchKernelGGL(k_kc_update, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)part, npa, (const double *)p, (const double *)t, y, r, part + 3 * KC_NPA, (const KCtrl *)ctrl);
                 hipLaunchKernelGGL(k_kc_direction, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)(part + 3 * KC_NPA), (const double *)r, p, (const double *)s, q, ctrl, tol2);
@@ -622,10 +826,11 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     if (kb) hipLaunchKernelGGL(k_kb_unscale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)y, (const double *)s, y_site);
     else hipLaunchKernelGGL(k_kc_unscale, dim3(vb), dim3(256), 0, st, m, y, (const double *)s);
     KCHK();
-    e.stats.kcg_blocked = kb ? 1 : 0;
-    e.stats.kcg_bytes = kb ? 4LL * kb->total + 16LL * kb->nb + 8LL * kb->winsum + 14LL * 8 * m : 4LL * nnz + 4LL * (m + 1) + 17LL * 8 * m;
+    e.stats.kcg_blocked = kb ? kb->form : 0;
+    if (kbw) e.stats.kcg_bytes = 4LL * kb->total + 16LL * kb->nb * (1 + KBW_MAXSEG) + 8LL * kb->winsum + 16LL * 8 * m;       // (product 5 + update 6 + direction 5 vector touches)
+    else e.stats.kcg_bytes = kb ? 4LL * kb->total + 16LL * kb->nb + 8LL * kb->winsum + 14LL * 8 * m : 4LL * nnz + 4LL * (m + 1) + 17LL * 8 * m;
     if (iters_out) *iters_out = h.iters;
-    if (rr_out) *rr_out = kb ? h.rr[0] : h.rr[h.iters & 1];
+    if (rr_out) *rr_out = kb && !kbw ? h.rr[0] : h.rr[h.iters & 1];
     return e.err_code;
 }
 

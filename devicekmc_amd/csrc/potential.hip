@@ -12,7 +12,7 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
                            const double *row_y, const double *row_z, int emu_nr, int emu_time_rank);
 void kcg_slab_report(double *times_us, long long *halo_rows);
 void kcg_slab_iter_cap(int cap);
-KBlocked *kblocked_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, hipStream_t st);
+KBlocked *kpattern_form_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st);
 void kblocked_free(KBlocked *kb);
 void tcache_invalidate(const void *key);
 void xstate_reset(const void *key);
@@ -168,7 +168,21 @@ extern "C" int dkmc_initialize_sparsity(dkmc_gpubuf *buf, int pbc, double nn_dis
                        buf->Device_col_indices_d, buf->contact_left_col_indices, buf->contact_right_col_indices);
     KCHK();
     HIPCHK(hipStreamSynchronize(st));
-    kpat_register(buf->Device_row_ptr_d, m, N_left, kblocked_build(buf->Device_row_ptr_d, buf->Device_col_indices_d, m, h_tot[0], buf->site_x + N_left, st));
+    kpat_register(buf->Device_row_ptr_d, m, N_left, kpattern_form_build(buf->Device_row_ptr_d, buf->Device_col_indices_d, m, h_tot[0], buf->site_x + N_left,
+                                                                         buf->site_y + N_left, buf->site_z + N_left, st));
+    return 0;
+}
+
+// measurement aid: the form the K solve of this buffer's pattern runs on and its window statistics (dkmc_kcg_form_info, devicekmc_hip_debug.h)
+extern "C" int dkmc_kcg_form_info(dkmc_gpubuf *buf, long long *info)
+{
+    if (!buf || !info) return dkmc_fail(13, "kcg_form_info: bad arguments", __FILE__, __LINE__);
+    for (int k = 0; k < 9; ++k) info[k] = 0;
+    const KBlocked *kb = buf->Device_row_ptr_d ? kpat_blocked(buf->Device_row_ptr_d) : nullptr;
+    if (kb) {
+        const long long v[9] = {kb->form, kb->m, kb->R, kb->nb, kb->maxwin, kb->winsum, kb->form == 2 ? kb->maxseg : 1, kb->form == 2 ? kb->segsum : kb->nb, kb->total};
+        for (int k = 0; k < 9; ++k) info[k] = v[k];
+    }
     return 0;
 }
 

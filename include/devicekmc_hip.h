@@ -93,7 +93,8 @@ typedef struct dkmc_stats {
     /* profiling on: HIP-event time of the whole iteration loop of the last CG solve on K (and the iterations it covers), and
      * of the last pair-sum kernel */
     double kcg_ms;
-    int kcg_iters_timed, kcg_blocked;      /* kcg_blocked: 1 if the last K solve ran on the blocked form of the pattern (dkmc_set_k_blocked) */
+    int kcg_iters_timed, kcg_blocked;      /* kcg_blocked: 1 if the last K solve ran on the blocked form of the pattern (dkmc_set_k_blocked),
+                                            * 2 if it ran on the windowed blocked form above 262 144 rows (dkmc_set_k_blocked_large), 0 on the CSR positions */
     double pair_ms;
     long long pair_evaluated;              /* (site, charged site) pairs inside the screening cut-off of the last pair sum (profiling on) */
     long long pair_tested;                 /* pairs whose distance was tested (all N x N_charged without the cell list; the 3 x 3 columns with it) */
@@ -199,6 +200,14 @@ int dkmc_get_x_aux_warm(void);
  * 0: the solve uses the CSR positions of the pattern (the only form above that size).  Read when a pattern is built. */
 void dkmc_set_k_blocked(int on);
 int dkmc_get_k_blocked(void);
+/* 0 (default): above 262 144 device rows the CG on K runs on the CSR positions of the pattern.  1: initialize_sparsity builds the WINDOWED blocked
+ * form for such patterns instead (csrc/kcg.hip, kbw_plan.h): rows in an internal spatial order (lateral columns of one neighbour distance in
+ * serpentine order, x within a column), blocks of rows whose window of the direction vector -- a few contiguous segments of that order -- is
+ * copied into LDS, and the K solve of the pattern runs there on one GPU (dkmc_stats.kcg_blocked = 2); nullptr-safe: a pattern whose windows do
+ * not fit falls back to the CSR positions.  Takes effect with dkmc_set_k_blocked(1) (the default); systems up to 262 144 rows keep the blocked
+ * form whatever this says, and the slab-distributed K loop (more than one rank attached) stays on the CSR positions.  Read when a pattern is built. */
+void dkmc_set_k_blocked_large(int on);
+int dkmc_get_k_blocked_large(void);
 /* Start vector of the current solve.  1 (default): the previous step's solution, from a private unscaled copy kept per GPUBuffers -- what
  * the reference's own comment asks for ("use the previous solution as the initial guess", current_solver_gpu.cu:976-977).  0: whatever
  * gpubuf.atom_virtual_potentials holds, exactly as the reference code does -- and that buffer was scaled by G0 in place after the previous

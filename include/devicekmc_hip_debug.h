@@ -74,6 +74,14 @@ int dkmc_xtb_slab_last(int *exchanges_per_sweep, long long *halo_doubles_per_exc
 int dkmc_kcg_emulate_slabs(dkmc_gpubuf *buf, int N, int N_left, int N_right, double Vd, double high_G, double low_G, int num_metals, int nranks, int time_rank,
                            int iter_cap, double *max_abs_diff, int *iters_slab, int *iters_ref, double *times_us, long long *halo_rows);
 
+/* Measurement aid: the form the K solve of this buffer's pattern runs on (built by initialize_sparsity) and its window statistics.  info[9]: form
+ * (0 CSR positions, 1 blocked, 2 windowed blocked), rows, rows per block, blocks, doubles of the largest window, doubles of all windows, segments of
+ * the most fragmented window, segments of all windows, stored column ints. */
+int dkmc_kcg_form_info(dkmc_gpubuf *buf, long long *info /* [9] */);
+/* Test aid: caps the segments of a window of the windowed blocked form of K (dkmc_set_k_blocked_large) below its fixed maximum (16) for the
+ * patterns built afterwards, so that the builder refuses and the solve falls back to the CSR positions.  cap <= 0 restores 16. */
+void dkmc_debug_kbw_segment_cap(int cap);
+
 #ifdef __cplusplus
 }
 #endif
