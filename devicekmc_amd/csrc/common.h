@@ -205,8 +205,12 @@ enum {
     S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z,
     S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,
+    // test aids of the preconditioner (xtb.hip: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
+    S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,
+    S_XTB_TEST_W1, S_XTB_TEST_W2, S_XTB_TEST_QS, S_XTB_TEST_CTRL, S_XTB_TEST_NPCNT, S_XTB_TEST_NPOFF, S_XTB_TEST_NPCOL, S_XTB_TEST_NPW,
     S_NSLOTS
 };
+static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");
 
 // exchange step of the sharded current solve (comm.hip)
 int comm_attached();

@@ -1917,6 +1917,129 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     return e.err_code;
 }
 
+// ---- test aids of the split polynomial preconditioner (tests/test_precond_coeffs.py, tests/test_gpu_precond_reference.py) -------------------
+// The production path (xtb_npack, xtb_nstep, xtb_applyL) on buffers of their own (S_XTB_TEST_*): nothing a solve reads or keeps is touched.
+// coefficients pc[0 ... degree] of L = p(N); host code only (no HIP call)
+extern "C" int dkmc_xtb_poly_coeffs(int degree, double *pc)
+{
+    if (degree < 1 || degree > XB_MAXPOLY || !pc) return dkmc_fail(13, "xtb_poly_coeffs: degree outside 1 ... 16", __FILE__, __LINE__);
+    xtb_poly_coeffs(degree, pc);
+    return 0;
+}
+// QS (interleaved, xtb_qs_pos) -> [ns][16]
+__global__ void k_xtb_test_qs_decode(int ns, const double *__restrict__ QS, double *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ns * XB_SP) out[i] = QS[xtb_qs_pos(i >> 4, i & 15)];
+}
+// the packed N of a test aid in its own slots (xtb_npack's alloc)
+static void *xtb_test_alloc(int slot, size_t bytes)
+{
+    return scratch(slot == S_XTB_NPACK_CNT ? S_XTB_TEST_NPCNT : slot == S_XTB_NPACK_OFF ? S_XTB_TEST_NPOFF : slot == S_XTB_NPACK_COL ? S_XTB_TEST_NPCOL : S_XTB_TEST_NPW, bytes);
+}
+// QS of the test aids zeroed, then decoded into qs [ns][16] after the step(s)
+static int xtb_test_qs_out(hipStream_t st, int ns, const double *QS, double *qs)
+{
+    double *dq = (double *)scratch(S_XTB_TEST_ADD, (size_t)ns * XB_SP * 8);      // (the add panel of a step is spent by now)
+    if (!dq) return eng().err_code;
+    hipLaunchKernelGGL(k_xtb_test_qs_decode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, QS, dq);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+// One Horner step out = ca add + cb (N in) over a caller-given CSR (m rows, rp[m] entries) and [m][16] panels: form 1 packs N (xtb_npack) first, form 0
+// runs on the CSR; rowlist (nlist rows): the LIST instantiations; nsrank (ns S rows): QS of out as well -- packed: from the step's registers, CSR:
+// k_xtb_qs_from over all m rows, as xtb_applyL takes it on its last step.  out is read before the step and written back after it.
+extern "C" int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
+                                   double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || !rp || !sc || !in || !add || !out || (form != 0 && form != 1)) return dkmc_fail(13, "xtb_test_nstep: bad arguments", __FILE__, __LINE__);
+    const long long nnz = rp[m];
+    if (rp[0] != 0 || nnz < 0 || nnz > 0x7fffffffll || (nnz > 0 && (!ci || !val))) return dkmc_fail(13, "xtb_test_nstep: bad row pointers", __FILE__, __LINE__);
+    for (int i = 0; i < m; ++i) if (rp[i + 1] < rp[i]) return dkmc_fail(13, "xtb_test_nstep: bad row pointers", __FILE__, __LINE__);
+    for (long long p = 0; p < nnz; ++p) if (ci[p] < 0 || ci[p] >= m) return dkmc_fail(13, "xtb_test_nstep: column outside the rows", __FILE__, __LINE__);
+    if (rowlist) {
+        if (nlist < 1 || nlist > m) return dkmc_fail(13, "xtb_test_nstep: bad row list", __FILE__, __LINE__);
+        for (int i = 0; i < nlist; ++i) if (rowlist[i] < 0 || rowlist[i] >= m) return dkmc_fail(13, "xtb_test_nstep: bad row list", __FILE__, __LINE__);
+    }
+    if (nsrank) {
+        if (ns < 1 || !qs) return dkmc_fail(13, "xtb_test_nstep: bad S ranks", __FILE__, __LINE__);
+        for (int i = 0; i < m; ++i) if (nsrank[i] < -1 || nsrank[i] >= ns) return dkmc_fail(13, "xtb_test_nstep: bad S ranks", __FILE__, __LINE__);
+    }
+    const size_t pan = (size_t)m * XB_SP * 8;
+    xrp_t *drp = (xrp_t *)scratch(S_XTB_TEST_RP, (size_t)(m + 1) * sizeof(xrp_t));
+    int *dci = (int *)scratch(S_XTB_TEST_CI, (size_t)nnz * 4);
+    double *dval = (double *)scratch(S_XTB_TEST_VAL, (size_t)nnz * 8), *dsc = (double *)scratch(S_XTB_TEST_SC, (size_t)m * 8);
+    double *din = (double *)scratch(S_XTB_TEST_IN, pan), *dadd = (double *)scratch(S_XTB_TEST_ADD, pan), *dout = (double *)scratch(S_XTB_TEST_OUT, pan);
+    int *dns = nsrank ? (int *)scratch(S_XTB_TEST_NSR, (size_t)m * 4) : nullptr;
+    int *dlist = rowlist ? (int *)scratch(S_XTB_TEST_LIST, (size_t)nlist * 4) : nullptr;
+    double *QS = nsrank ? (double *)scratch(S_XTB_TEST_QS, (size_t)(ns + 2) * XB_SP * 8) : nullptr;
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_TEST_CTRL, sizeof(XCtrl));
+    if (!drp || !dci || !dval || !dsc || !din || !dadd || !dout || (nsrank && (!dns || !QS)) || (rowlist && !dlist) || !ctrl) return e.err_code;
+    HIPCHK(hipMemcpyAsync(drp, rp, (size_t)(m + 1) * sizeof(xrp_t), hipMemcpyHostToDevice, st));
+    if (nnz > 0) {
+        HIPCHK(hipMemcpyAsync(dci, ci, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dval, val, (size_t)nnz * 8, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemcpyAsync(dsc, sc, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(din, in, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dadd, add, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dout, out, pan, hipMemcpyHostToDevice, st));
+    if (dns) HIPCHK(hipMemcpyAsync(dns, nsrank, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    if (dlist) HIPCHK(hipMemcpyAsync(dlist, rowlist, (size_t)nlist * 4, hipMemcpyHostToDevice, st));
+    if (QS) HIPCHK(hipMemsetAsync(QS, 0, (size_t)(ns + 2) * XB_SP * 8, st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
+    XtbArgs A{};
+    A.m = m; A.ns = ns; A.rp = drp; A.ci = dci; A.val = dval; A.sc = dsc; A.nsrank = dns;
+    const int n = rowlist ? nlist : m;
+    XbNPack npk{};
+    if (form == 1) { if (int rc = xtb_npack(A, n, (const int *)dlist, xtb_test_alloc, 0, &npk)) return rc; }
+    const XbNRank R{n, dlist, form == 1 ? &npk : nullptr, QS, ctrl};
+    (rowlist ? xtb_nstep<true> : xtb_nstep<false>)(st, A, R, din, dadd, ca, cb, dout, nsrank != nullptr);
+    if (nsrank && form == 0)
+        hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan / 8 + 255) / 256)), dim3(256), 0, st, m, (const double *)dout, (const double *)dsc, (const int *)dns, QS, (const XCtrl *)ctrl);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(out, dout, pan, hipMemcpyDeviceToHost, st));
+    if (nsrank) { if (int rc = xtb_test_qs_out(st, ns, QS, qs)) return rc; }
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+// L in (xtb_applyL with QS, as product_pre calls it) on the X left resident by the last single-GPU solve, with that solve's sc, Xs and S ranks:
+// in / out [m][16] (m = rows of X), qs [ns][16].  Neither the warm start nor the iteration hint of the next solve is touched.
+extern "C" int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs)
+{
+    Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0) return dkmc_fail(13, "xtb_check_poly: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    if (degree < 1 || degree > XB_MAXPOLY || (form != 0 && form != 1) || !in || !out || !qs) return dkmc_fail(13, "xtb_check_poly: bad arguments", __FILE__, __LINE__);
+    const int m = X.Nsub;
+    const size_t pan = (size_t)m * XB_SP * 8;
+    double *sc = (double *)e.buf[S_CG_S];
+    double *din = (double *)scratch(S_XTB_TEST_IN, pan), *dout = (double *)scratch(S_XTB_TEST_OUT, pan);
+    double *W1 = (double *)scratch(S_XTB_TEST_W1, pan), *W2 = (double *)scratch(S_XTB_TEST_W2, pan);
+    double *QS = (double *)scratch(S_XTB_TEST_QS, (size_t)X.ns_pad * XB_SP * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_TEST_CTRL, sizeof(XCtrl));
+    if (!din || !dout || !W1 || !W2 || !QS || !ctrl) return e.err_code;
+    if (!sc || !g_xb.rp || !g_xb.ci || !g_xb.val || !g_xb.nsrank) return dkmc_fail(13, "xtb_check_poly: no solver state", __FILE__, __LINE__);
+    HIPCHK(hipMemcpyAsync(din, in, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(QS, 0, (size_t)X.ns_pad * XB_SP * 8, st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
+    XtbArgs A{};
+    A.m = m; A.ns = X.ns; A.ns_pad = X.ns_pad; A.rp = g_xb.rp; A.ci = g_xb.ci; A.val = g_xb.val; A.sc = sc; A.nsrank = g_xb.nsrank;
+    XbNPack npk{};
+    if (form == 1) { if (int rc = xtb_npack(A, m, nullptr, xtb_test_alloc, 0, &npk)) return rc; }
+    const XbNRank nk{m, nullptr, form == 1 ? &npk : nullptr, QS, ctrl};
+    double pc[XB_MAXPOLY + 1] = {1.0};
+    xtb_poly_coeffs(degree, pc);
+    if (int rc = xtb_applyL(st, A, degree, pc, din, dout, W1, W2, true, [](int, double *) { return 0; },
+                            [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; })) return rc;
+    KCHK();
+    HIPCHK(hipMemcpyAsync(out, dout, pan, hipMemcpyDeviceToHost, st));
+    if (int rc = xtb_test_qs_out(st, X.ns, QS, qs)) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+
 // ---- measurement aid (bench.py / tools; no counterpart in the reference) ------------------------------------------------------------------
 // Average duration of the tile x panel kernel over the X left resident by the last single-GPU solve, `reps` launches back to back.
 // variant 0: the kernel as a solve runs it; 1: without its matrix instructions; 2: without re-reading the tile stream (see k_xtb_apply).

@@ -129,6 +129,9 @@ SYMBOLS = {
     "dkmc_xt_check_shares": (_I, [_I, c_dbl_p, c_dbl_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_int_p]),
     "dkmc_xtb_check_product": (_I, [_I, c_dbl_p, c_dbl_p]),
     "dkmc_xtb_time_apply": (_I, [_I, _I, _I, c_dbl_p]),
+    "dkmc_xtb_poly_coeffs": (_I, [_I, c_dbl_p]),
+    "dkmc_xtb_test_nstep": (_I, [_I, vp, vp, vp, vp, vp, vp, _D, _D, _I, vp, _I, vp, _I, vp, vp]),
+    "dkmc_xtb_check_poly": (_I, [_I, _I, vp, vp, vp]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),
     "dkmc_xtb_emulate_slabs": (_I, [_I, _I, _D, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong), c_int_p]),
     "dkmc_xtb_slab_last": (_I, [c_int_p, C.POINTER(C.c_longlong), c_dbl_p]),

@@ -24,6 +24,19 @@ int dkmc_xt_check_shares(int nranks, double *max_abs_diff, double *max_abs, long
 /* Test aid: on the X left resident by the last single-GPU solve, the MFMA tile x panel product of the block-CG (16 test vectors, one
  * sweep) against 16 passes of the single-vector tile kernel; largest absolute deviation and largest sum over the S rows. */
 int dkmc_xtb_check_product(int width, double *max_abs_diff, double *max_abs);
+/* Test aids of the split polynomial preconditioner L = p(N) of the block-CG (dkmc_set_x_poly).
+ * dkmc_xtb_poly_coeffs: its coefficients pc[0 ... degree] (monomial basis, Horner order of the solve); host code only, no GPU needed.  degree: 1 ... 16.
+ * dkmc_xtb_test_nstep: ONE Horner step out = ca add + cb (N in) of the production kernels over a caller-given CSR (m rows, rp[m] entries, columns in
+ * [0, m)) and host panels in / add / out of [m][16]: out_r = ca add_r - cb sc_r sum val sc_c in_c over the entries with c >= 2 and c != r; rows 0 / 1
+ * take ca add.  form 1: N packed first (the default form of a solve), 0: the CSR form.  rowlist (nlist rows, may be null): the row-list variants of
+ * the slab-distributed loop -- only those rows are written.  nsrank (may be null; ranks -1 ... ns - 1): QS of out as well, returned as qs [ns][16] =
+ * sc_r out_r at the rows of rank >= 0 (0 where nothing was written).  out is read before the step and written back after it.
+ * dkmc_xtb_check_poly: L in (the full Horner sequence with QS, as a sweep applies it) on the X left resident by the last single-GPU solve, with that
+ * solve's scaling, neighbour part and S ranks: in / out [m][16], m = rows of X; qs [ns][16].  Leaves the next solve's start and launch batch alone. */
+int dkmc_xtb_poly_coeffs(int degree, double *pc);
+int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
+                        double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs);
+int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs);
 /* Measurement aid: average duration [us] of the tile x panel kernel of the block-CG over the X left resident by the last single-GPU solve
  * (`reps` launches).  variant 0: as a solve runs it; on the round-4 form of the loop: 1: without its matrix instructions (tile stream + LDS
  * traffic); 2: without re-reading the tile stream (matrix instructions + LDS traffic); 3: operand stages of one k-pair; 4: without LDS
