@@ -161,7 +161,8 @@ struct Engine {
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
     int x_apply_form = 0;          // tile x panel kernel of the block-CG: 0 = the product form, 1 = the round-4 form of its loop (same results; same-box comparisons, dkmc_set_x_apply_form)
-    int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
+    int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
+    int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
     int x_block = 16;              // block-CG width of the current solve on the tiled X (dkmc_set_x_block; xtb.hip): 16 by default, 1 = the reference's single-vector loop (its iterate sequence)
     int x_format = 1;              // 1: tiled X (xt.hip, default); 0: CSR X as the reference stores it (current.hip + cg.hip)
     int x_iter_hint = 0;           // iteration count of the previous CG solve of X (sizes the first launch batch)

@@ -58,6 +58,8 @@ void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }
 int dkmc_get_x_apply_form(void) { return eng().x_apply_form; }
 void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
+void dkmc_set_x_nmul_lane_bytes(int bytes) { eng().x_nmul_lane_bytes = bytes == 8 ? 8 : 16; }
+int dkmc_get_x_nmul_lane_bytes(void) { return eng().x_nmul_lane_bytes; }
 void dkmc_set_x_slab(int on) { eng().x_slab = on ? 1 : 0; }
 int dkmc_get_x_slab(void) { return eng().x_slab; }
 void dkmc_set_x_slab_poly(int on) { eng().x_slab_poly = on ? 1 : 0; }

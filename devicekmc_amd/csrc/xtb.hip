@@ -838,7 +838,7 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_nmul(int m, const xrp_t *__restri
     if (ok) out[(size_t)row * XB_SP + v] = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
 }
 // N packed for the solve (dkmc_set_x_nmul_form(1), the default): sc and Xs do not change during a solve, so the 2 d N products of every sweep
-// read a copy with the column's scaling folded in.  Slice q = rows 4 q ... 4 q + 3 (one wave of k_xtb_nmulp); it is as wide as its longest row,
+// read a copy with the column's scaling folded in.  Slice q = rows 4 q ... 4 q + 3 (one wave of k_xtb_nmulp16 / k_xtb_nmulp); it is as wide as its longest row,
 // w_q slots; slot k of row 4 q + r at off[q] + 4 k + r (a wave's 16 slots x 4 rows are 64 contiguous entries).  Slot k of a row is its CSR
 // position rp[row] + k, so the sums run in the same order as k_xtb_nmul's; entries outside N (driver columns, the diagonal), the driver rows 0 / 1,
 // rows past m and the padding are zero weights on a column whose panel row is read anyway (the row itself): they add exactly +0.
@@ -928,6 +928,69 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_nmulp(int m, const long long *__r
         const double o = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
         out[(size_t)row * XB_SP + v] = o;
         if (QSF) { const int sr = nsrank[row]; if (sr >= 0) QS[xtb_qs_pos(sr, v)] = sc[row] * o; }
+    }
+}
+// k_xtb_nmulp with 16 bytes per lane (dkmc_set_x_nmul_lane_bytes(16), the default): the same packed N, the same slices, half the gather instructions.  A 16-lane row still
+// owns matrix row r and lane v still loads slot k0 + v of it, but one gather takes two slots: lanes 0 ... 7 read columns 2 v, 2 v + 1 of slot 2 j's panel
+// row, lanes 8 ... 15 those of slot 2 j + 1's (column and weight reach the halves by row broadcasts under the bank masks 0x3 / 0xC).  The low half so
+// holds k_xtb_nmulp's s0 (slots 0 mod 4, sA) and s2 (2 mod 4, sB) of two columns, the high half s1 and s3, each summed in increasing slot index over the
+// same batches and groups of four; the halves meet once per row (row_ror:8) as (s0 + s1) + (s2 + s3): every element is k_xtb_nmulp's sequence of
+// operations, the same bits.  add, out: 16 bytes from the low eight lanes.
+template <bool QSF, bool LIST = false>
+__global__ __launch_bounds__(XT_NT) void k_xtb_nmulp16(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
+                                                       const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
+                                                       double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS,
+                                                       const int *__restrict__ rowlist = nullptr)
+{
+    if (ctrl->done) return;
+    const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3, v8 = v & 7;
+    const int nb = (int)gridDim.x, b = (int)blockIdx.x;
+    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
+    const int q = (xc * xq + min(xc, xr) + (b >> 3)) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // XCD-contiguous row blocks (see k_xtb_neigh)
+    if (q >= (m + 3) / 4) return;
+    const bool ok = 4 * q + r < m, wr = ok && v < 8;
+    const int row = LIST ? (ok ? rowlist[4 * q + r] : 0) : 4 * q + r;
+    const long long o0 = off[q];
+    const int w = (int)((off[q + 1] - o0) >> 2);
+    const int *__restrict__ cq = pcol + o0 + r;
+    const double *__restrict__ wq = pw + o0 + r;
+    const double scr = ok ? sc[row] : 0.0;
+    const double2 av = wr ? *reinterpret_cast<const double2 *>(add + (size_t)row * XB_SP + 2 * v8) : make_double2(0.0, 0.0);
+    double sA0 = 0.0, sA1 = 0.0, sB0 = 0.0, sB1 = 0.0;
+    // slots past the width (lanes of the last batch): weight 0 on column 0
+    int cn = v < w ? cq[4 * v] : 0;
+    double wn = v < w ? wq[4 * v] : 0.0;
+    for (int k0 = 0; k0 < w; k0 += 16) {
+        const int t = w - k0, cmb = cn, wlo = __double2loint(wn), whi = __double2hiint(wn);
+        if (t > 16) { const int k = k0 + 16 + v; cn = k < w ? cq[4 * k] : 0; wn = k < w ? wq[4 * k] : 0.0; }        // next batch in flight
+        // slot 2 j to lanes 0 ... 7, slot 2 j + 1 to lanes 8 ... 15 of every row
+#define XN_BC2(x_, j_) __builtin_amdgcn_update_dpp(__builtin_amdgcn_update_dpp(0, (x_), 0x150 + 2 * (j_), 0xf, 0x3, false), (x_), 0x151 + 2 * (j_), 0xf, 0xc, false)
+#define XN_GATHER2(j_) { const int cu_ = XN_BC2(cmb, j_); \
+            x[j_] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(in) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v8 * 16))); }
+#define XN_ACC2(j_) { const double wa_ = __hiloint2double(XN_BC2(whi, j_), XN_BC2(wlo, j_)), wb_ = __hiloint2double(XN_BC2(whi, j_ + 1), XN_BC2(wlo, j_ + 1)); \
+            sA0 += wa_ * x[j_].x; sA1 += wa_ * x[j_].y; sB0 += wb_ * x[j_ + 1].x; sB1 += wb_ * x[j_ + 1].y; }
+        double2 x[8];
+        XN_GATHER2(0) XN_GATHER2(1)
+        if (t > 4) { XN_GATHER2(2) XN_GATHER2(3) }
+        if (t > 8) { XN_GATHER2(4) XN_GATHER2(5) }
+        if (t > 12) { XN_GATHER2(6) XN_GATHER2(7) }
+        XN_ACC2(0)
+        if (t > 4) XN_ACC2(2)
+        if (t > 8) XN_ACC2(4)
+        if (t > 12) XN_ACC2(6)
+#undef XN_BC2
+#undef XN_GATHER2
+#undef XN_ACC2
+    }
+    // the other half's sums (row_ror:8); on the low half (sA + tA) + (sB + tB) is (s0 + s1) + (s2 + s3)
+#define XN_ROR8(x_) __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(x_), 0x128, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, __double2loint(x_), 0x128, 0xf, 0xf, false))
+    const double tA0 = XN_ROR8(sA0), tA1 = XN_ROR8(sA1), tB0 = XN_ROR8(sB0), tB1 = XN_ROR8(sB1);
+#undef XN_ROR8
+    if (wr) {
+        const double o0_ = ca * av.x - cb * (scr * ((sA0 + tA0) + (sB0 + tB0)));
+        const double o1_ = ca * av.y - cb * (scr * ((sA1 + tA1) + (sB1 + tB1)));
+        *reinterpret_cast<double2 *>(out + (size_t)row * XB_SP + 2 * v8) = make_double2(o0_, o1_);
+        if (QSF) { const int sr = nsrank[row]; if (sr >= 0) { const double s = sc[row]; QS[xtb_qs_pos(sr, 2 * v8)] = s * o0_; QS[xtb_qs_pos(sr, 2 * v8 + 1)] = s * o1_; } }
     }
 }
 // QS (the compact, interleaved copy of the S rows the tile kernel reads) of an arbitrary panel
@@ -1409,7 +1472,7 @@ static int xtb_aux_setup(const XtbArgs &A, XbAux **aux, int *hs)
     return 0;
 }
 // the packed N of one solve (k_xtb_npack): slice offsets, columns, weights
-struct XbNPack { const long long *off; const int *col; const double *w; };
+struct XbNPack { const long long *off; const int *col; const double *w; int lane_bytes; };      // lane_bytes: 16 = k_xtb_nmulp16, 8 = k_xtb_nmulp (dkmc_set_x_nmul_lane_bytes)
 // N packed over n rows: rows 0 ... n - 1, or the entries of rowlist (a rank of the slab loop).  alloc(slot, bytes) provides the buffers (scratch, or a
 // virtual rank's own); pad: spare slots behind the packed ones
 template <class Alloc>
@@ -1430,7 +1493,7 @@ static int xtb_npack(const XtbArgs &A, int n, const int *rowlist, Alloc alloc, l
     if (!col || !w) return e.err_code;
     hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, n, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, rowlist);
     KCHK();
-    np->off = off; np->col = col; np->w = w;
+    np->off = off; np->col = col; np->w = w; np->lane_bytes = e.x_nmul_lane_bytes;
     return 0;
 }
 // one rank's N for the preconditioner's products: n rows (rowlist: the entries of a rank's list, the slab loop), packed (np) or CSR (np null), the
@@ -1442,6 +1505,11 @@ static void xtb_nstep(hipStream_t st, const XtbArgs &A, const XbNRank &R, const 
 {
     const dim3 g((R.n + 15) / 16), b(XT_NT);
     if (!R.np) hipLaunchKernelGGL(k_xtb_nmul<LIST>, g, b, 0, st, R.n, A.rp, A.ci, A.val, A.sc, in, add, ca, cb, out, R.ctrl, R.rowlist);
+    else if (R.np->lane_bytes == 16) {
+        if (qsf) hipLaunchKernelGGL((k_xtb_nmulp16<true, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, A.nsrank, R.QS, R.rowlist);
+        else hipLaunchKernelGGL((k_xtb_nmulp16<false, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, (const int *)nullptr,
+                                (double *)nullptr, R.rowlist);
+    }
     else if (qsf) hipLaunchKernelGGL((k_xtb_nmulp<true, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, A.nsrank, R.QS, R.rowlist);
     else hipLaunchKernelGGL((k_xtb_nmulp<false, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, (const int *)nullptr,
                             (double *)nullptr, R.rowlist);
@@ -1947,8 +2015,8 @@ static int xtb_test_qs_out(hipStream_t st, int ns, const double *QS, double *qs)
     HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
     return 0;
 }
-// One Horner step out = ca add + cb (N in) over a caller-given CSR (m rows, rp[m] entries) and [m][16] panels: form 1 packs N (xtb_npack) first, form 0
-// runs on the CSR; rowlist (nlist rows): the LIST instantiations; nsrank (ns S rows): QS of out as well -- packed: from the step's registers, CSR:
+// One Horner step out = ca add + cb (N in) over a caller-given CSR (m rows, rp[m] entries) and [m][16] panels: form 1 packs N (xtb_npack) first and runs the
+// packed kernel dkmc_set_x_nmul_lane_bytes selects, form 0 runs on the CSR; rowlist (nlist rows): the LIST instantiations; nsrank (ns S rows): QS of out as well -- packed: from the step's registers, CSR:
 // k_xtb_qs_from over all m rows, as xtb_applyL takes it on its last step.  out is read before the step and written back after it.
 extern "C" int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
                                    double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs)

@@ -68,6 +68,8 @@ SYMBOLS = {
     "dkmc_get_x_poly": (_I, []),
     "dkmc_set_x_nmul_form": (None, [_I]),
     "dkmc_get_x_nmul_form": (_I, []),
+    "dkmc_set_x_nmul_lane_bytes": (None, [_I]),
+    "dkmc_get_x_nmul_lane_bytes": (_I, []),
     "dkmc_set_x_apply_form": (None, [_I]),
     "dkmc_get_x_apply_form": (_I, []),
     "dkmc_set_x_slab": (None, [_I]),

@@ -159,10 +159,15 @@ int dkmc_get_x_block(void);
 void dkmc_set_x_poly(int degree);
 int dkmc_get_x_poly(void);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
- * the column's scaling folded into the weights (csrc/xtb.hip: k_xtb_npack, k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
+ * the column's scaling folded into the weights (csrc/xtb.hip: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
  * Both give the same bits; 0 is kept for comparisons. */
 void dkmc_set_x_nmul_form(int form);
 int dkmc_get_x_nmul_form(void);
+/* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
+ * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
+ * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */
+void dkmc_set_x_nmul_lane_bytes(int bytes);
+int dkmc_get_x_nmul_lane_bytes(void);
 void dkmc_set_x_slab(int on);
 int dkmc_get_x_slab(void);
 /* Opt-in: 1 runs the slab-distributed block-CG (dkmc_set_x_slab(1), more than one rank) on L A L with the degree and the coefficients of the one-GPU
