@@ -156,7 +156,7 @@ struct Engine {
     int x_aux = 2;                 // auxiliary columns of the block-CG (dkmc_set_x_aux; xtb.hip): 0 hash set, 1 smooth set, 2 smooth at tolerances >= 1e-8
     int x_slab = 1;                // > 1 rank: distribute the STATE of the block-CG by row slabs (xtb_slab.inc; dkmc_set_x_slab); 0: all-gather variant (tile stream sharded only)
     int k_slab = 1;                // > 1 rank, system above the size of the blocked form: CG on K distributed by row slabs (kcg.hip; dkmc_set_k_slab); 0: replicated
-    int x_poly = 8;                // degree d of the split polynomial preconditioner of the block-CG (dkmc_set_x_poly; xtb.hip): the loop runs on L A L, L = the degree-d Chebyshev interpolant of (1 - x)^(-1/2) in N (neighbour part); 0 = off
+    int x_poly = 8;                // degree d of the split polynomial preconditioner of the block-CG (dkmc_set_x_poly; xtb_precond.h): the loop runs on L A L, L = the degree-d Chebyshev interpolant of (1 - x)^(-1/2) in N (neighbour part); 0 = off
     int x_slab_poly = 0;           // 1: the slab-distributed block-CG (> 1 rank, x_slab) runs on L A L too (dkmc_set_x_slab_poly; xtb_slab.inc); 0 (default): plain
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
@@ -206,7 +206,7 @@ enum {
     S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z,
     S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,
-    // test aids of the preconditioner (xtb.hip: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
+    // test aids of the preconditioner (xtb_precond.h: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
     S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,
     S_XTB_TEST_W1, S_XTB_TEST_W2, S_XTB_TEST_QS, S_XTB_TEST_CTRL, S_XTB_TEST_NPCNT, S_XTB_TEST_NPOFF, S_XTB_TEST_NPCOL, S_XTB_TEST_NPW,
     S_NSLOTS

@@ -36,6 +36,7 @@
 // combined record; row sums (32 x s) go to a grid-indexed array per tile.
 // Only column 0 of Y is kept (a vector): the auxiliary solutions are never needed.  The neighbour part gathers P and the scaling, so no
 // scaled full-length copy of P exists; the compact scaled copy over S (QS) feeds the tiles.
+// The split polynomial preconditioner (dkmc_set_x_poly) and the row gather the neighbour part shares with it: xtb_precond.h.
 #include "xtiles.h"
 #include "slab.h"
 #include <hip/hip_ext.h>
@@ -475,6 +476,8 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
     }
 }
 
+#include "xtb_precond.h"
+
 // ---- neighbour part Xs x panel ------------------------------------------------------------------------------------------------------
 // Workgroups [0, 2 XB_DSPLIT): the two driver rows (thousands of entries each), XB_DSPLIT slices per row, partial sums to drvpart (finished
 // by k_xtb_rows).  The rest: 16 atom rows per workgroup, 16 lanes per row (one per vector).  Non-S rows are finished (scaled) here; S rows
@@ -527,53 +530,31 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_neigh(int m, const xrp_t *__restr
         return;
     }
     // atom rows (<= nn + 3 entries): the 16 lanes of a row first fetch ALL its entries, up to four per lane (64 entries per trip), and fold the column's
-    // scaling into the values; then, batch of 16 by batch of 16, every entry is handed round the group (shuffles) and the 16 panel reads of the batch
-    // are issued together.  A latency-bound kernel (its bytes need 0.05 ms per sweep at 9.4e5 sites, it took 0.27): what counts is dependent memory
+    // scaling into the values; then, batch of 16 by batch of 16, every entry is handed round the group and the 16 panel reads of the batch are issued
+    // together (xn_batch16, xtb_precond.h).  A latency-bound kernel (its bytes need 0.05 ms per sweep at 9.4e5 sites, it took 0.27): what counts is dependent memory
     // rounds per row x registers per wave.  Round 4 fetched the entries of a batch inside the batch loop -- two dependent rounds per batch; here the row
     // pointer, the entries and one round per batch, at the same registers.  The additions keep the entry order of the row: same bits.
-    // XCD-aware order of the row blocks: workgroups b and b + 8 share an XCD (and its 4 MiB L2), so XCD x takes the x-th CONTIGUOUS eighth of the
-    // row blocks -- neighbouring rows (atoms in structure order: neighbours in space) then re-read panel rows from their own L2 instead of each of
-    // the eight L2s pulling the whole panel from the Infinity Cache (1.4 GB of 128-byte gathers per sweep at 9.4e5 sites)
-    const int nb = (int)gridDim.x - 2 * XB_DSPLIT, b = (int)blockIdx.x - 2 * XB_DSPLIT;     // (2 XB_DSPLIT is a multiple of 8)
-    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int lb = xc * xq + min(xc, xr) + (b >> 3);
-    const int li = lb * 16 + g;
+    const int li = xtb_xcd_block((int)gridDim.x - 2 * XB_DSPLIT, (int)blockIdx.x - 2 * XB_DSPLIT) * 16 + g;       // XCD-contiguous row blocks (2 XB_DSPLIT is a multiple of 8)
     const int row = rowlist ? (li < nlist ? rowlist[li] : m) : 2 + li;
     const bool ok = row < m;
     const xrp_t p0 = ok ? rp[row] : 0, p1 = ok ? rp[row + 1] : 0;
     const int nsr = ok ? nsrank[row] : 0;
     const double scr = ok ? sc[row] : 0.0;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    XnSums s = {0.0, 0.0, 0.0, 0.0};
     for (xrp_t base = p0; base < p1; base += 64) {
         int cm[4]; double wm[4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) { const xrp_t pe = base + 16 * b + v; cm[b] = pe < p1 ? ci[pe] : -1; wm[b] = pe < p1 ? val[pe] : 0.0; }
 #pragma unroll
         for (int b = 0; b < 4; ++b) wm[b] = cm[b] >= 0 ? wm[b] * sc[cm[b]] : 0.0;
-        // entry u of the batch to all 16 lanes of the row's group: DPP row_newbcast (a VALU move; __shfl would be an LDS ds_bpermute per value -- three
-        // per entry, 1.6e7 of them per sweep at 9.4e5 sites: that, not the gathers, was what the kernel took its time for)
-#define XN_BC(x_, u_) __builtin_amdgcn_update_dpp(0, (x_), 0x150 + (u_), 0xf, 0xf, false)
-#define XN_GATHER(u_) { const int cu_ = XN_BC(cmb, u_); \
-            x[u_] = cu_ >= 0 ? *reinterpret_cast<const double *>(reinterpret_cast<const char *>(P) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v * 8))) : 0.0; }
-#define XN_W(u_) __hiloint2double(XN_BC(whi, u_), XN_BC(wlo, u_))
-#define XN_ACC(u_) { s0 += XN_W(u_) * x[u_]; s1 += XN_W(u_ + 1) * x[u_ + 1]; s2 += XN_W(u_ + 2) * x[u_ + 2]; s3 += XN_W(u_ + 3) * x[u_ + 3]; }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             if (base + 16 * b >= p1) break;
-            double x[16];
-            const int cmb = cm[b], wlo = __double2loint(wm[b]), whi = __double2hiint(wm[b]);
-            // (32-bit byte offsets from the panel's base: the panel is m x 128 B, far below 4 GB)
-            XN_GATHER(0) XN_GATHER(1) XN_GATHER(2) XN_GATHER(3) XN_GATHER(4) XN_GATHER(5) XN_GATHER(6) XN_GATHER(7)
-            XN_GATHER(8) XN_GATHER(9) XN_GATHER(10) XN_GATHER(11) XN_GATHER(12) XN_GATHER(13) XN_GATHER(14) XN_GATHER(15)
-            XN_ACC(0) XN_ACC(4) XN_ACC(8) XN_ACC(12)
+            s = xn_batch16(P, v, xn_entry(cm[b], wm[b]), s);
         }
-#undef XN_BC
-#undef XN_GATHER
-#undef XN_W
-#undef XN_ACC
     }
-    const double s = (s0 + s1) + (s2 + s3);
-    if (ok) T[(size_t)row * XB_SP + v] = nsr < 0 ? scr * s : s;
+    const double sum = (s.s0 + s.s1) + (s.s2 + s.s3);
+    if (ok) T[(size_t)row * XB_SP + v] = nsr < 0 ? scr * sum : sum;
 }
 
 // ---- row kernel: partial sums -> S rows of T, then the partial Gram matrices of this workgroup's rows ------------------------------------
@@ -783,225 +764,6 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows(int ns, int nK, int nW, int 
         }
     }
 }
-
-// ---- split polynomial preconditioner (dkmc_set_x_poly(d), one GPU) -------------------------------------------------------------------------
-// The block loop runs on L A L, A = S X S the Jacobi-scaled operator, L = sum_j c_j N^j the degree-d truncation of the series of (I - N)^(-1/2),
-// N = I - An, An = the neighbour part of A with A's full (unit) diagonal -- the couplings of the two driver nodes stay outside N.  CG on A
-// preconditioned with An EXACTLY needs 8 iterations where A needs 666 (85 k sites, tools/precond_proto.py): the ill-conditioning of X lives in its
-// sparse part, and 2 d sparse panel products per sweep buy 2-3x fewer passes over the tiles (tools/precond_block_proto.py).  The loop's algebra
-// is untouched: it sees another SPD operator.  A start vector y0 enters as the right-hand side: A d = b - A y0, d = L dh, dh from zero.
-// out = ca * add + cb * (N in): 16 lanes per row as in k_xtb_neigh; rows 0 / 1 (driver nodes) and their columns take no part in N.
-// LIST (slab-distributed loop, xtb_slab.inc): the rows are the m entries of rowlist (a rank's two driver rows + the rows it owns); every row is
-// formed exactly as without the list: the same bits.
-template <bool LIST>
-__global__ __launch_bounds__(XT_NT) void k_xtb_nmul(int m, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
-                                                    const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
-                                                    double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ rowlist)
-{
-    if (ctrl->done) return;
-    const int v = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int nb = (int)gridDim.x, b = (int)blockIdx.x;
-    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int li = (xc * xq + min(xc, xr) + (b >> 3)) * 16 + g;                // XCD-contiguous row blocks (see k_xtb_neigh)
-    const bool ok = li < m;
-    const int row = LIST ? (ok ? rowlist[li] : 0) : li;
-    const bool atom = ok && row >= 2;
-    const xrp_t p0 = atom ? rp[row] : 0, p1 = atom ? rp[row + 1] : 0;
-    const double scr = ok ? sc[row] : 0.0;
-    const double av = ok ? add[(size_t)row * XB_SP + v] : 0.0;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (xrp_t base = p0; base < p1; base += 64) {
-        int cm[4]; double wm[4];
-#pragma unroll
-        for (int bq = 0; bq < 4; ++bq) { const xrp_t pe = base + 16 * bq + v; int c = pe < p1 ? ci[pe] : -1; if (c < 2 || c == row) c = -1; cm[bq] = c; wm[bq] = c >= 0 ? val[pe] : 0.0; }
-#pragma unroll
-        for (int bq = 0; bq < 4; ++bq) wm[bq] = cm[bq] >= 0 ? wm[bq] * sc[cm[bq]] : 0.0;
-#define XN_BC(x_, u_) __builtin_amdgcn_update_dpp(0, (x_), 0x150 + (u_), 0xf, 0xf, false)
-#define XN_GATHER(u_) { const int cu_ = XN_BC(cmb, u_); \
-            x[u_] = cu_ >= 0 ? *reinterpret_cast<const double *>(reinterpret_cast<const char *>(in) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v * 8))) : 0.0; }
-#define XN_W(u_) __hiloint2double(XN_BC(whi, u_), XN_BC(wlo, u_))
-#define XN_ACC(u_) { s0 += XN_W(u_) * x[u_]; s1 += XN_W(u_ + 1) * x[u_ + 1]; s2 += XN_W(u_ + 2) * x[u_ + 2]; s3 += XN_W(u_ + 3) * x[u_ + 3]; }
-#pragma unroll
-        for (int bq = 0; bq < 4; ++bq) {
-            if (base + 16 * bq >= p1) break;
-            double x[16];
-            const int cmb = cm[bq], wlo = __double2loint(wm[bq]), whi = __double2hiint(wm[bq]);
-            XN_GATHER(0) XN_GATHER(1) XN_GATHER(2) XN_GATHER(3) XN_GATHER(4) XN_GATHER(5) XN_GATHER(6) XN_GATHER(7)
-            XN_GATHER(8) XN_GATHER(9) XN_GATHER(10) XN_GATHER(11) XN_GATHER(12) XN_GATHER(13) XN_GATHER(14) XN_GATHER(15)
-            XN_ACC(0) XN_ACC(4) XN_ACC(8) XN_ACC(12)
-        }
-#undef XN_BC
-#undef XN_GATHER
-#undef XN_W
-#undef XN_ACC
-    }
-    if (ok) out[(size_t)row * XB_SP + v] = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
-}
-// N packed for the solve (dkmc_set_x_nmul_form(1), the default): sc and Xs do not change during a solve, so the 2 d N products of every sweep
-// read a copy with the column's scaling folded in.  Slice q = rows 4 q ... 4 q + 3 (one wave of k_xtb_nmulp16 / k_xtb_nmulp); it is as wide as its longest row,
-// w_q slots; slot k of row 4 q + r at off[q] + 4 k + r (a wave's 16 slots x 4 rows are 64 contiguous entries).  Slot k of a row is its CSR
-// position rp[row] + k, so the sums run in the same order as k_xtb_nmul's; entries outside N (driver columns, the diagonal), the driver rows 0 / 1,
-// rows past m and the padding are zero weights on a column whose panel row is read anyway (the row itself): they add exactly +0.
-// rowlist != nullptr (slab-distributed loop): slice q = list entries 4 q ... 4 q + 3 of the m entries of a rank's row list, same slots per row.
-__global__ void k_xtb_npack_width(int m, const xrp_t *__restrict__ rp, int *__restrict__ cnt, const int *__restrict__ rowlist = nullptr)
-{
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (m + 3) / 4) return;
-    int w = 0;
-    for (int r = 0; r < 4; ++r) {
-        const int li = 4 * q + r; if (li >= m) continue;
-        const int row = rowlist ? rowlist[li] : li;
-        if (row >= 2) w = max(w, (int)(rp[row + 1] - rp[row]));
-    }
-    cnt[q] = 4 * w;
-}
-// one wave per slice; the weight is the product k_xtb_nmul forms in its register (val * sc[col], same rounding)
-__global__ __launch_bounds__(256) void k_xtb_npack(int m, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
-                                                   const double *__restrict__ sc, const long long *__restrict__ off, int *__restrict__ pcol, double *__restrict__ pw,
-                                                   const int *__restrict__ rowlist = nullptr)
-{
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (q >= (m + 3) / 4) return;
-    const long long o0 = off[q], n = off[q + 1] - o0;
-    for (long long i = lane; i < n; i += 64) {
-        const int r = (int)(i & 3), k = (int)(i >> 2), li = 4 * q + r;
-        const int row = rowlist ? rowlist[li < m ? li : m - 1] : li;
-        const bool atom = row >= 2 && li < m;
-        const xrp_t p0 = atom ? rp[row] : 0, len = atom ? rp[row + 1] - p0 : 0;
-        int c = k < len ? ci[p0 + k] : -1;
-        double w = 0.0;
-        if (c < 2 || c == row) c = rowlist ? row : (row < m ? row : m - 1);
-        else w = val[p0 + k] * sc[c];
-        pcol[o0 + i] = c; pw[o0 + i] = w;
-    }
-}
-// out = ca * add + cb * (N in) on the packed N: the loop runs the slice's width, no row pointers, no scaling gather, no filter.  Entry e of a row goes
-// to accumulator e % 4 in increasing e, the result is formed as in k_xtb_nmul: the same bits.  QSF: also QS (as k_xtb_qs_from) from the rows in registers.
-// LIST (slab-distributed loop): N packed over the m entries of rowlist (k_xtb_npack with a row list); row = rowlist[4 q + r].
-template <bool QSF, bool LIST = false>
-__global__ __launch_bounds__(XT_NT) void k_xtb_nmulp(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
-                                                     const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
-                                                     double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS,
-                                                     const int *__restrict__ rowlist = nullptr)
-{
-    if (ctrl->done) return;
-    const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3;
-    const int nb = (int)gridDim.x, b = (int)blockIdx.x;
-    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int q = (xc * xq + min(xc, xr) + (b >> 3)) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // XCD-contiguous row blocks (see k_xtb_neigh)
-    if (q >= (m + 3) / 4) return;
-    const bool ok = 4 * q + r < m;
-    const int row = LIST ? (ok ? rowlist[4 * q + r] : 0) : 4 * q + r;
-    const long long o0 = off[q];
-    const int w = (int)((off[q + 1] - o0) >> 2);
-    const int *__restrict__ cq = pcol + o0 + r;
-    const double *__restrict__ wq = pw + o0 + r;
-    const double scr = ok ? sc[row] : 0.0;
-    const double av = ok ? add[(size_t)row * XB_SP + v] : 0.0;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    // slots past the width (lanes of the last batch): weight 0 on column 0
-    int cn = v < w ? cq[4 * v] : 0;
-    double wn = v < w ? wq[4 * v] : 0.0;
-    for (int k0 = 0; k0 < w; k0 += 16) {
-        const int t = w - k0, cmb = cn, wlo = __double2loint(wn), whi = __double2hiint(wn);
-        if (t > 16) { const int k = k0 + 16 + v; cn = k < w ? cq[4 * k] : 0; wn = k < w ? wq[4 * k] : 0.0; }        // next batch in flight
-#define XN_BC(x_, u_) __builtin_amdgcn_update_dpp(0, (x_), 0x150 + (u_), 0xf, 0xf, false)
-#define XN_GATHER(u_) { const int cu_ = XN_BC(cmb, u_); \
-            x[u_] = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(in) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v * 8))); }
-#define XN_W(u_) __hiloint2double(XN_BC(whi, u_), XN_BC(wlo, u_))
-#define XN_ACC(u_) { s0 += XN_W(u_) * x[u_]; s1 += XN_W(u_ + 1) * x[u_ + 1]; s2 += XN_W(u_ + 2) * x[u_ + 2]; s3 += XN_W(u_ + 3) * x[u_ + 3]; }
-        double x[16];
-        XN_GATHER(0) XN_GATHER(1) XN_GATHER(2) XN_GATHER(3)
-        if (t > 4) { XN_GATHER(4) XN_GATHER(5) XN_GATHER(6) XN_GATHER(7) }
-        if (t > 8) { XN_GATHER(8) XN_GATHER(9) XN_GATHER(10) XN_GATHER(11) }
-        if (t > 12) { XN_GATHER(12) XN_GATHER(13) XN_GATHER(14) XN_GATHER(15) }
-        XN_ACC(0)
-        if (t > 4) XN_ACC(4)
-        if (t > 8) XN_ACC(8)
-        if (t > 12) XN_ACC(12)
-#undef XN_BC
-#undef XN_GATHER
-#undef XN_W
-#undef XN_ACC
-    }
-    if (ok) {
-        const double o = ca * av - cb * (scr * ((s0 + s1) + (s2 + s3)));
-        out[(size_t)row * XB_SP + v] = o;
-        if (QSF) { const int sr = nsrank[row]; if (sr >= 0) QS[xtb_qs_pos(sr, v)] = sc[row] * o; }
-    }
-}
-// k_xtb_nmulp with 16 bytes per lane (dkmc_set_x_nmul_lane_bytes(16), the default): the same packed N, the same slices, half the gather instructions.  A 16-lane row still
-// owns matrix row r and lane v still loads slot k0 + v of it, but one gather takes two slots: lanes 0 ... 7 read columns 2 v, 2 v + 1 of slot 2 j's panel
-// row, lanes 8 ... 15 those of slot 2 j + 1's (column and weight reach the halves by row broadcasts under the bank masks 0x3 / 0xC).  The low half so
-// holds k_xtb_nmulp's s0 (slots 0 mod 4, sA) and s2 (2 mod 4, sB) of two columns, the high half s1 and s3, each summed in increasing slot index over the
-// same batches and groups of four; the halves meet once per row (row_ror:8) as (s0 + s1) + (s2 + s3): every element is k_xtb_nmulp's sequence of
-// operations, the same bits.  add, out: 16 bytes from the low eight lanes.
-template <bool QSF, bool LIST = false>
-__global__ __launch_bounds__(XT_NT) void k_xtb_nmulp16(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
-                                                       const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
-                                                       double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS,
-                                                       const int *__restrict__ rowlist = nullptr)
-{
-    if (ctrl->done) return;
-    const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3, v8 = v & 7;
-    const int nb = (int)gridDim.x, b = (int)blockIdx.x;
-    const int xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int q = (xc * xq + min(xc, xr) + (b >> 3)) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // XCD-contiguous row blocks (see k_xtb_neigh)
-    if (q >= (m + 3) / 4) return;
-    const bool ok = 4 * q + r < m, wr = ok && v < 8;
-    const int row = LIST ? (ok ? rowlist[4 * q + r] : 0) : 4 * q + r;
-    const long long o0 = off[q];
-    const int w = (int)((off[q + 1] - o0) >> 2);
-    const int *__restrict__ cq = pcol + o0 + r;
-    const double *__restrict__ wq = pw + o0 + r;
-    const double scr = ok ? sc[row] : 0.0;
-    const double2 av = wr ? *reinterpret_cast<const double2 *>(add + (size_t)row * XB_SP + 2 * v8) : make_double2(0.0, 0.0);
-    double sA0 = 0.0, sA1 = 0.0, sB0 = 0.0, sB1 = 0.0;
-    // slots past the width (lanes of the last batch): weight 0 on column 0
-    int cn = v < w ? cq[4 * v] : 0;
-    double wn = v < w ? wq[4 * v] : 0.0;
-    for (int k0 = 0; k0 < w; k0 += 16) {
-        const int t = w - k0, cmb = cn, wlo = __double2loint(wn), whi = __double2hiint(wn);
-        if (t > 16) { const int k = k0 + 16 + v; cn = k < w ? cq[4 * k] : 0; wn = k < w ? wq[4 * k] : 0.0; }        // next batch in flight
-        // slot 2 j to lanes 0 ... 7, slot 2 j + 1 to lanes 8 ... 15 of every row
-#define XN_BC2(x_, j_) __builtin_amdgcn_update_dpp(__builtin_amdgcn_update_dpp(0, (x_), 0x150 + 2 * (j_), 0xf, 0x3, false), (x_), 0x151 + 2 * (j_), 0xf, 0xc, false)
-#define XN_GATHER2(j_) { const int cu_ = XN_BC2(cmb, j_); \
-            x[j_] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(in) + ((unsigned)cu_ * (unsigned)(XB_SP * 8) + (unsigned)(v8 * 16))); }
-#define XN_ACC2(j_) { const double wa_ = __hiloint2double(XN_BC2(whi, j_), XN_BC2(wlo, j_)), wb_ = __hiloint2double(XN_BC2(whi, j_ + 1), XN_BC2(wlo, j_ + 1)); \
-            sA0 += wa_ * x[j_].x; sA1 += wa_ * x[j_].y; sB0 += wb_ * x[j_ + 1].x; sB1 += wb_ * x[j_ + 1].y; }
-        double2 x[8];
-        XN_GATHER2(0) XN_GATHER2(1)
-        if (t > 4) { XN_GATHER2(2) XN_GATHER2(3) }
-        if (t > 8) { XN_GATHER2(4) XN_GATHER2(5) }
-        if (t > 12) { XN_GATHER2(6) XN_GATHER2(7) }
-        XN_ACC2(0)
-        if (t > 4) XN_ACC2(2)
-        if (t > 8) XN_ACC2(4)
-        if (t > 12) XN_ACC2(6)
-#undef XN_BC2
-#undef XN_GATHER2
-#undef XN_ACC2
-    }
-    // the other half's sums (row_ror:8); on the low half (sA + tA) + (sB + tB) is (s0 + s1) + (s2 + s3)
-#define XN_ROR8(x_) __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(x_), 0x128, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, __double2loint(x_), 0x128, 0xf, 0xf, false))
-    const double tA0 = XN_ROR8(sA0), tA1 = XN_ROR8(sA1), tB0 = XN_ROR8(sB0), tB1 = XN_ROR8(sB1);
-#undef XN_ROR8
-    if (wr) {
-        const double o0_ = ca * av.x - cb * (scr * ((sA0 + tA0) + (sB0 + tB0)));
-        const double o1_ = ca * av.y - cb * (scr * ((sA1 + tA1) + (sB1 + tB1)));
-        *reinterpret_cast<double2 *>(out + (size_t)row * XB_SP + 2 * v8) = make_double2(o0_, o1_);
-        if (QSF) { const int sr = nsrank[row]; if (sr >= 0) { const double s = sc[row]; QS[xtb_qs_pos(sr, 2 * v8)] = s * o0_; QS[xtb_qs_pos(sr, 2 * v8 + 1)] = s * o1_; } }
-    }
-}
-// QS (the compact, interleaved copy of the S rows the tile kernel reads) of an arbitrary panel
-__global__ void k_xtb_qs_from(int m, const double *__restrict__ V, const double *__restrict__ sc, const int *__restrict__ nsrank, double *__restrict__ QS, const XCtrl *ctrl)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m * XB_SP || ctrl->done) return;
-    const int row = i >> 4, v = i & 15;
-    const int sr = nsrank[row];
-    if (sr >= 0) QS[xtb_qs_pos(sr, v)] = sc[row] * V[i];
-}
 // the fold of k_xtb_rows alone: S rows of T <- scaling x (sparse sum + tile sums), driver rows from their partial sums
 __global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW, int so, const int2 *__restrict__ wrange, const int *__restrict__ nitem_w,
                                                          const double *__restrict__ rowpartB, const double *__restrict__ colpartB, const int *__restrict__ srow,
@@ -1037,38 +799,6 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW,
         if (sB < ns) { const size_t o = (size_t)srow[sB] * XB_SP + v; T[o] = sS[sB] * (T[o] + tB); }
     }
 }
-// start of a preconditioned solve: W <- [T(:, 0) - b | 0 ... 0] (T = A Y0: the residual of the start vector, sign r = A y - b)
-__global__ void k_xtb_pre_resid(int m, const double *__restrict__ T, const double *__restrict__ b, double *__restrict__ W)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m * XB_SP) return;
-    W[i] = (i & 15) == 0 ? T[i] - b[i >> 4] : 0.0;
-}
-// W <- [y | 0 ... 0]
-__global__ void k_xtb_pre_col0(int m, const double *__restrict__ y, double *__restrict__ W)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m * XB_SP) return;
-    W[i] = (i & 15) == 0 ? y[i >> 4] : 0.0;
-}
-// end of a preconditioned solve: y <- y + Z(:, 0)  (Z = L dh, the correction)
-__global__ void k_xtb_pre_add(int m, const double *__restrict__ Z, double *__restrict__ y)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) y[i] += Z[(size_t)i * XB_SP];
-}
-// ||T(:, 0) - b||^2 in one workgroup (fixed order): the TRUE residual of the unpreconditioned scaled system, for the stop test a caller relies on
-__global__ __launch_bounds__(1024) void k_xtb_pre_rr(int m, const double *__restrict__ T, const double *__restrict__ b, double *__restrict__ out)
-{
-    __shared__ double red[1024];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < m; i += 1024) { const double d = T[(size_t)i * XB_SP] - b[i]; a += d * d; }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) out[0] = red[0];
-}
-
 // ---- Gram matrices: the row kernel's partials, reduced in a fixed order ----------------------------------------------------------------
 // 16 entries per workgroup, 16 slices of the partial list per entry (slice q adds partials q, q + 16, ...), the slices combined in order.
 __global__ __launch_bounds__(XT_NT) void k_xtb_gred(int npart, const double *__restrict__ gpart, double *__restrict__ gfin, const XCtrl *ctrl)
@@ -1471,73 +1201,6 @@ static int xtb_aux_setup(const XtbArgs &A, XbAux **aux, int *hs)
     e.stats.xb_aux = *aux ? (*hs >= A.s ? 1 : 2) : 0;
     return 0;
 }
-// the packed N of one solve (k_xtb_npack): slice offsets, columns, weights
-struct XbNPack { const long long *off; const int *col; const double *w; int lane_bytes; };      // lane_bytes: 16 = k_xtb_nmulp16, 8 = k_xtb_nmulp (dkmc_set_x_nmul_lane_bytes)
-// N packed over n rows: rows 0 ... n - 1, or the entries of rowlist (a rank of the slab loop).  alloc(slot, bytes) provides the buffers (scratch, or a
-// virtual rank's own); pad: spare slots behind the packed ones
-template <class Alloc>
-static int xtb_npack(const XtbArgs &A, int n, const int *rowlist, Alloc alloc, long long pad, XbNPack *np)
-{
-    Engine &e = eng(); hipStream_t st = e.stream;
-    const int nsl = (n + 3) / 4;
-    int *cnt = (int *)alloc(S_XTB_NPACK_CNT, (size_t)nsl * 4);
-    long long *off = (long long *)alloc(S_XTB_NPACK_OFF, (size_t)(nsl + 1) * 8);
-    if (!cnt || !off) return e.err_code;
-    hipLaunchKernelGGL(k_xtb_npack_width, dim3((nsl + 255) / 256), dim3(256), 0, st, n, A.rp, cnt, rowlist);
-    if (int rc = dkmc_exclusive_scan_i32_i64(cnt, off, nsl, off + nsl)) return rc;
-    long long nslot = 0;
-    HIPCHK(hipMemcpyAsync(&nslot, off + nsl, sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    int *col = (int *)alloc(S_XTB_NPACK_COL, (size_t)(nslot + pad) * 4);
-    double *w = (double *)alloc(S_XTB_NPACK_W, (size_t)(nslot + pad) * 8);
-    if (!col || !w) return e.err_code;
-    hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, n, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, rowlist);
-    KCHK();
-    np->off = off; np->col = col; np->w = w; np->lane_bytes = e.x_nmul_lane_bytes;
-    return 0;
-}
-// one rank's N for the preconditioner's products: n rows (rowlist: the entries of a rank's list, the slab loop), packed (np) or CSR (np null), the
-// rank's QS and control words
-struct XbNRank { int n; const int *rowlist; const XbNPack *np; double *QS; const XCtrl *ctrl; };
-// one Horner step out = ca add + cb (N in); qsf: QS of out as well, from the rows in registers (packed form)
-template <bool LIST>
-static void xtb_nstep(hipStream_t st, const XtbArgs &A, const XbNRank &R, const double *in, const double *add, double ca, double cb, double *out, bool qsf)
-{
-    const dim3 g((R.n + 15) / 16), b(XT_NT);
-    if (!R.np) hipLaunchKernelGGL(k_xtb_nmul<LIST>, g, b, 0, st, R.n, A.rp, A.ci, A.val, A.sc, in, add, ca, cb, out, R.ctrl, R.rowlist);
-    else if (R.np->lane_bytes == 16) {
-        if (qsf) hipLaunchKernelGGL((k_xtb_nmulp16<true, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, A.nsrank, R.QS, R.rowlist);
-        else hipLaunchKernelGGL((k_xtb_nmulp16<false, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, (const int *)nullptr,
-                                (double *)nullptr, R.rowlist);
-    }
-    else if (qsf) hipLaunchKernelGGL((k_xtb_nmulp<true, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, A.nsrank, R.QS, R.rowlist);
-    else hipLaunchKernelGGL((k_xtb_nmulp<false, LIST>), g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, (const int *)nullptr,
-                            (double *)nullptr, R.rowlist);
-}
-// dst = L src (Horner: pd N products out = c_j src + N in, j = pd - 1 - i, the first step carries c_d); out rotates over w1 / w2 and is dst on the last
-// step, so dst must be none of src, w1, w2.  qs: QS of dst as well -- the packed form writes it from the last step's registers, the CSR form by
-// k_xtb_qs_from.  Panels are named by Pn: ranks(product, f) calls f(R, at) for every rank of the loop (one GPU: one), R its N and at(p) its panel p
-// (product: f issues an N product -- the slab loop times those); pre(i, in) runs before step i (the slab loop's halo exchange of the step's input).
-template <class Pn, class Pre, class Ranks>
-static int xtb_applyL(hipStream_t st, const XtbArgs &A, int pd, const double *pc, Pn src, Pn dst, Pn w1, Pn w2, bool qs, Pre pre, Ranks ranks)
-{
-    Pn in = src;
-    for (int i = 0; i < pd; ++i) {
-        const Pn out = (i == pd - 1) ? dst : ((i & 1) ? w2 : w1);
-        const int j = pd - 1 - i;
-        const double cb = i == 0 ? pc[pd] : 1.0;
-        if (int rc = pre(i, in)) return rc;
-        if (int rc = ranks(true, [&](const XbNRank &R, auto at) {
-                (R.rowlist ? xtb_nstep<true> : xtb_nstep<false>)(st, A, R, at(in), at(src), pc[j], cb, at(out), qs && i == pd - 1);
-            })) return rc;
-        in = out;
-    }
-    if (!qs || pd <= 0) return 0;
-    return ranks(false, [&](const XbNRank &R, auto at) {
-        if (!R.np) hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)(((size_t)A.m * XB_SP + 255) / 256)), dim3(256), 0, st, A.m, (const double *)at(dst), A.sc, A.nsrank,
-                                      R.QS, R.ctrl);
-    });
-}
 // the tile x panel kernel (one wave per tile run, four runs per workgroup) at NG = so / 4 vector groups: the product form, or the round-4 form
 // (dkmc_set_x_apply_form(1) = variant 8); variant != 0 (dkmc_xtb_time_apply in a DKMC_MEASURE_VARIANTS build): a measurement variant, where one exists
 struct XbApplyArgs { int n; const XItem *items; const XTile *tiles; int sub_base; const double *tval; const double *QS; int nW; double *rowpartB, *colpartB; const XCtrl *ctrl; };
@@ -1628,37 +1291,6 @@ static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, const Xb
     }
     if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
     return again ? DKMC_XTB_AGAIN : 0;
-}
-// coefficients pc[0 ... pd] of the preconditioner L = p(N) (dkmc_set_x_poly; shared by the one-GPU and the slab-distributed loop)
-static void xtb_poly_coeffs(int pd, double *pc)
-{
-    // coefficients of L = p(N), p ~ (1 - x)^(-1/2): the Chebyshev interpolant of degree d on [-1, 1 - delta], delta = min(0.5, 1.6 / d^2), in the monomial
-    // basis (Horner).  Against the Taylor series of the same degree -- which is exact at 0 and weakest where it matters, towards x -> 1 (the largest
-    // eigenvalue of N is 0.99994 at 9.4 k sites) -- the block loop needs a third fewer sweeps (85 k sites, d = 4: 34 -> 24, 95 without preconditioner).
-    if (pd > 0) {
-        const int d = pd, n = d + 1;
-        const double a = -1.0, b = 1.0 - std::min(0.5, 1.6 / (double)(d * d));
-        double fx[XB_MAXPOLY + 1], c[XB_MAXPOLY + 1], pt[XB_MAXPOLY + 1] = {0}, Tm2[XB_MAXPOLY + 1] = {0}, Tm1[XB_MAXPOLY + 1] = {0};
-        for (int k = 0; k < n; ++k) { const double t = cos(M_PI * (k + 0.5) / n), x = 0.5 * (b - a) * t + 0.5 * (b + a); fx[k] = 1.0 / sqrt(1.0 - x); }
-        for (int j = 0; j < n; ++j) { double acc = 0.0; for (int k = 0; k < n; ++k) acc += fx[k] * cos(M_PI * j * (k + 0.5) / n); c[j] = acc * 2.0 / n; }
-        c[0] *= 0.5;
-        Tm2[0] = 1.0; Tm1[1] = 1.0;                                           // T_0, T_1 in powers of t
-        pt[0] += c[0]; pt[1] += c[1];
-        for (int j = 2; j <= d; ++j) {
-            double Tj[XB_MAXPOLY + 1];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) Tj[i] = (i >= 1 ? 2.0 * Tm1[i - 1] : 0.0) - Tm2[i];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) { pt[i] += c[j] * Tj[i]; Tm2[i] = Tm1[i]; Tm1[i] = Tj[i]; }
-        }
-        const double al = 2.0 / (b - a), be = -(a + b) / (b - a);             // t = al x + be
-        double res[XB_MAXPOLY + 2] = {0}; res[0] = pt[d]; int deg = 0;
-        for (int i = d - 1; i >= 0; --i) {
-            double nr[XB_MAXPOLY + 2] = {0};
-            for (int q = 0; q <= deg; ++q) { nr[q] += res[q] * be; nr[q + 1] += res[q] * al; }
-            ++deg; nr[0] += pt[i];
-            for (int q = 0; q <= XB_MAXPOLY + 1; ++q) res[q] = nr[q];
-        }
-        for (int q = 0; q <= d; ++q) pc[q] = res[q];
-    }
 }
 static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
@@ -1982,129 +1614,6 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     HIPCHK(hipStreamSynchronize(st));
     if (max_abs_diff) *max_abs_diff = h[0];
     if (max_abs) *max_abs = h[1];
-    return e.err_code;
-}
-
-// ---- test aids of the split polynomial preconditioner (tests/test_precond_coeffs.py, tests/test_gpu_precond_reference.py) -------------------
-// The production path (xtb_npack, xtb_nstep, xtb_applyL) on buffers of their own (S_XTB_TEST_*): nothing a solve reads or keeps is touched.
-// coefficients pc[0 ... degree] of L = p(N); host code only (no HIP call)
-extern "C" int dkmc_xtb_poly_coeffs(int degree, double *pc)
-{
-    if (degree < 1 || degree > XB_MAXPOLY || !pc) return dkmc_fail(13, "xtb_poly_coeffs: degree outside 1 ... 16", __FILE__, __LINE__);
-    xtb_poly_coeffs(degree, pc);
-    return 0;
-}
-// QS (interleaved, xtb_qs_pos) -> [ns][16]
-__global__ void k_xtb_test_qs_decode(int ns, const double *__restrict__ QS, double *__restrict__ out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < ns * XB_SP) out[i] = QS[xtb_qs_pos(i >> 4, i & 15)];
-}
-// the packed N of a test aid in its own slots (xtb_npack's alloc)
-static void *xtb_test_alloc(int slot, size_t bytes)
-{
-    return scratch(slot == S_XTB_NPACK_CNT ? S_XTB_TEST_NPCNT : slot == S_XTB_NPACK_OFF ? S_XTB_TEST_NPOFF : slot == S_XTB_NPACK_COL ? S_XTB_TEST_NPCOL : S_XTB_TEST_NPW, bytes);
-}
-// QS of the test aids zeroed, then decoded into qs [ns][16] after the step(s)
-static int xtb_test_qs_out(hipStream_t st, int ns, const double *QS, double *qs)
-{
-    double *dq = (double *)scratch(S_XTB_TEST_ADD, (size_t)ns * XB_SP * 8);      // (the add panel of a step is spent by now)
-    if (!dq) return eng().err_code;
-    hipLaunchKernelGGL(k_xtb_test_qs_decode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, QS, dq);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
-    return 0;
-}
-// One Horner step out = ca add + cb (N in) over a caller-given CSR (m rows, rp[m] entries) and [m][16] panels: form 1 packs N (xtb_npack) first and runs the
-// packed kernel dkmc_set_x_nmul_lane_bytes selects, form 0 runs on the CSR; rowlist (nlist rows): the LIST instantiations; nsrank (ns S rows): QS of out as well -- packed: from the step's registers, CSR:
-// k_xtb_qs_from over all m rows, as xtb_applyL takes it on its last step.  out is read before the step and written back after it.
-extern "C" int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
-                                   double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs)
-{
-    Engine &e = eng(); hipStream_t st = e.stream;
-    if (m < 1 || !rp || !sc || !in || !add || !out || (form != 0 && form != 1)) return dkmc_fail(13, "xtb_test_nstep: bad arguments", __FILE__, __LINE__);
-    const long long nnz = rp[m];
-    if (rp[0] != 0 || nnz < 0 || nnz > 0x7fffffffll || (nnz > 0 && (!ci || !val))) return dkmc_fail(13, "xtb_test_nstep: bad row pointers", __FILE__, __LINE__);
-    for (int i = 0; i < m; ++i) if (rp[i + 1] < rp[i]) return dkmc_fail(13, "xtb_test_nstep: bad row pointers", __FILE__, __LINE__);
-    for (long long p = 0; p < nnz; ++p) if (ci[p] < 0 || ci[p] >= m) return dkmc_fail(13, "xtb_test_nstep: column outside the rows", __FILE__, __LINE__);
-    if (rowlist) {
-        if (nlist < 1 || nlist > m) return dkmc_fail(13, "xtb_test_nstep: bad row list", __FILE__, __LINE__);
-        for (int i = 0; i < nlist; ++i) if (rowlist[i] < 0 || rowlist[i] >= m) return dkmc_fail(13, "xtb_test_nstep: bad row list", __FILE__, __LINE__);
-    }
-    if (nsrank) {
-        if (ns < 1 || !qs) return dkmc_fail(13, "xtb_test_nstep: bad S ranks", __FILE__, __LINE__);
-        for (int i = 0; i < m; ++i) if (nsrank[i] < -1 || nsrank[i] >= ns) return dkmc_fail(13, "xtb_test_nstep: bad S ranks", __FILE__, __LINE__);
-    }
-    const size_t pan = (size_t)m * XB_SP * 8;
-    xrp_t *drp = (xrp_t *)scratch(S_XTB_TEST_RP, (size_t)(m + 1) * sizeof(xrp_t));
-    int *dci = (int *)scratch(S_XTB_TEST_CI, (size_t)nnz * 4);
-    double *dval = (double *)scratch(S_XTB_TEST_VAL, (size_t)nnz * 8), *dsc = (double *)scratch(S_XTB_TEST_SC, (size_t)m * 8);
-    double *din = (double *)scratch(S_XTB_TEST_IN, pan), *dadd = (double *)scratch(S_XTB_TEST_ADD, pan), *dout = (double *)scratch(S_XTB_TEST_OUT, pan);
-    int *dns = nsrank ? (int *)scratch(S_XTB_TEST_NSR, (size_t)m * 4) : nullptr;
-    int *dlist = rowlist ? (int *)scratch(S_XTB_TEST_LIST, (size_t)nlist * 4) : nullptr;
-    double *QS = nsrank ? (double *)scratch(S_XTB_TEST_QS, (size_t)(ns + 2) * XB_SP * 8) : nullptr;
-    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_TEST_CTRL, sizeof(XCtrl));
-    if (!drp || !dci || !dval || !dsc || !din || !dadd || !dout || (nsrank && (!dns || !QS)) || (rowlist && !dlist) || !ctrl) return e.err_code;
-    HIPCHK(hipMemcpyAsync(drp, rp, (size_t)(m + 1) * sizeof(xrp_t), hipMemcpyHostToDevice, st));
-    if (nnz > 0) {
-        HIPCHK(hipMemcpyAsync(dci, ci, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(dval, val, (size_t)nnz * 8, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(hipMemcpyAsync(dsc, sc, (size_t)m * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(din, in, pan, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dadd, add, pan, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dout, out, pan, hipMemcpyHostToDevice, st));
-    if (dns) HIPCHK(hipMemcpyAsync(dns, nsrank, (size_t)m * 4, hipMemcpyHostToDevice, st));
-    if (dlist) HIPCHK(hipMemcpyAsync(dlist, rowlist, (size_t)nlist * 4, hipMemcpyHostToDevice, st));
-    if (QS) HIPCHK(hipMemsetAsync(QS, 0, (size_t)(ns + 2) * XB_SP * 8, st));
-    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
-    XtbArgs A{};
-    A.m = m; A.ns = ns; A.rp = drp; A.ci = dci; A.val = dval; A.sc = dsc; A.nsrank = dns;
-    const int n = rowlist ? nlist : m;
-    XbNPack npk{};
-    if (form == 1) { if (int rc = xtb_npack(A, n, (const int *)dlist, xtb_test_alloc, 0, &npk)) return rc; }
-    const XbNRank R{n, dlist, form == 1 ? &npk : nullptr, QS, ctrl};
-    (rowlist ? xtb_nstep<true> : xtb_nstep<false>)(st, A, R, din, dadd, ca, cb, dout, nsrank != nullptr);
-    if (nsrank && form == 0)
-        hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan / 8 + 255) / 256)), dim3(256), 0, st, m, (const double *)dout, (const double *)dsc, (const int *)dns, QS, (const XCtrl *)ctrl);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(out, dout, pan, hipMemcpyDeviceToHost, st));
-    if (nsrank) { if (int rc = xtb_test_qs_out(st, ns, QS, qs)) return rc; }
-    HIPCHK(hipStreamSynchronize(st));
-    return e.err_code;
-}
-// L in (xtb_applyL with QS, as product_pre calls it) on the X left resident by the last single-GPU solve, with that solve's sc, Xs and S ranks:
-// in / out [m][16] (m = rows of X), qs [ns][16].  Neither the warm start nor the iteration hint of the next solve is touched.
-extern "C" int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs)
-{
-    Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
-    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0) return dkmc_fail(13, "xtb_check_poly: needs the X of a single-GPU solve", __FILE__, __LINE__);
-    if (degree < 1 || degree > XB_MAXPOLY || (form != 0 && form != 1) || !in || !out || !qs) return dkmc_fail(13, "xtb_check_poly: bad arguments", __FILE__, __LINE__);
-    const int m = X.Nsub;
-    const size_t pan = (size_t)m * XB_SP * 8;
-    double *sc = (double *)e.buf[S_CG_S];
-    double *din = (double *)scratch(S_XTB_TEST_IN, pan), *dout = (double *)scratch(S_XTB_TEST_OUT, pan);
-    double *W1 = (double *)scratch(S_XTB_TEST_W1, pan), *W2 = (double *)scratch(S_XTB_TEST_W2, pan);
-    double *QS = (double *)scratch(S_XTB_TEST_QS, (size_t)X.ns_pad * XB_SP * 8);
-    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_TEST_CTRL, sizeof(XCtrl));
-    if (!din || !dout || !W1 || !W2 || !QS || !ctrl) return e.err_code;
-    if (!sc || !g_xb.rp || !g_xb.ci || !g_xb.val || !g_xb.nsrank) return dkmc_fail(13, "xtb_check_poly: no solver state", __FILE__, __LINE__);
-    HIPCHK(hipMemcpyAsync(din, in, pan, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(QS, 0, (size_t)X.ns_pad * XB_SP * 8, st));
-    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
-    XtbArgs A{};
-    A.m = m; A.ns = X.ns; A.ns_pad = X.ns_pad; A.rp = g_xb.rp; A.ci = g_xb.ci; A.val = g_xb.val; A.sc = sc; A.nsrank = g_xb.nsrank;
-    XbNPack npk{};
-    if (form == 1) { if (int rc = xtb_npack(A, m, nullptr, xtb_test_alloc, 0, &npk)) return rc; }
-    const XbNRank nk{m, nullptr, form == 1 ? &npk : nullptr, QS, ctrl};
-    double pc[XB_MAXPOLY + 1] = {1.0};
-    xtb_poly_coeffs(degree, pc);
-    if (int rc = xtb_applyL(st, A, degree, pc, din, dout, W1, W2, true, [](int, double *) { return 0; },
-                            [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; })) return rc;
-    KCHK();
-    HIPCHK(hipMemcpyAsync(out, dout, pan, hipMemcpyDeviceToHost, st));
-    if (int rc = xtb_test_qs_out(st, X.ns, QS, qs)) return rc;
-    HIPCHK(hipStreamSynchronize(st));
     return e.err_code;
 }
 

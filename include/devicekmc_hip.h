@@ -150,7 +150,7 @@ int dkmc_get_x_block(void);
  * slab of the device: neighbour part, Gram pass and panel updates run on its rows only; per sweep the tile sums of the S rows go to their owners
  * (all-to-all-v), 6 x 256 Gram entries are all-gathered and added in rank order, the own rows of Q = S P and the halo rows of P go out
  * (all-to-all-v) (csrc/xtb_slab.inc).  0: the all-gather variant -- only the tile stream is sharded, everything else replicated. */
-/* Split polynomial preconditioner of the block-CG of the current solve (csrc/xtb.hip): degree d > 0 runs the block loop on L A L with
+/* Split polynomial preconditioner of the block-CG of the current solve (csrc/xtb_precond.h): degree d > 0 runs the block loop on L A L with
  * L = p(N), p the degree-d Chebyshev interpolant of (1 - x)^(-1/2) on [-1, 1 - min(0.5, 1.6 / d^2)], N = I - (neighbour part + diagonal of the
  * Jacobi-scaled X).  A sweep then costs 2 d more sparse panel products and the loop needs 2-3x fewer sweeps (tools/precond_block_proto.py); the start
  * vector enters through the right-hand side L (b - A y0), the result meets the reference's stop test in the TRUE residual (checked, the loop is
@@ -159,7 +159,7 @@ int dkmc_get_x_block(void);
 void dkmc_set_x_poly(int degree);
 int dkmc_get_x_poly(void);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
- * the column's scaling folded into the weights (csrc/xtb.hip: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
+ * the column's scaling folded into the weights (csrc/xtb_precond.h: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
  * Both give the same bits; 0 is kept for comparisons. */
 void dkmc_set_x_nmul_form(int form);
 int dkmc_get_x_nmul_form(void);

@@ -24,7 +24,7 @@ int dkmc_xt_check_shares(int nranks, double *max_abs_diff, double *max_abs, long
 /* Test aid: on the X left resident by the last single-GPU solve, the MFMA tile x panel product of the block-CG (16 test vectors, one
  * sweep) against 16 passes of the single-vector tile kernel; largest absolute deviation and largest sum over the S rows. */
 int dkmc_xtb_check_product(int width, double *max_abs_diff, double *max_abs);
-/* Test aids of the split polynomial preconditioner L = p(N) of the block-CG (dkmc_set_x_poly).
+/* Test aids of the split polynomial preconditioner L = p(N) of the block-CG (dkmc_set_x_poly; csrc/xtb_precond.h).
  * dkmc_xtb_poly_coeffs: its coefficients pc[0 ... degree] (monomial basis, Horner order of the solve); host code only, no GPU needed.  degree: 1 ... 16.
  * dkmc_xtb_test_nstep: ONE Horner step out = ca add + cb (N in) of the production kernels over a caller-given CSR (m rows, rp[m] entries, columns in
  * [0, m)) and host panels in / add / out of [m][16]: out_r = ca add_r - cb sc_r sum val sc_c in_c over the entries with c >= 2 and c != r; rows 0 / 1

@@ -1,4 +1,4 @@
-"""The split polynomial preconditioner L = p(N) of the block-CG (csrc/xtb.hip: k_xtb_nmul, k_xtb_npack*, k_xtb_nmulp, k_xtb_qs_from, xtb_applyL)
+"""The split polynomial preconditioner L = p(N) of the block-CG (csrc/xtb_precond.h: k_xtb_nmul, k_xtb_npack*, k_xtb_nmulp, k_xtb_qs_from, xtb_applyL)
 against a plain long-double reference of the same operation.  The loop only sees "another SPD operator" and re-enters on its true residual,
 so a wrong L shows up as more sweeps at most; these tests compare L itself.
 

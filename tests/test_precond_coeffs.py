@@ -1,4 +1,4 @@
-"""Coefficients of the split polynomial preconditioner L = p(N) (csrc/xtb.hip: xtb_poly_coeffs, through dkmc_xtb_poly_coeffs) against a 50-digit
+"""Coefficients of the split polynomial preconditioner L = p(N) (csrc/xtb_precond.h: xtb_poly_coeffs, through dkmc_xtb_poly_coeffs) against a 50-digit
 reference: p is the Chebyshev interpolant of degree d of f(x) = (1 - x)^(-1/2) on [-1, 1 - delta], delta = min(0.5, 1.6 / d^2), in the monomial basis.
 The block loop only sees "another SPD operator", so a wrong coefficient shows up as more sweeps at most; this pins p itself (no GPU needed)."""
 import ctypes as C
