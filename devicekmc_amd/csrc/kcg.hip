@@ -10,11 +10,22 @@
 //   * 8 lanes per row (26 entries on average), every load of a row issued before the first use: three dependent memory latencies
 //     per row (row pointers -> columns -> q) instead of one per 16 entries.
 // Bytes per iteration: 4 nnz + 4 (m + 1) + 15 vector touches of 8 m  (CSR formulation, SURVEY 8d: 12 nnz + 4 (m + 1) + 96 m).
+//
+// K is stored in one of three forms, each with its own assemble and product kernels; what fixes the physics and the rounding is written once:
+//   CSR positions (k_kc_*)                                            any size; also what the slab-distributed loop (k_ks_*, row lists) runs on
+//   blocked form (k_kb_*), one x-sorted LDS window per block          up to KB_MAXROWS rows (default there)
+//   windowed blocked form (k_kbw_*), a window of up to KBW_MAXSEG segments   above KB_MAXROWS rows, opt-in (dkmc_set_k_blocked_large)
+// Shared bodies (__forceinline__, values in and out, so every kernel compiles to what its written-out text did):
+//   assembly   k_link (the rule of one entry), k_word (what is stored for it), k_contacts (the two contact sums), k_assemble_tail (diagonal and rhs)
+//   product    kb_rows: the pass loop of k_kb_apply and k_kbw_apply (k_kc_apply: 8 lanes per row, no LDS -- another algorithm, on its own)
+//   vectors    kc_check0 / kc_update / kc_direction / kc_q<LIST>: all rows (k_kc_*) or the rows of a list (k_ks_*)
+//   host       kc_with_cb, kb_raise_lds_limit, kpattern_download, kblocked_upload, kcg_poll (the poll loop of both host loops)
 #include "common.h"
 #include "slab.h"
 #include "kbw_plan.h"
 #include <algorithm>
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #define KC_NT 256
@@ -33,6 +44,45 @@ __device__ __forceinline__ bool k_high(int ei, int ej, int qi, int qj, const Met
     return (m1 && m2) || (cv1 && cv2);                                  // :202-217
 }
 
+// The rule of one stored entry: the link of site i (element ei, charge qi) to site j
+enum { K_NOLINK = 0, K_LOW = 1, K_HIGH = 2 };
+template <int CB>
+__device__ __forceinline__ int k_link(int ei, int qi, int j, const int *__restrict__ element, const int *__restrict__ charge, const MetalSet &ms)
+{
+    const int ej = element[j];
+    if (CB == 2 && (k_interstitial(ei) || k_interstitial(ej))) return K_NOLINK;
+    return k_high<CB>(ei, ej, qi, charge[j], ms) ? K_HIGH : K_LOW;
+}
+// what is stored for a link to column c: class bit 31 (no link: the column the form's product skips, the row itself, like the padding)
+__device__ __forceinline__ int k_word(int link, int c) { return link == K_HIGH ? (c | (int)0x80000000) : c; }
+// the links of row r (site i) to the left and to the right contact, lane l of the row's LPR
+struct KContacts { double kl, kr; };
+template <int CB, int LPR>
+__device__ __forceinline__ KContacts k_contacts(int r, int l, int m, int N_left, int ei, int qi, const int *__restrict__ element, const int *__restrict__ charge,
+                                                const MetalSet &ms, double high_G, double low_G, const int *__restrict__ lrp, const int *__restrict__ lci,
+                                                const int *__restrict__ rrp, const int *__restrict__ rci)
+{
+    double kl = 0.0, kr = 0.0;
+    const bool cut = CB == 2 && k_interstitial(ei);
+    for (int p = lrp[r] + l; p < lrp[r + 1] && !cut; p += LPR) { const int j = lci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kl += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
+    for (int p = rrp[r] + l; p < rrp[r + 1] && !cut; p += LPR) { const int j = N_left + m + rci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kr += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
+    return {kl, kr};
+}
+// diagonal and rhs of a row from its lanes' sums, stored at `row` (the row's index in the form's own order)
+template <int CB, int LPR>
+__device__ __forceinline__ void k_assemble_tail(int row, int l, double off, KContacts k, double VL, double VR, double *diag, double *rhs)
+{
+    { off = group_sum<LPR>(off); k.kl = group_sum<LPR>(k.kl); k.kr = group_sum<LPR>(k.kr); }
+    if (l == 0) {
+        double d = off;          // reduce_rows_into_diag: -(sum of off-diagonals)
+        d += k.kl;               // add_vector_to_diagonal (left)
+        d += k.kr;               // add_vector_to_diagonal (right)
+        if (CB == 2 && d == 0.0) d = 1.0;      // an unlinked interstitial site: identity row, value 0
+        diag[row] = d;
+        rhs[row] = k.kl * VL + k.kr * VR;
+    }
+}
+// The three assemble kernels keep what differs between the forms: how a row finds its stored entries and how a stored column maps to a site.
 template <int CB>
 __global__ __launch_bounds__(KC_NT) void k_kc_assemble(int m, int N_left, const int *__restrict__ element, const int *__restrict__ charge,
                                                        MetalSet ms, double high_G, double low_G,
@@ -47,29 +97,16 @@ __global__ __launch_bounds__(KC_NT) void k_kc_assemble(int m, int N_left, const 
     if (r >= m) return;
     const int i = N_left + r;
     const int ei = element[i], qi = charge[i];
-    double off = 0.0, kl = 0.0, kr = 0.0;
+    double off = 0.0;
     for (int p = rp[r] + l; p < rp[r + 1]; p += LPR) {
         const int c = ci[p];
-        if (c == r) { cf[p] = c; continue; }
-        const int j = N_left + c;
-        const int ej = element[j];
-        if (CB == 2 && (k_interstitial(ei) || k_interstitial(ej))) { cf[p] = r; continue; }      // no link: stored as the row's own column, which k_kc_apply skips
-        const bool hi = k_high<CB>(ei, ej, qi, charge[j], ms);
-        cf[p] = hi ? (c | (int)0x80000000) : c;
-        off += hi ? high_G : low_G;
+        if (c == r) { cf[p] = r; continue; }        // the diagonal
+        const int link = k_link<CB>(ei, qi, N_left + c, element, charge, ms);
+        if (link == K_NOLINK) { cf[p] = r; continue; }        // no link: stored as the row's own column, which k_kc_apply skips
+        cf[p] = k_word(link, c);
+        off += link == K_HIGH ? high_G : low_G;
     }
-    const bool cut = CB == 2 && k_interstitial(ei);
-    for (int p = lrp[r] + l; p < lrp[r + 1] && !cut; p += LPR) { const int j = lci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kl += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    for (int p = rrp[r] + l; p < rrp[r + 1] && !cut; p += LPR) { const int j = N_left + m + rci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kr += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    { off = group_sum<LPR>(off); kl = group_sum<LPR>(kl); kr = group_sum<LPR>(kr); }
-    if (l == 0) {
-        double d = off;          // reduce_rows_into_diag: -(sum of off-diagonals)
-        d += kl;                 // add_vector_to_diagonal (left)
-        d += kr;                 // add_vector_to_diagonal (right)
-        if (CB == 2 && d == 0.0) d = 1.0;      // an unlinked interstitial site: identity row, value 0
-        diag[r] = d;
-        rhs[r] = kl * VL + kr * VR;
-    }
+    k_assemble_tail<CB, LPR>(r, l, off, k_contacts<CB, LPR>(r, l, m, N_left, ei, qi, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci), VL, VR, diag, rhs);
 }
 
 // s = 1/sqrt(diag); b *= s; y /= s; q = s y
@@ -205,29 +242,16 @@ __global__ __launch_bounds__(KC_NT) void k_kb_assemble(int m, int N_left, int R,
     const int base = kb_row_base(blk[bb], rb - bb * R, &width);
     const int r = perm[rb], i = N_left + r;
     const int ei = element[i], qi = charge[i];
-    double off = 0.0, kl = 0.0, kr = 0.0;
+    double off = 0.0;
     for (int k = l; k < width; k += LPR) {
         const int c = pcol[base + k];
         if (c == rb) { cf[base + k] = rb; continue; }        // padding
-        const int j = N_left + perm[c];
-        const int ej = element[j];
-        if (CB == 2 && (k_interstitial(ei) || k_interstitial(ej))) { cf[base + k] = rb; continue; }      // no link: stored like padding
-        const bool hi = k_high<CB>(ei, ej, qi, charge[j], ms);
-        cf[base + k] = hi ? (c | (int)0x80000000) : c;
-        off += hi ? high_G : low_G;
+        const int link = k_link<CB>(ei, qi, N_left + perm[c], element, charge, ms);
+        if (link == K_NOLINK) { cf[base + k] = rb; continue; }        // no link: stored like padding
+        cf[base + k] = k_word(link, c);
+        off += link == K_HIGH ? high_G : low_G;
     }
-    const bool cut = CB == 2 && k_interstitial(ei);
-    for (int p = lrp[r] + l; p < lrp[r + 1] && !cut; p += LPR) { const int j = lci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kl += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    for (int p = rrp[r] + l; p < rrp[r + 1] && !cut; p += LPR) { const int j = N_left + m + rci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kr += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    { off = group_sum<LPR>(off); kl = group_sum<LPR>(kl); kr = group_sum<LPR>(kr); }
-    if (l == 0) {
-        double d = off;
-        d += kl;
-        d += kr;
-        if (CB == 2 && d == 0.0) d = 1.0;
-        diag[rb] = d;
-        rhs[rb] = kl * VL + kr * VR;
-    }
+    k_assemble_tail<CB, LPR>(rb, l, off, k_contacts<CB, LPR>(r, l, m, N_left, ei, qi, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci), VL, VR, diag, rhs);
 }
 // s = 1/sqrt(diag); b *= s; yb = y[perm] / s; q = s yb   (entry into the blocked order)
 __global__ void k_kb_scale(int m, const int *__restrict__ perm, const double *__restrict__ diag, double *__restrict__ s, double *__restrict__ b,
@@ -258,6 +282,61 @@ __device__ __forceinline__ void kb_load_row(const int *__restrict__ cf, const in
         if (width == 64) { cc[2] = cr[8]; cc[3] = cr[12]; }
     }
 }
+// The pass loop of the two blocked products: lane l of the 4 of row k, k + KB_NT / 4, ... of a block of nrows rows that starts at row r0.
+// win: the block's window of q in LDS; a stored column c is read at win[c - woff] (blocked form: woff = first column of the window; windowed
+// form: a literal 0, the columns are offsets into the window) and is the row itself -- padding, no link: skipped -- when it equals self0 + k.
+// row: the stored columns of the first pass, requested by the kernel before it waits for its window.
+// The products of a row are added pairwise: t = s (d q - sum) cancels to a small fraction of its terms, and the rounding of that sum is what
+// limits the residual K-CG can reach (k_kc_apply: at the crossbar log's 1e-12 a left-to-right sum needed 820 instead of 735 iterations).
+// Every load of a pass is requested before anything is waited for -- the columns of the NEXT pass as soon as this pass's gathers are issued --:
+// one global latency + LDS per pass instead of a chain.  113 VGPR (MODE 0; MODE 1: 107), no scratch: 4 waves per SIMD, what one 1024-thread
+// workgroup per CU (the LDS window) runs at.
+struct KbRow { int4 cc[4]; bool lg; };
+template <int MODE>
+__device__ __forceinline__ void kb_rows(const double *win, int woff, int self0, int r0, int nrows, int k, int l, KbRow row0, const int4 bi, const int *__restrict__ cf,
+                                        const double *__restrict__ diag, const double *__restrict__ s, double high_G, double low_G, const double *__restrict__ pv,
+                                        double *__restrict__ t, double *__restrict__ part, const double *__restrict__ b, double *__restrict__ r, double *__restrict__ p,
+                                        double (*red)[KB_NT / 64])
+{
+    KbRow cur = row0;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (; k < nrows; k += KB_NT / 4) {
+        const int row = r0 + k, self = self0 + k;
+        const double qr = win[self - woff], dg = diag[row], sv = s[row];
+        const double a1 = MODE == 0 ? pv[row] : b[row], a2 = MODE == 0 ? r[row] : 0.0;
+        int c[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[4 * j] = cur.cc[j].x; c[4 * j + 1] = cur.cc[j].y; c[4 * j + 2] = cur.cc[j].z; c[4 * j + 3] = cur.cc[j].w; }
+        const bool lgc = cur.lg;
+        double x[16];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = win[(c[u] & 0x7fffffff) - woff];
+        if (lgc) {
+#pragma unroll
+            for (int u = 8; u < 16; ++u) x[u] = win[(c[u] & 0x7fffffff) - woff];
+        }
+        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cur.cc, &cur.lg);      // next pass
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
+        double sum = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
+        if (lgc) {
+#pragma unroll
+            for (int u = 8; u < 16; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
+            sum += ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
+        }
+        sum = group_sum<4>(sum);
+        if (l == 0) {
+            const double tv = sv * (dg * qr - sum);
+            if (MODE == 0) { t[row] = tv; acc[0] += a1 * tv; acc[1] += a2 * tv; acc[2] += tv * tv; }
+            else { const double rv = -a1 + tv; r[row] = rv; p[row] = -rv; acc[0] += rv * rv; }
+        }
+    }
+    block_sum_n<KB_NT, 3>(acc, red);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = acc[0];
+        if (MODE == 0) { part[KC_NPA + blockIdx.x] = acc[1]; part[2 * KC_NPA + blockIdx.x] = acc[2]; }
+    }
+}
 template <int MODE>
 __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__restrict__ blk, const int *__restrict__ cf, const double *__restrict__ diag,
                                                     const double *__restrict__ s, const double *__restrict__ q, double high_G, double low_G,
@@ -275,52 +354,14 @@ __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__
     double wv[KB_WREG];
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; wv[j] = idx < wn ? q[wlo + idx] : 0.0; }
-    int4 cc[4];
-    bool lg;
-    int k = g;
-    kb_load_row(cf, bi, k, l, k < nrows, cc, &lg);
+    KbRow row;
+    kb_load_row(cf, bi, g, l, g < nrows, row.cc, &row.lg);
     if (MODE == 0 && threadIdx.x == 0) sdone = ctrl->done;
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; if (idx < wn) win[idx] = wv[j]; }
     __syncthreads();
     if (MODE == 0 && sdone) return;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (; k < nrows; k += KB_NT / 4) {
-        const int row = r0 + k;
-        const double qr = win[row - wlo], dg = diag[row], sv = s[row];
-        const double a1 = MODE == 0 ? pv[row] : b[row], a2 = MODE == 0 ? r[row] : 0.0;
-        int c[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { c[4 * j] = cc[j].x; c[4 * j + 1] = cc[j].y; c[4 * j + 2] = cc[j].z; c[4 * j + 3] = cc[j].w; }
-        const bool lgc = lg;
-        double x[16];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = win[(c[u] & 0x7fffffff) - wlo];
-        if (lgc) {
-#pragma unroll
-            for (int u = 8; u < 16; ++u) x[u] = win[(c[u] & 0x7fffffff) - wlo];
-        }
-        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cc, &lg);      // next pass
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = (c[u] & 0x7fffffff) == row ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
-        double sum = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
-        if (lgc) {
-#pragma unroll
-            for (int u = 8; u < 16; ++u) x[u] = (c[u] & 0x7fffffff) == row ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
-            sum += ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
-        }
-        sum = group_sum<4>(sum);
-        if (l == 0) {
-            const double tv = sv * (dg * qr - sum);
-            if (MODE == 0) { t[row] = tv; acc[0] += a1 * tv; acc[1] += a2 * tv; acc[2] += tv * tv; }
-            else { const double rv = -a1 + tv; r[row] = rv; p[row] = -rv; acc[0] += rv * rv; }
-        }
-    }
-    block_sum_n<KB_NT, 3>(acc, red);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = acc[0];
-        if (MODE == 0) { part[KC_NPA + blockIdx.x] = acc[1]; part[2 * KC_NPA + blockIdx.x] = acc[2]; }
-    }
+    kb_rows<MODE>(win, wlo, r0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
 }
 
 // ---- the windowed blocked form of K (above KB_MAXROWS rows, opt-in: dkmc_set_k_blocked_large) --------------------------------------------
@@ -329,7 +370,7 @@ __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__
 // rows of a column in x -- and cuts them into blocks of R rows whose window (every row the block reads) is a short list of contiguous
 // segments of that order (at most KBW_MAXSEG), copied one after the other into one LDS image; the stored columns are offsets into that image.
 // Same storage of the rows (no row pointers; > 32 entries first, padded to 64, the others to 32; padding = the row's own offset), same
-// pairwise row sums and fused partials as k_kb_apply; more blocks than CUs run as a grid, several workgroups per CU one after the other.
+// pass loop (kb_rows: pairwise row sums, fused partials) as k_kb_apply; more blocks than CUs run as a grid, several workgroups per CU one after the other.
 // The iteration keeps the reference-order three launches (product, k_kc_update, k_kc_direction; see k_kc_update for why beta is summed directly).
 // LDS budget KB_MAXWIN doubles (112 KiB of the 160 KiB per CU): one 1024-thread workgroup per CU, 16 waves = 4 per SIMD.
 // k_kbw_apply<0>: 113 VGPR, 79 SGPR, no scratch (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; <1>: 107 VGPR): registers and LDS window
@@ -370,29 +411,16 @@ __global__ __launch_bounds__(KC_NT) void k_kbw_assemble(int m, int N_left, int R
     const int self = bi.y + (rb - bb * R);                   // the row's own offset in the window
     const int r = perm[rb], i = N_left + r;
     const int ei = element[i], qi = charge[i];
-    double off = 0.0, kl = 0.0, kr = 0.0;
+    double off = 0.0;
     for (int k = l; k < width; k += LPR) {
         const int c = pcol[base + k];
-        if (c == self) { cf[base + k] = self; continue; }    // padding
-        const int j = N_left + perm[kbw_row(sg, c)];
-        const int ej = element[j];
-        if (CB == 2 && (k_interstitial(ei) || k_interstitial(ej))) { cf[base + k] = self; continue; }      // no link: stored like padding
-        const bool hi = k_high<CB>(ei, ej, qi, charge[j], ms);
-        cf[base + k] = hi ? (c | (int)0x80000000) : c;
-        off += hi ? high_G : low_G;
+        if (c == self) { cf[base + k] = self; continue; }        // padding
+        const int link = k_link<CB>(ei, qi, N_left + perm[kbw_row(sg, c)], element, charge, ms);
+        if (link == K_NOLINK) { cf[base + k] = self; continue; }        // no link: stored like padding
+        cf[base + k] = k_word(link, c);
+        off += link == K_HIGH ? high_G : low_G;
     }
-    const bool cut = CB == 2 && k_interstitial(ei);
-    for (int p = lrp[r] + l; p < lrp[r + 1] && !cut; p += LPR) { const int j = lci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kl += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    for (int p = rrp[r] + l; p < rrp[r + 1] && !cut; p += LPR) { const int j = N_left + m + rci[p]; const int ej = element[j]; if (CB == 2 && k_interstitial(ej)) continue; kr += k_high<CB>(ei, ej, qi, charge[j], ms) ? high_G : low_G; }
-    { off = group_sum<LPR>(off); kl = group_sum<LPR>(kl); kr = group_sum<LPR>(kr); }
-    if (l == 0) {
-        double d = off;
-        d += kl;
-        d += kr;
-        if (CB == 2 && d == 0.0) d = 1.0;
-        diag[rb] = d;
-        rhs[rb] = kl * VL + kr * VR;
-    }
+    k_assemble_tail<CB, LPR>(rb, l, off, k_contacts<CB, LPR>(r, l, m, N_left, ei, qi, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci), VL, VR, diag, rhs);
 }
 template <int MODE>
 __global__ __launch_bounds__(KB_NT) void k_kbw_apply(int m, int R, const int4 *__restrict__ blk, const int4 *__restrict__ seg, const int *__restrict__ cf,
@@ -422,60 +450,28 @@ __global__ __launch_bounds__(KB_NT) void k_kbw_apply(int m, int R, const int4 *_
         for (int u = 0; u < KBW_MAXSEG; ++u) gb = idx >= slo[u] ? sbase[u] : gb;
         wv[j] = idx < wn ? q[gb + idx] : 0.0;
     }
-    int4 cc[4];
-    bool lg;
-    int k = g;
-    kb_load_row(cf, bi, k, l, k < nrows, cc, &lg);
+    KbRow row;
+    kb_load_row(cf, bi, g, l, g < nrows, row.cc, &row.lg);
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; if (idx < wn) win[idx] = wv[j]; }
     __syncthreads();
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (; k < nrows; k += KB_NT / 4) {
-        const int row = r0 + k, self = self0 + k;
-        const double qr = win[self], dg = diag[row], sv = s[row];
-        const double a1 = MODE == 0 ? pv[row] : b[row], a2 = MODE == 0 ? r[row] : 0.0;
-        int c[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { c[4 * j] = cc[j].x; c[4 * j + 1] = cc[j].y; c[4 * j + 2] = cc[j].z; c[4 * j + 3] = cc[j].w; }
-        const bool lgc = lg;
-        double x[16];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = win[c[u] & 0x7fffffff];
-        if (lgc) {
-#pragma unroll
-            for (int u = 8; u < 16; ++u) x[u] = win[c[u] & 0x7fffffff];
-        }
-        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cc, &lg);      // next pass
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
-        double sum = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
-        if (lgc) {
-#pragma unroll
-            for (int u = 8; u < 16; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
-            sum += ((x[8] + x[9]) + (x[10] + x[11])) + ((x[12] + x[13]) + (x[14] + x[15]));
-        }
-        sum = group_sum<4>(sum);
-        if (l == 0) {
-            const double tv = sv * (dg * qr - sum);
-            if (MODE == 0) { t[row] = tv; acc[0] += a1 * tv; acc[1] += a2 * tv; acc[2] += tv * tv; }
-            else { const double rv = -a1 + tv; r[row] = rv; p[row] = -rv; acc[0] += rv * rv; }
-        }
-    }
-    block_sum_n<KB_NT, 3>(acc, red);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = acc[0];
-        if (MODE == 0) { part[KC_NPA + blockIdx.x] = acc[1]; part[2 * KC_NPA + blockIdx.x] = acc[2]; }
-    }
+    kb_rows<MODE>(win, 0, self0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
 }
 
-__global__ __launch_bounds__(KC_NT) void k_kc_check0(double *part, KCtrl *ctrl, double tol2)
+// The vector kernels of the reference-order loop, written once: LIST = false over all rows i < n (k_kc_*), LIST = true over the n rows of a
+// list (k_ks_*, the slab-distributed loop: a rank's own rows).  A compile-time flag: the dense kernels carry neither a branch nor an argument for it.
+// xa: block partials of the start's r.r (n of them); LIST = false also leaves the total in *rr0 (slot 0 of the first r.r array, whose other slots are zero).
+template <bool LIST>
+__device__ __forceinline__ void kc_check0(int n, const double *xa, double *rr0, KCtrl *ctrl, double tol2)
 {
     __shared__ double red[KC_NT / 64];
     double s = 0.0;
-    for (int i = threadIdx.x; i < KC_NPA; i += KC_NT) s += part[i];
+    for (int i = threadIdx.x; i < n; i += KC_NT) s += xa[i];
     const double rr = block_sum_all<KC_NT>(s, red);
-    if (threadIdx.x == 0) { part[3 * KC_NPA] = rr; ctrl->rr[0] = rr; ctrl->rr[1] = rr; ctrl->iters = 0; ctrl->done = !(sqrt(rr) > tol2); }
+    if (threadIdx.x == 0) { if (!LIST) *rr0 = rr; ctrl->rr[0] = rr; ctrl->rr[1] = rr; ctrl->iters = 0; ctrl->done = !(sqrt(rr) > tol2); }
 }
+// (rr0 points into part[]: slot 0 of the r.r array that iteration 0 reads; the partials summed are MODE 1's r.r in the p.t array)
+__global__ __launch_bounds__(KC_NT) void k_kc_check0(double *part, KCtrl *ctrl, double tol2) { kc_check0<false>(KC_NPA, part, part + 3 * KC_NPA, ctrl, tol2); }
 __global__ __launch_bounds__(KC_NT) void k_kc_step(int m, int it, double *__restrict__ part, double *__restrict__ p, const double *__restrict__ t,
                                                    double *__restrict__ y, double *__restrict__ r, const double *__restrict__ s, double *__restrict__ q,
                                                    KCtrl *ctrl, double tol2, int npa)
@@ -529,9 +525,9 @@ __global__ __launch_bounds__(KC_NT) void k_kc_step(int m, int it, double *__rest
 // events; with the direct sums it follows the reference-order iterate to rounding and the events of the 9.4e5-site superstep are the oracle's.
 // At a converged tolerance (the reference's logs: 1e-12) the two loops agree to 1e-9 V, and below 2.6e5 rows the K solve is latency-bound:
 // the blocked form keeps the two-launch loop.
-__global__ __launch_bounds__(KC_NT) void k_kc_update(int m, int it, const double *__restrict__ part, int npa, const double *__restrict__ p,
-                                                     const double *__restrict__ t, double *__restrict__ y, double *__restrict__ r,
-                                                     double *__restrict__ part_rr, const KCtrl *ctrl)
+template <bool LIST>
+__device__ __forceinline__ void kc_update(int n, const int *__restrict__ rows, int it, const double *__restrict__ part, int npa, const double *__restrict__ p,
+                                          const double *__restrict__ t, double *__restrict__ y, double *__restrict__ r, double *__restrict__ part_rr, const KCtrl *ctrl)
 {
     __shared__ double red[KC_NT / 64];
     __shared__ int sdone;
@@ -542,30 +538,33 @@ __global__ __launch_bounds__(KC_NT) void k_kc_update(int m, int it, const double
     if (sdone) return;
     const double alpha = ctrl->rr[it & 1] / pAp;
     double acc = 0.0;
-    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < m; i += gridDim.x * KC_NT) {
-        y[i] += alpha * p[i];
-        const double rn = r[i] + alpha * t[i];
-        r[i] = rn;
+    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < n; i += gridDim.x * KC_NT) {
+        const int row = LIST ? rows[i] : i;
+        y[row] += alpha * p[row];
+        const double rn = r[row] + alpha * t[row];
+        r[row] = rn;
         acc += rn * rn;
     }
     const double tot = block_sum_all<KC_NT>(acc, red);
     if (threadIdx.x == 0) part_rr[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(KC_NT) void k_kc_direction(int m, int it, const double *__restrict__ part_rr, const double *__restrict__ r,
-                                                        double *__restrict__ p, const double *__restrict__ s, double *__restrict__ q, KCtrl *ctrl, double tol2)
+template <bool LIST>
+__device__ __forceinline__ void kc_direction(int n, const int *__restrict__ rows, int it, const double *__restrict__ part_rr, int np, const double *__restrict__ r,
+                                             double *__restrict__ p, const double *__restrict__ s, double *__restrict__ q, KCtrl *ctrl, double tol2)
 {
     __shared__ double red[KC_NT / 64];
     __shared__ int sdone;
     if (threadIdx.x == 0) sdone = ctrl->done;
     double a = 0.0;
-    for (int j = threadIdx.x; j < KC_NP; j += KC_NT) a += part_rr[j];
+    for (int j = threadIdx.x; j < np; j += KC_NT) a += part_rr[j];
     const double rr_new = block_sum_all<KC_NT>(a, red);
     if (sdone) return;
     const double beta = rr_new / ctrl->rr[it & 1];
-    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < m; i += gridDim.x * KC_NT) {
-        const double pn = p[i] * beta - r[i];
-        p[i] = pn;
-        q[i] = s[i] * pn;
+    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < n; i += gridDim.x * KC_NT) {
+        const int row = LIST ? rows[i] : i;
+        const double pn = p[row] * beta - r[row];
+        p[row] = pn;
+        q[row] = s[row] * pn;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         ctrl->rr[(it + 1) & 1] = rr_new;
@@ -573,11 +572,20 @@ __global__ __launch_bounds__(KC_NT) void k_kc_direction(int m, int it, const dou
         if (!(rr_new > tol2)) ctrl->done = 1;
     }
 }
-__global__ void k_kc_q(int m, const double *__restrict__ s, const double *__restrict__ p, double *__restrict__ q)
+__global__ __launch_bounds__(KC_NT) void k_kc_update(int m, int it, const double *__restrict__ part, int npa, const double *__restrict__ p,
+                                                     const double *__restrict__ t, double *__restrict__ y, double *__restrict__ r,
+                                                     double *__restrict__ part_rr, const KCtrl *ctrl)
+{ kc_update<false>(m, nullptr, it, part, npa, p, t, y, r, part_rr, ctrl); }
+__global__ __launch_bounds__(KC_NT) void k_kc_direction(int m, int it, const double *__restrict__ part_rr, const double *__restrict__ r,
+                                                        double *__restrict__ p, const double *__restrict__ s, double *__restrict__ q, KCtrl *ctrl, double tol2)
+{ kc_direction<false>(m, nullptr, it, part_rr, KC_NP, r, p, s, q, ctrl, tol2); }
+template <bool LIST>
+__device__ __forceinline__ void kc_q(int n, const int *__restrict__ rows, const double *__restrict__ s, const double *__restrict__ p, double *__restrict__ q)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) q[i] = s[i] * p[i];
+    if (i < n) { const int row = LIST ? rows[i] : i; q[row] = s[row] * p[row]; }
 }
+__global__ void k_kc_q(int m, const double *__restrict__ s, const double *__restrict__ p, double *__restrict__ q) { kc_q<false>(m, nullptr, s, p, q); }
 __global__ void k_kc_unscale(int m, double *__restrict__ y, const double *__restrict__ s)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -592,20 +600,73 @@ static inline int kc_grid(long long work, int per_block, int cap)
     return (int)b;
 }
 
+// cb (0 potential rule, 1 CB-edge rule, 2 CB-edge rule on atoms only) as the CB template argument: f(std::integral_constant<int, CB>)
+template <class F> static void kc_with_cb(int cb, F &&f)
+{
+    if (cb == 2) f(std::integral_constant<int, 2>{}); else if (cb) f(std::integral_constant<int, 1>{}); else f(std::integral_constant<int, 0>{});
+}
+// the dynamic-LDS limit of the two instantiations of a blocked product, raised to the largest window once per process (*set)
+template <class K> static int kb_raise_lds_limit(K apply0, K apply1, bool *set)
+{
+    if (*set) return 0;
+    HIPCHK(hipFuncSetAttribute((const void *)apply0, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
+    HIPCHK(hipFuncSetAttribute((const void *)apply1, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
+    *set = true;
+    return 0;
+}
+// The host's poll loop of both K-CG loops: reads *ctrl_d into h, stops on done, on iter_cap (> 0: the emulation's cap) or after 200 000 iterations
+// (recorded as a failure), else enqueues a batch of iterations (8, 16, 32, then 64 at a time) through enqueue(it), whose error code ends the loop at once.
+template <class F> static int kcg_poll(const KCtrl *ctrl_d, KCtrl &h, int iter_cap, hipStream_t st, F &&enqueue)
+{
+    int it = 0, batch = 8;
+    for (;;) {
+        HIPCHK(hipMemcpyAsync(&h, ctrl_d, sizeof(KCtrl), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h.done) break;
+        if (iter_cap > 0 && it >= iter_cap) break;
+        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
+        for (int b = 0; b < batch; ++b, ++it) if (int rc = enqueue(it)) return rc;
+        KCHK();
+        if (batch < 64) batch *= 2;
+    }
+    return 0;
+}
+// a K pattern on the host: row pointers, columns, x and (y_d, z_d not null) y, z of its rows
+namespace { struct KPattern { std::vector<int> rp, ci; std::vector<double> x, y, z; }; }
+static bool kpattern_download(KPattern &P, const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st)
+{
+    P.rp = std::vector<int>(m + 1); P.ci = std::vector<int>(nnz); P.x = std::vector<double>(m);
+    if (hipMemcpyAsync(P.rp.data(), rp_d, (size_t)(m + 1) * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+    if (hipMemcpyAsync(P.ci.data(), ci_d, (size_t)nnz * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+    if (hipMemcpyAsync(P.x.data(), x_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+    if (y_d) { P.y = std::vector<double>(m); if (hipMemcpyAsync(P.y.data(), y_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return false; }
+    if (z_d) { P.z = std::vector<double>(m); if (hipMemcpyAsync(P.z.data(), z_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return false; }
+    return hipStreamSynchronize(st) == hipSuccess;
+}
+void kblocked_free(KBlocked *kb);
+// the tables of a blocked form onto the device (seg: the windowed form's segment tables, or null); frees kb and returns nullptr when that fails
+static KBlocked *kblocked_upload(KBlocked *kb, const int *perm, const int *pcol, const void *blk, const void *seg)
+{
+    const size_t nperm = (size_t)kb->m * 4, npcol = (size_t)kb->total * 4, nblk = (size_t)kb->nb * sizeof(int4), nseg = (size_t)kb->nb * KBW_MAXSEG * sizeof(int4);
+    bool ok = hipMalloc((void **)&kb->perm, nperm) == hipSuccess && hipMalloc((void **)&kb->pcol, npcol) == hipSuccess &&
+              hipMalloc((void **)&kb->blk, nblk) == hipSuccess && (!seg || hipMalloc((void **)&kb->seg, nseg) == hipSuccess);
+    ok = ok && hipMemcpy(kb->perm, perm, nperm, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(kb->pcol, pcol, npcol, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(kb->blk, blk, nblk, hipMemcpyHostToDevice) == hipSuccess && (!seg || hipMemcpy(kb->seg, seg, nseg, hipMemcpyHostToDevice) == hipSuccess);
+    if (!ok) { kblocked_free(kb); (void)hipGetLastError(); return nullptr; }
+    return kb;
+}
+
 // Builds the blocked form of a K pattern (host side, once per initialize_sparsity; nullptr when the system is too large for it, a row has
 // more than 64 off-diagonal entries or a window does not fit the LDS: the solve then uses the CSR positions).  x: device pointer to the x
 // coordinate of the pattern's rows.
 #define KB_MAXROWS 262144
-void kblocked_free(KBlocked *kb);
 KBlocked *kblocked_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, hipStream_t st)
 {
     if (!eng().k_blocked || m < 1 || m > KB_MAXROWS || nnz < 1) return nullptr;
-    std::vector<int> rp(m + 1), ci(nnz);
-    std::vector<double> x(m);
-    if (hipMemcpyAsync(rp.data(), rp_d, (size_t)(m + 1) * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(ci.data(), ci_d, (size_t)nnz * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(x.data(), x_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+    KPattern H;
+    if (!kpattern_download(H, rp_d, ci_d, m, nnz, x_d, nullptr, nullptr, st)) return nullptr;
+    const std::vector<int> &rp = H.rp, &ci = H.ci;
+    const std::vector<double> &x = H.x;
     std::vector<int> perm(m);
     for (int i = 0; i < m; ++i) perm[i] = i;
     std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return x[a] < x[b]; });
@@ -647,14 +708,7 @@ KBlocked *kblocked_build(const int *rp_d, const int *ci_d, int m, int nnz, const
         maxwin = std::max(maxwin, blk[b].y); winsum += blk[b].y;
     }
     if (maxwin > KB_MAXWIN) return nullptr;
-    KBlocked *kb = new KBlocked{m, R, nb, (int)total, maxwin, maxints, winsum, nullptr, nullptr, nullptr};
-    bool ok = hipMalloc((void **)&kb->perm, (size_t)m * 4) == hipSuccess && hipMalloc((void **)&kb->pcol, (size_t)total * 4) == hipSuccess &&
-              hipMalloc((void **)&kb->blk, (size_t)nb * sizeof(int4)) == hipSuccess;
-    ok = ok && hipMemcpy(kb->perm, perm.data(), (size_t)m * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(kb->pcol, pcol.data(), (size_t)total * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(kb->blk, blk.data(), (size_t)nb * sizeof(int4), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { kblocked_free(kb); (void)hipGetLastError(); return nullptr; }
-    return kb;
+    return kblocked_upload(new KBlocked{m, R, nb, (int)total, maxwin, maxints, winsum, nullptr, nullptr, nullptr}, perm.data(), pcol.data(), blk.data(), nullptr);
 }
 void kblocked_free(KBlocked *kb)
 {
@@ -673,30 +727,16 @@ static int g_kbw_segcap = KBW_MAXSEG;       // dkmc_debug_kbw_segment_cap (test 
 extern "C" void dkmc_debug_kbw_segment_cap(int cap) { g_kbw_segcap = (cap < 1 || cap > KBW_MAXSEG) ? KBW_MAXSEG : cap; }
 static KBlocked *kbw_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st)
 {
-    std::vector<int> rp(m + 1), ci(nnz);
-    std::vector<double> x(m), y(m), z(m);
-    if (hipMemcpyAsync(rp.data(), rp_d, (size_t)(m + 1) * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(ci.data(), ci_d, (size_t)nnz * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(x.data(), x_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(y.data(), y_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(z.data(), z_d, (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return nullptr;
-    if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+    KPattern H;
+    if (!kpattern_download(H, rp_d, ci_d, m, nnz, x_d, y_d, z_d, st)) return nullptr;
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 256;
     KbwPlan P;
-    if (kbw_plan(m, rp.data(), ci.data(), x.data(), y.data(), z.data(), ncu, KB_MAXWIN, g_kbw_segcap, KC_NPA, P) || P.R < KC_NT / 16) return nullptr;
+    if (kbw_plan(m, H.rp.data(), H.ci.data(), H.x.data(), H.y.data(), H.z.data(), ncu, KB_MAXWIN, g_kbw_segcap, KC_NPA, P) || P.R < KC_NT / 16) return nullptr;
     KBlocked *kb = new KBlocked{m, P.R, P.nb, P.total, P.maxwin, P.maxints, P.winsum, nullptr, nullptr, nullptr};
     kb->form = 2; kb->maxseg = P.maxseg; kb->segsum = P.segsum;
     static_assert(sizeof(KbwI4) == sizeof(int4), "segment table layout");
-    bool ok = hipMalloc((void **)&kb->perm, (size_t)m * 4) == hipSuccess && hipMalloc((void **)&kb->pcol, (size_t)P.total * 4) == hipSuccess &&
-              hipMalloc((void **)&kb->blk, (size_t)P.nb * sizeof(int4)) == hipSuccess &&
-              hipMalloc((void **)&kb->seg, (size_t)P.nb * KBW_MAXSEG * sizeof(int4)) == hipSuccess;
-    ok = ok && hipMemcpy(kb->perm, P.perm.data(), (size_t)m * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(kb->pcol, P.pcol.data(), (size_t)P.total * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(kb->blk, P.blk.data(), (size_t)P.nb * sizeof(int4), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(kb->seg, P.seg.data(), (size_t)P.nb * KBW_MAXSEG * sizeof(int4), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { kblocked_free(kb); (void)hipGetLastError(); return nullptr; }
-    return kb;
+    return kblocked_upload(kb, P.perm.data(), P.pcol.data(), P.blk.data(), P.seg.data());
 }
 // The form initialize_sparsity keeps for a K pattern: the windowed form above KB_MAXROWS rows when dkmc_set_k_blocked_large(1), else the
 // blocked form (nullptr above KB_MAXROWS).
@@ -736,35 +776,20 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const double tol2 = e.cg_tol * e.cg_tol;
     const int ab = (m + 15) / 16, vb = (m + 255) / 256;
     const size_t lds = kb ? (size_t)kb->maxwin * 8 : 0;
-    if (kbw) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            HIPCHK(hipFuncSetAttribute((const void *)k_kbw_apply<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
-            HIPCHK(hipFuncSetAttribute((const void *)k_kbw_apply<1>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
-            attr_set = true;
-        }
-#define KBW_ASM(CBV) hipLaunchKernelGGL((k_kbw_assemble<CBV>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm, \
-                                        (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs)
-        if (cb == 2) KBW_ASM(2); else if (cb) KBW_ASM(1); else KBW_ASM(0);
-#undef KBW_ASM
-        hipLaunchKernelGGL(k_kb_scale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)diag, s, rhs, (const double *)y_site, y, q);
-    } else if (kb) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            HIPCHK(hipFuncSetAttribute((const void *)k_kb_apply<0>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
-            HIPCHK(hipFuncSetAttribute((const void *)k_kb_apply<1>, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
-            attr_set = true;
-        }
-        if (cb == 2) hipLaunchKernelGGL((k_kb_assemble<2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else if (cb) hipLaunchKernelGGL((k_kb_assemble<1>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else hipLaunchKernelGGL((k_kb_assemble<0>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        hipLaunchKernelGGL(k_kb_scale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)diag, s, rhs, (const double *)y_site, y, q);
-    } else {
-        if (cb == 2) hipLaunchKernelGGL((k_kc_assemble<2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else if (cb) hipLaunchKernelGGL((k_kc_assemble<1>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else hipLaunchKernelGGL((k_kc_assemble<0>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        hipLaunchKernelGGL(k_kc_scale, dim3(vb), dim3(256), 0, st, m, (const double *)diag, s, rhs, y, q);
+    if (kb) {
+        static bool lds_set[2] = {false, false};
+        if (int rc = kbw ? kb_raise_lds_limit(k_kbw_apply<0>, k_kbw_apply<1>, &lds_set[1]) : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
     }
+    kc_with_cb(cb, [&](auto cbv) {
+        constexpr int CB = decltype(cbv)::value;
+        if (kbw) hipLaunchKernelGGL((k_kbw_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
+                                    (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else if (kb) hipLaunchKernelGGL((k_kb_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol,
+                                        element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else hipLaunchKernelGGL((k_kc_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+    });
+    if (kb) hipLaunchKernelGGL(k_kb_scale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)diag, s, rhs, (const double *)y_site, y, q);
+    else hipLaunchKernelGGL(k_kc_scale, dim3(vb), dim3(256), 0, st, m, (const double *)diag, s, rhs, y, q);
     static hipEvent_t evk[2]; static bool evk_ready = false;
     const bool prof = e.profiling != 0;
     if (prof && !evk_ready) { HIPCHK(hipEventCreate(&evk[0])); HIPCHK(hipEventCreate(&evk[1])); evk_ready = true; }
@@ -798,13 +823,7 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     hipLaunchKernelGGL(k_kc_check0, dim3(1), dim3(KC_NT), 0, st, part, ctrl, tol2);
     KCHK();
     if (prof) HIPCHK(hipEventRecord(evk[0], st));
-    int it = 0, batch = 8;
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(KCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h.done) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int b = 0; b < batch; ++b, ++it) {
+    if (int rc = kcg_poll(ctrl, h, 0, st, [&](int it) -> int {
             KC_APPLY(0, (const int *)cf, (const double *)diag, (const double *)s, (const double *)q, high_G, low_G,
                      (const double *)p, t, part, (const KCtrl *)ctrl, (const double *)nullptr, r, (double *)nullptr);
             if (kb && !kbw) hipLaunchKernelGGL(k_kc_step, dim3(gv), dim3(KC_NT), 0, st, m, it, part, p, (const double *)t, y, r, (const double *)s, q, ctrl, tol2, npa);
@@ -812,10 +831,8 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
                 hipLaunchKernelGGL(k_kc_update, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)part, npa, (const double *)p, (const double *)t, y, r, part + 3 * KC_NPA, (const KCtrl *)ctrl);
                 hipLaunchKernelGGL(k_kc_direction, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)(part + 3 * KC_NPA), (const double *)r, p, (const double *)s, q, ctrl, tol2);
             }
-        }
-        KCHK();
-        if (batch < 64) batch *= 2;
-    }
+            return 0;
+        })) return rc;
     if (prof) {
         HIPCHK(hipEventRecord(evk[1], st));
         HIPCHK(hipEventSynchronize(evk[1]));
@@ -846,66 +863,15 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
 // -- identical scalars on every rank by construction, so all ranks stop at the same iteration and no flag has to travel.  Vectors keep their full
 // length on every rank (29 MB each at 3.6e6 rows); entries a rank neither owns nor reads are never touched.  The solution's own rows are
 // all-gathered once at the end.  The same host loop runs N VIRTUAL ranks in one process (dkmc_kcg_emulate_slabs): how it is tested on one GPU.
-#define KS_NPA 2048         // block partials of the product per rank (its largest grid: 8 workgroups per CU; 16 KB per rank in exchange 1)
-#define KS_NP 512           // block partials of r'.r' per rank (4 KB per rank in exchange 2)
-__global__ __launch_bounds__(KC_NT) void k_ks_check0(int n, const double *__restrict__ xa, KCtrl *ctrl, double tol2)
-{
-    __shared__ double red[KC_NT / 64];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += KC_NT) s += xa[i];
-    const double rr = block_sum_all<KC_NT>(s, red);
-    if (threadIdx.x == 0) { ctrl->rr[0] = rr; ctrl->rr[1] = rr; ctrl->iters = 0; ctrl->done = !(sqrt(rr) > tol2); }
-}
+// (the block partials per rank are KC_NPA / KC_NP as on one GPU -- k_kc_apply stores at KC_NPA strides --: 16 KB per rank in exchange 1, 4 KB in exchange 2)
+__global__ __launch_bounds__(KC_NT) void k_ks_check0(int n, const double *__restrict__ xa, KCtrl *ctrl, double tol2) { kc_check0<true>(n, xa, nullptr, ctrl, tol2); }
 __global__ __launch_bounds__(KC_NT) void k_ks_update(int n, const int *__restrict__ rows, int it, const double *__restrict__ xa, int na, const double *__restrict__ p,
                                                      const double *__restrict__ t, double *__restrict__ y, double *__restrict__ r, double *__restrict__ xb_mine, const KCtrl *ctrl)
-{
-    __shared__ double red[KC_NT / 64];
-    __shared__ int sdone;
-    if (threadIdx.x == 0) sdone = ctrl->done;
-    double a = 0.0;
-    for (int j = threadIdx.x; j < na; j += KC_NT) a += xa[j];
-    const double pAp = block_sum_all<KC_NT>(a, red);
-    if (sdone) return;
-    const double alpha = ctrl->rr[it & 1] / pAp;
-    double acc = 0.0;
-    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < n; i += gridDim.x * KC_NT) {
-        const int row = rows[i];
-        y[row] += alpha * p[row];
-        const double rn = r[row] + alpha * t[row];
-        r[row] = rn;
-        acc += rn * rn;
-    }
-    const double tot = block_sum_all<KC_NT>(acc, red);
-    if (threadIdx.x == 0) xb_mine[blockIdx.x] = tot;
-}
+{ kc_update<true>(n, rows, it, xa, na, p, t, y, r, xb_mine, ctrl); }
 __global__ __launch_bounds__(KC_NT) void k_ks_direction(int n, const int *__restrict__ rows, int it, const double *__restrict__ xb, int nb, const double *__restrict__ r,
                                                         double *__restrict__ p, const double *__restrict__ s, double *__restrict__ q, KCtrl *ctrl, double tol2)
-{
-    __shared__ double red[KC_NT / 64];
-    __shared__ int sdone;
-    if (threadIdx.x == 0) sdone = ctrl->done;
-    double a = 0.0;
-    for (int j = threadIdx.x; j < nb; j += KC_NT) a += xb[j];
-    const double rr_new = block_sum_all<KC_NT>(a, red);
-    if (sdone) return;
-    const double beta = rr_new / ctrl->rr[it & 1];
-    for (int i = blockIdx.x * KC_NT + threadIdx.x; i < n; i += gridDim.x * KC_NT) {
-        const int row = rows[i];
-        const double pn = p[row] * beta - r[row];
-        p[row] = pn;
-        q[row] = s[row] * pn;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctrl->rr[(it + 1) & 1] = rr_new;
-        ctrl->iters = it + 1;
-        if (!(rr_new > tol2)) ctrl->done = 1;
-    }
-}
-__global__ void k_ks_q(int n, const int *__restrict__ rows, const double *__restrict__ s, const double *__restrict__ p, double *__restrict__ q)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { const int row = rows[i]; q[row] = s[row] * p[row]; }
-}
+{ kc_direction<true>(n, rows, it, xb, nb, r, p, s, q, ctrl, tol2); }
+__global__ void k_ks_q(int n, const int *__restrict__ rows, const double *__restrict__ s, const double *__restrict__ p, double *__restrict__ q) { kc_q<true>(n, rows, s, p, q); }
 __global__ void k_ks_gather(int n, const int *__restrict__ list, const double *__restrict__ v, double *__restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1006,7 +972,7 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
         for (int d = 0; d < nr; ++d) { if (d == v) continue; K.nhs += hal[v * nr + d]; K.nhr += hal[d * nr + v]; }
         int *li = (int *)salloc(iv, S_KS_RLISTS, ((size_t)K.nhs + K.nhr + 8) * 4);
         double *vec = iv == 0 ? nullptr : (double *)salloc(iv, 0, (size_t)m * 8 * 5);
-        K.xa = (double *)salloc(iv, S_KS_XA, (size_t)nr * KS_NPA * 8); K.xb = (double *)salloc(iv, S_KS_XB, (size_t)nr * KS_NP * 8);
+        K.xa = (double *)salloc(iv, S_KS_XA, (size_t)nr * KC_NPA * 8); K.xb = (double *)salloc(iv, S_KS_XB, (size_t)nr * KC_NP * 8);
         K.send = (double *)salloc(iv, S_KS_SEND, (size_t)(K.nhs + 8) * 8); K.recv = (double *)salloc(iv, S_KS_RECV, (size_t)(K.nhr + 8) * 8);
         K.ybuf = (double *)salloc(iv, S_KS_YBUF, (size_t)nr * maxown * 8);
         K.ctrl = iv == 0 ? (KCtrl *)scratch(S_CG_CTRL, sizeof(KCtrl)) : (KCtrl *)salloc(iv, 0, sizeof(KCtrl));
@@ -1040,21 +1006,21 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
             ro_ += hal[d * nr + v];
         }
         HIPCHK(hipMemsetAsync(K.ctrl, 0, sizeof(KCtrl), st));
-        HIPCHK(hipMemsetAsync(K.xa, 0, (size_t)nr * KS_NPA * 8, st));
-        HIPCHK(hipMemsetAsync(K.xb, 0, (size_t)nr * KS_NP * 8, st));
+        HIPCHK(hipMemsetAsync(K.xa, 0, (size_t)nr * KC_NPA * 8, st));
+        HIPCHK(hipMemsetAsync(K.xb, 0, (size_t)nr * KC_NP * 8, st));
     }
     KCHK();
     // ---- exchanges ----
     auto xchg = [&](int which) -> int {          // 1: product partials, 2: r.r partials (all-gathers); 3: halo of q (all-to-all-v); 4: the solution's own rows (all-gather)
         if (!emu) {
             KsRank &K = RK[0];
-            if (which == 1) return comm_allgather_f64(K.xa, (size_t)KS_NPA);
-            if (which == 2) return comm_allgather_f64(K.xb, (size_t)KS_NP);
+            if (which == 1) return comm_allgather_f64(K.xa, (size_t)KC_NPA);
+            if (which == 2) return comm_allgather_f64(K.xb, (size_t)KC_NP);
             if (which == 3) return comm_alltoallv_f64(K.send, K.recv, cnt3.data());
             return comm_allgather_f64(K.ybuf, (size_t)maxown);
         }
         if (which != 3) {
-            const size_t n = which == 1 ? KS_NPA : (which == 2 ? KS_NP : (size_t)maxown);
+            const size_t n = which == 1 ? KC_NPA : (which == 2 ? KC_NP : (size_t)maxown);
             for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) {
                 if (a == d) continue;
                 double *src = (which == 1 ? RK[a].xa : which == 2 ? RK[a].xb : RK[a].ybuf) + (size_t)a * n;
@@ -1096,57 +1062,48 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
     // ---- r = A y - b, p = -r, q = S p ----
     for (int iv = 0; iv < nv; ++iv) {
         KsRank &K = RK[iv];
-        const int ga = kc_grid(K.n_own, KC_NT / 8, KS_NPA);
+        const int ga = kc_grid(K.n_own, KC_NT / 8, KC_NPA);
         if (K.n_own > 0) {
             hipLaunchKernelGGL((k_kc_apply<1>), dim3(ga), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G, (const double *)nullptr, K.t,
-                               K.xa + (size_t)K.v * KS_NPA, (const KCtrl *)K.ctrl, b, K.r, K.p, (const int *)K.own);
+                               K.xa + (size_t)K.v * KC_NPA, (const KCtrl *)K.ctrl, b, K.r, K.p, (const int *)K.own);
             hipLaunchKernelGGL(k_ks_q, dim3((K.n_own + 255) / 256), dim3(256), 0, st, K.n_own, (const int *)K.own, s, (const double *)K.p, K.q);
         }
     }
     if (int rcx = xchg(1)) return rcx;
-    for (int iv = 0; iv < nv; ++iv) hipLaunchKernelGGL(k_ks_check0, dim3(1), dim3(KC_NT), 0, st, nr * KS_NPA, (const double *)RK[iv].xa, RK[iv].ctrl, tol2);
+    for (int iv = 0; iv < nv; ++iv) hipLaunchKernelGGL(k_ks_check0, dim3(1), dim3(KC_NT), 0, st, nr * KC_NPA, (const double *)RK[iv].xa, RK[iv].ctrl, tol2);
     if (int rcx = halo(false)) return rcx;
     KCHK();
     KCtrl h{};
-    int it = 0, batch = 8;
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, RK[0].ctrl, sizeof(KCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h.done) break;
-        if (emu && g_ks_iter_cap > 0 && it >= g_ks_iter_cap) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int bq = 0; bq < batch; ++bq, ++it) {
-            const bool on = timing && it >= 2 && tcount < 24;
-            for (int iv = 0; iv < nv; ++iv) {
-                KsRank &K = RK[iv];
-                if (K.n_own <= 0) continue;
-                int rc = timed(iv, 0, on, [&]() {
-                    hipLaunchKernelGGL((k_kc_apply<2>), dim3(kc_grid(K.n_own, KC_NT / 8, KS_NPA)), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G,
-                                       (const double *)K.p, K.t, K.xa + (size_t)K.v * KS_NPA, (const KCtrl *)K.ctrl, (const double *)nullptr, K.r, (double *)nullptr, (const int *)K.own);
-                }); if (rc) return rc;
-            }
-            if (int rcx = xchg(1)) return rcx;
-            for (int iv = 0; iv < nv; ++iv) {
-                KsRank &K = RK[iv];
-                int rc = timed(iv, 1, on, [&]() {
-                    hipLaunchKernelGGL(k_ks_update, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KS_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xa, nr * KS_NPA,
-                                       (const double *)K.p, (const double *)K.t, K.y, K.r, K.xb + (size_t)K.v * KS_NP, (const KCtrl *)K.ctrl);
-                }); if (rc) return rc;
-            }
-            if (int rcx = xchg(2)) return rcx;
-            for (int iv = 0; iv < nv; ++iv) {
-                KsRank &K = RK[iv];
-                int rc = timed(iv, 2, on, [&]() {
-                    hipLaunchKernelGGL(k_ks_direction, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KS_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xb, nr * KS_NP,
-                                       (const double *)K.r, K.p, s, K.q, K.ctrl, tol2);
-                }); if (rc) return rc;
-            }
-            if (int rcx = halo(on)) return rcx;
-            if (on) ++tcount;
+    if (int rc = kcg_poll(RK[0].ctrl, h, emu ? g_ks_iter_cap : 0, st, [&](int it) -> int {
+        const bool on = timing && it >= 2 && tcount < 24;
+        for (int iv = 0; iv < nv; ++iv) {
+            KsRank &K = RK[iv];
+            if (K.n_own <= 0) continue;
+            int rc = timed(iv, 0, on, [&]() {
+                hipLaunchKernelGGL((k_kc_apply<2>), dim3(kc_grid(K.n_own, KC_NT / 8, KC_NPA)), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G,
+                                   (const double *)K.p, K.t, K.xa + (size_t)K.v * KC_NPA, (const KCtrl *)K.ctrl, (const double *)nullptr, K.r, (double *)nullptr, (const int *)K.own);
+            }); if (rc) return rc;
         }
-        KCHK();
-        if (batch < 64) batch *= 2;
-    }
+        if (int rcx = xchg(1)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) {
+            KsRank &K = RK[iv];
+            int rc = timed(iv, 1, on, [&]() {
+                hipLaunchKernelGGL(k_ks_update, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xa, nr * KC_NPA,
+                                   (const double *)K.p, (const double *)K.t, K.y, K.r, K.xb + (size_t)K.v * KC_NP, (const KCtrl *)K.ctrl);
+            }); if (rc) return rc;
+        }
+        if (int rcx = xchg(2)) return rcx;
+        for (int iv = 0; iv < nv; ++iv) {
+            KsRank &K = RK[iv];
+            int rc = timed(iv, 2, on, [&]() {
+                hipLaunchKernelGGL(k_ks_direction, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xb, nr * KC_NP,
+                                   (const double *)K.r, K.p, s, K.q, K.ctrl, tol2);
+            }); if (rc) return rc;
+        }
+        if (int rcx = halo(on)) return rcx;
+        if (on) ++tcount;
+        return 0;
+    })) return rc;
     if (e.err_code) return e.err_code;
     if (emu) {
         for (int iv = 1; iv < nv; ++iv) {
