@@ -140,6 +140,7 @@ struct KBlocked {
     int maxseg = 0;     // segments of the most fragmented window
     long long segsum = 0;
     int4 *seg = nullptr;
+    int word_bytes = 4; // form 2: bytes of a stored word of the assembled cf (dkmc_set_k_window_word_bytes when the pattern was built); pcol stays 32-bit
 };
 // ---- host side ---------------------------------------------------------------------------------
 struct Engine {
@@ -153,6 +154,7 @@ struct Engine {
     double pair_cut = 6.5;         // screening cut-off of the pair sum in units of sigma sqrt 2 (dkmc_set_pair_cutoff; 0 = all pairs like the reference)
     int k_blocked = 1;             // build the blocked form of K patterns (dkmc_set_k_blocked; kcg.hip)
     int k_blocked_large = 0;       // 1: above KB_MAXROWS rows build the windowed blocked form instead (dkmc_set_k_blocked_large; kcg.hip)
+    int k_window_word_bytes = 4;   // stored words of the windowed blocked form: 4 = one int per entry, 2 = 16 bits per entry (14-bit LDS offset + class bit 15); same results (dkmc_set_k_window_word_bytes; kcg.hip)
     int x_aux = 2;                 // auxiliary columns of the block-CG (dkmc_set_x_aux; xtb.hip): 0 hash set, 1 smooth set, 2 smooth at tolerances >= 1e-8
     int x_slab = 1;                // > 1 rank: distribute the STATE of the block-CG by row slabs (xtb_slab.inc; dkmc_set_x_slab); 0: all-gather variant (tile stream sharded only)
     int k_slab = 1;                // > 1 rank, system above the size of the blocked form: CG on K distributed by row slabs (kcg.hip; dkmc_set_k_slab); 0: replicated

@@ -72,6 +72,8 @@ void dkmc_set_k_blocked(int on) { eng().k_blocked = on ? 1 : 0; }
 int dkmc_get_k_blocked(void) { return eng().k_blocked; }
 void dkmc_set_k_blocked_large(int on) { eng().k_blocked_large = on ? 1 : 0; }
 int dkmc_get_k_blocked_large(void) { return eng().k_blocked_large; }
+void dkmc_set_k_window_word_bytes(int bytes) { eng().k_window_word_bytes = bytes == 2 ? 2 : 4; }
+int dkmc_get_k_window_word_bytes(void) { return eng().k_window_word_bytes; }
 void dkmc_set_cb_edge_domain(int atoms_only) { eng().cb_edge_domain = atoms_only ? 1 : 0; }
 
 int dkmc_get_gpu_info(char *gpu_string, int capacity, int dev)

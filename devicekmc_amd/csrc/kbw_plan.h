@@ -17,6 +17,18 @@
 #define KBW_MAXSEG 16           // segments per block window (fixed: the table has KBW_MAXSEG entries per block)
 #define KBW_GAP 256             // rows of the order between two used runs that are copied rather than starting a new segment
 
+// The 2-byte layout of a row's stored words (dkmc_set_k_window_word_bytes(2)): position, in 16-bit words from the start of the row, of entry e of a
+// row padded to `width` (32 or 64) entries.  The product gives a row 4 lanes, and lane l holds entries 4l..4l+3 and 16+4l..16+4l+3 (of a 64-wide row
+// also 32+4l.. and 48+4l..) in that order; with 16-bit words those eight entries are the 16-byte chunk l of the row (the second eight: chunk 4 + l),
+// so one 16-byte load per lane and chunk delivers them in the same slots.  A permutation of 0..width-1; -1 outside the row or for another width.
+// (constexpr: k_kbw_assemble calls it on the device, the host and the tests through dkmc_debug_kbw_halfword_pos)
+constexpr inline int kbw_halfword_pos(int width, int e)
+{
+    if ((width != 32 && width != 64) || e < 0 || e >= width) return -1;
+    const int j = e / 16, l = e % 16 / 4, u = e % 4;          // j: which four-entry group of the lane (ints 16 j + 4 l ...)
+    return ((j / 2 * 4 + l) * 2 + j % 2) * 4 + u;
+}
+
 struct KbwI4 { int x, y, z, w; };
 struct KbwPlan {
     int R = 0, nb = 0, total = 0, maxwin = 0, maxints = 0, maxseg = 0;

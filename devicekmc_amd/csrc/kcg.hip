@@ -14,7 +14,8 @@
 // K is stored in one of three forms, each with its own assemble and product kernels; what fixes the physics and the rounding is written once:
 //   CSR positions (k_kc_*)                                            any size; also what the slab-distributed loop (k_ks_*, row lists) runs on
 //   blocked form (k_kb_*), one x-sorted LDS window per block          up to KB_MAXROWS rows (default there)
-//   windowed blocked form (k_kbw_*), a window of up to KBW_MAXSEG segments   above KB_MAXROWS rows, opt-in (dkmc_set_k_blocked_large)
+//   windowed blocked form (k_kbw_*), a window of up to KBW_MAXSEG segments   above KB_MAXROWS rows, opt-in (dkmc_set_k_blocked_large); its stored words
+//                                                                     take 4 or, opt-in, 2 bytes (dkmc_set_k_window_word_bytes): same operations, same bits
 // Shared bodies (__forceinline__, values in and out, so every kernel compiles to what its written-out text did):
 //   assembly   k_link (the rule of one entry), k_word (what is stored for it), k_contacts (the two contact sums), k_assemble_tail (diagonal and rhs)
 //   product    kb_rows: the pass loop of k_kb_apply and k_kbw_apply (k_kc_apply: 8 lanes per row, no LDS -- another algorithm, on its own)
@@ -55,6 +56,8 @@ __device__ __forceinline__ int k_link(int ei, int qi, int j, const int *__restri
 }
 // what is stored for a link to column c: class bit 31 (no link: the column the form's product skips, the row itself, like the padding)
 __device__ __forceinline__ int k_word(int link, int c) { return link == K_HIGH ? (c | (int)0x80000000) : c; }
+// the 16-bit word of the windowed form (WB = 2): c is an offset into an LDS window of at most KB_MAXWIN <= 2^14 doubles, class bit 15, bit 14 zero
+__device__ __forceinline__ unsigned short k_word16(int link, int c) { return (unsigned short)(link == K_HIGH ? (c | 0x8000) : c); }
 // the links of row r (site i) to the left and to the right contact, lane l of the row's LPR
 struct KContacts { double kl, kr; };
 template <int CB, int LPR>
@@ -271,15 +274,45 @@ __global__ void k_kb_unscale(int m, const int *__restrict__ perm, const double *
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) y[perm[i]] = yb[i] * s[i];
 }
-__device__ __forceinline__ void kb_load_row(const int *__restrict__ cf, const int4 &bi, int k, int l, bool in, int4 (&cc)[4], bool *lg)
+// The stored words of one row as lane l of its 4 lanes loads them, 16 bytes per load.  WB = 4 (ints): ints 4l.. and 16+4l.. (wide rows: 32+4l.., 48+4l.. too),
+// four loads.  WB = 2 (the windowed form with dkmc_set_k_window_word_bytes(2)): the same entries as 16-bit words, chunk l of the row (wide rows: chunk
+// 4 + l too; kbw_plan.h: kbw_halfword_pos), two loads.  kb_unpack gives both the ints c[0..15] of the 4-byte form -- offset | class bit 31 -- in the same
+// slots, so everything after it is one text.
+static_assert(KB_MAXWIN <= 1 << 14, "a 16-bit stored word keeps the LDS offset in bits 0-13");
+template <int WB> struct KbRow { int4 cc[WB == 2 ? 2 : 4]; bool lg; };
+template <int WB>
+__device__ __forceinline__ void kb_load_row(const int *__restrict__ cf, const int4 &bi, int k, int l, bool in, KbRow<WB> &row)
 {
     int width;
-    const int base = kb_row_base(bi, k, &width);
-    *lg = in && width == 64;
-    if (in) {
+    const int base = kb_row_base(bi, k, &width);          // in words of WB bytes
+    row.lg = in && width == 64;
+    if (!in) return;
+    if (WB == 2) {
+        const int4 *cr = (const int4 *)((const unsigned short *)cf + base) + l;
+        row.cc[0] = cr[0];
+        if (width == 64) row.cc[1] = cr[4];
+    } else {
         const int4 *cr = (const int4 *)(cf + base) + l;
-        cc[0] = cr[0]; cc[1] = cr[4];
-        if (width == 64) { cc[2] = cr[8]; cc[3] = cr[12]; }
+        row.cc[0] = cr[0]; row.cc[1] = cr[4];
+        if (width == 64) { row.cc[2] = cr[8]; row.cc[3] = cr[12]; }
+    }
+}
+template <int WB>
+__device__ __forceinline__ void kb_unpack(const KbRow<WB> &row, int (&c)[16])
+{
+    if (WB == 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const unsigned v[4] = {(unsigned)row.cc[j].x, (unsigned)row.cc[j].y, (unsigned)row.cc[j].z, (unsigned)row.cc[j].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {          // low half: the even entry, high half: the odd one
+                c[8 * j + 2 * i] = (int)((v[i] & 0x3fffu) | ((v[i] << 16) & 0x80000000u));
+                c[8 * j + 2 * i + 1] = (int)(((v[i] >> 16) & 0x3fffu) | (v[i] & 0x80000000u));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[4 * j] = row.cc[j].x; c[4 * j + 1] = row.cc[j].y; c[4 * j + 2] = row.cc[j].z; c[4 * j + 3] = row.cc[j].w; }
     }
 }
 // The pass loop of the two blocked products: lane l of the 4 of row k, k + KB_NT / 4, ... of a block of nrows rows that starts at row r0.
@@ -290,23 +323,22 @@ __device__ __forceinline__ void kb_load_row(const int *__restrict__ cf, const in
 // limits the residual K-CG can reach (k_kc_apply: at the crossbar log's 1e-12 a left-to-right sum needed 820 instead of 735 iterations).
 // Every load of a pass is requested before anything is waited for -- the columns of the NEXT pass as soon as this pass's gathers are issued --:
 // one global latency + LDS per pass instead of a chain.  113 VGPR (MODE 0; MODE 1: 107), no scratch: 4 waves per SIMD, what one 1024-thread
-// workgroup per CU (the LDS window) runs at.
-struct KbRow { int4 cc[4]; bool lg; };
-template <int MODE>
-__device__ __forceinline__ void kb_rows(const double *win, int woff, int self0, int r0, int nrows, int k, int l, KbRow row0, const int4 bi, const int *__restrict__ cf,
+// workgroup per CU (the LDS window) runs at.  WB: bytes of a stored word (KbRow<WB>, kb_load_row, kb_unpack); only the load of a row's words and
+// their unpacking differ (WB = 2: 106 / 100 VGPR, no scratch -- two int4 of words in flight per lane instead of four).
+template <int MODE, int WB>
+__device__ __forceinline__ void kb_rows(const double *win, int woff, int self0, int r0, int nrows, int k, int l, KbRow<WB> row0, const int4 bi, const int *__restrict__ cf,
                                         const double *__restrict__ diag, const double *__restrict__ s, double high_G, double low_G, const double *__restrict__ pv,
                                         double *__restrict__ t, double *__restrict__ part, const double *__restrict__ b, double *__restrict__ r, double *__restrict__ p,
                                         double (*red)[KB_NT / 64])
 {
-    KbRow cur = row0;
+    KbRow<WB> cur = row0;
     double acc[3] = {0.0, 0.0, 0.0};
     for (; k < nrows; k += KB_NT / 4) {
         const int row = r0 + k, self = self0 + k;
         const double qr = win[self - woff], dg = diag[row], sv = s[row];
         const double a1 = MODE == 0 ? pv[row] : b[row], a2 = MODE == 0 ? r[row] : 0.0;
         int c[16];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { c[4 * j] = cur.cc[j].x; c[4 * j + 1] = cur.cc[j].y; c[4 * j + 2] = cur.cc[j].z; c[4 * j + 3] = cur.cc[j].w; }
+        kb_unpack(cur, c);
         const bool lgc = cur.lg;
         double x[16];
 #pragma unroll
@@ -315,7 +347,7 @@ __device__ __forceinline__ void kb_rows(const double *win, int woff, int self0, 
 #pragma unroll
             for (int u = 8; u < 16; ++u) x[u] = win[(c[u] & 0x7fffffff) - woff];
         }
-        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cur.cc, &cur.lg);      // next pass
+        kb_load_row(cf, bi, k + KB_NT / 4, l, k + KB_NT / 4 < nrows, cur);      // next pass
 #pragma unroll
         for (int u = 0; u < 8; ++u) x[u] = (c[u] & 0x7fffffff) == self ? 0.0 : (c[u] < 0 ? high_G : low_G) * x[u];
         double sum = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
@@ -354,14 +386,14 @@ __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__
     double wv[KB_WREG];
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; wv[j] = idx < wn ? q[wlo + idx] : 0.0; }
-    KbRow row;
-    kb_load_row(cf, bi, g, l, g < nrows, row.cc, &row.lg);
+    KbRow<4> row;
+    kb_load_row(cf, bi, g, l, g < nrows, row);
     if (MODE == 0 && threadIdx.x == 0) sdone = ctrl->done;
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; if (idx < wn) win[idx] = wv[j]; }
     __syncthreads();
     if (MODE == 0 && sdone) return;
-    kb_rows<MODE>(win, wlo, r0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
+    kb_rows<MODE, 4>(win, wlo, r0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
 }
 
 // ---- the windowed blocked form of K (above KB_MAXROWS rows, opt-in: dkmc_set_k_blocked_large) --------------------------------------------
@@ -378,6 +410,12 @@ __global__ __launch_bounds__(KB_NT) void k_kb_apply(int m, int R, const int4 *__
 // 3 189 rows, windows 3.4 x the rows, 7.2 segments per window): 173 us per launch against 304 us for k_kc_apply in the same run, 783 MB
 // per launch (4 B per stored entry, 36.8 per row with the padding; window copies; 5 vector touches) = 4.5 TB/s
 // (profiles/kcg_forms_tile20_product_launches.txt, kcg_forms_tile20_tile10.jsonl).
+// WB = 2 (dkmc_set_k_window_word_bytes(2), opt-in): a stored word is an offset into that LDS image (< KB_MAXWIN <= 2^14: bits 0-13) and the class (bit 15),
+// 16 bits; a row takes 64 or 128 bytes, its words placed (kbw_plan.h: kbw_halfword_pos) so that lane l's one 16-byte load per chunk holds the entries its
+// two loads of ints hold, in the same slots.  Every element of t is then the same sequence of fp64 operations as with WB = 4: the same bits.
+// k_kbw_apply<0, 2>: 106 VGPR, 79 SGPR, no scratch; <1, 2>: 100 VGPR, no scratch; <0, 4> / <1, 4>: 113 / 107 as before (same command); LDS unchanged.
+// tile:20: 514 MB per launch instead of 783, 135.6 us against 176.5 us for <0, 4> in the same run (3.8 against 4.4 TB/s on their bytes: no longer bound by
+// HBM alone), 191 against 234 us per iteration (profiles/kcg_words_tile20_product_launches.txt, kcg_words_tile20_tile10.jsonl).
 __device__ __forceinline__ int kbw_row(const int4 *sg, int off)
 {
     int g = 0;
@@ -386,7 +424,8 @@ __device__ __forceinline__ int kbw_row(const int4 *sg, int off)
     return g;
 }
 // (R >= KC_NT / 16: the 16 rows of a workgroup lie in at most two blocks, whose segment tables it keeps in LDS)
-template <int CB>
+// (WB = 2: cf holds 16-bit words, entry k of a row at kbw_halfword_pos(width, k); pcol, read once per solve, keeps its ints in entry order)
+template <int CB, int WB>
 __global__ __launch_bounds__(KC_NT) void k_kbw_assemble(int m, int N_left, int R, int nb, const int4 *__restrict__ blk, const int4 *__restrict__ seg,
                                                         const int *__restrict__ perm, const int *__restrict__ pcol, const int *__restrict__ element,
                                                         const int *__restrict__ charge, MetalSet ms, double high_G, double low_G,
@@ -414,15 +453,16 @@ __global__ __launch_bounds__(KC_NT) void k_kbw_assemble(int m, int N_left, int R
     double off = 0.0;
     for (int k = l; k < width; k += LPR) {
         const int c = pcol[base + k];
-        if (c == self) { cf[base + k] = self; continue; }        // padding
-        const int link = k_link<CB>(ei, qi, N_left + perm[kbw_row(sg, c)], element, charge, ms);
-        if (link == K_NOLINK) { cf[base + k] = self; continue; }        // no link: stored like padding
-        cf[base + k] = k_word(link, c);
-        off += link == K_HIGH ? high_G : low_G;
+        int link = K_NOLINK;                                      // padding, no link: stored as the row's own offset
+        if (c != self) link = k_link<CB>(ei, qi, N_left + perm[kbw_row(sg, c)], element, charge, ms);
+        const int cs = link == K_NOLINK ? self : c;
+        if (WB == 2) ((unsigned short *)cf)[base + kbw_halfword_pos(width, k)] = k_word16(link, cs);
+        else cf[base + k] = k_word(link, cs);
+        if (link != K_NOLINK) off += link == K_HIGH ? high_G : low_G;
     }
     k_assemble_tail<CB, LPR>(rb, l, off, k_contacts<CB, LPR>(r, l, m, N_left, ei, qi, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci), VL, VR, diag, rhs);
 }
-template <int MODE>
+template <int MODE, int WB>
 __global__ __launch_bounds__(KB_NT) void k_kbw_apply(int m, int R, const int4 *__restrict__ blk, const int4 *__restrict__ seg, const int *__restrict__ cf,
                                                      const double *__restrict__ diag, const double *__restrict__ s, const double *__restrict__ q,
                                                      double high_G, double low_G, const double *__restrict__ pv, double *__restrict__ t,
@@ -450,12 +490,12 @@ __global__ __launch_bounds__(KB_NT) void k_kbw_apply(int m, int R, const int4 *_
         for (int u = 0; u < KBW_MAXSEG; ++u) gb = idx >= slo[u] ? sbase[u] : gb;
         wv[j] = idx < wn ? q[gb + idx] : 0.0;
     }
-    KbRow row;
-    kb_load_row(cf, bi, g, l, g < nrows, row.cc, &row.lg);
+    KbRow<WB> row;
+    kb_load_row(cf, bi, g, l, g < nrows, row);
 #pragma unroll
     for (int j = 0; j < KB_WREG; ++j) { const int idx = threadIdx.x + j * KB_NT; if (idx < wn) win[idx] = wv[j]; }
     __syncthreads();
-    kb_rows<MODE>(win, 0, self0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
+    kb_rows<MODE, WB>(win, 0, self0, r0, nrows, g, l, row, bi, cf, diag, s, high_G, low_G, pv, t, part, b, r, p, red);
 }
 
 // The vector kernels of the reference-order loop, written once: LIST = false over all rows i < n (k_kc_*), LIST = true over the n rows of a
@@ -725,6 +765,7 @@ void kblocked_free(KBlocked *kb)
 // positions).  x, y, z: device pointers to the coordinates of the pattern's rows.
 static int g_kbw_segcap = KBW_MAXSEG;       // dkmc_debug_kbw_segment_cap (test aid)
 extern "C" void dkmc_debug_kbw_segment_cap(int cap) { g_kbw_segcap = (cap < 1 || cap > KBW_MAXSEG) ? KBW_MAXSEG : cap; }
+extern "C" int dkmc_debug_kbw_halfword_pos(int width, int entry) { return kbw_halfword_pos(width, entry); }
 static KBlocked *kbw_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st)
 {
     KPattern H;
@@ -734,7 +775,7 @@ static KBlocked *kbw_build(const int *rp_d, const int *ci_d, int m, int nnz, con
     KbwPlan P;
     if (kbw_plan(m, H.rp.data(), H.ci.data(), H.x.data(), H.y.data(), H.z.data(), ncu, KB_MAXWIN, g_kbw_segcap, KC_NPA, P) || P.R < KC_NT / 16) return nullptr;
     KBlocked *kb = new KBlocked{m, P.R, P.nb, P.total, P.maxwin, P.maxints, P.winsum, nullptr, nullptr, nullptr};
-    kb->form = 2; kb->maxseg = P.maxseg; kb->segsum = P.segsum;
+    kb->form = 2; kb->maxseg = P.maxseg; kb->segsum = P.segsum; kb->word_bytes = eng().k_window_word_bytes == 2 ? 2 : 4;
     static_assert(sizeof(KbwI4) == sizeof(int4), "segment table layout");
     return kblocked_upload(kb, P.perm.data(), P.pcol.data(), P.blk.data(), P.seg.data());
 }
@@ -764,7 +805,8 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     // the windowed form runs on one GPU only: more than one rank (or the emulation of it) keeps the slab-distributed loop on the CSR positions
     if (kb && kb->form == 2 && row_y && row_z && (emu_nr > 0 || (e.k_slab && comm_attached() && comm_nranks() > 1 && comm_nranks() <= XS_MAXR))) kb = nullptr;
     const bool kbw = kb && kb->form == 2;
-    int *cf = (int *)scratch(S_K_DATA, kb ? (size_t)kb->total * 4 : (size_t)nnz * 4);
+    const bool kbw2 = kbw && kb->word_bytes == 2;           // 16-bit stored words (dkmc_set_k_window_word_bytes when the pattern was built)
+    int *cf = (int *)scratch(S_K_DATA, kb ? (size_t)kb->total * (kbw2 ? 2 : 4) : (size_t)nnz * 4);
     double *rhs = (double *)scratch(S_K_RHS, (size_t)m * 8 * 3);
     double *s = (double *)scratch(S_CG_S, (size_t)m * 8), *r = (double *)scratch(S_CG_R, (size_t)m * 8);
     double *p = (double *)scratch(S_CG_P, (size_t)m * 8), *t = (double *)scratch(S_CG_T, (size_t)m * 8);
@@ -777,13 +819,16 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const int ab = (m + 15) / 16, vb = (m + 255) / 256;
     const size_t lds = kb ? (size_t)kb->maxwin * 8 : 0;
     if (kb) {
-        static bool lds_set[2] = {false, false};
-        if (int rc = kbw ? kb_raise_lds_limit(k_kbw_apply<0>, k_kbw_apply<1>, &lds_set[1]) : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
+        static bool lds_set[3] = {false, false, false};
+        if (int rc = kbw2 ? kb_raise_lds_limit(k_kbw_apply<0, 2>, k_kbw_apply<1, 2>, &lds_set[2]) : kbw ? kb_raise_lds_limit(k_kbw_apply<0, 4>, k_kbw_apply<1, 4>, &lds_set[1])
+                                                                                                        : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
     }
     kc_with_cb(cb, [&](auto cbv) {
         constexpr int CB = decltype(cbv)::value;
-        if (kbw) hipLaunchKernelGGL((k_kbw_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
-                                    (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        if (kbw2) hipLaunchKernelGGL((k_kbw_assemble<CB, 2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
+                                     (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else if (kbw) hipLaunchKernelGGL((k_kbw_assemble<CB, 4>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
+                                         (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
         else if (kb) hipLaunchKernelGGL((k_kb_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol,
                                         element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
         else hipLaunchKernelGGL((k_kc_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
@@ -799,7 +844,8 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const int npa = (ga + KC_NT - 1) / KC_NT * KC_NT;
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(KCtrl), st));
     HIPCHK(hipMemsetAsync(part, 0, (size_t)KC_PART_DOUBLES * 8, st));       // the slots beyond either grid stay zero
-#define KC_APPLY(MODE, ...) do { if (kbw) hipLaunchKernelGGL((k_kbw_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
+#define KC_APPLY(MODE, ...) do { if (kbw2) hipLaunchKernelGGL((k_kbw_apply<MODE, 2>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
+                                 else if (kbw) hipLaunchKernelGGL((k_kbw_apply<MODE, 4>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
                                  else if (kb) hipLaunchKernelGGL((k_kb_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, __VA_ARGS__); \
                                  else hipLaunchKernelGGL((k_kc_apply<MODE>), dim3(ga), dim3(KC_NT), 0, st, m, rp, __VA_ARGS__); } while (0)
     // more than one rank (or the emulation of it) on a system above the size of the blocked form: the loop distributed by row slabs
@@ -844,7 +890,7 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     else hipLaunchKernelGGL(k_kc_unscale, dim3(vb), dim3(256), 0, st, m, y, (const double *)s);
     KCHK();
     e.stats.kcg_blocked = kb ? kb->form : 0;
-    if (kbw) e.stats.kcg_bytes = 4LL * kb->total + 16LL * kb->nb * (1 + KBW_MAXSEG) + 8LL * kb->winsum + 16LL * 8 * m;       // (product 5 + update 6 + direction 5 vector touches)
+    if (kbw) e.stats.kcg_bytes = (kbw2 ? 2LL : 4LL) * kb->total + 16LL * kb->nb * (1 + KBW_MAXSEG) + 8LL * kb->winsum + 16LL * 8 * m;       // (product 5 + update 6 + direction 5 vector touches)
     else e.stats.kcg_bytes = kb ? 4LL * kb->total + 16LL * kb->nb + 8LL * kb->winsum + 14LL * 8 * m : 4LL * nnz + 4LL * (m + 1) + 17LL * 8 * m;
     if (iters_out) *iters_out = h.iters;
     if (rr_out) *rr_out = kb && !kbw ? h.rr[0] : h.rr[h.iters & 1];

@@ -186,6 +186,16 @@ extern "C" int dkmc_kcg_form_info(dkmc_gpubuf *buf, long long *info)
     return 0;
 }
 
+// measurement aid: word bytes, stored words and bytes of the assembled words of the buffer's windowed form (dkmc_kcg_form_words, devicekmc_hip_debug.h)
+extern "C" int dkmc_kcg_form_words(dkmc_gpubuf *buf, long long *info)
+{
+    if (!buf || !info) return dkmc_fail(13, "kcg_form_words: bad arguments", __FILE__, __LINE__);
+    for (int k = 0; k < 3; ++k) info[k] = 0;
+    const KBlocked *kb = buf->Device_row_ptr_d ? kpat_blocked(buf->Device_row_ptr_d) : nullptr;
+    if (kb && kb->form == 2) { info[0] = kb->word_bytes; info[1] = kb->total; info[2] = (long long)kb->total * kb->word_bytes; }
+    return 0;
+}
+
 // K values, rhs and the solve: kcg.hip (the off-diagonals of K take two values: the matrix is kept as class bits)
 __global__ void k_fill_contacts(double *field, int N, int N_left, int N_right, double vl, double vr, double scale_all)
 {

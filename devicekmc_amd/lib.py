@@ -84,7 +84,11 @@ SYMBOLS = {
     "dkmc_get_k_blocked": (_I, []),
     "dkmc_set_k_blocked_large": (None, [_I]),
     "dkmc_get_k_blocked_large": (_I, []),
+    "dkmc_set_k_window_word_bytes": (None, [_I]),
+    "dkmc_get_k_window_word_bytes": (_I, []),
     "dkmc_kcg_form_info": (_I, [C.POINTER(dkmc_gpubuf), C.POINTER(C.c_longlong)]),
+    "dkmc_kcg_form_words": (_I, [C.POINTER(dkmc_gpubuf), C.POINTER(C.c_longlong)]),
+    "dkmc_debug_kbw_halfword_pos": (_I, [_I, _I]),
     "dkmc_debug_kbw_segment_cap": (None, [_I]),
     "dkmc_set_pair_cutoff": (None, [_D]),
     "dkmc_reset_pair_sum_cache": (None, []),

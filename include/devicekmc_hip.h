@@ -100,7 +100,7 @@ typedef struct dkmc_stats {
     long long pair_tested;                 /* pairs whose distance was tested (all N x N_charged without the cell list; the 3 x 3 columns with it) */
     long long xt_records;                  /* records of column partial sums one matrix-vector product writes (= runs; runs / 4 on one GPU, where the four waves of a workgroup share one) */
     long long tcache_bytes;                /* bytes of tunnelling-coefficient cache THIS rank holds (sharded solve on the tiled X: what its tiles read) */
-    long long kcg_bytes;                   /* bytes one iteration of the last K solve moves: column/class words + the q windows (or one read of q per row) + 14 (15) vector touches */
+    long long kcg_bytes;                   /* bytes one iteration of the last K solve moves: column/class words (2 B each on the windowed form with dkmc_set_k_window_word_bytes(2)) + the q windows (or one read of q per row) + 14 (15) vector touches */
     int xb_aux, xb_pad;                    /* 1: the last block solve used the smooth auxiliary columns (dkmc_set_x_aux) */
     int xb_width, xb_fallback;             /* block-CG width of the last current solve (1 = single-vector loop); 1 if the block loop lost definiteness and the single-vector loop finished the solve */
 } dkmc_stats;
@@ -213,6 +213,14 @@ int dkmc_get_k_blocked(void);
  * form whatever this says, and the slab-distributed K loop (more than one rank attached) stays on the CSR positions.  Read when a pattern is built. */
 void dkmc_set_k_blocked_large(int on);
 int dkmc_get_k_blocked_large(void);
+/* Bytes of a stored word of the windowed blocked form (dkmc_set_k_blocked_large(1), above 262 144 rows, one GPU).  4 (default): one int per stored
+ * entry.  2: 16 bits per entry -- the entry is an offset into the block's LDS window (at most 14 336 doubles: bits 0-13) and the class of the link
+ * (bit 15) --, a row of 64 or 128 bytes laid out so that one 16-byte load per lane delivers the entries the lane holds with 4-byte words, in the same
+ * slots: every element of the product is formed by the same sequence of fp64 operations, the same bits, half the column bytes.  Any other value
+ * selects 4.  Nothing else changes: the blocked form up to 262 144 rows, the CSR positions and the slab-distributed K loop keep their words;
+ * dkmc_stats.kcg_blocked stays 2.  Read when a pattern is built. */
+void dkmc_set_k_window_word_bytes(int bytes);
+int dkmc_get_k_window_word_bytes(void);
 /* Start vector of the current solve.  1 (default): the previous step's solution, from a private unscaled copy kept per GPUBuffers -- what
  * the reference's own comment asks for ("use the previous solution as the initial guess", current_solver_gpu.cu:976-977).  0: whatever
  * gpubuf.atom_virtual_potentials holds, exactly as the reference code does -- and that buffer was scaled by G0 in place after the previous

@@ -91,6 +91,13 @@ int dkmc_kcg_emulate_slabs(dkmc_gpubuf *buf, int N, int N_left, int N_right, dou
  * (0 CSR positions, 1 blocked, 2 windowed blocked), rows, rows per block, blocks, doubles of the largest window, doubles of all windows, segments of
  * the most fragmented window, segments of all windows, stored column ints. */
 int dkmc_kcg_form_info(dkmc_gpubuf *buf, long long *info /* [9] */);
+/* Measurement aid: the stored words of the windowed blocked form of this buffer's pattern.  info[3]: bytes of a stored word (4 or 2,
+ * dkmc_set_k_window_word_bytes when the pattern was built; 0 when the pattern has no windowed form: the other two are 0 then too), stored words,
+ * bytes of the assembled words one product reads (words x word bytes). */
+int dkmc_kcg_form_words(dkmc_gpubuf *buf, long long *info /* [3] */);
+/* Test aid: position, in 16-bit words from the start of its row, of stored entry `entry` of a row padded to `width` (32 or 64) entries in the 2-byte
+ * layout of the windowed blocked form (csrc/kbw_plan.h: kbw_halfword_pos); -1 for any other width or an entry outside the row. */
+int dkmc_debug_kbw_halfword_pos(int width, int entry);
 /* Test aid: caps the segments of a window of the windowed blocked form of K (dkmc_set_k_blocked_large) below its fixed maximum (16) for the
  * patterns built afterwards, so that the builder refuses and the solve falls back to the CSR positions.  cap <= 0 restores 16. */
 void dkmc_debug_kbw_segment_cap(int cap);

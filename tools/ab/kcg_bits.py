@@ -5,7 +5,8 @@ Every case: cg_tol 1e-10, CB edge (setLaplacePotential) and background potential
 solve used (stats kcg_blocked), cg_iters_K / cg_iters_CB, cg_rr_K / cg_rr_CB as hex floats, sha256 of site_potential_boundary and of site_CB_edge.
   2.5nm    blocked form and CSR positions (dkmc_set_k_blocked 1 / 0) x CB edge on sites / on atoms: CB = 0, 1, 2 of k_kb_assemble and k_kc_assemble
   7.5nm    (85 071 sites: blocks with 64-wide and 32-wide rows) the same two forms; the slab emulation (dkmc_kcg_emulate_slabs) with 1, 2, 5 virtual ranks
-  tile:6   (338 364 sites, the smallest tile:K above 262 144 rows) dkmc_set_k_blocked_large(1): form 2 (dkmc_kcg_form_info), both solves
+  tile:6   (338 364 sites, the smallest tile:K above 262 144 rows) dkmc_set_k_blocked_large(1): form 2 (dkmc_kcg_form_info), both solves, with 4-byte and
+           with 2-byte stored words (dkmc_set_k_window_word_bytes): the two lines differ in `words` alone
 usage: python tools/ab/kcg_bits.py [2.5nm 7.5nm tile:6]"""
 import ctypes as C
 import hashlib
@@ -21,12 +22,13 @@ def sha(a):
     return hashlib.sha256(a.tobytes()).hexdigest()[:32]
 
 
-def solve(name, blocked, domain, large=0, slabs=()):
+def solve(name, blocked, domain, large=0, slabs=(), word_bytes=4):
     import torch
     from bench import make_workload
     from devicekmc_amd import host, lib
     L = lib.load()
     L.dkmc_set_k_blocked(blocked); L.dkmc_set_k_blocked_large(large)
+    L.dkmc_set_k_window_word_bytes(word_bytes)
     try:
         s, p = make_workload(name)
         p.cg_tol = 1e-10; p.cb_edge_domain = domain
@@ -51,13 +53,13 @@ def solve(name, blocked, domain, large=0, slabs=()):
         dev.updatePotential(gb, p, Vd, 0)
         torch.cuda.synchronize()
         st = host.get_stats()
-        print("%s k_blocked=%d large=%d cb_domain=%s form_info %d form_K %d form_CB %d iters_K %d iters_CB %d rr_K %s rr_CB %s phi %s cb_edge %s"
-              % (name, blocked, large, domain, info[0], int(st["kcg_blocked"]), form_cb, int(st["cg_iters_K"]), it_cb, float(st["cg_rr_K"]).hex(), rr_cb.hex(),
+        print("%s k_blocked=%d large=%d words=%d cb_domain=%s form_info %d form_K %d form_CB %d iters_K %d iters_CB %d rr_K %s rr_CB %s phi %s cb_edge %s"
+              % (name, blocked, large, word_bytes, domain, info[0], int(st["kcg_blocked"]), form_cb, int(st["cg_iters_K"]), it_cb, float(st["cg_rr_K"]).hex(), rr_cb.hex(),
                  sha(gb.site_potential_boundary.cpu().numpy()), sha(cb)), flush=True)
         del gb, dev
         torch.cuda.empty_cache()
     finally:
-        L.dkmc_set_k_blocked(1); L.dkmc_set_k_blocked_large(0); L.dkmc_set_cb_edge_domain(0); L.dkmc_set_cg_tolerance(1e-6)
+        L.dkmc_set_k_blocked(1); L.dkmc_set_k_blocked_large(0); L.dkmc_set_cb_edge_domain(0); L.dkmc_set_cg_tolerance(1e-6); L.dkmc_set_k_window_word_bytes(4)
 
 
 def main():
@@ -73,6 +75,7 @@ def main():
         else:
             for domain in ("sites", "atoms"):
                 solve(name, 1, domain, large=1)
+                solve(name, 1, domain, large=1, word_bytes=2)
 
 
 if __name__ == "__main__":

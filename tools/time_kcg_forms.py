@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""The CG on K on its CSR positions (default above 262 144 rows) against the windowed blocked form (dkmc_set_k_blocked_large(1)), on the same
-workloads with the current solve off: per form one background-potential solve from the Laplace start at the library's default tolerance (iterations,
+"""The CG on K on its CSR positions (default above 262 144 rows) against the windowed blocked form (dkmc_set_k_blocked_large(1)) with 4-byte and with
+2-byte stored words (dkmc_set_k_window_word_bytes), on the same workloads with the current solve off; the 4-byte case runs twice (first and last), so
+that the run-to-run spread of the reference point is on record.  Per case one background-potential solve from the Laplace start at the library's default tolerance (iterations,
 HIP-event time of the iteration loop per iteration: kcg_ms / kcg_iters_timed) and the superstep rate (charge + potential + events) over `steps`
 supersteps after one untimed one; for the windowed form the window and segment statistics of the build (dkmc_kcg_form_info).  The product's own
-launch time comes from a rocprofv3 --kernel-trace --stats run of this script (k_kc_apply against k_kbw_apply).
+launch time comes from a rocprofv3 --kernel-trace --stats run of this script (k_kc_apply against k_kbw_apply<0, 4> and k_kbw_apply<0, 2>).
 usage: python tools/time_kcg_forms.py [tile:20 tile:10 ...] [--steps 3]"""
 import argparse
 import ctypes as C
@@ -17,12 +18,12 @@ sys.path.insert(0, ROOT)
 Vd = 5.0
 
 
-def run(name, large, steps):
+def run(name, large, word_bytes, steps):
     import torch
     from bench import make_workload
     from devicekmc_amd import host, lib
     L = lib.load()
-    L.dkmc_set_k_blocked_large(large)
+    L.dkmc_set_k_blocked_large(large); L.dkmc_set_k_window_word_bytes(word_bytes)
     try:
         s, p = make_workload(name)
         p.solve_current = False; p.solve_heating_global = False
@@ -36,6 +37,8 @@ def run(name, large, steps):
         build_s = time.perf_counter() - t0
         info = (C.c_longlong * 9)()
         lib.check(L.dkmc_kcg_form_info(C.byref(gb.c), info))
+        words = (C.c_longlong * 3)()
+        lib.check(L.dkmc_kcg_form_words(C.byref(gb.c), words))
         dev.updateCharge(gb)
         L.dkmc_set_profiling(1)
         dev.updatePotential(gb, p, Vd, 0)
@@ -48,7 +51,8 @@ def run(name, large, steps):
         if info[0] == 2:
             f, rows, R, nb, maxwin, winsum, maxseg, segsum, ints = list(info)
             out.update(rows_per_block=R, blocks=nb, window_max=maxwin, window_mean=round(winsum / nb, 1), window_over_rows=round(winsum / rows, 3),
-                       segments_max=maxseg, segments_mean=round(segsum / nb, 2), stored_ints=ints, stored_ints_per_row=round(ints / rows, 2))
+                       segments_max=maxseg, segments_mean=round(segsum / nb, 2), stored_ints=ints, stored_ints_per_row=round(ints / rows, 2),
+                       word_bytes=int(words[0]), word_bytes_total=int(words[2]))
         _, dt = sim.executeKMCStep(gb, dev)
         k = 1
         torch.cuda.synchronize()
@@ -64,7 +68,7 @@ def run(name, large, steps):
         torch.cuda.empty_cache()
         return out
     finally:
-        L.dkmc_set_k_blocked_large(0); L.dkmc_set_profiling(0)
+        L.dkmc_set_k_blocked_large(0); L.dkmc_set_k_window_word_bytes(4); L.dkmc_set_profiling(0)
 
 
 def main():
@@ -73,8 +77,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     a = ap.parse_args()
     for name in a.workloads:
-        for large in (0, 1):
-            print(json.dumps(run(name, large, a.steps)), flush=True)
+        for large, word_bytes in ((1, 4), (0, 4), (1, 2), (1, 4)):
+            print(json.dumps(run(name, large, word_bytes, a.steps)), flush=True)
 
 
 if __name__ == "__main__":
