@@ -163,6 +163,8 @@ struct Engine {
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
     int x_apply_form = 0;          // tile x panel kernel of the block-CG: 0 = the product form, 1 = the round-4 form of its loop (same results; same-box comparisons, dkmc_set_x_apply_form)
+    int x_tile_f32 = 1;            // tile values of the block-CG's sweeps: 1 (auto) = the fp32 image inside the one-GPU preconditioned loop at cg_tol >= 1e-8, when the copy could be made; 0 = always the fp64 store (dkmc_set_x_tile_f32; xtb.hip)
+    int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
     int x_block = 16;              // block-CG width of the current solve on the tiled X (dkmc_set_x_block; xtb.hip): 16 by default, 1 = the reference's single-vector loop (its iterate sequence)
@@ -184,6 +186,8 @@ Engine &eng();
 int dkmc_fail(int code, const char *what, const char *file, int line);
 // persistent scratch: returns a device buffer of at least `bytes`, identified by slot
 void *scratch(int slot, size_t bytes);
+// the same for a buffer the caller can do without: null and NO error recorded when the allocation fails
+void *scratch_try(int slot, size_t bytes);
 inline MetalSet load_metals(const int *d_metals, int num_metals) { MetalSet ms; ms.n = num_metals; ms.e = d_metals; return ms; }
 
 #define HIPCHK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return dkmc_fail((int)e__, hipGetErrorString(e__), __FILE__, __LINE__); } while (0)
@@ -201,7 +205,7 @@ enum {
     S_P_IMACRO, S_HEAT, S_HEAT_A, S_HEAT_B, S_HEAT_Y,
     S_MISC0, S_MISC1, S_MISC2, S_MISC3,
     S_XT_DPOS, S_XT_SNODE_D, S_XT_SNODE_I, S_XT_CMASK, S_XT_ISTILE, S_XT_NSUBC, S_XT_TOFF, S_XT_SOFF, S_XT_TILES, S_XT_NITEMW, S_XT_WRANGE,
-    S_XT_ITEMS, S_XT_SPLIT, S_XT_TVAL, S_XT_ROWPART, S_XT_COLPART, S_XT_CNT, S_XT_Q,
+    S_XT_ITEMS, S_XT_SPLIT, S_XT_TVAL, S_XT_TVAL32, S_XT_ROWPART, S_XT_COLPART, S_XT_CNT, S_XT_Q,
     S_XT_T_NITEMW, S_XT_T_ITEMS, S_XT_T_SPLIT, S_XT_T_COLPART, S_XT_T_MISC,
     S_XTB_PANELS, S_XTB_QS, S_XTB_ROWPART, S_XTB_COLPART, S_XTB_GRAM, S_XTB_SMALL, S_XTB_XI,
     S_XTB_SLAB_BOX, S_XTB_SLAB_TAB, S_XTB_SLAB_OWNER, S_XTB_SLAB_LISTS, S_XTB_SLAB_SDST, S_XTB_SLAB_FLAG, S_XTB_SLAB_RLISTS, S_XTB_SLAB_GX, S_XTB_SLAB_S1, S_XTB_SLAB_S3, S_XTB_SLAB_R3,

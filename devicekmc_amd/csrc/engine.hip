@@ -34,6 +34,20 @@ void *scratch(int slot, size_t bytes)
     return e.buf[slot];
 }
 
+void *scratch_try(int slot, size_t bytes)
+{
+    Engine &e = eng();
+    if (bytes == 0) bytes = 16;
+    if (e.bufsz[slot] < bytes) {
+        if (e.buf[slot]) { (void)hipStreamSynchronize(e.stream); (void)hipFree(e.buf[slot]); }
+        e.buf[slot] = nullptr; e.bufsz[slot] = 0;
+        const size_t want = bytes + bytes / 8 + 256;
+        if (hipMalloc(&e.buf[slot], want) != hipSuccess) { (void)hipGetLastError(); e.buf[slot] = nullptr; return nullptr; }
+        e.bufsz[slot] = want;
+    }
+    return e.buf[slot];
+}
+
 extern "C" {
 
 const char *dkmc_last_error(void) { return eng().err; }
@@ -56,6 +70,9 @@ void dkmc_set_x_poly(int degree) { eng().x_poly = degree < 0 ? 0 : (degree > 16 
 int dkmc_get_x_poly(void) { return eng().x_poly; }
 void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }
 int dkmc_get_x_apply_form(void) { return eng().x_apply_form; }
+void dkmc_set_x_tile_f32(int mode) { eng().x_tile_f32 = mode == 0 ? 0 : 1; }
+int dkmc_get_x_tile_f32(void) { return eng().x_tile_f32; }
+void dkmc_debug_fail_true_residual_once(void) { eng().x_tile_f32_fail_once = 1; }
 void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
 void dkmc_set_x_nmul_lane_bytes(int bytes) { eng().x_nmul_lane_bytes = bytes == 8 ? 8 : 16; }

@@ -211,9 +211,10 @@ __global__ void k_xt_rank_items(const int *__restrict__ nitems_dev, int ntiles, 
 // ---- fill: values of the stored sub-blocks --------------------------------------------------------------------------------
 // One workgroup per tile; thread (q = tid / 32, c = tid % 32) owns column 32 q + c of the tile and walks its 32 rows.
 // Element (row r, column 32 q + c) of sub-block slot sl sits at ((sl * 32 + r) * 32 + c): a sub-block is 8 consecutive
-// 1-KiB wave loads of the apply kernel.
+// 1-KiB wave loads of the apply kernel.  tval32 != null: every value also goes, rounded to float, into the fp32 image of the store (xt_tval32_pos: the
+// same sub-block order at half width; a value that rounds to zero or to a subnormal stays within the image's error bound 2^-24 |v|).
 __global__ __launch_bounds__(XT_NT) void k_xt_fill(XParams P, int ns, const XTile *__restrict__ tiles, int sub_base, SNodes S, TCacheView TC,
-                                                   double *__restrict__ tval, unsigned long long *__restrict__ nnz_upper)
+                                                   double *__restrict__ tval, unsigned long long *__restrict__ nnz_upper, float *__restrict__ tval32)
 {
     __shared__ double rx[XT_R], ry[XT_R], rz[XT_R], rcb[XT_R];
     __shared__ int rf[XT_R], rslot[XT_R], rslotA[XT_R], rmr[XT_R];
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(XT_NT) void k_xt_fill(XParams P, int ns, const XTil
     if ((td.mask >> q) & 1u) {
         const int sl = __popc(td.mask & ((1u << q) - 1u));
         double *dst = tval + ((size_t)(td.soff - sub_base) + sl) * XT_SUB + c;
+        float *dst32 = tval32 ? tval32 + ((size_t)(td.soff - sub_base) + sl) * XT_SUB : nullptr;
         const int sc = XT_C * td.w + XT_SBW * q + c;
         const double cx = S.x[sc], cy = S.y[sc], cz = S.z[sc], ccb = S.cb[sc];
         const int cf = S.flag[sc], cslot = S.slot[sc], cslotA = S.slotA[sc], cmr = S.mr[sc];
@@ -239,6 +241,7 @@ __global__ __launch_bounds__(XT_NT) void k_xt_fill(XParams P, int ns, const XTil
             if (sc > s && cf && rf[r])
                 v = xt_tvalue(P, prefac, TC, rx[r], ry[r], rz[r], rcb[r], rf[r], rslot[r], rslotA[r], rmr[r], cx, cy, cz, ccb, cf, cslot, cslotA, cmr);
             dst[r * XT_SBW] = v;
+            if (dst32) dst32[xt_tval32_pos(r, c)] = (float)v;
             cnt += v != 0.0;
         }
     }
@@ -1021,6 +1024,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     double *val = nullptr, *sd = nullptr, *tval = nullptr, *rowpart = nullptr, *colpart = nullptr, *sc = nullptr, *r = nullptr, *p = nullptr, *t = nullptr,
            *q = nullptr, *vS = nullptr, *part = nullptr, *qS = nullptr, *sS = nullptr, *xS = nullptr, *part_pt = nullptr, *part_rr = nullptr;
     XTile *tiles = nullptr; int2 *wrange = nullptr; XItem *items = nullptr; unsigned long long *d_cnt = nullptr; XCtrl *ctrl = nullptr;
+    float *tval32 = nullptr;
     SNodes SN{};
     double *xbuf = nullptr;
     auto assemble = [&]() -> int {
@@ -1123,12 +1127,21 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         colpart = (double *)scratch(S_XT_COLPART, (size_t)(X.nitems + 1) * XT_C * 8);       // one 256-entry record per run (32 MB at 9.4e5 sites; [run position][S rank] took 1.8 GB)
         d_cnt = (unsigned long long *)scratch(S_XT_CNT, 16);
         if (!tval || !rowpart || !colpart || !d_cnt) return e.err_code;
+        // fp32 image of the values for the sweeps of the preconditioned block-CG (dkmc_set_x_tile_f32), made only where xtb_cg can use it; a copy that does
+        // not fit is not an error: the solve runs on the fp64 store and the stats say so
+        tval32 = nullptr; e.stats.x_tile_stream = 0; e.stats.x_tile_f64_rounds = 0; e.stats.x_tile_f32_bytes = 0;
+        if (e.x_tile_f32 != 0 && !sharded && e.x_block > 1 && e.x_poly > 0 && e.cg_tol >= 1e-8 && X.tile_n > 0) {
+            const size_t b32 = (size_t)(X.sub_n + 4) * XT_SUB * 4;
+            tval32 = (float *)scratch_try(S_XT_TVAL32, b32);
+            if (tval32) e.stats.x_tile_f32_bytes = (long long)b32; else e.stats.x_tile_stream = -1;
+        }
         HIPCHK(hipMemsetAsync(rowpart, 0, (size_t)(ncell + 1) * XT_R * 8, st));
         HIPCHK(hipMemsetAsync(colpart, 0, (size_t)(X.nitems + 1) * XT_C * 8, st));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 16, st));
         if (X.tile_n > 0)
-            hipLaunchKernelGGL(k_xt_fill, dim3(X.tile_n), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles + X.tile_lo, (int)X.sub_base, SN, TC, tval, d_cnt);
+            hipLaunchKernelGGL(k_xt_fill, dim3(X.tile_n), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles + X.tile_lo, (int)X.sub_base, SN, TC, tval, d_cnt, tval32);
         KCHK();
+        g_xb.tval32 = tval32;
         g_xb.tval = tval; g_xb.rowpart = rowpart; g_xb.colpart = colpart;
         X.valid = true;
 
@@ -1237,7 +1250,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     if (e.x_block > 1 && ns > 0) {
         XtbArgs B{};
         B.m = m; B.ns = ns; B.ns_pad = ns_pad; B.nK = nK; B.nW = nW; B.s = e.x_block;
-        B.items = (const XItem *)items + X.item_lo; B.item_n = X.item_n; B.tiles = tiles; B.sub_base = (int)X.sub_base; B.tval = tval;
+        B.items = (const XItem *)items + X.item_lo; B.item_n = X.item_n; B.tiles = tiles; B.sub_base = (int)X.sub_base; B.tval = tval; B.tval32 = tval32;
         B.wrange = wrange; B.nitem_w = nitem_w; B.nrecords = X.nitems >> X.rec_shift;
         B.srow = srow; B.sS = sS; B.nsrank = nsrank; B.rp = rp; B.ci = col; B.val = val; B.sc = sc; B.ax = buf->atom_x; B.ay = buf->atom_y; B.az = buf->atom_z; B.b = rhs; B.y = y;
         B.yaux = yaux; B.yaux_valid = yaux_valid;
@@ -1615,6 +1628,20 @@ extern "C" int dkmc_xtb_emulate_slabs(int nranks, int width, double tol, int tim
     return e.err_code;
 }
 
+// Test aid (tests/test_gpu_tile_f32.py): the tile list {k, w, mask, first sub-block slot} and the fp64 values of the stored sub-blocks of the last
+// single-GPU assembly (element (row r, column c) of slot sl at tval[(sl * 32 + r) * 32 + c]).  Null arrays: the counts only.
+extern "C" int dkmc_xt_get_tiles(long long *ntiles, long long *nsub, int *tiles4, double *tval)
+{
+    Engine &e = eng(); const XTState &X = g_xt;
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles) return dkmc_fail(13, "xt_get_tiles: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    HIPCHK(hipStreamSynchronize(e.stream));
+    if (ntiles) *ntiles = X.ntiles;
+    if (nsub) *nsub = X.nsub_total;
+    static_assert(sizeof(XTile) == 16, "XTile is four ints");
+    if (tiles4 && X.ntiles) HIPCHK(hipMemcpy(tiles4, g_xb.tiles, (size_t)X.ntiles * sizeof(XTile), hipMemcpyDeviceToHost));
+    if (tval && X.nsub_total) HIPCHK(hipMemcpy(tval, g_xb.tval, (size_t)X.nsub_total * XT_SUB * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
 const xrp_t *xt_xs_rp() { return g_xb.rp; }
 const int *xt_xs_col() { return g_xb.ci; }
 const double *xt_xs_val() { return g_xb.val; }

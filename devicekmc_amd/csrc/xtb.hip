@@ -42,6 +42,7 @@
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <functional>
+#include <type_traits>
 #include <vector>
 
 #define XB_SP 16                      // vectors per panel row (padded block width)
@@ -142,9 +143,24 @@ __device__ __forceinline__ size_t xtb_qs_pos(int r, int v) { return (size_t)(r >
 // measured chip-wide, twice the 16x16x4 form (tools/bench_mfma_f64.hip: 140 cycles, 34 TFLOP/s).  The four blocks of an instruction are
 // four groups of tile rows (row sums) or columns (column sums) against the SAME four vectors, so the panel operand is replicated over the
 // blocks and the cost scales with NG = ceil(s / 4) vector groups: 32 NG instructions per 32 x 32 sub-block.
-template <int NTL, int NG, int variant = 0>
+// TV: the stored type of the tile values.  double: the fp64 store, 8 wave loads of 16 bytes per lane and sub-block.  float (dkmc_set_x_tile_f32): its
+// fp32 image at half width (xt_tval32_pos), 4 wave loads per sub-block, each lane's float4 widened (v_cvt_f64_f32) into the two dbl2 the fp64 loads
+// 2 u, 2 u + 1 would have brought -- where the registers are first used (the image write, XB_WIMG / XB_COL), so everything behind the load is the same
+// instruction stream on the same fp64 operands.
+typedef float flt4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void xtb_widen(const dbl2 (&s)[8], dbl2 (&v)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = s[j];
+}
+__device__ __forceinline__ void xtb_widen(const flt4 (&s)[4], dbl2 (&v)[8])
+{
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { v[2 * u].x = (double)s[u].x; v[2 * u].y = (double)s[u].y; v[2 * u + 1].x = (double)s[u].z; v[2 * u + 1].y = (double)s[u].w; }
+}
+template <int NTL, int NG, int variant = 0, typename TV = double>
 __global__ __launch_bounds__(XT_NT) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__restrict__ tiles, int sub_base, const double *__restrict__ tval,
+void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__restrict__ tiles, int sub_base, const TV *__restrict__ tval,
                  const double *__restrict__ QS, int nW, double *__restrict__ rowpartB, double *__restrict__ colpartB, const XCtrl *ctrl)
 {
     // variant 0 = the product kernel.  Every other value is the ROUND-4 FORM of the loop (stages issued in bursts, conditional loads at the tile end,
@@ -155,6 +171,9 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
     // results of 1, 2, 4, 7 and 10 are meaningless
     constexpr int so = 4 * NG;                                                 // vectors per row of the partial-sum arrays
     constexpr bool PF = variant == 0 || variant == 10 || variant == 12;        // product form of the loop (12, measurement: partial tiles skipped)
+    constexpr bool F32 = sizeof(TV) == 4;
+    constexpr int NL = F32 ? 4 : 8;                                            // wave loads (16 bytes per lane) per sub-block
+    typedef typename std::conditional<F32, flt4, dbl2>::type XV;               // what a lane loads at once
     __shared__ __attribute__((aligned(16))) double qc[XT_C * XB_SP];          // the strip's 256 panel rows in QS order (32 KiB)
     __shared__ __attribute__((aligned(16))) double ts[4 * 2 * XT_SUB];        // per wave: two sub-block images (2 x 8 KiB)
     __shared__ __attribute__((aligned(16))) double brs[PF ? 4 * XT_R * XB_SP : 2];   // per wave: the next tile's 32 panel rows (4 KiB)
@@ -190,7 +209,9 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
     int qoff[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) qoff[g] = rr * 32 + ((2 * (4 * g + jv)) ^ (rr << 3));      // + (16 q + 4 kk) * 32
-#define XB_LD(dst, slot) if ((variant != 2 && variant != 7 && variant != 10) || (slot) < 2) { _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) dst[j_] = NTL ? __builtin_nontemporal_load(base + (size_t)(8 * (slot) + j_) * 64) : base[(size_t)(8 * (slot) + j_) * 64]; }
+    // the stream registers of `dst` are dst_s (as loaded); dst itself holds the fp64 operands from XB_WIDEN on
+#define XB_LD(dst, slot) if ((variant != 2 && variant != 7 && variant != 10) || (slot) < 2) { _Pragma("unroll") for (int j_ = 0; j_ < NL; ++j_) dst##_s[j_] = NTL ? __builtin_nontemporal_load(base + (size_t)(NL * (slot) + j_) * 64) : base[(size_t)(NL * (slot) + j_) * 64]; }
+#define XB_WIDEN(vv) xtb_widen(vv##_s, vv);
     // panel operands of the column sums: rows 4 j + rr of a tile's 32 panel rows, vectors 4 g + jv (the same in all four blocks)
 #define XB_LDBR(k_)                                                                                                            \
     {                                                                                                                           \
@@ -265,6 +286,7 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
 #define XB_COL(vv, q, bufi)                                                                                                    \
     {                                                                                                                           \
         double *img_ = tsw + (bufi) * XT_SUB;                                                                                   \
+        XB_WIDEN(vv)                                                                                                            \
         if (variant != 4 && variant != 7) { _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) *reinterpret_cast<dbl2 *>(img_ + woff[j_]) = vv[j_]; } \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                                  \
         __builtin_amdgcn_wave_barrier();                                                                                        \
@@ -306,6 +328,7 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
 #define XB_WIMG(vv, bufi)                                                                                                      \
     {                                                                                                                           \
         double *img_ = tsw + (bufi) * XT_SUB;                                                                                   \
+        XB_WIDEN(vv)                                                                                                            \
         _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) *reinterpret_cast<dbl2 *>(img_ + woff[j_]) = vv[j_];                    \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                                  \
         __builtin_amdgcn_wave_barrier();                                                                                        \
@@ -317,10 +340,12 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
         _Pragma("unroll") for (int g_ = 0; g_ < NG; ++g_) br[j_][g_] = brw[r32_ * 32 + 2 * (4 * g_ + jv) + (rho_ & 1)];         \
     }
     // groups: 0x008 matrix instruction, 0x020 VMEM read, 0x100 LDS read, 0x200 LDS write.  MF = matrix instructions of a stage (8 NG)
+    // (fp32 stream: the two conversions of an image write, 0x002 VALU, ride in front of it; a stage carries NL stream loads)
+#define XB_GV(n_) if (F32) { XB_G(0x002, n_) }
 #define XB6_S1(vv, q) { XB_RDROW(R0, q, (q) & 1, 0) XB_COLH(vv, q, 0) XB_GREP(2 + NG, XB_G(0x008, 2) XB_G(0x100, 2)) XB_G(0x008, 8 * NG - 2 * (2 + NG)) } XB_SB()
 #define XB6_S2(vv, q) { XB_RDROW(R1, q, (q) & 1, 2) XB_COLH(vv, q, 4) XB_GREP(2 + NG, XB_G(0x008, 2) XB_G(0x100, 2)) XB_G(0x008, 8 * NG - 2 * (2 + NG)) } XB_SB()
-#define XB6_S3(LOAD, EXTRA, NEX) { LOAD EXTRA XB_ROWH(R0) XB_GREP(8 + (NEX), XB_G(0x008, 1) XB_G(0x020, 1)) XB_G(0x008, 8 * NG - 8 - (NEX)) } XB_SB()
-#define XB6_S4(vo, qn, EXTRA, NEX) { XB_WIMG(vo, (qn) & 1) EXTRA XB_ROWH(R1) XB_GREP(8 + (NEX), XB_G(0x008, 1) XB_G(0x200, 1)) XB_G(0x008, 8 * NG - 8 - (NEX)) } XB_SB()
+#define XB6_S3(LOAD, EXTRA, NEX) { LOAD EXTRA XB_ROWH(R0) XB_GREP(NL + (NEX), XB_G(0x008, 1) XB_G(0x020, 1)) XB_G(0x008, 8 * NG - NL - (NEX)) } XB_SB()
+#define XB6_S4(vo, qn, EXTRA, NEX) { XB_WIMG(vo, (qn) & 1) EXTRA XB_ROWH(R1) XB_GREP(8 + (NEX), XB_G(0x008, 1) XB_GV(2) XB_G(0x200, 1)) XB_G(0x008, 8 * NG - 8 - (NEX)) } XB_SB()
 #define XB6_SUB(vv, vo, q, LOAD, E3, N3, E4, N4) XB6_S1(vv, q) XB6_S2(vv, q) XB6_S3(LOAD, E3, N3) XB6_S4(vo, (q) + 1, E4, N4)
 #define XB_SUBBLOCK(vv, q, bufi) XB_COL(vv, q, bufi) XB_ROW(q, bufi)
     // The stream is pipelined ACROSS tiles: the first two sub-blocks of the next tile of the run (contiguous in the store) and its panel
@@ -345,12 +370,12 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
             double Yr[2][NG];
 #pragma unroll
             for (int g = 0; g < NG; ++g) { Yr[0][g] = 0.0; Yr[1][g] = 0.0; }
-            const dbl2 *base = reinterpret_cast<const dbl2 *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
+            const XV *base = reinterpret_cast<const XV *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
             int sl = 0;
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 if (variant != 12 && ((td.mask >> q) & 1u)) {
-                    dbl2 vp[8];
+                    dbl2 vp[8]; XV vp_s[NL];
                     XB_LD(vp, sl)
                     XB_SUBBLOCK(vp, q, q & 1)
                     ++sl;
@@ -363,9 +388,9 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
         }
         // a chain of full tiles (64 KiB each, contiguous in the store): two sub-blocks in flight, primed once per chain and carried across
         // its tiles (a ring of four was measured: no faster, the registers are better spent on the operand pipeline above)
-        dbl2 va[8], vb[8];
+        dbl2 va[8], vb[8]; XV va_s[NL], vb_s[NL];
         {
-            const dbl2 *base = reinterpret_cast<const dbl2 *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
+            const XV *base = reinterpret_cast<const XV *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
             XB_LD(va, 0)
             XB_LD(vb, 1)
             if (PF) XB_WIMG(va, 0)
@@ -382,7 +407,7 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
             double Yr[2][NG];
 #pragma unroll
             for (int g = 0; g < NG; ++g) { Yr[0][g] = 0.0; Yr[1][g] = 0.0; }
-            const dbl2 *base = reinterpret_cast<const dbl2 *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
+            const XV *base = reinterpret_cast<const XV *>(tval + (size_t)(td.soff - sub_base) * XT_SUB) + lane;
             // (the stream registers of a sub-block are free once its image is written and its COLUMN sums are issued -- the row sums read the image --:
             // the loads of sub-block n + 2 go out there, a sub-block and a half ahead of their use instead of one: at 1.1 us of matrix work per
             // sub-block the loaded HBM latency of ~1.8 us was exposed on every sub-block)
@@ -390,9 +415,9 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
                 // No load under a condition in the body of a chain: hipcc's vmcnt counts must assume a conditional load was NOT issued, and the wait
                 // for an older one then waits for it too (round-4 form: a full drain in sub-block 7 and at every tile start).  Past the end of a chain
                 // the two slots re-read the first KiB of this tile (stride 0: cache hits, discarded)
-                const dbl2 *base1 = base;
+                const XV *base1 = base;
                 const size_t lstr = chain ? 64 : 0;
-#define XB_LDN(dst, slot) if (variant != 10) { _Pragma("unroll") for (int j_ = 0; j_ < 8; ++j_) dst[j_] = NTL ? __builtin_nontemporal_load(base1 + (size_t)(8 * (slot) + j_) * lstr) : base1[(size_t)(8 * (slot) + j_) * lstr]; }
+#define XB_LDN(dst, slot) if (variant != 10) { _Pragma("unroll") for (int j_ = 0; j_ < NL; ++j_) dst##_s[j_] = NTL ? __builtin_nontemporal_load(base1 + (size_t)(NL * (slot) + j_) * lstr) : base1[(size_t)(NL * (slot) + j_) * lstr]; }
                 XB6_SUB(va, vb, 0, XB_LD(va, 2), , 0, , 0)
                 XB6_SUB(vb, va, 1, XB_LD(vb, 3), XB_LDBN(nxt.k), 4, , 0)
                 XB6_SUB(va, vb, 2, XB_LD(va, 4), , 0, , 0)
@@ -403,9 +428,9 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
                 // the tile's last column sums are issued after S2: the next tile's panel rows come back from LDS inside S3 and S4
                 XB6_S1(vb, 7) XB6_S2(vb, 7)
                 { XB_LDN(vb, 9) XB_RDBRH(0) XB_ROWH(R0)
-                  XB_GREP(4 * NG, XB_G(0x008, 1) XB_G(0x100, 1)) XB_GREP(8, XB_G(0x008, 1) XB_G(0x020, 1)) XB_G(0x008, 4 * NG - 8) } XB_SB()
+                  XB_GREP(4 * NG, XB_G(0x008, 1) XB_G(0x100, 1)) XB_GREP(NL, XB_G(0x008, 1) XB_G(0x020, 1)) XB_G(0x008, 4 * NG - NL) } XB_SB()
                 { XB_WIMG(va, 0) XB_RDBRH(4) XB_ROWH(R1)
-                  XB_GREP(8, XB_G(0x008, 1) XB_G(0x200, 1)) XB_GREP(4 * NG, XB_G(0x008, 1) XB_G(0x100, 1)) XB_G(0x008, 4 * NG - 8) } XB_SB()
+                  XB_GREP(8, XB_G(0x008, 1) XB_GV(2) XB_G(0x200, 1)) XB_GREP(4 * NG, XB_G(0x008, 1) XB_G(0x100, 1)) XB_G(0x008, 4 * NG - 8) } XB_SB()
 #undef XB_LDN
             } else {
                 // round-4 form
@@ -430,6 +455,8 @@ void k_xtb_apply(int nitems, const XItem *__restrict__ items, const XTile *__res
     }
 #undef XB_ROWSUMS
 #undef XB_LD
+#undef XB_WIDEN
+#undef XB_GV
 #undef XB_LDBR
 #undef XB_LDBN
 #undef XB_WBN
@@ -1203,11 +1230,18 @@ static int xtb_aux_setup(const XtbArgs &A, XbAux **aux, int *hs)
 }
 // the tile x panel kernel (one wave per tile run, four runs per workgroup) at NG = so / 4 vector groups: the product form, or the round-4 form
 // (dkmc_set_x_apply_form(1) = variant 8); variant != 0 (dkmc_xtb_time_apply in a DKMC_MEASURE_VARIANTS build): a measurement variant, where one exists
-struct XbApplyArgs { int n; const XItem *items; const XTile *tiles; int sub_base; const double *tval; const double *QS; int nW; double *rowpartB, *colpartB; const XCtrl *ctrl; };
+// tval32 != null: the launch streams the fp32 image of the tile values instead of tval (the product form only)
+struct XbApplyArgs { int n; const XItem *items; const XTile *tiles; int sub_base; const double *tval; const double *QS; int nW; double *rowpartB, *colpartB; const XCtrl *ctrl; const float *tval32 = nullptr; };
 template <int NTL, int NG, int V>
 static void xtb_apply_v(const XbApplyArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
     hipExtLaunchKernelGGL((k_xtb_apply<NTL, NG, V>), dim3((a.n + 3) / 4), dim3(XT_NT), 0, st, e0, e1, 0, a.n, a.items, a.tiles, a.sub_base, a.tval, a.QS, a.nW,
+                          a.rowpartB, a.colpartB, a.ctrl);
+}
+template <int NTL, int NG>
+static void xtb_apply_f32(const XbApplyArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+    hipExtLaunchKernelGGL((k_xtb_apply<NTL, NG, 0, float>), dim3((a.n + 3) / 4), dim3(XT_NT), 0, st, e0, e1, 0, a.n, a.items, a.tiles, a.sub_base, a.tval32, a.QS, a.nW,
                           a.rowpartB, a.colpartB, a.ctrl);
 }
 template <int NTL, int NG>
@@ -1221,6 +1255,7 @@ static void xtb_apply_ng(const XbApplyArgs &a, int variant, hipStream_t st, hipE
 #else
     (void)variant;
 #endif
+    if (a.tval32) return xtb_apply_f32<NTL, NG>(a, st, e0, e1);
     if (eng().x_apply_form == 1) xtb_apply_v<NTL, NG, 8>(a, st, e0, e1);
     else xtb_apply_v<NTL, NG, 0>(a, st, e0, e1);
 }
@@ -1292,7 +1327,7 @@ static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, const Xb
     if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
     return again ? DKMC_XTB_AGAIN : 0;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np);
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
 // split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
 // solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body / xtb_cg_slab).  A round that no longer
@@ -1329,13 +1364,20 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     const bool packed = !A.sharded && A.m > 2 && A.ns > 0 && eng().x_poly > 0 && eng().x_nmul_form == 1;
     if (packed) { if (int rcp = xtb_npack(A, A.m, nullptr, scratch, 0, &npk)) return rcp; }
     const XbNPack *np = packed ? &npk : nullptr;
-    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np);
-    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { return xtb_cg_body(A, it, rr, &peer_used, np); });
+    // tile values of the sweeps (dkmc_set_x_tile_f32): the fp32 image inside the first round of the one-GPU preconditioned loop, at tolerances where
+    // its perturbation (2^-24 |At|, 1e-10 of ||A||) stays far below the stop test; a round that follows a failed true-residual check runs on the fp64
+    // store -- a failed check never loops on the perturbed operator
+    Engine &e = eng();
+    const bool f32 = e.x_tile_f32 != 0 && A.tval32 != nullptr && !A.sharded && A.m > 2 && A.ns > 0 && e.x_poly > 0 && A.tol2 >= 1e-16;
+    if (f32) e.stats.x_tile_stream = 1; else if (e.stats.x_tile_stream == 1) e.stats.x_tile_stream = 0;      // (-1, no image, stays: the assembly set it)
+    e.stats.x_tile_f64_rounds = f32 ? 0 : 1;
+    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32);
+    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false); });
     // a sharded solve that failed with the peer-write exchange in use: the ranks' sequence counters may have drifted (comm.hip)
     if (rc != 0 && rc != DKMC_XTB_BREAKDOWN && peer_used) comm_peer_drop();
     return rc;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np)
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     const int m = A.m, s = A.s, so = 4 * ((s + 3) / 4);                       // vector groups of four: the matrix instruction's width
@@ -1402,6 +1444,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     // kernels share the memory system, the tile pass slows by what the neighbour part takes (9.4e5 sites: 3.95 + 0 against 3.65 + 0.32 ms; 85 k sites,
     // where both are latency-bound: 15.0 against 13.5 ms per superstep -- the two event hand-overs per sweep cost more than the overlap gains).
     const bool side = sharded && m > 20000 && ntb > 0 && xtb_side_init() == 0;
+    const float *t32 = nullptr;                                               // the tile launch of product() streams the fp32 image (product_pre) or the fp64 store
     auto product = [&](hipEvent_t e0, hipEvent_t e1) {
         int sl = 0;
         if (side) {
@@ -1411,7 +1454,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, S.st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
             (void)hipEventRecord(S.b[sl], S.st);
         }
-        if (ntb > 0) xtb_apply({A.item_n, A.items, A.tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl}, A.nt_loads, so, 0, st, e0, e1);
+        if (ntb > 0) xtb_apply({A.item_n, A.items, A.tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl, t32}, A.nt_loads, so, 0, st, e0, e1);
         if (side) (void)hipStreamWaitEvent(st, g_xb_side.b[sl], 0);           // the sparse sums are in T before the row kernel reads them
         else hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
     };
@@ -1428,7 +1471,9 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     auto product_pre = [&](hipEvent_t e0, hipEvent_t e1) {
         applyL(P, Vp, true);
         double *Pk = P, *Tk = T; P = Vp; T = Zp;                              // (the product reads P and QS, writes T)
+        t32 = f32 ? A.tval32 : nullptr;                                       // (the first product A y0 and the true-residual pass call product() themselves: fp64 store)
         product(e0, e1);
+        t32 = nullptr;
         P = Pk; T = Tk;
         fold_rows(Zp);
         applyL(Zp, T, false);
@@ -1501,12 +1546,15 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)P, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
             product(nullptr, nullptr);
             fold_rows(T);
-            hipLaunchKernelGGL(k_xtb_pre_rr, dim3(1), dim3(1024), 0, st, m, (const double *)T, A.b, bz + m);
+            const int nrp = std::min(XB_RR_MAXPART, (m + 1023) / 1024);       // (the partial Gram matrices have served: gpart holds the partial sums)
+            hipLaunchKernelGGL(k_xtb_pre_rr_part, dim3(nrp), dim3(256), 0, st, m, (const double *)T, A.b, gpart);
+            hipLaunchKernelGGL(k_xtb_pre_rr, dim3(1), dim3(256), 0, st, nrp, (const double *)gpart, bz + m);
             double rr_true = 0.0;
             HIPCHK(hipMemcpyAsync(&rr_true, bz + m, 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             h.rr[h.iters & 1] = rr_true;
             again = rr_true > A.tol2;
+            if (e.x_tile_f32_fail_once) { e.x_tile_f32_fail_once = 0; again = true; }       // test aid (dkmc_debug_fail_true_residual_once)
         }
     } else
     HIPCHK(hipMemcpyAsync(A.y, y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
@@ -1617,10 +1665,52 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     return e.err_code;
 }
 
+// Test aid (tests/test_gpu_tile_f32.py): the tile sums of the 16 test vectors of k_xtb_test_panel on the X left resident by the last single-GPU solve,
+// from the fp64 store (stored_bytes = 8) or its fp32 image (4): k_xtb_apply + the fold of the partial sums (k_xtb_fold_local), before any row scaling.
+// out (host): [S rank][so], so = width rounded up to a multiple of 4.
+extern "C" int dkmc_xtb_tile_product(int width, int stored_bytes, double *out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0) return dkmc_fail(13, "xtb_tile_product: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    if (stored_bytes != 8 && !(stored_bytes == 4 && g_xb.tval32)) return dkmc_fail(13, "xtb_tile_product: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
+    const int ns = X.ns, s = std::max(2, std::min(width, 16)), so = 4 * ((s + 3) / 4);
+    const long long ncell = (long long)X.nK * X.nW;
+    const int nrec = X.nitems >> X.rec_shift;
+    double *QS = (double *)scratch(S_XTB_QS, (size_t)X.ns_pad * XB_SP * 8);
+    double *rowpartB = (double *)scratch(S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
+    double *colpartB = (double *)scratch(S_XTB_COLPART, (size_t)(nrec + 1) * XT_C * so * 8);
+    double *sums = (double *)scratch(S_XTB_PANELS, ((size_t)X.ns_pad * so + 2) * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_MISC2, 256);
+    if (!QS || !rowpartB || !colpartB || !sums || !ctrl) return e.err_code;
+    HIPCHK(hipMemsetAsync(QS, 0, (size_t)X.ns_pad * XB_SP * 8, st));
+    HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
+    HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(nrec + 1) * XT_C * so * 8, st));
+    HIPCHK(hipMemsetAsync(sums, 0, ((size_t)X.ns_pad * so + 2) * 8, st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
+    hipLaunchKernelGGL(k_xtb_test_panel, dim3((ns * XB_SP + 255) / 256), dim3(256), 0, st, ns, QS);
+    const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
+                         colpartB, ctrl, stored_bytes == 4 ? (const float *)g_xb.tval32 : (const float *)nullptr};
+    xtb_apply(xa, true, so, 0, st);
+    hipLaunchKernelGGL(k_xtb_fold_local, dim3(std::max(X.nK, 1)), dim3(XT_NT), 0, st, ns, X.nK, X.nW, so, (const int2 *)g_xb.wrange, (const int *)g_xb.nitem_w,
+                       (const double *)rowpartB, (const double *)colpartB, sums, (const XCtrl *)ctrl, 0, 0, X.nW);
+    KCHK();
+    if (out) HIPCHK(hipMemcpyAsync(out, sums, (size_t)ns * so * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+
 // ---- measurement aid (bench.py / tools; no counterpart in the reference) ------------------------------------------------------------------
 // Average duration of the tile x panel kernel over the X left resident by the last single-GPU solve, `reps` launches back to back.
 // variant 0: the kernel as a solve runs it; 1: without its matrix instructions; 2: without re-reading the tile stream (see k_xtb_apply).
-extern "C" int dkmc_xtb_time_apply(int width, int variant, int reps, double *us)
+static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us);
+extern "C" int dkmc_xtb_time_apply(int width, int variant, int reps, double *us) { return xtb_time_apply(width, variant, reps, false, us); }
+// the same for the kernel as a solve runs it on the fp64 store (stored_bytes = 8) or on its fp32 image (4; fails when the last assembly made none)
+extern "C" int dkmc_xtb_time_apply_stored(int width, int stored_bytes, int reps, double *us)
+{
+    if (stored_bytes != 8 && !(stored_bytes == 4 && g_xb.tval32)) return dkmc_fail(13, "xtb_time_apply_stored: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
+    return xtb_time_apply(width, 0, reps, stored_bytes == 4, us);
+}
+static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us)
 {
     Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
     if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0 || reps < 1) return dkmc_fail(13, "xtb_time_apply: needs the X of a single-GPU solve", __FILE__, __LINE__);
@@ -1638,7 +1728,7 @@ extern "C" int dkmc_xtb_time_apply(int width, int variant, int reps, double *us)
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((X.ns * XB_SP + 255) / 256), dim3(256), 0, st, X.ns, QS);
     const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
-                         colpartB, ctrl};
+                         colpartB, ctrl, f32 ? (const float *)g_xb.tval32 : (const float *)nullptr};
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     for (int r = -1; r < reps; ++r) {
         if (r == 0) HIPCHK(hipEventRecord(e0, st));

@@ -256,16 +256,32 @@ __global__ void k_xtb_pre_add(int m, const double *__restrict__ Z, double *__res
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) y[i] += Z[(size_t)i * XB_SP];
 }
-// ||T(:, 0) - b||^2 in one workgroup (fixed order): the TRUE residual of the unpreconditioned scaled system, for the stop test a caller relies on
-__global__ __launch_bounds__(1024) void k_xtb_pre_rr(int m, const double *__restrict__ T, const double *__restrict__ b, double *__restrict__ out)
+// ||T(:, 0) - b||^2, the TRUE residual of the unpreconditioned scaled system, for the stop test a caller relies on: two stages in a fixed order (the
+// result depends on m alone, not on the launch).  Stage 1: up to XB_RR_MAXPART workgroups, thread t of workgroup g adds rows 256 g + t, + 256 G, ...,
+// then a tree over the workgroup; stage 2: one workgroup adds the partial sums the same way.  (One workgroup of 1024 for everything took 1.1 ms at
+// 9.4e5 rows, a launch at 0.007 TB/s.)
+#define XB_RR_MAXPART 1024
+__device__ __forceinline__ double xtb_tree256(double a)
 {
-    __shared__ double red[1024];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < m; i += 1024) { const double d = T[(size_t)i * XB_SP] - b[i]; a += d * d; }
+    __shared__ double red[256];
     red[threadIdx.x] = a;
     __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) out[0] = red[0];
+    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+    return red[0];
+}
+__global__ __launch_bounds__(256) void k_xtb_pre_rr_part(int m, const double *__restrict__ T, const double *__restrict__ b, double *__restrict__ part)
+{
+    double a = 0.0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) { const double d = T[(size_t)i * XB_SP] - b[i]; a += d * d; }
+    a = xtb_tree256(a);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+__global__ __launch_bounds__(256) void k_xtb_pre_rr(int np, const double *__restrict__ part, double *__restrict__ out)
+{
+    double a = 0.0;
+    for (int i = threadIdx.x; i < np; i += 256) a += part[i];
+    a = xtb_tree256(a);
+    if (threadIdx.x == 0) out[0] = a;
 }
 
 // ---- host side: the packed N of a solve, one Horner step, L = p(N) and its coefficients -----------------------------------------------------

@@ -12,6 +12,10 @@
 #define XT_PROF_STRIDE 8
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
+// fp32 image of the tile values (dkmc_set_x_tile_f32): the sub-block layout at half width.  A sub-block is 4 consecutive 1-KiB wave loads; lane
+// (rr, cc) of load u holds the two fp64 loads 2 u, 2 u + 1 of its lane: rows 8 u + rr and 8 u + 4 + rr, columns 2 cc, 2 cc + 1.
+// Position (floats) of element (row r, column c) inside its sub-block:
+__host__ __device__ static inline int xt_tval32_pos(int r, int c) { return (((r >> 3) * 64 + (r & 3) * 16 + (c >> 1)) << 2) + (((r >> 2) & 1) << 1) + (c & 1); }
 
 struct __attribute__((aligned(16))) XTile { int k, w; unsigned mask; int soff; };   // cell (k, w); present sub-blocks; first sub-block slot
 struct __attribute__((aligned(32))) XItem { int t0, t1, w, c, k0; unsigned mask0; int soff0, pad; };   // tiles [t0, t1) of strip w; c = position of the run in its strip; descriptor of tile t0; pad = record of its column sums, colpart[pad * 256]: the run's own (c = 0; pad = its index in the item list) or, on one GPU, one record per aligned group of four runs -- the four waves of a workgroup (c = 1; pad = index / 4; every strip's run count padded to a multiple of four with empty runs)
@@ -39,6 +43,7 @@ struct XTState {
 
 struct XTBuffers {
     SNodes S; int *srow; XTile *tiles; XItem *items; int2 *wrange; int *nitem_w; double *tval, *rowpart, *colpart;
+    float *tval32;                   // fp32 image of tval for the block-CG's sweeps (dkmc_set_x_tile_f32; xt_tval32_pos), null if none
     xrp_t *rp, *dpos; int *ci; double *val; int *nsrank;
     unsigned *cmask; int *toff;      // census of the last assembly (kept for dkmc_xt_time_share)
     const double *ax, *ay, *az;      // atom positions of the last assembly (dkmc_xtb_emulate_slabs)
@@ -63,6 +68,7 @@ struct XtbArgs {
     int s;                                        // block width (2 ... 16)
     const XItem *items; int item_n;               // this rank's runs (padded to groups of four per strip)
     const XTile *tiles; int sub_base; const double *tval;
+    const float *tval32;                          // fp32 image of tval (null: none): the sweeps of the one-GPU preconditioned loop stream it (dkmc_set_x_tile_f32)
     const int2 *wrange; const int *nitem_w; int nrecords;
     const int *srow; const double *sS; const int *nsrank;
     const xrp_t *rp; const int *ci; const double *val;      // neighbour part Xs (CSR, unscaled, diagonal included)

@@ -103,6 +103,8 @@ typedef struct dkmc_stats {
     long long kcg_bytes;                   /* bytes one iteration of the last K solve moves: column/class words (2 B each on the windowed form with dkmc_set_k_window_word_bytes(2)) + the q windows (or one read of q per row) + 14 (15) vector touches */
     int xb_aux, xb_pad;                    /* 1: the last block solve used the smooth auxiliary columns (dkmc_set_x_aux) */
     int xb_width, xb_fallback;             /* block-CG width of the last current solve (1 = single-vector loop); 1 if the block loop lost definiteness and the single-vector loop finished the solve */
+    int x_tile_stream, x_tile_f64_rounds;  /* tile values the sweeps of the last block solve's first round streamed: 0 the fp64 store, 1 its fp32 image (dkmc_set_x_tile_f32), -1 the fp64 store because the image could not be allocated; rounds of that solve that ran on the fp64 store (one-GPU loop: all of them at 0 / -1; at 1 only the re-entry rounds after a true-residual check above the stop test) */
+    long long x_tile_f32_bytes;            /* bytes of the fp32 image of the tile values (0: none was made) */
 } dkmc_stats;
 
 const char *dkmc_last_error(void);
@@ -163,6 +165,16 @@ int dkmc_get_x_poly(void);
  * Both give the same bits; 0 is kept for comparisons. */
 void dkmc_set_x_nmul_form(int form);
 int dkmc_get_x_nmul_form(void);
+/* Tile values inside the sweeps of the preconditioned block-CG.  1 (auto, default): on one GPU with block width > 1 and dkmc_set_x_poly > 0 the
+ * assembly keeps a float image of every stored tunnelling entry beside the fp64 store (4 KiB per 32 x 32 sub-block), and at cg_tol >= 1e-8 the
+ * sweeps stream that image and widen it to fp64 in front of the matrix instructions; accumulation and everything downstream stay fp64.  The
+ * rounding perturbs A = S X S symmetrically by at most 2^-24 |At| (1e-10 of ||A||: the tunnelling block is 2e-3 of it); the diagonal, the
+ * scaling, the first product A y0 and the TRUE residual that ends every solve use the fp64 store, and a solve whose check fails is re-entered
+ * on the fp64 store: the result meets the reference's stop test on column 0 as before, not bit for bit.  Below 1e-8, with the preconditioner
+ * off, at width 1, on more than one rank, or when the image does not fit in memory the loop is the fp64 one, bit for bit (dkmc_stats.x_tile_stream).
+ * 0: never. */
+void dkmc_set_x_tile_f32(int mode);
+int dkmc_get_x_tile_f32(void);
 /* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
  * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */

@@ -52,6 +52,20 @@ int dkmc_xt_tile_census(long long *hist);
 void dkmc_set_x_items(int kc);
 /* Same-box comparison aid: 1 = the solves (and variant 0 above) run the round-4 form of the tile x panel loop (stages issued in bursts,
  * conditional loads at the tile end, panel rows loaded directly) instead of the product form; same results bit for bit.  Default 0. */
+/* test aid: the next true-residual check that ends a round of the preconditioned block-CG reports "above tolerance" once (host side; nothing on
+ * the device changes): the solve is re-entered as after a real miss (dkmc_stats.x_tile_f64_rounds) */
+void dkmc_debug_fail_true_residual_once(void);
+/* test aid: the tile x panel product of dkmc_xtb_check_product's 16 test vectors (vector v of S rank r: 0.25 + (((r * 2654435761) ^ (v * 40503)) >> 20)
+ * / 4096 + 0.125 v in 32-bit unsigned arithmetic) on the X left by the last single-GPU solve, streamed from the fp64 store (stored_bytes 8) or from its
+ * fp32 image (4, dkmc_set_x_tile_f32; fails when the last assembly made none).  out (host): the tile sums of S rank r, vector v at [r * so + v],
+ * so = width rounded up to a multiple of 4, before any row scaling. */
+int dkmc_xtb_tile_product(int width, int stored_bytes, double *out);
+/* test aid: tile list (four ints per tile: row block k, column window w, mask of its present 32 x 32 sub-blocks, slot of its first one) and the fp64
+ * values of the stored sub-blocks (element (row r, column c) of slot sl at [(sl * 32 + r) * 32 + c]: S ranks 32 k + r and 256 w + 32 q + c for the
+ * q-th bit of the mask) of the last single-GPU assembly.  Null arrays: the counts only. */
+int dkmc_xt_get_tiles(long long *ntiles, long long *nsub, int *tiles4, double *tval);
+/* measurement aid: dkmc_xtb_time_apply of the kernel as a solve runs it, on the fp64 store (stored_bytes 8) or its fp32 image (4) */
+int dkmc_xtb_time_apply_stored(int width, int stored_bytes, int reps, double *us);
 void dkmc_set_x_apply_form(int form);
 int dkmc_get_x_apply_form(void);
 /* Test aid for the error path of a sharded current solve (no counterpart in the reference): the calling rank fails ONCE, in the
