@@ -20,17 +20,18 @@
 //   assembly   k_link (the rule of one entry), k_word (what is stored for it), k_contacts (the two contact sums), k_assemble_tail (diagonal and rhs)
 //   product    kb_rows: the pass loop of k_kb_apply and k_kbw_apply (k_kc_apply: 8 lanes per row, no LDS -- another algorithm, on its own)
 //   vectors    kc_check0 / kc_update / kc_direction / kc_q<LIST>: all rows (k_kc_*) or the rows of a list (k_ks_*)
-//   host       kc_with_cb, kb_raise_lds_limit, kpattern_download, kblocked_upload, kcg_poll (the poll loop of both host loops)
+//   host       kc_with_cb, kb_raise_lds_limit, kpattern_download, kblocked_upload, kcg_poll (the poll loop of both host loops),
+//              kcg_run_* (kcg_run.h: the one-GPU loop without K's assembly; K's solve and the local heat model of heat.hip run on it)
 #include "common.h"
 #include "slab.h"
 #include "kbw_plan.h"
+#include "kcg_run.h"
 #include <algorithm>
 #include <functional>
 #include <type_traits>
 #include <vector>
 
 #define KC_NT 256
-struct KCtrl { double rr[2]; double pad; int done; int iters; };
 
 // ---- assembly: class bits + diagonal + rhs in one pass (16 lanes per row) ------------------------------------------------
 // CB: 0 potential rule, 1 CB-edge rule, 2 CB-edge rule on atoms only (dkmc_set_cb_edge_domain(1): links to interstitial sites, DEFECT or
@@ -656,12 +657,16 @@ template <class K> static int kb_raise_lds_limit(K apply0, K apply1, bool *set)
 }
 // The host's poll loop of both K-CG loops: reads *ctrl_d into h, stops on done, on iter_cap (> 0: the emulation's cap) or after 200 000 iterations
 // (recorded as a failure), else enqueues a batch of iterations (8, 16, 32, then 64 at a time) through enqueue(it), whose error code ends the loop at once.
-template <class F> static int kcg_poll(const KCtrl *ctrl_d, KCtrl &h, int iter_cap, hipStream_t st, F &&enqueue)
+// first > 0: that many iterations are enqueued before the first poll (a caller that knows what the solve will need); syncs: counts the polls.
+template <class F> static int kcg_poll(const KCtrl *ctrl_d, KCtrl &h, int iter_cap, hipStream_t st, F &&enqueue, int first = 0, int *syncs = nullptr)
 {
     int it = 0, batch = 8;
+    for (; it < first; ++it) if (int rc = enqueue(it)) return rc;
+    if (first > 0) KCHK();
     for (;;) {
         HIPCHK(hipMemcpyAsync(&h, ctrl_d, sizeof(KCtrl), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        if (syncs) ++*syncs;
         if (h.done) break;
         if (iter_cap > 0 && it >= iter_cap) break;
         if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
@@ -788,6 +793,109 @@ KBlocked *kpattern_form_build(const int *rp_d, const int *ci_d, int m, int nnz, 
     return kblocked_build(rp_d, ci_d, m, nnz, x_d, st);
 }
 
+// ---- the one-GPU loop on an assembled system (kcg_run.h) -----------------------------------------------------------------------------------------
+int kcg_run_setup(KcgRun &c, int m, const int *rp, int nnz, const KBlocked *kb, const int *cf, const double *diag, double *rhs, double *yb,
+                  double w_high, double w_low, double tol, double *y_site)
+{
+    Engine &e = eng();
+    if (kb && kb->m != m) return dkmc_fail(6, "K-CG: the blocked form belongs to another pattern", __FILE__, __LINE__);
+    c = KcgRun{};
+    c.m = m; c.nnz = nnz; c.rp = rp; c.kb = kb; c.cf = cf; c.diag = diag; c.rhs = rhs; c.y_site = y_site; c.y = kb ? yb : y_site;
+    c.w_high = w_high; c.w_low = w_low; c.tol2 = tol * tol;
+    c.kbw = kb && kb->form == 2;
+    c.kbw2 = c.kbw && kb->word_bytes == 2;           // 16-bit stored words (dkmc_set_k_window_word_bytes when the pattern was built)
+    c.s = (double *)scratch(S_CG_S, (size_t)m * 8); c.r = (double *)scratch(S_CG_R, (size_t)m * 8);
+    c.p = (double *)scratch(S_CG_P, (size_t)m * 8); c.t = (double *)scratch(S_CG_T, (size_t)m * 8);
+    c.q = (double *)scratch(S_XT_Q, (size_t)m * 8);
+    c.part = (double *)scratch(S_CG_PART, (size_t)KC_PART_DOUBLES * 8);
+    c.ctrl = (KCtrl *)scratch(S_CG_CTRL, sizeof(KCtrl));
+    if (!c.s || !c.r || !c.p || !c.t || !c.q || !c.part || !c.ctrl) return e.err_code;
+    c.vb = (m + 255) / 256;
+    c.lds = kb ? (size_t)kb->maxwin * 8 : 0;
+    if (kb) {
+        static bool lds_set[3] = {false, false, false};
+        if (int rc = c.kbw2 ? kb_raise_lds_limit(k_kbw_apply<0, 2>, k_kbw_apply<1, 2>, &lds_set[2]) : c.kbw ? kb_raise_lds_limit(k_kbw_apply<0, 4>, k_kbw_apply<1, 4>, &lds_set[1])
+                                                                                                            : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
+    }
+    c.ga = kb ? kb->nb : kc_grid(m, KC_NT / 8, KC_NPA);         // product: one block of the blocked form, or 32 rows, per workgroup and pass
+    c.gv = kc_grid(m, KC_NT, KC_NP);
+    c.npa = (c.ga + KC_NT - 1) / KC_NT * KC_NT;
+    return 0;
+}
+#define KC_APPLY(MODE, ...) do { if (c.kbw2) hipLaunchKernelGGL((k_kbw_apply<MODE, 2>), dim3(c.ga), dim3(KB_NT), c.lds, st, c.m, c.kb->R, (const int4 *)c.kb->blk, (const int4 *)c.kb->seg, __VA_ARGS__); \
+                                 else if (c.kbw) hipLaunchKernelGGL((k_kbw_apply<MODE, 4>), dim3(c.ga), dim3(KB_NT), c.lds, st, c.m, c.kb->R, (const int4 *)c.kb->blk, (const int4 *)c.kb->seg, __VA_ARGS__); \
+                                 else if (c.kb) hipLaunchKernelGGL((k_kb_apply<MODE>), dim3(c.ga), dim3(KB_NT), c.lds, st, c.m, c.kb->R, (const int4 *)c.kb->blk, __VA_ARGS__); \
+                                 else hipLaunchKernelGGL((k_kc_apply<MODE>), dim3(c.ga), dim3(KC_NT), 0, st, c.m, c.rp, __VA_ARGS__); } while (0)
+int kcg_run_scale(KcgRun &c, KCtrl *ctrl_out)
+{
+    hipStream_t st = eng().stream;
+    if (c.kb) hipLaunchKernelGGL(k_kb_scale, dim3(c.vb), dim3(256), 0, st, c.m, (const int *)c.kb->perm, c.diag, c.s, c.rhs, (const double *)c.y_site, c.y, c.q);
+    else hipLaunchKernelGGL(k_kc_scale, dim3(c.vb), dim3(256), 0, st, c.m, c.diag, c.s, c.rhs, c.y, c.q);
+    HIPCHK(hipMemsetAsync(ctrl_out, 0, sizeof(KCtrl), st));
+    HIPCHK(hipMemsetAsync(c.part, 0, (size_t)KC_PART_DOUBLES * 8, st));       // the slots beyond either grid stay zero
+    return 0;
+}
+int kcg_run_start(KcgRun &c, KCtrl *ctrl_out)
+{
+    hipStream_t st = eng().stream;
+    KC_APPLY(1, c.cf, c.diag, (const double *)c.s, (const double *)c.q, c.w_high, c.w_low,
+             (const double *)nullptr, c.t, c.part, (const KCtrl *)c.ctrl, (const double *)c.rhs, c.r, c.p);
+    hipLaunchKernelGGL(k_kc_q, dim3(c.vb), dim3(256), 0, st, c.m, (const double *)c.s, (const double *)c.p, c.q);
+    hipLaunchKernelGGL(k_kc_check0, dim3(1), dim3(KC_NT), 0, st, c.part, ctrl_out, c.tol2);
+    KCHK();
+    return 0;
+}
+int kcg_run_iterate(KcgRun &c, int it)
+{
+    hipStream_t st = eng().stream;
+    KC_APPLY(0, c.cf, c.diag, (const double *)c.s, (const double *)c.q, c.w_high, c.w_low,
+             (const double *)c.p, c.t, c.part, (const KCtrl *)c.ctrl, (const double *)nullptr, c.r, (double *)nullptr);
+    if (c.kb && !c.kbw) hipLaunchKernelGGL(k_kc_step, dim3(c.gv), dim3(KC_NT), 0, st, c.m, it, c.part, c.p, (const double *)c.t, c.y, c.r, (const double *)c.s, c.q, c.ctrl, c.tol2, c.npa);
+    else {
+        hipLaunchKernelGGL(k_kc_update, dim3(c.gv), dim3(KC_NT), 0, st, c.m, it, (const double *)c.part, c.npa, (const double *)c.p, (const double *)c.t, c.y, c.r, c.part + 3 * KC_NPA, (const KCtrl *)c.ctrl);
+        hipLaunchKernelGGL(k_kc_direction, dim3(c.gv), dim3(KC_NT), 0, st, c.m, it, (const double *)(c.part + 3 * KC_NPA), (const double *)c.r, c.p, (const double *)c.s, c.q, c.ctrl, c.tol2);
+    }
+    return 0;
+}
+#undef KC_APPLY
+int kcg_run_poll(KcgRun &c, KCtrl &h, int first)
+{
+    return kcg_poll(c.ctrl, h, 0, eng().stream, [&](int it) -> int { return kcg_run_iterate(c, it); }, first, &c.syncs);
+}
+int kcg_run_unscale(KcgRun &c)
+{
+    hipStream_t st = eng().stream;
+    if (c.kb) hipLaunchKernelGGL(k_kb_unscale, dim3(c.vb), dim3(256), 0, st, c.m, (const int *)c.kb->perm, (const double *)c.y, (const double *)c.s, c.y_site);
+    else hipLaunchKernelGGL(k_kc_unscale, dim3(c.vb), dim3(256), 0, st, c.m, c.y, (const double *)c.s);
+    KCHK();
+    return 0;
+}
+long long kcg_run_bytes(const KcgRun &c)
+{
+    const KBlocked *kb = c.kb; const long long m = c.m;
+    if (c.kbw) return (c.kbw2 ? 2LL : 4LL) * kb->total + 16LL * kb->nb * (1 + KBW_MAXSEG) + 8LL * kb->winsum + 16LL * 8 * m;       // (product 5 + update 6 + direction 5 vector touches)
+    return kb ? 4LL * kb->total + 16LL * kb->nb + 8LL * kb->winsum + 14LL * 8 * m : 4LL * c.nnz + 4LL * (m + 1) + 17LL * 8 * m;
+}
+int kcg_run(KcgRun &c, KCtrl &h, int first)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (int rc = kcg_run_scale(c, c.ctrl)) return rc;
+    static hipEvent_t evk[2]; static bool evk_ready = false;
+    const bool prof = e.profiling != 0;
+    if (prof && !evk_ready) { HIPCHK(hipEventCreate(&evk[0])); HIPCHK(hipEventCreate(&evk[1])); evk_ready = true; }
+    if (int rc = kcg_run_start(c, c.ctrl)) return rc;
+    if (prof) HIPCHK(hipEventRecord(evk[0], st));
+    if (int rc = kcg_run_poll(c, h, first)) return rc;
+    if (prof) {
+        HIPCHK(hipEventRecord(evk[1], st));
+        HIPCHK(hipEventSynchronize(evk[1]));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, evk[0], evk[1]));
+        c.ms = ms; c.iters_timed = h.iters;
+    } else { c.ms = 0.0; c.iters_timed = 0; }
+    return kcg_run_unscale(c);
+}
+
 // Assemble K for the current elements / charges and solve K y = rhs in place in y (warm start = y on entry).
 // kb: the blocked form of the pattern (or nullptr): the whole solve then runs in the blocked order, y is gathered on entry and scattered on exit.
 static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag, const double *s, const double *b, double high_G, double low_G, double *y, double *q0,
@@ -808,21 +916,11 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     const bool kbw2 = kbw && kb->word_bytes == 2;           // 16-bit stored words (dkmc_set_k_window_word_bytes when the pattern was built)
     int *cf = (int *)scratch(S_K_DATA, kb ? (size_t)kb->total * (kbw2 ? 2 : 4) : (size_t)nnz * 4);
     double *rhs = (double *)scratch(S_K_RHS, (size_t)m * 8 * 3);
-    double *s = (double *)scratch(S_CG_S, (size_t)m * 8), *r = (double *)scratch(S_CG_R, (size_t)m * 8);
-    double *p = (double *)scratch(S_CG_P, (size_t)m * 8), *t = (double *)scratch(S_CG_T, (size_t)m * 8);
-    double *q = (double *)scratch(S_XT_Q, (size_t)m * 8);
-    double *part = (double *)scratch(S_CG_PART, (size_t)KC_PART_DOUBLES * 8);
-    KCtrl *ctrl = (KCtrl *)scratch(S_CG_CTRL, sizeof(KCtrl));
-    if (!cf || !rhs || !s || !r || !p || !t || !q || !part || !ctrl) return e.err_code;
-    double *diag = rhs + m, *y = kb ? rhs + 2 * (size_t)m : y_site;
-    const double tol2 = e.cg_tol * e.cg_tol;
-    const int ab = (m + 15) / 16, vb = (m + 255) / 256;
-    const size_t lds = kb ? (size_t)kb->maxwin * 8 : 0;
-    if (kb) {
-        static bool lds_set[3] = {false, false, false};
-        if (int rc = kbw2 ? kb_raise_lds_limit(k_kbw_apply<0, 2>, k_kbw_apply<1, 2>, &lds_set[2]) : kbw ? kb_raise_lds_limit(k_kbw_apply<0, 4>, k_kbw_apply<1, 4>, &lds_set[1])
-                                                                                                        : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
-    }
+    if (!cf || !rhs) return e.err_code;
+    double *diag = rhs + m;
+    KcgRun c;
+    if (int rc = kcg_run_setup(c, m, rp, nnz, kb, cf, diag, rhs, rhs + 2 * (size_t)m, high_G, low_G, e.cg_tol, y_site)) return rc;
+    const int ab = (m + 15) / 16;
     kc_with_cb(cb, [&](auto cbv) {
         constexpr int CB = decltype(cbv)::value;
         if (kbw2) hipLaunchKernelGGL((k_kbw_assemble<CB, 2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
@@ -833,65 +931,27 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
                                         element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
         else hipLaunchKernelGGL((k_kc_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
     });
-    if (kb) hipLaunchKernelGGL(k_kb_scale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)diag, s, rhs, (const double *)y_site, y, q);
-    else hipLaunchKernelGGL(k_kc_scale, dim3(vb), dim3(256), 0, st, m, (const double *)diag, s, rhs, y, q);
-    static hipEvent_t evk[2]; static bool evk_ready = false;
-    const bool prof = e.profiling != 0;
-    if (prof && !evk_ready) { HIPCHK(hipEventCreate(&evk[0])); HIPCHK(hipEventCreate(&evk[1])); evk_ready = true; }
-    KCtrl h{};
-    const int ga = kb ? kb->nb : kc_grid(m, KC_NT / 8, KC_NPA);         // product: one block of the blocked form, or 32 rows, per workgroup and pass
-    const int gv = kc_grid(m, KC_NT, KC_NP);
-    const int npa = (ga + KC_NT - 1) / KC_NT * KC_NT;
-    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(KCtrl), st));
-    HIPCHK(hipMemsetAsync(part, 0, (size_t)KC_PART_DOUBLES * 8, st));       // the slots beyond either grid stay zero
-#define KC_APPLY(MODE, ...) do { if (kbw2) hipLaunchKernelGGL((k_kbw_apply<MODE, 2>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
-                                 else if (kbw) hipLaunchKernelGGL((k_kbw_apply<MODE, 4>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, (const int4 *)kb->seg, __VA_ARGS__); \
-                                 else if (kb) hipLaunchKernelGGL((k_kb_apply<MODE>), dim3(ga), dim3(KB_NT), lds, st, m, kb->R, (const int4 *)kb->blk, __VA_ARGS__); \
-                                 else hipLaunchKernelGGL((k_kc_apply<MODE>), dim3(ga), dim3(KC_NT), 0, st, m, rp, __VA_ARGS__); } while (0)
     // more than one rank (or the emulation of it) on a system above the size of the blocked form: the loop distributed by row slabs
     const bool slab = !kb && row_y && row_z && (emu_nr > 0 || (e.k_slab && comm_attached() && comm_nranks() > 1 && comm_nranks() <= XS_MAXR));
     if (slab) {
+        if (int rc = kcg_run_scale(c, c.ctrl)) return rc;
         int rcs = 0;
         if (emu_nr <= 0) rcs = comm_agree(e.err_code, "assembly of K");                 // local set-up done: nobody enters the collectives of the loop alone
         if (rcs) return rcs;
-        rcs = kcg_slab_loop(m, rp, cf, diag, s, rhs, high_G, low_G, y, q, row_y, row_z, emu_nr > 0 ? emu_nr : comm_nranks(), emu_nr > 0 ? 0 : comm_rank(), emu_nr > 0,
-                            emu_time_rank, tol2, iters_out, rr_out);
+        rcs = kcg_slab_loop(m, rp, cf, diag, c.s, rhs, high_G, low_G, c.y, c.q, row_y, row_z, emu_nr > 0 ? emu_nr : comm_nranks(), emu_nr > 0 ? 0 : comm_rank(), emu_nr > 0,
+                            emu_time_rank, c.tol2, iters_out, rr_out);
         if (rcs) return rcs;
-        hipLaunchKernelGGL(k_kc_unscale, dim3(vb), dim3(256), 0, st, m, y, (const double *)s);
+        hipLaunchKernelGGL(k_kc_unscale, dim3(c.vb), dim3(256), 0, st, m, c.y, (const double *)c.s);
         KCHK();
         e.stats.kcg_blocked = 0; e.stats.kcg_ms = 0.0; e.stats.kcg_iters_timed = 0;
         e.stats.kcg_bytes = 4LL * nnz + 4LL * (m + 1) + 17LL * 8 * m;
         return e.err_code;
     }
-    KC_APPLY(1, (const int *)cf, (const double *)diag, (const double *)s, (const double *)q, high_G, low_G,
-             (const double *)nullptr, t, part, (const KCtrl *)ctrl, (const double *)rhs, r, p);
-    hipLaunchKernelGGL(k_kc_q, dim3(vb), dim3(256), 0, st, m, (const double *)s, (const double *)p, q);
-    hipLaunchKernelGGL(k_kc_check0, dim3(1), dim3(KC_NT), 0, st, part, ctrl, tol2);
-    KCHK();
-    if (prof) HIPCHK(hipEventRecord(evk[0], st));
-    if (int rc = kcg_poll(ctrl, h, 0, st, [&](int it) -> int {
-            KC_APPLY(0, (const int *)cf, (const double *)diag, (const double *)s, (const double *)q, high_G, low_G,
-                     (const double *)p, t, part, (const KCtrl *)ctrl, (const double *)nullptr, r, (double *)nullptr);
-            if (kb && !kbw) hipLaunchKernelGGL(k_kc_step, dim3(gv), dim3(KC_NT), 0, st, m, it, part, p, (const double *)t, y, r, (const double *)s, q, ctrl, tol2, npa);
-            else {
-                hipLaunchKernelGGL(k_kc_update, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)part, npa, (const double *)p, (const double *)t, y, r, part + 3 * KC_NPA, (const KCtrl *)ctrl);
-                hipLaunchKernelGGL(k_kc_direction, dim3(gv), dim3(KC_NT), 0, st, m, it, (const double *)(part + 3 * KC_NPA), (const double *)r, p, (const double *)s, q, ctrl, tol2);
-            }
-            return 0;
-        })) return rc;
-    if (prof) {
-        HIPCHK(hipEventRecord(evk[1], st));
-        HIPCHK(hipEventSynchronize(evk[1]));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, evk[0], evk[1]));
-        e.stats.kcg_ms = ms; e.stats.kcg_iters_timed = h.iters;
-    } else { e.stats.kcg_ms = 0.0; e.stats.kcg_iters_timed = 0; }
-    if (kb) hipLaunchKernelGGL(k_kb_unscale, dim3(vb), dim3(256), 0, st, m, (const int *)kb->perm, (const double *)y, (const double *)s, y_site);
-    else hipLaunchKernelGGL(k_kc_unscale, dim3(vb), dim3(256), 0, st, m, y, (const double *)s);
-    KCHK();
+    KCtrl h{};
+    if (int rc = kcg_run(c, h, 0)) return rc;
+    e.stats.kcg_ms = c.ms; e.stats.kcg_iters_timed = c.iters_timed;
     e.stats.kcg_blocked = kb ? kb->form : 0;
-    if (kbw) e.stats.kcg_bytes = (kbw2 ? 2LL : 4LL) * kb->total + 16LL * kb->nb * (1 + KBW_MAXSEG) + 8LL * kb->winsum + 16LL * 8 * m;       // (product 5 + update 6 + direction 5 vector touches)
-    else e.stats.kcg_bytes = kb ? 4LL * kb->total + 16LL * kb->nb + 8LL * kb->winsum + 14LL * 8 * m : 4LL * nnz + 4LL * (m + 1) + 17LL * 8 * m;
+    e.stats.kcg_bytes = kcg_run_bytes(c);
     if (iters_out) *iters_out = h.iters;
     if (rr_out) *rr_out = kb && !kbw ? h.rr[0] : h.rr[h.iters & 1];
     return e.err_code;

@@ -246,6 +246,12 @@ class Device:
                                                             C.byref(ns), C.byref(steady), C.byref(iters), C.byref(T)))
             self.T_bg = T.value
             self.last_heat_solves, self.last_heat_steady, self.last_heat_cg_iters = ns.value, bool(steady.value), iters.value
+            self.last_heat_info = None
+            if hasattr(_lib.load(), "dkmc_get_heat_info"):
+                info = (C.c_longlong * 8)()
+                check(_lib.load().dkmc_get_heat_info(info))
+                self.last_heat_info = dict(zip(("form", "rows", "stored_words", "sub_steps", "host_syncs", "resumed_sub_steps", "bytes_per_iteration"),
+                                               list(info)[:7]))
             result["Global temperature [K]"] = self.T_bg
         return result
 

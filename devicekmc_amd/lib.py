@@ -131,6 +131,10 @@ SYMBOLS = {
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),
+    "dkmc_set_heat_form": (None, [_I]),
+    "dkmc_get_heat_form": (_I, []),
+    "dkmc_get_heat_info": (_I, [C.POINTER(C.c_longlong)]),
+    "dkmc_debug_heat_chain": (None, [_I, _I]),
     "dkmc_construct_laplacian": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _D]),
     "dkmc_update_temperature_local": (_I, [C.POINTER(dkmc_gpubuf), _D, _D, _D, _D, _D, _D, _D, _I,
                                            C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), c_dbl_p]),

@@ -377,6 +377,23 @@ int dkmc_update_temperature_global_analytic(const double *d_site_power, double *
  * gpubuf.site_temperature and gpubuf.T_bg.  Tolerance of these solves: dkmc_set_heat_cg_tolerance (default 1e-10; the
  * reference applies an explicit inverse). */
 void dkmc_set_heat_cg_tolerance(double tol);
+/* Where the solves of the local model run.  0 (default): every solve writes the matrix out (8-byte values) and runs the general CSR loop of the
+ * Jacobi-CG (csrc/cg.hip), the host polling the stop word per solve.  1: dkmc_construct_laplacian additionally builds, for the heat pattern, the
+ * form the K solve would choose for it (csrc/kcg.hip: the blocked form up to 262 144 interface rows, above that the windowed blocked form with
+ * dkmc_set_k_blocked_large(1), else -- or when the builder refuses, or with dkmc_set_k_blocked(0) -- the CSR positions), always with 4-byte stored
+ * words, and the solves run on the pattern-only CG of the K solve: I - s L and -L have one off-diagonal value, so the matrix is never written out
+ * and the Jacobi scaling is applied to the vectors; with more than one transient sub-step the solves are chained on the device and the host
+ * synchronises once per batch of 16 sub-steps (a sub-step whose iteration budget was too small is solved again by the polled loop).  Same model,
+ * same stop test (dkmc_set_heat_cg_tolerance); results agree with 0 to the tolerance, not bit for bit.  The model itself stays unpinned against the
+ * reference, which ships nothing that exercises it: the switch changes how the systems are solved, not what pins them.
+ * Read by dkmc_construct_laplacian. */
+void dkmc_set_heat_form(int form);
+int dkmc_get_heat_form(void);
+/* The last dkmc_update_temperature_local.  info8: form of its solves (0 CSR positions, 1 blocked, 2 windowed blocked form of csrc/kcg.hip; -1 the
+ * general CSR loop of dkmc_set_heat_form(0)), rows, stored words, sub-steps (solves), host synchronisations of the solves (form -1: the polls the
+ * batch plan of the CSR loop makes for the iteration counts it reported), sub-steps that the chain handed back to the polled loop, bytes one
+ * iteration moves, 0 (reserved). */
+int dkmc_get_heat_info(long long *info8);
 int dkmc_construct_laplacian(const dkmc_gpubuf *buf, int N_left_tot, int N_right_tot, double gamma);
 int dkmc_update_temperature_local(dkmc_gpubuf *buf, double step_time, double delta_t, double tau, double background_temp,
                                   double k_th_interface, double k_th_vacancies, double nn_dist, int num_atoms_contact,

@@ -115,6 +115,11 @@ int dkmc_debug_kbw_halfword_pos(int width, int entry);
 /* Test aid: caps the segments of a window of the windowed blocked form of K (dkmc_set_k_blocked_large) below its fixed maximum (16) for the
  * patterns built afterwards, so that the builder refuses and the solve falls back to the CSR positions.  cap <= 0 restores 16. */
 void dkmc_debug_kbw_segment_cap(int cap);
+/* Test aid for the chained transient sub-steps of the local heat model (dkmc_set_heat_form(1), csrc/heat.hip).  on = 0: every sub-step is polled by
+ * the host (the chain is off); on != 0 (default): chained.  budget > 0 fixes the iterations enqueued per chained sub-step (default 0: 64 for the first
+ * batch, then the largest count seen, rounded up to a multiple of 8, plus 8), so that a budget below what a solve needs forces the resume path.
+ * The temperatures are the same bits either way. */
+void dkmc_debug_heat_chain(int on, int budget);
 
 #ifdef __cplusplus
 }
