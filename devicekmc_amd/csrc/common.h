@@ -143,6 +143,7 @@ struct KBlocked {
     int word_bytes = 4; // form 2: bytes of a stored word of the assembled cf (dkmc_set_k_window_word_bytes when the pattern was built); pcol stays 32-bit
 };
 // ---- host side ---------------------------------------------------------------------------------
+constexpr int X_POLY_DEFAULT = 8;   // base degree of the split polynomial preconditioner (Engine::x_poly)
 struct Engine {
     hipStream_t stream = nullptr;
     int device = 0;
@@ -158,7 +159,9 @@ struct Engine {
     int x_aux = 2;                 // auxiliary columns of the block-CG (dkmc_set_x_aux; xtb.hip): 0 hash set, 1 smooth set, 2 smooth at tolerances >= 1e-8
     int x_slab = 1;                // > 1 rank: distribute the STATE of the block-CG by row slabs (xtb_slab.inc; dkmc_set_x_slab); 0: all-gather variant (tile stream sharded only)
     int k_slab = 1;                // > 1 rank, system above the size of the blocked form: CG on K distributed by row slabs (kcg.hip; dkmc_set_k_slab); 0: replicated
-    int x_poly = 8;                // degree d of the split polynomial preconditioner of the block-CG (dkmc_set_x_poly; xtb_precond.h): the loop runs on L A L, L = the degree-d Chebyshev interpolant of (1 - x)^(-1/2) in N (neighbour part); 0 = off
+    int x_poly = X_POLY_DEFAULT;                // degree d of the split polynomial preconditioner of the block-CG (dkmc_set_x_poly; xtb_precond.h): the loop runs on L A L, L = the degree-d Chebyshev interpolant of (1 - x)^(-1/2) in N (neighbour part); 0 = off.  With x_poly_auto it is the base degree: on (> 0) or off, the one-GPU loop takes its degree from the system size
+    int x_poly_auto = 1;           // 1 (default): the one-GPU preconditioned loop takes its degree from the rows of the system (xtb_poly_rule, xtb_precond.h); dkmc_set_x_poly(d) pins d and clears it, dkmc_set_x_poly_auto(1) sets it again
+    int x_poly_rows[2] = {0, 0};   // test aid (dkmc_set_x_poly_auto_rows): breakpoints of that rule; {0, 0} = the measured ones
     int x_slab_poly = 0;           // 1: the slab-distributed block-CG (> 1 rank, x_slab) runs on L A L too (dkmc_set_x_slab_poly; xtb_slab.inc); 0 (default): plain
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)

@@ -66,8 +66,11 @@ int dkmc_get_k_slab(void) { return eng().k_slab; }
 void dkmc_set_x_aux_warm(int on) { eng().x_aux_warm = on ? 1 : 0; }
 int dkmc_get_x_aux_warm(void) { return eng().x_aux_warm; }
 void dkmc_set_x_items(int kc) { eng().x_items_kc = kc > 0 ? (kc < 256 ? kc : 256) : 0; }
-void dkmc_set_x_poly(int degree) { eng().x_poly = degree < 0 ? 0 : (degree > 16 ? 16 : degree); }
+void dkmc_set_x_poly(int degree) { eng().x_poly = degree < 0 ? 0 : (degree > 16 ? 16 : degree); eng().x_poly_auto = 0; }
 int dkmc_get_x_poly(void) { return eng().x_poly; }
+void dkmc_set_x_poly_auto(int on) { Engine &e = eng(); e.x_poly_auto = on ? 1 : 0; if (on && e.x_poly <= 0) e.x_poly = X_POLY_DEFAULT; }
+int dkmc_get_x_poly_auto(void) { return eng().x_poly_auto; }
+void dkmc_set_x_poly_auto_rows(int n0, int n1) { Engine &e = eng(); e.x_poly_rows[0] = n0 > 0 ? n0 : 0; e.x_poly_rows[1] = n1 > e.x_poly_rows[0] ? n1 : e.x_poly_rows[0]; }
 void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }
 int dkmc_get_x_apply_form(void) { return eng().x_apply_form; }
 void dkmc_set_x_tile_f32(int mode) { eng().x_tile_f32 = mode == 0 ? 0 : 1; }

@@ -1246,7 +1246,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     XCtrl h{};
     bool solved = false;
     double prof_long_ms = 0.0, prof_short_ms = 0.0, prof_comm_ms = 0.0; int prof_long_n = 0, prof_short_n = 0, prof_comm_n = 0;
-    e.stats.xb_width = 1; e.stats.xb_fallback = 0;
+    e.stats.xb_width = 1; e.stats.xb_fallback = 0; e.stats.xb_poly_used = 0;
     if (e.x_block > 1 && ns > 0) {
         XtbArgs B{};
         B.m = m; B.ns = ns; B.ns_pad = ns_pad; B.nK = nK; B.nW = nW; B.s = e.x_block;

@@ -1395,7 +1395,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     double *mats = small, *drvpart = small + 4 * 256, *gfin = drvpart + 2 * XB_DSPLIT * XB_SP;
     // split polynomial preconditioner (dkmc_set_x_poly; one GPU): see k_xtb_nmul.  Vp = L P, Zp = A Vp before the second L, W1 / W2 the Horner steps;
     // behind Vp: m zeros (the right-hand side of column 0 once the start vector has gone into it) and one double for the true residual
-    const int pd = (!A.sharded && m > 2 && A.ns > 0) ? std::min(e.x_poly, XB_MAXPOLY) : 0;
+    const int pd = xtb_poly_degree(e, A);                                     // pinned (dkmc_set_x_poly) or from the rows of the system (xtb_poly_rule)
+    e.stats.xb_poly_used = pd;
     double *Vp = nullptr, *W1 = nullptr, *W2 = nullptr, *Zp = nullptr, *bz = nullptr;
     if (pd > 0) {
         Vp = (double *)scratch(S_XTB_PRE_V, (pan + m + 16) * 8); W1 = (double *)scratch(S_XTB_PRE_W1, pan * 8); W2 = (double *)scratch(S_XTB_PRE_W2, pan * 8);

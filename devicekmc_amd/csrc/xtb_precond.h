@@ -379,6 +379,27 @@ static void xtb_poly_coeffs(int pd, double *pc)
         for (int q = 0; q <= d; ++q) pc[q] = res[q];
     }
 }
+// ---- the degree a solve runs ---------------------------------------------------------------------------------------------------------------
+// A sweep costs (tile pass + row passes) + 2 d N products and the sweep count falls with d, so the best degree grows with the share of the tile pass,
+// that is with the rows m of the system.  Step function of m from profiles/x_poly_degree_by_size.jsonl (steady warm-started steps, degrees 6 ... 16,
+// the fastest degree of a size, the lower neighbour where that lies within the size's run-to-run spread): 8 at 57.8 k and 160 526 rows (at 160 526
+// degree 10 ties with it), 10 at 314 630 (12 is 1.3 % ahead of it, inside the spread; 8 is 3.3 % behind), 16 at 642 101 (1.13 x degree 8).  The
+// breakpoints are the geometric midpoints between those sizes.
+// rows = {0, 0}: these breakpoints; anything else overrides them (dkmc_set_x_poly_auto_rows: lets a test reach every branch at a small size).
+static const int xb_poly_rows[2] = {225000, 450000};                          // rows below the first: step 0, below the second: step 1, else step 2
+static const int xb_poly_steps[3] = {8, 10, 16};
+static int xtb_poly_rule(int m, const int *rows)
+{
+    if (m <= 2) return 0;
+    const int *n = (rows && (rows[0] > 0 || rows[1] > 0)) ? rows : xb_poly_rows;
+    return std::min(xb_poly_steps[m < n[0] ? 0 : (m < n[1] ? 1 : 2)], XB_MAXPOLY);
+}
+// degree of the one-GPU loop's solve: 0 where it runs plain (base degree 0, no tunnelling set, sharded), the pinned degree, or the rule's
+static int xtb_poly_degree(const Engine &e, const XtbArgs &A)
+{
+    if (A.sharded || A.m <= 2 || A.ns <= 0 || e.x_poly <= 0) return 0;
+    return e.x_poly_auto ? xtb_poly_rule(A.m, e.x_poly_rows) : std::min(e.x_poly, XB_MAXPOLY);
+}
 
 // ---- test aids of the split polynomial preconditioner (tests/test_precond_coeffs.py, tests/test_gpu_precond_reference.py) -------------------
 // The production path (xtb_npack, xtb_nstep, xtb_applyL) on buffers of their own (S_XTB_TEST_*): nothing a solve reads or keeps is touched.
@@ -389,6 +410,8 @@ extern "C" int dkmc_xtb_poly_coeffs(int degree, double *pc)
     xtb_poly_coeffs(degree, pc);
     return 0;
 }
+// the degree the rule gives a one-GPU solve of m rows (breakpoints of dkmc_set_x_poly_auto_rows included); host code only (no HIP call)
+extern "C" int dkmc_xtb_poly_rule(int m) { return xtb_poly_rule(m, eng().x_poly_rows); }
 // QS (interleaved, xtb_qs_pos) -> [ns][16]
 __global__ void k_xtb_test_qs_decode(int ns, const double *__restrict__ QS, double *__restrict__ out)
 {

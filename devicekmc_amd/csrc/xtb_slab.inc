@@ -412,7 +412,8 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     KCHK();
 
     // split polynomial preconditioner (dkmc_set_x_slab_poly; opt-in): the loop runs on L A L with the degree and coefficients of the one-GPU loop
-    const int pd = (e.x_slab_poly && m > 2 && ns > 0) ? std::min(e.x_poly, XB_MAXPOLY) : 0;
+    const int pd = (e.x_slab_poly && m > 2 && ns > 0) ? std::min(e.x_poly, XB_MAXPOLY) : 0;       // (the explicit degree: the rule of the one-GPU loop was measured there only)
+    e.stats.xb_poly_used = pd;
     double pc[XB_MAXPOLY + 1] = {1.0};
     xtb_poly_coeffs(pd, pc);
     const double tol2_loop = pd > 0 ? A.tol2 / 2.25 : A.tol2;                  // as in xtb_cg_body: the true residual is checked at the end

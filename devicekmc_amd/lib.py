@@ -40,7 +40,7 @@ class dkmc_stats(C.Structure):
                 ("spmv_tiles", C.c_int), ("spmv_pad2", C.c_int), ("spmv_tile_entries", C.c_longlong),
                 ("xt_subblocks", C.c_longlong), ("xt_local_subblocks", C.c_longlong), ("xt_items", C.c_int), ("xt_kc", C.c_int),
                 ("xt_sparse_nnz", C.c_longlong), ("xt_ns", C.c_int), ("xt_split_launch", C.c_int),
-                ("kcg_ms", C.c_double), ("kcg_iters_timed", C.c_int), ("kcg_blocked", C.c_int), ("pair_ms", C.c_double), ("pair_evaluated", C.c_longlong), ("pair_tested", C.c_longlong), ("xt_records", C.c_longlong), ("tcache_bytes", C.c_longlong), ("kcg_bytes", C.c_longlong), ("xb_aux", C.c_int), ("xb_pad", C.c_int), ("xb_width", C.c_int), ("xb_fallback", C.c_int), ("x_tile_stream", C.c_int), ("x_tile_f64_rounds", C.c_int), ("x_tile_f32_bytes", C.c_longlong)]
+                ("kcg_ms", C.c_double), ("kcg_iters_timed", C.c_int), ("kcg_blocked", C.c_int), ("pair_ms", C.c_double), ("pair_evaluated", C.c_longlong), ("pair_tested", C.c_longlong), ("xt_records", C.c_longlong), ("tcache_bytes", C.c_longlong), ("kcg_bytes", C.c_longlong), ("xb_aux", C.c_int), ("xb_poly_used", C.c_int), ("xb_width", C.c_int), ("xb_fallback", C.c_int), ("x_tile_stream", C.c_int), ("x_tile_f64_rounds", C.c_int), ("x_tile_f32_bytes", C.c_longlong)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p)
@@ -66,6 +66,9 @@ SYMBOLS = {
     "dkmc_set_x_items": (None, [_I]),
     "dkmc_set_x_poly": (None, [_I]),
     "dkmc_get_x_poly": (_I, []),
+    "dkmc_set_x_poly_auto": (None, [_I]),
+    "dkmc_get_x_poly_auto": (_I, []),
+    "dkmc_set_x_poly_auto_rows": (None, [_I, _I]),
     "dkmc_set_x_tile_f32": (None, [_I]),
     "dkmc_get_x_tile_f32": (_I, []),
     "dkmc_debug_fail_true_residual_once": (None, []),
@@ -146,6 +149,7 @@ SYMBOLS = {
     "dkmc_xtb_tile_product": (_I, [_I, _I, vp]),
     "dkmc_xt_get_tiles": (_I, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp]),
     "dkmc_xtb_poly_coeffs": (_I, [_I, c_dbl_p]),
+    "dkmc_xtb_poly_rule": (_I, [_I]),
     "dkmc_xtb_test_nstep": (_I, [_I, vp, vp, vp, vp, vp, vp, _D, _D, _I, vp, _I, vp, _I, vp, vp]),
     "dkmc_xtb_check_poly": (_I, [_I, _I, vp, vp, vp]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),

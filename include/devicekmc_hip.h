@@ -101,7 +101,7 @@ typedef struct dkmc_stats {
     long long xt_records;                  /* records of column partial sums one matrix-vector product writes (= runs; runs / 4 on one GPU, where the four waves of a workgroup share one) */
     long long tcache_bytes;                /* bytes of tunnelling-coefficient cache THIS rank holds (sharded solve on the tiled X: what its tiles read) */
     long long kcg_bytes;                   /* bytes one iteration of the last K solve moves: column/class words (2 B each on the windowed form with dkmc_set_k_window_word_bytes(2)) + the q windows (or one read of q per row) + 14 (15) vector touches */
-    int xb_aux, xb_pad;                    /* 1: the last block solve used the smooth auxiliary columns (dkmc_set_x_aux) */
+    int xb_aux, xb_poly_used;              /* 1: the last block solve used the smooth auxiliary columns (dkmc_set_x_aux); degree of the split polynomial preconditioner the last current solve ran (0: plain loop; dkmc_set_x_poly / dkmc_set_x_poly_auto) */
     int xb_width, xb_fallback;             /* block-CG width of the last current solve (1 = single-vector loop); 1 if the block loop lost definiteness and the single-vector loop finished the solve */
     int x_tile_stream, x_tile_f64_rounds;  /* tile values the sweeps of the last block solve's first round streamed: 0 the fp64 store, 1 its fp32 image (dkmc_set_x_tile_f32), -1 the fp64 store because the image could not be allocated; rounds of that solve that ran on the fp64 store (one-GPU loop: all of them at 0 / -1; at 1 only the re-entry rounds after a true-residual check above the stop test) */
     long long x_tile_f32_bytes;            /* bytes of the fp32 image of the tile values (0: none was made) */
@@ -156,10 +156,16 @@ int dkmc_get_x_block(void);
  * L = p(N), p the degree-d Chebyshev interpolant of (1 - x)^(-1/2) on [-1, 1 - min(0.5, 1.6 / d^2)], N = I - (neighbour part + diagonal of the
  * Jacobi-scaled X).  A sweep then costs 2 d more sparse panel products and the loop needs 2-3x fewer sweeps (tools/precond_block_proto.py); the start
  * vector enters through the right-hand side L (b - A y0), the result meets the reference's stop test in the TRUE residual (checked, the loop is
- * re-entered if it does not).  d in 0 ... 16 (clamped), 0 = off; default 8.  Applies to the one-GPU loop; the slab-distributed loop of more than one
- * rank carries it only with dkmc_set_x_slab_poly(1). */
+ * re-entered if it does not).  d in 0 ... 16 (clamped), 0 = off; base degree 8.  Applies to the one-GPU loop; the slab-distributed loop of more than one
+ * rank carries it only with dkmc_set_x_slab_poly(1), at the base / pinned degree.
+ * By default (dkmc_set_x_poly_auto(1)) the one-GPU loop takes its degree from the rows of the system: a step function measured on steady warm-started
+ * steps (profiles/x_poly_degree_by_size.jsonl) -- the N products weigh less in a sweep the larger the tile pass is, so larger systems run a
+ * higher degree.  dkmc_set_x_poly(d) pins d (d > 0) or turns the preconditioner off (0) and clears the rule; dkmc_set_x_poly_auto(1) turns the rule
+ * back on (a base degree of 0 returns to 8).  dkmc_get_x_poly(): the pinned or base degree; dkmc_stats.xb_poly_used: the degree the last solve ran. */
 void dkmc_set_x_poly(int degree);
 int dkmc_get_x_poly(void);
+void dkmc_set_x_poly_auto(int on);
+int dkmc_get_x_poly_auto(void);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
  * the column's scaling folded into the weights (csrc/xtb_precond.h: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
  * Both give the same bits; 0 is kept for comparisons. */

@@ -34,6 +34,12 @@ int dkmc_xtb_check_product(int width, double *max_abs_diff, double *max_abs);
  * dkmc_xtb_check_poly: L in (the full Horner sequence with QS, as a sweep applies it) on the X left resident by the last single-GPU solve, with that
  * solve's scaling, neighbour part and S ranks: in / out [m][16], m = rows of X; qs [ns][16].  Leaves the next solve's start and launch batch alone. */
 int dkmc_xtb_poly_coeffs(int degree, double *pc);
+/* The degree rule of the one-GPU preconditioned loop (dkmc_set_x_poly_auto; csrc/xtb_precond.h: xtb_poly_rule).
+ * dkmc_xtb_poly_rule: the degree it gives a system of m rows (0 for m <= 2); host code only, no GPU needed.
+ * dkmc_set_x_poly_auto_rows: test aid -- overrides the rule's two breakpoints (rows below n0: first step, below n1: second, else third) so that
+ * every branch can be reached at a small size; (0, 0) restores the measured ones. */
+int dkmc_xtb_poly_rule(int m);
+void dkmc_set_x_poly_auto_rows(int n0, int n1);
 int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
                         double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs);
 int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs);
