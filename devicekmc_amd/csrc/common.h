@@ -153,6 +153,7 @@ struct Engine {
     int cb_edge_domain = 0;        // 0: CB-edge system over every site (snapshot source); 1: over atoms only (dkmc_set_cb_edge_domain)
     long long tcache_budget = -1;  // bytes the tunnelling-coefficient cache may take; -1 = a third of the free device memory, 8-128 GiB (dkmc_set_tcache_budget)
     double pair_cut = 6.5;         // screening cut-off of the pair sum in units of sigma sqrt 2 (dkmc_set_pair_cutoff; 0 = all pairs like the reference)
+    int pair_form = 0;             // sum kernels of the pair sum: 0 = a term is evaluated where it is tested; 1 = a wave queues the passing pairs and evaluates 64 at a time; same bits (dkmc_set_pair_form; potential.hip)
     int k_blocked = 1;             // build the blocked form of K patterns (dkmc_set_k_blocked; kcg.hip)
     int k_blocked_large = 0;       // 1: above KB_MAXROWS rows build the windowed blocked form instead (dkmc_set_k_blocked_large; kcg.hip)
     int k_window_word_bytes = 4;   // stored words of the windowed blocked form: 4 = one int per entry, 2 = 16 bits per entry (14-bit LDS offset + class bit 15); same results (dkmc_set_k_window_word_bytes; kcg.hip)

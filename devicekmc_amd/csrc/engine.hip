@@ -61,6 +61,8 @@ void dkmc_set_x_format(int tiled) { eng().x_format = tiled ? 1 : 0; }
 int dkmc_get_x_format(void) { return eng().x_format; }
 void dkmc_set_tcache_budget(long long bytes) { eng().tcache_budget = bytes; }
 void dkmc_set_pair_cutoff(double x_cut) { eng().pair_cut = x_cut > 0.0 ? x_cut : 0.0; }
+void dkmc_set_pair_form(int form) { eng().pair_form = form == 1 ? 1 : 0; }
+int dkmc_get_pair_form(void) { return eng().pair_form; }
 void dkmc_set_k_slab(int on) { eng().k_slab = on ? 1 : 0; }
 int dkmc_get_k_slab(void) { return eng().k_slab; }
 void dkmc_set_x_aux_warm(int on) { eng().x_aux_warm = on ? 1 : 0; }

@@ -335,8 +335,7 @@ __global__ void k_charge_scatter(int N, const int *__restrict__ charge, const in
 // 3.8e-20 k Q / r, i.e. < 1e-19 of a nearest-neighbour term; all such terms of a 1e6-site stack together stay under 2e-17 V, below
 // the rounding of the sum itself (the reference's atomicAdd order already moves the last bits).  Those pairs pay the
 // distance (12 flops) but not erfc / sqrt / divide: 95 % of the pairs at 9.4e5 sites.  The count of evaluated pairs is reported.
-__device__ __forceinline__ double pw_term(double xi, double yi, double zi, const ChargedSite &c, int i, double laty, double latz, int pbc,
-                                          double sigma, double kk, double cut2, int &neval)
+__device__ __forceinline__ double pw_d2(double xi, double yi, double zi, const ChargedSite &c, double laty, double latz, int pbc)
 {
     double dx, dy, dz;
     if (pbc) {
@@ -345,12 +344,112 @@ __device__ __forceinline__ double pw_term(double xi, double yi, double zi, const
         double fz = (zi - c.z) / latz; fz -= round(fz);
         dy = fy * laty; dz = fz * latz;
     } else { dx = c.x - xi; dy = c.y - yi; dz = c.z - zi; }
-    const double d2 = dx * dx + dy * dy + dz * dz;                 // the argument of site_dist's sqrt (gpu_solvers.h:225-257), same order
+    return dx * dx + dy * dy + dz * dz;                            // the argument of site_dist's sqrt (gpu_solvers.h:225-257), same order
+}
+__device__ __forceinline__ double pw_term(double xi, double yi, double zi, const ChargedSite &c, int i, double laty, double latz, int pbc,
+                                          double sigma, double kk, double cut2, int &neval)
+{
+    const double d2 = pw_d2(xi, yi, zi, c, laty, latz, pbc);
     if (c.idx == i || d2 > cut2) return 0.0;
     ++neval;
     return v_solve(1e-10 * sqrt(d2), c.q, sigma, kk);
 }
-__global__ __launch_bounds__(PW_NT) void k_pairwise(int N, const double *__restrict__ x, const double *__restrict__ y,
+// ---- the two forms of the sweep (dkmc_set_pair_form) ------------------------------------------------------------------------------
+// Form 0 evaluates a term where it is tested: the branch in pw_term is per lane, so a wave runs erfc / sqrt / the divisions whenever ANY of its 64
+// sites passes.  Form 1 tests the same way but only QUEUES the passing (site, entry) pairs, in a ring of PW_RING slots per wave in LDS, and evaluates
+// 64 queued pairs at a time with every lane busy.  The bits stay: a site's potential is (p0 + p1) + (p2 + p3), p_w = v0_w + v1_w, v0_w / v1_w the
+// sums in ascending list order of the terms at tile positions = w / w + 4 (mod 8) -- a pair that fails adds 0.0, which changes nothing.  Form 1
+// keeps these eight class sums per site in LDS (rows w and w + 4 belong to wave w), a batch adds its terms entry by entry in the order they were
+// queued (a site occurs once per entry: no conflict inside a round), and the classes are combined as before.  A slot carries the d2 of the test (not
+// recomputed: a second copy of the expression need not be contracted into the same FMAs), the charge, and a tag: lane of the site (bits 0-5), class
+// (bit 6), ordinal of the entry in this wave's walk (bits 7-31: 2^25 entries per wave, i.e. 1.3e8 charged sites; full width, so that two entries far
+// apart in the list never share one).  Queue and class sums are private to a wave: LDS operations of a wave complete in order, the wave barriers
+// only keep the compiler from moving them.
+#define PW_RING 128
+template <int FORM> struct PwShared;
+template <> struct PwShared<0> { double partial[PW_NT / 64][PW_SITES]; };
+template <> struct PwShared<1> {
+    double partial[2 * (PW_NT / 64)][PW_SITES];                    // class sums, rows w / w + 4 of wave w; at the end rows 0-3 hold the waves' partial sums
+    double d2[PW_NT / 64][PW_RING];
+    int q[PW_NT / 64][PW_RING];
+    unsigned tag[PW_NT / 64][PW_RING];
+};
+struct PwWalk { double v0, v1; int neval, ntest, head, tail, ord, nstep, nbatch; };      // of a wave; all but v0 / v1 / ntest (and form 0's neval) are wave-uniform
+template <int FORM> __device__ __forceinline__ void pw_begin(PwWalk &L, PwShared<FORM> &S, int w, int lane)
+{
+    L.v0 = L.v1 = 0.0; L.neval = L.ntest = L.head = L.tail = L.ord = L.nstep = L.nbatch = 0;
+    if constexpr (FORM == 1) { S.partial[w][lane] = 0.0; S.partial[w + 4][lane] = 0.0; __builtin_amdgcn_wave_barrier(); }
+}
+// evaluates the `cnt` (<= 64) oldest queued pairs of wave w, one per lane, and adds the terms to the class sums in queue order
+__device__ __forceinline__ void pw_drain(PwWalk &L, PwShared<1> &S, int w, int lane, int cnt, double sigma, double kk)
+{
+    __builtin_amdgcn_wave_barrier();
+    const bool on = lane < cnt;
+    double term = 0.0; unsigned tag = 0u;
+    if (on) {
+        const int s = (L.head + lane) & (PW_RING - 1);
+        tag = S.tag[w][s];
+        term = v_solve(1e-10 * sqrt(S.d2[w][s]), S.q[w][s], sigma, kk);
+    }
+    unsigned long long rem = __ballot(on);
+    while (rem) {                                                  // one round per entry with a pair in this batch, ascending
+        const unsigned o = (unsigned)__builtin_amdgcn_readlane((int)tag, __ffsll((long long)rem) - 1) >> 7;
+        const bool mine = on && (tag >> 7) == o;
+        if (mine) S.partial[((tag >> 6) & 1u) * 4 + w][tag & 63u] += term;
+        rem &= ~__ballot(mine);
+    }
+    __builtin_amdgcn_wave_barrier();
+    L.head += cnt; ++L.nbatch;
+}
+// one LDS tile of n charged sites: wave w takes entries w, w + 4, ...; `valid`: the lane holds a site of this call
+template <int FORM> __device__ __forceinline__ void pw_sweep(PwWalk &L, PwShared<FORM> &S, const ChargedSite *tile, int n, bool valid, int i, double xi, double yi, double zi,
+                                                             double laty, double latz, int pbc, double sigma, double kk, double cut2, int w, int lane)
+{
+    if constexpr (FORM == 0) {
+        if (valid) {
+            int c = w;
+            L.ntest += (n - w + 3) / 4;                              // entries w, w + 4, ... of this tile
+            for (; c + 4 < n; c += 8) {
+                L.v0 += pw_term(xi, yi, zi, tile[c], i, laty, latz, pbc, sigma, kk, cut2, L.neval);
+                L.v1 += pw_term(xi, yi, zi, tile[c + 4], i, laty, latz, pbc, sigma, kk, cut2, L.neval);
+            }
+            if (c < n) L.v0 += pw_term(xi, yi, zi, tile[c], i, laty, latz, pbc, sigma, kk, cut2, L.neval);
+        }
+    } else {
+        if (valid) L.ntest += (n - w + 3) / 4;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        for (int c = w; c < n; c += 4, ++L.ord) {                   // every lane takes part in the ballots, also one without a site
+            const double d2 = pw_d2(xi, yi, zi, tile[c], laty, latz, pbc);
+            const bool pass = valid && tile[c].idx != i && !(d2 > cut2);
+            const unsigned long long bal = __ballot(pass);
+            if (pass) {
+                const int s = (L.tail + __popcll(bal & below)) & (PW_RING - 1);
+                S.d2[w][s] = d2; S.q[w][s] = tile[c].q; S.tag[w][s] = (unsigned)lane | (unsigned)((c >> 2) & 1) << 6 | (unsigned)L.ord << 7;
+            }
+            const int np = __popcll(bal);
+            L.tail += np; L.neval += np; L.nstep += bal != 0ull;
+            if (L.tail - L.head >= 64) pw_drain(L, S, w, lane, 64, sigma, kk);      // at most 63 + 64 <= PW_RING pairs are ever queued
+        }
+    }
+}
+// the wave's partial sum of every site into S.partial[w] and its counters: nevaluated[0] pairs inside the cut-off, [1] pairs tested; form 1 also
+// [2] entries with at least one passing lane (what form 0 spends on the expensive part, in units of 64 lane slots), [3] batches
+template <int FORM> __device__ __forceinline__ void pw_end(PwWalk &L, PwShared<FORM> &S, int w, int lane, double sigma, double kk, unsigned long long *nevaluated)
+{
+    if constexpr (FORM == 0) {
+        S.partial[w][lane] = L.v0 + L.v1;
+        L.neval = wave_sum_all_i(L.neval);
+    } else {
+        if (L.tail > L.head) pw_drain(L, S, w, lane, L.tail - L.head, sigma, kk);
+        S.partial[w][lane] = S.partial[w][lane] + S.partial[w + 4][lane];
+        if (lane == 0 && L.nstep) atomicAdd(nevaluated + 2, (unsigned long long)L.nstep);
+        if (lane == 0 && L.nbatch) atomicAdd(nevaluated + 3, (unsigned long long)L.nbatch);
+    }
+    L.ntest = wave_sum_all_i(L.ntest);
+    if (lane == 0 && L.neval) atomicAdd(nevaluated, (unsigned long long)L.neval);
+    if (lane == 0 && L.ntest) atomicAdd(nevaluated + 1, (unsigned long long)L.ntest);
+}
+template <int FORM> __global__ __launch_bounds__(PW_NT) void k_pairwise(int N, const double *__restrict__ x, const double *__restrict__ y,
                                                     const double *__restrict__ z, const double *__restrict__ lattice, int pbc,
                                                     const double *__restrict__ sigma_p, const double *__restrict__ k_p,
                                                     const ChargedSite *__restrict__ list, const int *__restrict__ ncharged,
@@ -359,7 +458,7 @@ __global__ __launch_bounds__(PW_NT) void k_pairwise(int N, const double *__restr
 {
     if (*cells_in_use) return;                                     // the cell-list kernel (k_pairwise_cells, below) does this call
     __shared__ ChargedSite tile[PW_NT];
-    __shared__ double partial[PW_NT / 64][PW_SITES];
+    __shared__ PwShared<FORM> S;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int i = i0 + blockIdx.x * PW_SITES + lane;               // sites [i0, N): all of them on one GPU, this rank's slab in a sharded run
     const int nc = *ncharged;
@@ -367,29 +466,18 @@ __global__ __launch_bounds__(PW_NT) void k_pairwise(int N, const double *__restr
     const double rc = xcut * sigma * sqrt(2.0) * 1e10;             // [A]; xcut = 0: every pair, as the reference sums (dkmc_set_pair_cutoff)
     const double cut2 = xcut > 0.0 ? rc * rc : 1.0e300;
     const double xi = i < N ? x[i] : 0.0, yi = i < N ? y[i] : 0.0, zi = i < N ? z[i] : 0.0;
-    double v0 = 0.0, v1 = 0.0;
-    int neval = 0, ntest = 0;
+    PwWalk L;
+    pw_begin(L, S, w, lane);
     for (int base = 0; base < nc; base += PW_NT) {
         const int n = min(PW_NT, nc - base);
         __syncthreads();
         if (threadIdx.x < n) tile[threadIdx.x] = list[base + threadIdx.x];
         __syncthreads();
-        if (i < N) {
-            int c = w;
-            ntest += (n - w + 3) / 4;                                // entries w, w + 4, ... of this tile
-            for (; c + 4 < n; c += 8) {
-                v0 += pw_term(xi, yi, zi, tile[c], i, laty, latz, pbc, sigma, kk, cut2, neval);
-                v1 += pw_term(xi, yi, zi, tile[c + 4], i, laty, latz, pbc, sigma, kk, cut2, neval);
-            }
-            if (c < n) v0 += pw_term(xi, yi, zi, tile[c], i, laty, latz, pbc, sigma, kk, cut2, neval);
-        }
+        pw_sweep(L, S, tile, n, i < N, i, xi, yi, zi, laty, latz, pbc, sigma, kk, cut2, w, lane);
     }
-    partial[w][lane] = v0 + v1;
-    neval = wave_sum_all_i(neval); ntest = wave_sum_all_i(ntest);
-    if (lane == 0 && neval) atomicAdd(nevaluated, (unsigned long long)neval);
-    if (lane == 0 && ntest) atomicAdd(nevaluated + 1, (unsigned long long)ntest);
+    pw_end(L, S, w, lane, sigma, kk, nevaluated);
     __syncthreads();
-    if (w == 0 && i < N) out[i] = (partial[0][lane] + partial[1][lane]) + (partial[2][lane] + partial[3][lane]);
+    if (w == 0 && i < N) out[i] = (S.partial[0][lane] + S.partial[1][lane]) + (S.partial[2][lane] + S.partial[3][lane]);
 }
 
 // ---- pair sum over a cell list of the charged sites ---------------------------------------------------------------------------
@@ -621,7 +709,7 @@ __global__ __launch_bounds__(64) void k_pw_partition_x(const PwGrid *__restrict_
 // the sum itself: block -> (column, chunk of 64 of its sites, x-ordered); the columns within reach in a fixed order, of each the x bins within
 // rc of the chunk's span; the segments are gathered into LDS tiles of 256 entries
 #define PW_MAXSEG 32
-__global__ __launch_bounds__(PW_NT) void k_pairwise_cells(int N, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
+template <int FORM> __global__ __launch_bounds__(PW_NT) void k_pairwise_cells(int N, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                                           int pbc, const double *__restrict__ sigma_p, const double *__restrict__ k_p,
                                                           const PwGrid *__restrict__ g, const int *__restrict__ tstart, const int *__restrict__ cstart,
                                                           const int *__restrict__ chunk0, const int *__restrict__ perm, const ChargedSite *__restrict__ clist,
@@ -632,7 +720,7 @@ __global__ __launch_bounds__(PW_NT) void k_pairwise_cells(int N, const double *_
     const PwGrid G = *g;
     if ((int)blockIdx.x >= G.nchunks) return;
     __shared__ ChargedSite tile[PW_NT];
-    __shared__ double partial[PW_NT / 64][PW_SITES];
+    __shared__ PwShared<FORM> S;
     __shared__ int seg_lo[PW_MAXSEG], seg_pre[PW_MAXSEG + 1], nseg_s;
     __shared__ double xspan[2];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -687,8 +775,8 @@ __global__ __launch_bounds__(PW_NT) void k_pairwise_cells(int N, const double *_
     }
     __syncthreads();
     const int nseg = nseg_s, total = seg_pre[nseg];
-    double v0 = 0.0, v1 = 0.0;
-    int neval = 0, ntest = 0;
+    PwWalk L;
+    pw_begin(L, S, w, lane);
     for (int base = 0; base < total; base += PW_NT) {
         const int n = min(PW_NT, total - base);
         __syncthreads();
@@ -699,28 +787,27 @@ __global__ __launch_bounds__(PW_NT) void k_pairwise_cells(int N, const double *_
             tile[threadIdx.x] = clist[seg_lo[k_] + (vp - seg_pre[k_])];
         }
         __syncthreads();
-        if (i >= 0) {
-            int q = w;
-            ntest += (n - w + 3) / 4;
-            for (; q + 4 < n; q += 8) {
-                v0 += pw_term(xi, yi, zi, tile[q], i, G.ly, G.lz, pbc, sigma, kk, cut2, neval);
-                v1 += pw_term(xi, yi, zi, tile[q + 4], i, G.ly, G.lz, pbc, sigma, kk, cut2, neval);
-            }
-            if (q < n) v0 += pw_term(xi, yi, zi, tile[q], i, G.ly, G.lz, pbc, sigma, kk, cut2, neval);
-        }
+        pw_sweep(L, S, tile, n, i >= 0, i, xi, yi, zi, G.ly, G.lz, pbc, sigma, kk, cut2, w, lane);
     }
-    partial[w][lane] = v0 + v1;
-    neval = wave_sum_all_i(neval); ntest = wave_sum_all_i(ntest);
-    if (lane == 0 && neval) atomicAdd(nevaluated, (unsigned long long)neval);
-    if (lane == 0 && ntest) atomicAdd(nevaluated + 1, (unsigned long long)ntest);
+    pw_end(L, S, w, lane, sigma, kk, nevaluated);
     __syncthreads();
-    if (w == 0 && i >= 0) out[i] = (partial[0][lane] + partial[1][lane]) + (partial[2][lane] + partial[3][lane]);
+    if (w == 0 && i >= 0) out[i] = (S.partial[0][lane] + S.partial[1][lane]) + (S.partial[2][lane] + S.partial[3][lane]);
 }
 
 // what the host knows of the cached grouping of the sites by column (see dkmc_poisson_gridless_gpu)
 static struct PwKey { const void *x, *y, *z, *lattice, *perm, *cells; int N, pbc; double cut; int possible, ncell; } g_pw_key = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, -1.0, 0, 0};
 void pairsum_invalidate() { g_pw_key.x = nullptr; g_pw_key.N = 0; }
 extern "C" void dkmc_reset_pair_sum_cache(void) { pairsum_invalidate(); }
+// the last pair sum made with profiling on (dkmc_get_pair_sum_info, devicekmc_hip_debug.h)
+static struct PwInfo { long long info[6]; double ms[2]; int valid; } g_pw_info = {{0, 0, 0, -1, -1, 0}, {0.0, 0.0}, 0};
+extern "C" int dkmc_get_pair_sum_info(long long *info, double *ms)
+{
+    if (!info || !ms) return dkmc_fail(13, "get_pair_sum_info: bad arguments", __FILE__, __LINE__);
+    if (!g_pw_info.valid) return dkmc_fail(13, "get_pair_sum_info: no pair sum has run with profiling on", __FILE__, __LINE__);
+    for (int k = 0; k < 6; ++k) info[k] = g_pw_info.info[k];
+    ms[0] = g_pw_info.ms[0]; ms[1] = g_pw_info.ms[1];
+    return 0;
+}
 
 extern "C" int dkmc_poisson_gridless_gpu(int num_atoms_contact, int pbc, int N, const double *lattice, const double *sigma,
                                          const double *k, const double *x, const double *y, const double *z,
@@ -729,7 +816,7 @@ extern "C" int dkmc_poisson_gridless_gpu(int num_atoms_contact, int pbc, int N, 
     (void)num_atoms_contact;
     Engine &e = eng(); hipStream_t st = e.stream;
     int *flag = (int *)scratch(S_MISC0, (size_t)N * 4), *off = (int *)scratch(S_MISC1, (size_t)N * 4);
-    int *cnt = (int *)scratch(S_PW_CNT, 32);
+    int *cnt = (int *)scratch(S_PW_CNT, 48);                          // word 0: charged sites (k_ev_loop reads it too); bytes 16-47: the sum kernels' four counters
     ChargedSite *list = (ChargedSite *)scratch(S_PW_LIST, (size_t)N * sizeof(ChargedSite));
     if (!flag || !off || !cnt || !list) return e.err_code;
     const int blocks = (N + 255) / 256;
@@ -741,8 +828,13 @@ extern "C" int dkmc_poisson_gridless_gpu(int num_atoms_contact, int pbc, int N, 
         if (!evp_ready) { HIPCHK(hipEventCreate(&evp[0])); HIPCHK(hipEventCreate(&evp[1])); evp_ready = true; }
         HIPCHK(hipEventRecord(evp[0], st));
     }
-    unsigned long long *d_ne = (unsigned long long *)(cnt + 4);          // [0] pairs evaluated (inside the cut-off), [1] pairs tested
-    HIPCHK(hipMemsetAsync(d_ne, 0, 16, st));
+    unsigned long long *d_ne = (unsigned long long *)(cnt + 4);          // [0] pairs evaluated (inside the cut-off), [1] pairs tested; form 1: [2] entries with a passing lane, [3] batches
+    HIPCHK(hipMemsetAsync(d_ne, 0, 32, st));
+    const int form = e.pair_form;                                      // read at every call (dkmc_set_pair_form)
+    static hipEvent_t evs[2]; static bool evs_ready = false;          // profiling: the sum kernels alone
+    if (e.profiling && !evs_ready) { HIPCHK(hipEventCreate(&evs[0])); HIPCHK(hipEventCreate(&evs[1])); evs_ready = true; }
+    int sum_blocks = 0;                                                // workgroups of k_pairwise in this call
+#define PW_LAUNCH(KERNEL, ...) do { if (form == 1) hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); else hipLaunchKernelGGL(KERNEL<0>, __VA_ARGS__); } while (0)
     // cell list over the charged sites (taken on the device when the cut-off is on, the box has >= 3 columns along y or z and
     // enough sites are charged; otherwise these launches return at once and k_pairwise sums over the whole list)
     int *cells = (int *)scratch(S_PW_CELLS, (size_t)(8 * (PW_MAXCELL + 1) + PW_MAXCELL * (PW_MAXX + 1)) * 4 + sizeof(PwGrid) + 16);
@@ -797,21 +889,28 @@ extern "C" int dkmc_poisson_gridless_gpu(int num_atoms_contact, int pbc, int N, 
         double *xbuf = (double *)scratch(S_CG_XCHG, (size_t)nr * chunk * 8);
         if (!xbuf) return e.err_code;
         const int lo = std::min(N, me * chunk), hi = std::min(N, lo + chunk);
+        if (e.profiling) HIPCHK(hipEventRecord(evs[0], st));
+        sum_blocks = (hi - lo + PW_SITES - 1) / PW_SITES;
         if (hi > lo)
-            hipLaunchKernelGGL(k_pairwise, dim3((hi - lo + PW_SITES - 1) / PW_SITES), dim3(PW_NT), 0, st, hi, x, y, z, lattice, pbc, sigma, k, list, cnt, xbuf, d_ne, lo, e.pair_cut, cells_in_use);
+            PW_LAUNCH(k_pairwise, dim3(sum_blocks), dim3(PW_NT), 0, st, hi, x, y, z, lattice, pbc, sigma, k, list, cnt, xbuf, d_ne, lo, e.pair_cut, cells_in_use);
         if (hi > lo && key.possible)
-            hipLaunchKernelGGL(k_pairwise_cells, dim3(cell_blocks), dim3(PW_NT), 0, st, N, x, y, z, pbc, sigma, k, (const PwGrid *)grid, (const int *)tstart, (const int *)cstart,
+            PW_LAUNCH(k_pairwise_cells, dim3(cell_blocks), dim3(PW_NT), 0, st, N, x, y, z, pbc, sigma, k, (const PwGrid *)grid, (const int *)tstart, (const int *)cstart,
                                (const int *)chunk0, (const int *)pperm2, (const ChargedSite *)clist3, (const int *)cxoff, xbuf, d_ne, lo, hi, e.pair_cut);
         KCHK();
+        if (e.profiling) HIPCHK(hipEventRecord(evs[1], st));
         rc = comm_allgather_f64(xbuf, (size_t)chunk); if (rc) return rc;
         HIPCHK(hipMemcpyAsync(out, xbuf, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
     } else {
-        hipLaunchKernelGGL(k_pairwise, dim3((N + PW_SITES - 1) / PW_SITES), dim3(PW_NT), 0, st, N, x, y, z, lattice, pbc, sigma, k, list, cnt, out, d_ne, 0, e.pair_cut, cells_in_use);
+        if (e.profiling) HIPCHK(hipEventRecord(evs[0], st));
+        sum_blocks = (N + PW_SITES - 1) / PW_SITES;
+        PW_LAUNCH(k_pairwise, dim3(sum_blocks), dim3(PW_NT), 0, st, N, x, y, z, lattice, pbc, sigma, k, list, cnt, out, d_ne, 0, e.pair_cut, cells_in_use);
         if (key.possible)
-            hipLaunchKernelGGL(k_pairwise_cells, dim3(cell_blocks), dim3(PW_NT), 0, st, N, x, y, z, pbc, sigma, k, (const PwGrid *)grid, (const int *)tstart, (const int *)cstart,
+            PW_LAUNCH(k_pairwise_cells, dim3(cell_blocks), dim3(PW_NT), 0, st, N, x, y, z, pbc, sigma, k, (const PwGrid *)grid, (const int *)tstart, (const int *)cstart,
                                (const int *)chunk0, (const int *)pperm2, (const ChargedSite *)clist3, (const int *)cxoff, out, d_ne, 0, N, e.pair_cut);
         KCHK();
+        if (e.profiling) HIPCHK(hipEventRecord(evs[1], st));
     }
+#undef PW_LAUNCH
     e.stats.pair_ms = 0.0;
     if (e.profiling) {
         HIPCHK(hipEventRecord(evp[1], st));
@@ -819,9 +918,15 @@ extern "C" int dkmc_poisson_gridless_gpu(int num_atoms_contact, int pbc, int N, 
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, evp[0], evp[1]));
         e.stats.pair_ms = ms;
-        unsigned long long ne[2] = {0, 0};
-        HIPCHK(hipMemcpy(ne, d_ne, 16, hipMemcpyDeviceToHost));
+        unsigned long long ne[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpy(ne, d_ne, 32, hipMemcpyDeviceToHost));
         e.stats.pair_evaluated = (long long)ne[0]; e.stats.pair_tested = (long long)ne[1];
+        // dkmc_get_pair_sum_info: which kernel summed is the device's decision (PwGrid::use); of the cell-list launch only the chunks of the grid work
+        PwGrid hg{};
+        if (key.possible) HIPCHK(hipMemcpy(&hg, grid, sizeof(PwGrid), hipMemcpyDeviceToHost));
+        HIPCHK(hipEventElapsedTime(&ms, evs[0], evs[1]));
+        g_pw_info = PwInfo{{form, hg.use ? 1 : 0, hg.use ? std::min(cell_blocks, hg.nchunks) : sum_blocks, form == 1 ? 64 * (long long)ne[2] : -1,
+                            form == 1 ? 64 * (long long)ne[3] : -1, 0}, {e.stats.pair_ms, ms}, 1};
     }
     return 0;
 }

@@ -98,6 +98,9 @@ SYMBOLS = {
     "dkmc_debug_kbw_segment_cap": (None, [_I]),
     "dkmc_set_pair_cutoff": (None, [_D]),
     "dkmc_reset_pair_sum_cache": (None, []),
+    "dkmc_set_pair_form": (None, [_I]),
+    "dkmc_get_pair_form": (_I, []),
+    "dkmc_get_pair_sum_info": (_I, [C.POINTER(C.c_longlong), C.POINTER(_D)]),
     "dkmc_set_tcache_budget": (None, [C.c_longlong]),
     "dkmc_set_current_warm_start": (None, [_I]),
     "dkmc_get_current_warm_start": (_I, []),

@@ -139,6 +139,12 @@ void dkmc_set_pair_cutoff(double x_cut);
  * cut-off; freeing or re-initialising a GPUBuffers drops it.  A host that rewrites site positions IN PLACE behind the same device pointers
  * (only possible through the raw-pointer entry dkmc_poisson_gridless_gpu; the reference never moves a site) calls this afterwards. */
 void dkmc_reset_pair_sum_cache(void);
+/* Form of the two sum kernels of the pair sum (csrc/potential.hip).  0 (default): a lane evaluates a term where it tests it, so a wave pays
+ * erfc / sqrt / the divisions whenever any of its 64 sites is inside the cut-off.  1: a wave queues the passing (site, charged site) pairs in LDS
+ * and evaluates them 64 at a time with every lane busy; the terms are added per site in the same order into the same partial sums, so every
+ * potential keeps its bits.  Any other value is kept as 0.  Read at every call of dkmc_poisson_gridless_gpu, on one GPU and on several. */
+void dkmc_set_pair_form(int form);
+int dkmc_get_pair_form(void);
 /* Width s of the block-CG of the current solve on the tiled X (csrc/xtb.hip).  1: the reference's single-vector loop
  * (solve_sparse_CG_Jacobi, iterative_solvers_gpu.cu:309-480: same iterate sequence, same start vector).  2 ... 16: block-CG over s
  * columns -- column 0 carries the physical right-hand side and start vector, columns 1 ... s - 1 fixed-seed auxiliary right-hand sides

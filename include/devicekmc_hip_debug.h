@@ -121,6 +121,12 @@ int dkmc_debug_kbw_halfword_pos(int width, int entry);
 /* Test aid: caps the segments of a window of the windowed blocked form of K (dkmc_set_k_blocked_large) below its fixed maximum (16) for the
  * patterns built afterwards, so that the builder refuses and the solve falls back to the CSR positions.  cap <= 0 restores 16. */
 void dkmc_debug_kbw_segment_cap(int cap);
+/* Measurement aid: the last pair sum (dkmc_poisson_gridless_gpu) made with profiling on; fails before the first one.  info[6]: form that ran
+ * (dkmc_set_pair_form); kernel that summed (0 k_pairwise, 1 k_pairwise_cells); its workgroups (of the cell-list launch those that own a chunk of
+ * sites); lane slots form 0 spends on the expensive part of a term, 64 x the (wave, list entry) steps with at least one site inside the cut-off;
+ * lane slots form 1 issued for it, 64 x its batches; 0 (reserved).  The two slot counts are taken by the form-1 kernels and are -1 after a form-0
+ * call.  ms[2]: HIP-event time of the whole call (dkmc_stats.pair_ms: compaction, binning and sum) and of the sum kernels alone. */
+int dkmc_get_pair_sum_info(long long *info /* [6] */, double *ms /* [2] */);
 /* Test aid for the chained transient sub-steps of the local heat model (dkmc_set_heat_form(1), csrc/heat.hip).  on = 0: every sub-step is polled by
  * the host (the chain is off); on != 0 (default): chained.  budget > 0 fixes the iterations enqueued per chained sub-step (default 0: 64 for the first
  * batch, then the largest count seen, rounded up to a multiple of 8, plus 8), so that a budget below what a solve needs forces the resume path.
