@@ -168,6 +168,7 @@ struct Engine {
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
     int x_apply_form = 0;          // tile x panel kernel of the block-CG: 0 = the product form, 1 = the round-4 form of its loop (same results; same-box comparisons, dkmc_set_x_apply_form)
     int x_tile_f32 = 1;            // tile values of the block-CG's sweeps: 1 (auto) = the fp32 image inside the one-GPU preconditioned loop at cg_tol >= 1e-8, when the copy could be made; 0 = always the fp64 store (dkmc_set_x_tile_f32; xtb.hip)
+    double x_tile_drop = 0.0;      // > 0: where the sweeps stream the fp32 image they stream a compacted one of the LIVE tiles only -- stored 32 x 256 tiles with a scaled entry sc_i |v_ij| sc_j >= this threshold (dkmc_set_x_tile_drop; xt_live.h); 0 (default) = off
     int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
@@ -215,6 +216,7 @@ enum {
     S_XTB_SLAB_BOX, S_XTB_SLAB_TAB, S_XTB_SLAB_OWNER, S_XTB_SLAB_LISTS, S_XTB_SLAB_SDST, S_XTB_SLAB_FLAG, S_XTB_SLAB_RLISTS, S_XTB_SLAB_GX, S_XTB_SLAB_S1, S_XTB_SLAB_S3, S_XTB_SLAB_R3,
     S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z,
     S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
+    S_XTL_CELLS, S_XTL_TFLAG, S_XTL_TVAL32, S_XTL_TILES, S_XTL_WRANGE, S_XTL_NITEMW, S_XTL_ITEMS, S_XTL_SPLIT,      // live view of the tile list (xt_live.h)
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,
     // test aids of the preconditioner (xtb_precond.h: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
     S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,

@@ -975,6 +975,8 @@ static int xt_build_items(int nK, int nW, int kc, int ntiles, long long nsub_tot
     return 0;
 }
 
+#include "xt_live.h"
+
 // Second stream of the sharded solve: the neighbour part of the product (replicated on every rank, ~0.3 GB at 9.4e5 sites) runs
 // here, beside the tile pass, the partial row sums and the all-reduce on the engine's stream; the two meet again before the rows
 // are finished.  Events from a ring: a wait refers to the record that preceded it, the host may run a whole batch ahead.
@@ -1002,6 +1004,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     TCacheView TC{};                     // brought up to date for this rank's share inside assemble() (tc_prepare_tiled, current.hip)
     Engine &e = eng(); hipStream_t st = e.stream;
     XTState &X = g_xt; X.valid = false;
+    g_xlive = XLive{};                   // (the report of dkmc_get_x_tile_live_info is the last solve's: 0 wherever the block loop does not build a live view)
     const int Na = P.Na, Nsub = Na + 1;
     X.Nsub = Nsub; X.ns = ns;
     const int ns_pad = ((ns + XT_C - 1) / XT_C) * XT_C + XT_C;          // one window of slack: tiles of the last row block read pS[32k + ...] up to ns_pad

@@ -1327,7 +1327,7 @@ static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, const Xb
     if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
     return again ? DKMC_XTB_AGAIN : 0;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32);
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
 // split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
 // solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body / xtb_cg_slab).  A round that no longer
@@ -1371,13 +1371,20 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     const bool f32 = e.x_tile_f32 != 0 && A.tval32 != nullptr && !A.sharded && A.m > 2 && A.ns > 0 && e.x_poly > 0 && A.tol2 >= 1e-16;
     if (f32) e.stats.x_tile_stream = 1; else if (e.stats.x_tile_stream == 1) e.stats.x_tile_stream = 0;      // (-1, no image, stays: the assembly set it)
     e.stats.x_tile_f64_rounds = f32 ? 0 : 1;
-    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32);
-    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false); });
+    // live tiles only (dkmc_set_x_tile_drop, xt_live.h): where the sweeps stream the image, and a live view of the resident X is worth having and fits,
+    // they stream its compact image on its own launch view; everything else of the solve -- and every re-entry round -- keeps the full view
+    XLive *lv = nullptr;
+    if (f32 && e.x_tile_drop > 0.0 && A.item_n > 0 && A.tiles == g_xb.tiles && A.tval32 == g_xb.tval32) {
+        if (int rcl = xt_live_build(e.x_tile_drop, A.sS, &g_xlive)) return rcl;
+        if (g_xlive.state == 1) lv = &g_xlive;
+    }
+    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32, lv);
+    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false, nullptr); });
     // a sharded solve that failed with the peer-write exchange in use: the ranks' sequence counters may have drifted (comm.hip)
     if (rc != 0 && rc != DKMC_XTB_BREAKDOWN && peer_used) comm_peer_drop();
     return rc;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32)
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     const int m = A.m, s = A.s, so = 4 * ((s + 3) / 4);                       // vector groups of four: the matrix instruction's width
@@ -1387,7 +1394,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     double *panels = (double *)scratch(S_XTB_PANELS, (pan * 3 + m + 16) * 8);
     double *QS = (double *)scratch(S_XTB_QS, (size_t)A.ns_pad * XB_SP * 8);
     double *rowpartB = (double *)scratch(S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
-    double *colpartB = (double *)scratch(S_XTB_COLPART, (size_t)(A.nrecords + 1) * XT_C * so * 8);
+    const int nrec = std::max(A.nrecords, lv ? lv->nrecords : 0);             // records of column sums: the larger of the two views'
+    double *colpartB = (double *)scratch(S_XTB_COLPART, (size_t)(nrec + 1) * XT_C * so * 8);
     double *gpart = (double *)scratch(S_XTB_GRAM, (size_t)ng * XB_NG * 256 * 8);
     double *small = (double *)scratch(S_XTB_SMALL, (size_t)(4 * 256 + 2 * XB_DSPLIT * XB_SP + XB_NG * 256) * 8);
     if (!panels || !QS || !rowpartB || !colpartB || !gpart || !small) return e.err_code;
@@ -1410,7 +1418,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     const double tol2_loop = pd > 0 ? A.tol2 / 2.25 : A.tol2;                 // ||r|| <= 1.42 ||L r||: the loop stops a little early, the true residual is checked at the end
     HIPCHK(hipMemsetAsync(QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
     HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
-    HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(A.nrecords + 1) * XT_C * so * 8, st));
+    HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(nrec + 1) * XT_C * so * 8, st));
     HIPCHK(hipMemsetAsync(A.ctrl, 0, sizeof(XCtrl), st));
     // sharded solve (comm.hip): this rank streams its share of the tiles; the tile sums of the S rows are completed by ONE all-gather of
     // ns x so doubles (+ two control words) per rank and sweep, added in rank order by every rank (k_xtb_rows): a sixteenth of the
@@ -1435,6 +1443,11 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     int local_fail = 0;
     hipLaunchKernelGGL(k_xtb_init, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, A.sc, A.nsrank, y0, P, QS,
                        (const double *)((keep_aux && A.yaux_valid) ? A.yaux : nullptr), hs, s, Ypanel);
+    // launch view of the tile kernel and of the folds of its partial sums: the full one, or -- inside product_pre, with a live view -- the live one
+    struct XbView { const XItem *items; int item_n; const XTile *tiles; const int2 *wrange; const int *nitem_w; };
+    const XbView full{A.items, A.item_n, A.tiles, A.wrange, A.nitem_w};
+    const XbView live = lv ? XbView{lv->items, lv->item_n, lv->tiles, lv->wrange, lv->nitem_w} : full;
+    const XbView *vw = &full;
     const int ntb = (A.item_n + 3) / 4;
     const int nnb = 2 * XB_DSPLIT + (std::max(m - 2, 1) + 15) / 16;
     const int gs = xt_grid((m + 15) / 16, 4, 2048);
@@ -1455,7 +1468,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, S.st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
             (void)hipEventRecord(S.b[sl], S.st);
         }
-        if (ntb > 0) xtb_apply({A.item_n, A.items, A.tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl, t32}, A.nt_loads, so, 0, st, e0, e1);
+        if (vw->item_n > 0) xtb_apply({vw->item_n, vw->items, vw->tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl, t32}, A.nt_loads, so, 0, st, e0, e1);
         if (side) (void)hipStreamWaitEvent(st, g_xb_side.b[sl], 0);           // the sparse sums are in T before the row kernel reads them
         else hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
     };
@@ -1465,7 +1478,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         xtb_applyL(st, A, pd, pc, src, dst, W1, W2, qs, [](int, double *) { return 0; }, [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; });
     };
     auto fold_rows = [&](double *Tt) {
-        hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB,
+        hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, vw->wrange, vw->nitem_w, (const double *)rowpartB, (const double *)colpartB,
                            A.srow, A.sS, A.sc, (const double *)drvpart, Tt, (const XCtrl *)A.ctrl);
     };
     // T = L A L P
@@ -1473,14 +1486,16 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         applyL(P, Vp, true);
         double *Pk = P, *Tk = T; P = Vp; T = Zp;                              // (the product reads P and QS, writes T)
         t32 = f32 ? A.tval32 : nullptr;                                       // (the first product A y0 and the true-residual pass call product() themselves: fp64 store)
+        if (lv) { vw = &live; t32 = lv->tval32; }                             // dkmc_set_x_tile_drop: the live view and its compact image instead
         product(e0, e1);
         t32 = nullptr;
         P = Pk; T = Tk;
         fold_rows(Zp);
+        vw = &full;
         applyL(Zp, T, false);
     };
     const double *bsel = A.b;
-#define XB_ROWS_ARGS(IT_) A.ns, A.nK, A.nW, m, s, so, A.wrange, A.nitem_w, (const double *)rowpartB, (const double *)colpartB, A.srow, A.sS, A.nsrank, A.sc, \
+#define XB_ROWS_ARGS(IT_) A.ns, A.nK, A.nW, m, s, so, (lv && !init ? live : full).wrange, (lv && !init ? live : full).nitem_w, (const double *)rowpartB, (const double *)colpartB, A.srow, A.sS, A.nsrank, A.sc, \
                      (const double *)drvpart, T, (const double *)P, R, bsel, gpart, A.ctrl, (const double *)xbuf, IT_, nr, (const XbAux *)aux, A.ax, A.ay, A.az
     // S rows of T + partial Gram matrices; a sharded solve exchanges the tile sums first.  A host-side failure of this rank between two
     // collectives must not leave the peers in the all-reduce: it still joins, with the abort word set, and every rank leaves together.
@@ -1507,6 +1522,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     if (pd > 0) {
         // the start vector goes into the right-hand side: column 0 solves L A L dh = L (b - A y0) from zero, the auxiliary columns keep their own
         fold_rows(T);                                                         // T = A Y0
+        if (lv) xt_live_zero_dead(*lv, rowpartB, so);                         // the sweeps fold on the live view: the dead tiles' row sums of this launch must not be added
         hipLaunchKernelGGL(k_xtb_pre_resid, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)T, A.b, Zp);
         applyL(Zp, T, false);                                                 // T(:, 0) = L (A y0 - b), the other columns 0
         bsel = bz;                                                            // R = T - [0 | auxiliary right-hand sides]
@@ -1520,7 +1536,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
                        (const int *)nullptr, Ypanel);
     KCHK();
     XCtrl h{};
-    if (int rcx = xtb_sweeps(A.ctrl, h, true, 0, prof && ntb > 0, sharded, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {     // (no tile launch: no events)
+    if (int rcx = xtb_sweeps(A.ctrl, h, true, 0, prof && ntb > 0 && live.item_n > 0, sharded, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {     // (no tile launch: no events)
             if (pd > 0) product_pre(ev[0], ev[1]);
             else product(ev[0], ev[1]);
             if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
@@ -1531,6 +1547,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             return 0;
         })) return rcx;
 #undef XB_ROWS_ARGS
+    if (lv) lv->info[7] = h.iters;
     if (local_fail) return local_fail;                                         // the peers were told (abort word)
     if (h.xchg_timeout) return dkmc_fail(48, "block-CG: the peer-write exchange timed out waiting for a peer's slot", __FILE__, __LINE__);
     if (h.aborted) return dkmc_fail(46, "a peer rank aborted the sharded current solve", __FILE__, __LINE__);
@@ -1668,15 +1685,20 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
 
 // Test aid (tests/test_gpu_tile_f32.py): the tile sums of the 16 test vectors of k_xtb_test_panel on the X left resident by the last single-GPU solve,
 // from the fp64 store (stored_bytes = 8) or its fp32 image (4): k_xtb_apply + the fold of the partial sums (k_xtb_fold_local), before any row scaling.
+// -4 (tests/test_gpu_tile_drop.py): the compact image of the live tiles at the current dkmc_set_x_tile_drop threshold on its launch view, behind a
+// full-view launch as in a solve.
 // out (host): [S rank][so], so = width rounded up to a multiple of 4.
 extern "C" int dkmc_xtb_tile_product(int width, int stored_bytes, double *out)
 {
     Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
     if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0) return dkmc_fail(13, "xtb_tile_product: needs the X of a single-GPU solve", __FILE__, __LINE__);
-    if (stored_bytes != 8 && !(stored_bytes == 4 && g_xb.tval32)) return dkmc_fail(13, "xtb_tile_product: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
+    if (stored_bytes != 8 && !((stored_bytes == 4 || stored_bytes == -4) && g_xb.tval32)) return dkmc_fail(13, "xtb_tile_product: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
+    XLive lv;                                                                 // stored_bytes -4: the compact image of the live tiles at the current threshold, on its own view
+    if (stored_bytes == -4) { if (int rcl = xt_live_for_test(&lv)) return rcl; }
+    const bool lvu = stored_bytes == -4;
     const int ns = X.ns, s = std::max(2, std::min(width, 16)), so = 4 * ((s + 3) / 4);
     const long long ncell = (long long)X.nK * X.nW;
-    const int nrec = X.nitems >> X.rec_shift;
+    const int nrec = std::max(X.nitems >> X.rec_shift, lvu ? lv.nrecords : 0);
     double *QS = (double *)scratch(S_XTB_QS, (size_t)X.ns_pad * XB_SP * 8);
     double *rowpartB = (double *)scratch(S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
     double *colpartB = (double *)scratch(S_XTB_COLPART, (size_t)(nrec + 1) * XT_C * so * 8);
@@ -1689,10 +1711,17 @@ extern "C" int dkmc_xtb_tile_product(int width, int stored_bytes, double *out)
     HIPCHK(hipMemsetAsync(sums, 0, ((size_t)X.ns_pad * so + 2) * 8, st));
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((ns * XB_SP + 255) / 256), dim3(256), 0, st, ns, QS);
-    const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
-                         colpartB, ctrl, stored_bytes == 4 ? (const float *)g_xb.tval32 : (const float *)nullptr};
-    xtb_apply(xa, true, so, 0, st);
-    hipLaunchKernelGGL(k_xtb_fold_local, dim3(std::max(X.nK, 1)), dim3(XT_NT), 0, st, ns, X.nK, X.nW, so, (const int2 *)g_xb.wrange, (const int *)g_xb.nitem_w,
+    const XbApplyArgs xa{lvu ? lv.item_n : X.item_n, lvu ? lv.items : (const XItem *)g_xb.items + X.item_lo, lvu ? lv.tiles : (const XTile *)g_xb.tiles, (int)X.sub_base,
+                         (const double *)g_xb.tval, QS, X.nW, rowpartB, colpartB, ctrl,
+                         lvu ? lv.tval32 : (stored_bytes == 4 ? (const float *)g_xb.tval32 : (const float *)nullptr)};
+    if (lvu) {
+        // as a solve does it: a full-view launch on the fp64 store first (its first product), then the dead tiles' cells cleared, then the live view
+        const XbApplyArgs xf{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB, colpartB, ctrl};
+        xtb_apply(xf, true, so, 0, st);
+        xt_live_zero_dead(lv, rowpartB, so);
+    }
+    if (xa.n > 0) xtb_apply(xa, true, so, 0, st);
+    hipLaunchKernelGGL(k_xtb_fold_local, dim3(std::max(X.nK, 1)), dim3(XT_NT), 0, st, ns, X.nK, X.nW, so, lvu ? lv.wrange : (const int2 *)g_xb.wrange, lvu ? lv.nitem_w : (const int *)g_xb.nitem_w,
                        (const double *)rowpartB, (const double *)colpartB, sums, (const XCtrl *)ctrl, 0, 0, X.nW);
     KCHK();
     if (out) HIPCHK(hipMemcpyAsync(out, sums, (size_t)ns * so * 8, hipMemcpyDeviceToHost, st));

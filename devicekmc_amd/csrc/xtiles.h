@@ -52,6 +52,21 @@ struct XTBuffers {
 extern XTState g_xt;
 extern XTBuffers g_xb;
 
+// the live view of the resident tile list (xt_live.h; dkmc_set_x_tile_drop): what the sweeps of the one-GPU preconditioned block-CG launch on instead of
+// the full view when state == 1 -- the tiles with a scaled entry at or above the threshold, their fp32 sub-blocks compacted, their own items,
+// nitem_w, wrange and records.  info / ms: the report of dkmc_get_x_tile_live_info (info[0] is `state`)
+struct XLive {
+    int state = 0;                   // 0 off or not applicable, 1 usable, -1 no buffer for the compact image, -2 nothing to drop
+    const XTile *tiles = nullptr; const XItem *items = nullptr; int item_n = 0; const int2 *wrange = nullptr; const int *nitem_w = nullptr; int nrecords = 0;
+    const float *tval32 = nullptr;   // the compact image (sub-block slot = the live tile's soff)
+    const int *tflag = nullptr;      // per STORED tile: 1 live, 0 dead
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double ms[2] = {0.0, 0.0};
+};
+extern XLive g_xlive;                // the last solve's
+int xt_live_build(double theta, const double *sS, XLive *lv);
+void xt_live_zero_dead(const XLive &lv, double *rowpartB, int so);
+int xt_live_for_test(XLive *lv);
+
 static inline int xt_grid(long long work, int per_block, int cap)
 {
     long long b = (work + per_block - 1) / per_block;

@@ -187,6 +187,19 @@ int dkmc_get_x_nmul_form(void);
  * 0: never. */
 void dkmc_set_x_tile_f32(int mode);
 int dkmc_get_x_tile_f32(void);
+/* Opt-in: sweeps that skip the tunnelling tiles too small to matter.  theta > 0: wherever the sweeps stream the fp32 image above (one GPU, block
+ * width > 1, dkmc_set_x_poly > 0, tol^2 >= 1e-16, an image exists) they stream a COMPACTED image that holds only the LIVE tiles -- stored 32 x 256
+ * tiles with at least one stored entry of sc_i |v_ij| sc_j >= theta (sc: the Jacobi scaling of the solve, v: the fp64 stored value) -- on a launch
+ * view of its own (census, scan, compaction and view once per solve: csrc/xt_live.h).  The tile x panel kernel is the same.  The first product A y0,
+ * the diagonal, the scaling, the TRUE residual that ends every solve and every re-entry round keep the full fp64 store, and the start vector goes
+ * through the right-hand side, so the dropped entries act on the correction only; a solve whose check fails is re-entered on the fp64 store.  The
+ * stored X is unchanged (dkmc_get_last_X).  When fewer than 1 / 64 of the stored sub-blocks would go, or the compact buffer does not fit, the
+ * existing image and views are streamed (never an error).  IGNORED by the slab-distributed and sharded loops, at width 1, with dkmc_set_x_poly(0)
+ * and with dkmc_set_x_tile_f32(0).  0 (default) = off: every solve as without the switch, bit for bit.  theta <= 0 or NaN turns it off; values
+ * above 1e-4 are kept as 1e-4; recommended 1e-10.  Read at every current solve.  What the last solve did: dkmc_get_x_tile_live_info
+ * (devicekmc_hip_debug.h). */
+void dkmc_set_x_tile_drop(double theta);
+double dkmc_get_x_tile_drop(void);
 /* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
  * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */
