@@ -79,6 +79,8 @@ void dkmc_set_x_tile_f32(int mode) { eng().x_tile_f32 = mode == 0 ? 0 : 1; }
 int dkmc_get_x_tile_f32(void) { return eng().x_tile_f32; }
 void dkmc_set_x_tile_drop(double theta) { eng().x_tile_drop = theta > 0.0 ? (theta > 1e-4 ? 1e-4 : theta) : 0.0; }      // (NaN compares false: off)
 double dkmc_get_x_tile_drop(void) { return eng().x_tile_drop; }
+void dkmc_set_x_tile_drop_unit(int unit) { eng().x_tile_drop_unit = unit == 1 ? 1 : 0; }
+int dkmc_get_x_tile_drop_unit(void) { return eng().x_tile_drop_unit; }
 void dkmc_debug_fail_true_residual_once(void) { eng().x_tile_f32_fail_once = 1; }
 void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }

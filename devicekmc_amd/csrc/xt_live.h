@@ -13,6 +13,11 @@
 //   k_xt_tile_list, k_xt_wrange, xt_build_items   the builders of the assembly on the live cell mask: a complete second launch view (tiles with the
 //                   same k, w, mask and a new soff; items; nitem_w; wrange; records) -- the view of a one-rank share whose tile list is the live list
 // k_xtb_apply is not touched: it gets another tile list, item list and image pointer.
+// SUB-BLOCK UNIT (dkmc_set_x_tile_drop_unit(1)): the same rule one level down -- a stored sub-block is live when one of its stored entries reaches theta,
+// a tile when one of its sub-blocks is, so the SET OF LIVE TILES is the same in both units (tflag, k_xtl_zero_dead and the argument below stand as
+// they are).  The census then writes the live tiles' REDUCED masks, the compaction copies the selected sub-blocks (source slot by the stored mask,
+// destination slot by the live one), and the builders, being functions of the cell mask, give tiles with the reduced mask: k_xtb_apply walks them in
+// its partial-tile branch.  A sub-block carries its row sums and its column sums (both triangles from one stored value): the operator stays symmetric.
 // What stays on the full view and the fp64 store: the first product A y0, the diagonal, the scaling, the true-residual pass that ends every solve and
 // every re-entry round.  The start vector goes through the right-hand side, so the perturbation acts on the correction only.
 // The partial-sum arrays of the block loop are grid- and record-indexed and a launch rewrites only the cells of its own tiles: after a full-view launch
@@ -23,11 +28,12 @@
 XLive g_xlive;
 
 __global__ __launch_bounds__(XT_NT) void k_xtl_census(int nK, const XTile *__restrict__ tiles, int sub_base, const double *__restrict__ tval,
-                                                      const double *__restrict__ sS, double theta, unsigned *__restrict__ lcmask, int *__restrict__ tflag,
-                                                      unsigned long long *__restrict__ cnt)
+                                                      const double *__restrict__ sS, double theta, int unit, unsigned *__restrict__ lcmask,
+                                                      int *__restrict__ tflag, unsigned long long *__restrict__ cnt)
 {
     // thread (q = tid / 32, c = tid % 32) owns column 32 q + c of the tile and walks its 32 rows (the map of k_xt_fill); cnt: live tiles, sub-blocks in
-    // live tiles, sub-blocks live on their own (integer atomics: the sums do not depend on their order)
+    // live tiles, sub-blocks live on their own (integer atomics: the sums do not depend on their order).  unit 1: a live tile's cell mask holds the
+    // sub-blocks live on their own only (not empty: the tile's largest magnitude is one of theirs)
     __shared__ double rs[XT_R], mx[XT_C / XT_SBW];
     const XTile td = tiles[blockIdx.x];
     const int tid = threadIdx.x, q = tid >> 5, c = tid & 31;
@@ -46,27 +52,31 @@ __global__ __launch_bounds__(XT_NT) void k_xtl_census(int nK, const XTile *__res
     if (c == 0) mx[q] = m;
     __syncthreads();
     if (tid == 0) {
-        double tm = 0.0; int own = 0;
+        double tm = 0.0; int own = 0; unsigned lm = 0u;
 #pragma unroll
-        for (int u = 0; u < XT_C / XT_SBW; ++u) if ((td.mask >> u) & 1u) { tm = fmax(tm, mx[u]); own += mx[u] >= theta ? 1 : 0; }
+        for (int u = 0; u < XT_C / XT_SBW; ++u) if ((td.mask >> u) & 1u) { tm = fmax(tm, mx[u]); if (mx[u] >= theta) { ++own; lm |= 1u << u; } }
         const bool live = tm >= theta;
-        lcmask[(size_t)td.w * nK + td.k] = live ? td.mask : 0u;
+        lcmask[(size_t)td.w * nK + td.k] = live ? (unit == 1 ? lm : td.mask) : 0u;
         tflag[blockIdx.x] = live ? 1 : 0;
         if (live) { atomicAdd(cnt, 1ull); atomicAdd(cnt + 1, (unsigned long long)__popc(td.mask)); }
         if (own) atomicAdd(cnt + 2, (unsigned long long)own);
     }
 }
-// one workgroup per stored tile: a live tile's fp32 sub-blocks (1024 floats = 256 float4 each) to their slots in the compact image
+// one workgroup per stored tile: a live tile's selected fp32 sub-blocks (1024 floats = 256 float4 each; lcmask: all of them, or the live ones -- a
+// subset of the stored mask) to their slots in the compact image: from the slot counted on the STORED mask to the slot counted on the LIVE mask
 __global__ __launch_bounds__(XT_NT) void k_xtl_compact(int nK, const XTile *__restrict__ tiles, int sub_base, const unsigned *__restrict__ lcmask,
                                                        const int *__restrict__ lsoff, const float4 *__restrict__ src32, float4 *__restrict__ dst32)
 {
     const XTile td = tiles[blockIdx.x];
     const size_t ci = (size_t)td.w * nK + td.k;
-    if (!lcmask[ci]) return;
-    const int n = __popc(td.mask);
+    const unsigned lm = lcmask[ci] & td.mask;
+    if (!lm) return;
     const float4 *s = src32 + (size_t)(td.soff - sub_base) * (XT_SUB / 4) + threadIdx.x;
     float4 *d = dst32 + (size_t)lsoff[ci] * (XT_SUB / 4) + threadIdx.x;
-    for (int u = 0; u < n; ++u) d[(size_t)u * (XT_SUB / 4)] = s[(size_t)u * (XT_SUB / 4)];
+    int dl = 0;
+#pragma unroll
+    for (int q = 0; q < XT_C / XT_SBW; ++q)
+        if ((lm >> q) & 1u) { d[(size_t)dl * (XT_SUB / 4)] = s[(size_t)__popc(td.mask & ((1u << q) - 1u)) * (XT_SUB / 4)]; ++dl; }
 }
 // the DEAD tiles' cells of the block loop's grid-indexed row sums (per = 32 x so doubles per cell) <- 0; one thread per double of a stored tile's cell
 __global__ __launch_bounds__(XT_NT) void k_xtl_zero_dead(long long n, int per, int nW, const XTile *__restrict__ tiles, const int *__restrict__ tflag,
@@ -83,8 +93,8 @@ __global__ __launch_bounds__(XT_NT) void k_xtl_zero_dead(long long n, int per, i
 static hipEvent_t g_xl_ev[3]; static bool g_xl_ev_ready = false;
 
 // census of the resident X (one GPU: this rank holds every tile) against theta with the scaling sS (device, by S rank, padded): lcmask (cells),
-// tflag (stored tiles) and the three counts h3 (host) -- the stream is synchronised
-static int xt_live_census(double theta, const double *sS, unsigned **lcmask_out, int **tflag_out, unsigned long long *h3)
+// tflag (stored tiles) and the three counts h3 (host) -- the stream is synchronised.  unit: what lcmask holds for a live tile (k_xtl_census)
+static int xt_live_census(double theta, int unit, const double *sS, unsigned **lcmask_out, int **tflag_out, unsigned long long *h3)
 {
     Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
     const long long ncell = (long long)X.nK * X.nW;
@@ -95,7 +105,7 @@ static int xt_live_census(double theta, const double *sS, unsigned **lcmask_out,
     HIPCHK(hipMemsetAsync(lcmask, 0, (size_t)(ncell + 4) * 4, st));
     HIPCHK(hipMemsetAsync(cnt, 0, 24, st));
     hipLaunchKernelGGL(k_xtl_census, dim3(X.ntiles), dim3(XT_NT), 0, st, X.nK, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, sS, theta,
-                       lcmask, tflag, cnt);
+                       unit, lcmask, tflag, cnt);
     KCHK();
     HIPCHK(hipMemcpyAsync(h3, cnt, 24, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -104,8 +114,8 @@ static int xt_live_census(double theta, const double *sS, unsigned **lcmask_out,
 }
 
 // Builds the live view of the resident X for this solve into lv (state, the launch view, the report).  Never an error for a view that is not worth
-// having or does not fit: the caller streams the existing image then (state -2 / -1).
-int xt_live_build(double theta, const double *sS, XLive *lv)
+// having or does not fit: the caller streams the existing image then (state -2 / -1).  unit 0: whole tiles, 1: the live sub-blocks of the live tiles.
+int xt_live_build(double theta, int unit, const double *sS, XLive *lv)
 {
     Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
     *lv = XLive{};
@@ -116,10 +126,10 @@ int xt_live_build(double theta, const double *sS, XLive *lv)
     const int nK = X.nK, nW = X.nW;
     const long long ncell = (long long)nK * nW;
     unsigned *lcmask = nullptr; int *tflag = nullptr; unsigned long long h3[3] = {0, 0, 0};
-    if (int rc = xt_live_census(theta, sS, &lcmask, &tflag, h3)) return rc;
+    if (int rc = xt_live_census(theta, unit, sS, &lcmask, &tflag, h3)) return rc;
     lv->tflag = tflag;
     lv->info[1] = X.ntiles; lv->info[2] = (long long)h3[0]; lv->info[3] = X.nsub_total; lv->info[4] = (long long)h3[1]; lv->info[5] = (long long)h3[2];
-    const int nlive = (int)h3[0]; const long long nsub_live = (long long)h3[1];
+    const int nlive = (int)h3[0]; const long long nsub_live = (long long)h3[unit == 1 ? 2 : 1];      // the sub-blocks streamed
     // every tile live, or none dead enough to matter (fewer than 1 / 64 of the sub-blocks would go): the existing image and views
     if ((X.nsub_total - nsub_live) * 64 < X.nsub_total) { lv->state = -2; return 0; }
     int *ltoff = (int *)lcmask + (ncell + 4), *lsoff = ltoff + (ncell + 4);
@@ -183,16 +193,39 @@ extern "C" int dkmc_xt_get_live(double theta, int *live_per_tile, double *sS_out
     const double *sS = xt_live_sS();
     if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ntiles <= 0 || !sS) return dkmc_fail(13, "xt_get_live: needs the X of a single-GPU solve", __FILE__, __LINE__);
     unsigned *lcmask = nullptr; int *tflag = nullptr; unsigned long long h3[3];
-    if (int rc = xt_live_census(theta, sS, &lcmask, &tflag, h3)) return rc;
+    if (int rc = xt_live_census(theta, 0, sS, &lcmask, &tflag, h3)) return rc;
     if (live_per_tile) HIPCHK(hipMemcpy(live_per_tile, tflag, (size_t)X.ntiles * 4, hipMemcpyDeviceToHost));
     if (sS_out) HIPCHK(hipMemcpy(sS_out, sS, (size_t)X.ns * 8, hipMemcpyDeviceToHost));
     return e.err_code;
 }
-// xtb.hip (dkmc_xtb_tile_product with stored_bytes = -4): the live view of the resident X at the current theta, built afresh into *lv; state 1 or an error
+// the sub-block unit's live mask of every stored tile (0: dead tile), from the same census
+__global__ void k_xtl_tile_masks(int ntiles, int nK, const XTile *__restrict__ tiles, const unsigned *__restrict__ lcmask, int *__restrict__ out)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < ntiles) out[t] = (int)lcmask[(size_t)tiles[t].w * nK + tiles[t].k];
+}
+extern "C" int dkmc_xt_get_live_masks(double theta, int *mask_per_tile)
+{
+    Engine &e = eng(); const XTState &X = g_xt;
+    const double *sS = xt_live_sS();
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ntiles <= 0 || !sS) return dkmc_fail(13, "xt_get_live_masks: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    unsigned *lcmask = nullptr; int *tflag = nullptr; unsigned long long h3[3];
+    if (int rc = xt_live_census(theta, 1, sS, &lcmask, &tflag, h3)) return rc;
+    if (mask_per_tile) {
+        // (tflag has served: the masks take its place, tile by tile)
+        hipLaunchKernelGGL(k_xtl_tile_masks, dim3((X.ntiles + 255) / 256), dim3(256), 0, e.stream, X.ntiles, X.nK, (const XTile *)g_xb.tiles, (const unsigned *)lcmask, tflag);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(mask_per_tile, tflag, (size_t)X.ntiles * 4, hipMemcpyDeviceToHost, e.stream));
+        HIPCHK(hipStreamSynchronize(e.stream));
+    }
+    return e.err_code;
+}
+// xtb.hip (dkmc_xtb_tile_product and dkmc_xtb_time_apply_stored with stored_bytes = -4): the live view of the resident X at the current theta and unit,
+// built afresh into *lv; state 1 or an error
 int xt_live_for_test(XLive *lv)
 {
     const double *sS = xt_live_sS();
-    if (int rc = xt_live_build(eng().x_tile_drop, sS, lv)) return rc;
-    if (lv->state != 1) return dkmc_fail(13, "xtb_tile_product: no live image at the current threshold (dkmc_set_x_tile_drop; dkmc_get_x_tile_live_info)", __FILE__, __LINE__);
+    if (int rc = xt_live_build(eng().x_tile_drop, eng().x_tile_drop_unit, sS, lv)) return rc;
+    if (lv->state != 1) return dkmc_fail(13, "no live image at the current threshold and unit (dkmc_set_x_tile_drop; dkmc_get_x_tile_live_info)", __FILE__, __LINE__);
     return 0;
 }

@@ -1375,7 +1375,7 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     // they stream its compact image on its own launch view; everything else of the solve -- and every re-entry round -- keeps the full view
     XLive *lv = nullptr;
     if (f32 && e.x_tile_drop > 0.0 && A.item_n > 0 && A.tiles == g_xb.tiles && A.tval32 == g_xb.tval32) {
-        if (int rcl = xt_live_build(e.x_tile_drop, A.sS, &g_xlive)) return rcl;
+        if (int rcl = xt_live_build(e.x_tile_drop, e.x_tile_drop_unit, A.sS, &g_xlive)) return rcl;
         if (g_xlive.state == 1) lv = &g_xlive;
     }
     int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32, lv);
@@ -1685,8 +1685,8 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
 
 // Test aid (tests/test_gpu_tile_f32.py): the tile sums of the 16 test vectors of k_xtb_test_panel on the X left resident by the last single-GPU solve,
 // from the fp64 store (stored_bytes = 8) or its fp32 image (4): k_xtb_apply + the fold of the partial sums (k_xtb_fold_local), before any row scaling.
-// -4 (tests/test_gpu_tile_drop.py): the compact image of the live tiles at the current dkmc_set_x_tile_drop threshold on its launch view, behind a
-// full-view launch as in a solve.
+// -4 (tests/test_gpu_tile_drop.py, test_gpu_tile_drop_unit.py): the compact image of the live tiles (or live sub-blocks) at the current
+// dkmc_set_x_tile_drop threshold and dkmc_set_x_tile_drop_unit on its launch view, behind a full-view launch as in a solve.
 // out (host): [S rank][so], so = width rounded up to a multiple of 4.
 extern "C" int dkmc_xtb_tile_product(int width, int stored_bytes, double *out)
 {
@@ -1732,24 +1732,27 @@ extern "C" int dkmc_xtb_tile_product(int width, int stored_bytes, double *out)
 // ---- measurement aid (bench.py / tools; no counterpart in the reference) ------------------------------------------------------------------
 // Average duration of the tile x panel kernel over the X left resident by the last single-GPU solve, `reps` launches back to back.
 // variant 0: the kernel as a solve runs it; 1: without its matrix instructions; 2: without re-reading the tile stream (see k_xtb_apply).
-static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us);
+static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us, bool live = false);
 extern "C" int dkmc_xtb_time_apply(int width, int variant, int reps, double *us) { return xtb_time_apply(width, variant, reps, false, us); }
-// the same for the kernel as a solve runs it on the fp64 store (stored_bytes = 8) or on its fp32 image (4; fails when the last assembly made none)
+// the same for the kernel as a solve runs it on the fp64 store (stored_bytes = 8) or on its fp32 image (4; fails when the last assembly made none);
+// -4: on the live view and its compact image at the current dkmc_set_x_tile_drop threshold and unit (built afresh; fails where there is none)
 extern "C" int dkmc_xtb_time_apply_stored(int width, int stored_bytes, int reps, double *us)
 {
-    if (stored_bytes != 8 && !(stored_bytes == 4 && g_xb.tval32)) return dkmc_fail(13, "xtb_time_apply_stored: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
-    return xtb_time_apply(width, 0, reps, stored_bytes == 4, us);
+    if (stored_bytes != 8 && !((stored_bytes == 4 || stored_bytes == -4) && g_xb.tval32)) return dkmc_fail(13, "xtb_time_apply_stored: no fp32 image of the tile values (dkmc_set_x_tile_f32)", __FILE__, __LINE__);
+    return xtb_time_apply(width, 0, reps, stored_bytes != 8, us, stored_bytes == -4);
 }
-static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us)
+static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us, bool live)
 {
     Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
     if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0 || reps < 1) return dkmc_fail(13, "xtb_time_apply: needs the X of a single-GPU solve", __FILE__, __LINE__);
 #ifndef DKMC_MEASURE_VARIANTS
     if (variant != 0) return dkmc_fail(13, "xtb_time_apply: this build carries no measurement variants (DKMC_MEASURE_VARIANTS=1 python __graft_entry__.py)", __FILE__, __LINE__);
 #endif
+    XLive lv;
+    if (live) { if (int rcl = xt_live_for_test(&lv)) return rcl; }
     const int s = std::max(2, std::min(width, 16)), so = 4 * ((s + 3) / 4);
     const long long ncell = (long long)X.nK * X.nW;
-    const int nrec = X.nitems >> X.rec_shift;
+    const int nrec = std::max(X.nitems >> X.rec_shift, live ? lv.nrecords : 0);
     double *QS = (double *)scratch(S_XTB_QS, (size_t)X.ns_pad * XB_SP * 8);
     double *rowpartB = (double *)scratch(S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
     double *colpartB = (double *)scratch(S_XTB_COLPART, (size_t)(nrec + 1) * XT_C * so * 8);
@@ -1757,8 +1760,9 @@ static int xtb_time_apply(int width, int variant, int reps, bool f32, double *us
     if (!QS || !rowpartB || !colpartB || !ctrl) return e.err_code;
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((X.ns * XB_SP + 255) / 256), dim3(256), 0, st, X.ns, QS);
-    const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
-                         colpartB, ctrl, f32 ? (const float *)g_xb.tval32 : (const float *)nullptr};
+    const XbApplyArgs xa{live ? lv.item_n : X.item_n, live ? lv.items : (const XItem *)g_xb.items + X.item_lo, live ? lv.tiles : (const XTile *)g_xb.tiles, (int)X.sub_base,
+                         (const double *)g_xb.tval, QS, X.nW, rowpartB, colpartB, ctrl, live ? lv.tval32 : (f32 ? (const float *)g_xb.tval32 : (const float *)nullptr)};
+    if (live && xa.n <= 0) return dkmc_fail(13, "xtb_time_apply: the live view holds no tile", __FILE__, __LINE__);
     hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     for (int r = -1; r < reps; ++r) {
         if (r == 0) HIPCHK(hipEventRecord(e0, st));

@@ -58,12 +58,12 @@ extern XTBuffers g_xb;
 struct XLive {
     int state = 0;                   // 0 off or not applicable, 1 usable, -1 no buffer for the compact image, -2 nothing to drop
     const XTile *tiles = nullptr; const XItem *items = nullptr; int item_n = 0; const int2 *wrange = nullptr; const int *nitem_w = nullptr; int nrecords = 0;
-    const float *tval32 = nullptr;   // the compact image (sub-block slot = the live tile's soff)
+    const float *tval32 = nullptr;   // the compact image (sub-block slot = the live tile's soff; with dkmc_set_x_tile_drop_unit(1) only the live sub-blocks of a tile, its mask reduced to them)
     const int *tflag = nullptr;      // per STORED tile: 1 live, 0 dead
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double ms[2] = {0.0, 0.0};
 };
 extern XLive g_xlive;                // the last solve's
-int xt_live_build(double theta, const double *sS, XLive *lv);
+int xt_live_build(double theta, int unit, const double *sS, XLive *lv);
 void xt_live_zero_dead(const XLive &lv, double *rowpartB, int so);
 int xt_live_for_test(XLive *lv);
 

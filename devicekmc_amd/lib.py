@@ -73,8 +73,11 @@ SYMBOLS = {
     "dkmc_get_x_tile_f32": (_I, []),
     "dkmc_set_x_tile_drop": (None, [_D]),
     "dkmc_get_x_tile_drop": (_D, []),
+    "dkmc_set_x_tile_drop_unit": (None, [_I]),
+    "dkmc_get_x_tile_drop_unit": (_I, []),
     "dkmc_get_x_tile_live_info": (_I, [C.POINTER(C.c_longlong), c_dbl_p]),
     "dkmc_xt_get_live": (_I, [_D, vp, vp]),
+    "dkmc_xt_get_live_masks": (_I, [_D, vp]),
     "dkmc_debug_fail_true_residual_once": (None, []),
     "dkmc_set_x_nmul_form": (None, [_I]),
     "dkmc_get_x_nmul_form": (_I, []),

@@ -200,6 +200,17 @@ int dkmc_get_x_tile_f32(void);
  * (devicekmc_hip_debug.h). */
 void dkmc_set_x_tile_drop(double theta);
 double dkmc_get_x_tile_drop(void);
+/* Opt-in: what dkmc_set_x_tile_drop drops.  0 (default): whole tiles, as described above -- every solve exactly as without this switch, bit for bit.
+ * 1: SUB-BLOCKS.  A stored 32 x 32 sub-block is live when one of its stored entries has (sc_i |v_ij|) sc_j >= theta (fp64 stored value, this order
+ * of the multiplications); a tile is live when one of its sub-blocks is, so the set of live tiles is the same in both units; the compact image and
+ * the launch view hold only the live sub-blocks of the live tiles (a live tile keeps its cell and carries a reduced mask).  A dropped sub-block
+ * loses its row sums and its column sums together -- both triangles come from the one stored value --, so the streamed operator stays symmetric,
+ * and every dropped entry is below theta, as with whole tiles.  The tile x panel kernel is the same; everything that keeps the full fp64 store
+ * above keeps it here.  Any other value is stored as 0.  Read at every current solve.  Without effect while dkmc_set_x_tile_drop is 0 and wherever
+ * that switch is ignored (slab-distributed and sharded loops, width 1, dkmc_set_x_poly(0), dkmc_set_x_tile_f32(0), tol^2 < 1e-16).  The "fewer
+ * than 1 / 64 of the stored sub-blocks would go" rule counts the sub-blocks this unit would drop.  What it is worth: DESIGN.md section 6. */
+void dkmc_set_x_tile_drop_unit(int unit);
+int dkmc_get_x_tile_drop_unit(void);
 /* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
  * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */

@@ -65,22 +65,29 @@ void dkmc_debug_fail_true_residual_once(void);
  * / 4096 + 0.125 v in 32-bit unsigned arithmetic) on the X left by the last single-GPU solve, streamed from the fp64 store (stored_bytes 8) or from its
  * fp32 image (4, dkmc_set_x_tile_f32; fails when the last assembly made none).  out (host): the tile sums of S rank r, vector v at [r * so + v],
  * so = width rounded up to a multiple of 4, before any row scaling.  stored_bytes -4: from the compact image of the live tiles at the current
- * dkmc_set_x_tile_drop threshold, on its launch view (built afresh with the last solve's scaling; fails when there is none, e.g. nothing to drop). */
+ * dkmc_set_x_tile_drop threshold and dkmc_set_x_tile_drop_unit (unit 1: of the live sub-blocks), on its launch view (built afresh with the last
+ * solve's scaling; fails when there is none, e.g. nothing to drop). */
 int dkmc_xtb_tile_product(int width, int stored_bytes, double *out);
 /* test aid: tile list (four ints per tile: row block k, column window w, mask of its present 32 x 32 sub-blocks, slot of its first one) and the fp64
  * values of the stored sub-blocks (element (row r, column c) of slot sl at [(sl * 32 + r) * 32 + c]: S ranks 32 k + r and 256 w + 32 q + c for the
  * q-th bit of the mask) of the last single-GPU assembly.  Null arrays: the counts only. */
 int dkmc_xt_get_tiles(long long *ntiles, long long *nsub, int *tiles4, double *tval);
-/* measurement aid: dkmc_xtb_time_apply of the kernel as a solve runs it, on the fp64 store (stored_bytes 8) or its fp32 image (4) */
+/* measurement aid: dkmc_xtb_time_apply of the kernel as a solve runs it, on the fp64 store (stored_bytes 8) or its fp32 image (4); stored_bytes -4:
+ * on the live view and its compact image at the current dkmc_set_x_tile_drop threshold and dkmc_set_x_tile_drop_unit, built afresh as for
+ * dkmc_xtb_tile_product (error 13 where there is no such view); what it streamed: dkmc_xt_get_live_masks / dkmc_get_x_tile_live_info */
 int dkmc_xtb_time_apply_stored(int width, int stored_bytes, int reps, double *us);
 /* Report of dkmc_set_x_tile_drop for the last current solve.  info8: [0] state -- 0 off or not applicable, 1 the compact image of the live tiles was
  * streamed, -1 no buffer for it, -2 nothing to drop (fewer than 1 / 64 of the sub-blocks); [1] tiles stored; [2] tiles live; [3] sub-blocks stored;
- * [4] sub-blocks in live tiles; [5] sub-blocks live on their own (the image does not use it: it is there to judge sub-block granularity); [6] bytes
- * of the compact image; [7] sweeps run on it.  ms2 (written only with dkmc_set_profiling on): census + scan, compaction + view build. */
+ * [4] sub-blocks in live tiles; [5] sub-blocks live on their own (what dkmc_set_x_tile_drop_unit(1) streams; with unit 0 the image does not use
+ * it); [6] bytes of the compact image: 4096 x ([4] + 4) with unit 0, 4096 x ([5] + 4) with unit 1; [7] sweeps run on it.  [1]-[5] and [7] mean the
+ * same in both units.  ms2 (written only with dkmc_set_profiling on): census + scan, compaction + view build. */
 int dkmc_get_x_tile_live_info(long long *info8, double *ms2);
 /* Test aid: for the X left by the last one-GPU solve, the live flag (1 / 0) of every stored tile at threshold theta, in dkmc_xt_get_tiles order, and
  * that solve's scaling by S rank (sS_out[xt_ns]).  Either array may be null. */
 int dkmc_xt_get_live(double theta, int *live_per_tile, double *sS_out);
+/* Test aid: from the same census, the mask of the sub-blocks LIVE ON THEIR OWN of every stored tile at threshold theta (a subset of the tile's stored
+ * mask; 0 = dead tile), in dkmc_xt_get_tiles order: what dkmc_set_x_tile_drop_unit(1) streams of the tile. */
+int dkmc_xt_get_live_masks(double theta, int *mask_per_tile);
 void dkmc_set_x_apply_form(int form);
 int dkmc_get_x_apply_form(void);
 /* Test aid for the error path of a sharded current solve (no counterpart in the reference): the calling rank fails ONCE, in the
