@@ -20,7 +20,7 @@
 //     completes the long rows' sums.
 // HBM traffic per iteration in the CSR formulation: 12*nnz + 4*(m+1) + 96*m bytes; with the segments the
 // matrix part of X drops to 8 B per entry.
-#include "common.h"
+#include "cg_host.h"
 #include <hip/hip_ext.h>
 #include <vector>
 #include <algorithm>
@@ -28,7 +28,6 @@
 
 #define CG_NT 256
 #define CG_MAX_PART 8192        // max blocks writing partials per kernel family
-#define PROF_STRIDE 8
 #define LONG_ROW_NNZ 192        // rows with more entries go to the wave-per-row bin
 
 struct CgCtrl {                 // device-resident control block
@@ -477,14 +476,6 @@ __global__ void k_row_lists(int m, const int *is_long, const int *off_long, cons
     if (i < m) { if (is_long[i]) long_rows[off_long[i]] = i; else short_rows[off_short[i]] = i; }
 }
 
-static inline int grid_for(int work_items, int per_block)
-{
-    long long b = ((long long)work_items + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > CG_MAX_PART / 2) b = CG_MAX_PART / 2;
-    return (int)b;
-}
-
 // Internal entry: uniform_rows != 0 skips the binning (K: every row is short).  srank (optional, per row/column of
 // the system: rank in the tunnelling set or -1) enables the dense-run view of the long rows.
 template <typename RP>
@@ -519,14 +510,14 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
         hipLaunchKernelGGL(k_row_lists, dim3((m + 255) / 256), dim3(256), 0, st, m, fl, ol, os, lr, sr);
         long_rows = lr; short_rows = sr;
     }
-    const int gs = n_short > 0 ? grid_for(n_short, CG_NT / 16) : 0;    // short-row blocks
-    const int gl = n_long > 0 ? grid_for(n_long, CG_NT / 64) : 0;      // long-row blocks
-    const int gv = grid_for(m, CG_NT);                                 // vector-kernel blocks
+    const int gs = n_short > 0 ? grid_blocks(n_short, CG_NT / 16, CG_MAX_PART / 2) : 0;    // short-row blocks
+    const int gl = n_long > 0 ? grid_blocks(n_long, CG_NT / 64, CG_MAX_PART / 2) : 0;      // long-row blocks
+    const int gv = grid_blocks(m, CG_NT, CG_MAX_PART / 2);                                 // vector-kernel blocks
     const int np_spmv = gs + gl;
     // hot SpMV (k_spmv_ap): 1024-thread workgroups, short rows 64 per pass, long rows 16 per pass
-    const int hs = n_short > 0 ? grid_for(n_short, SPMV_NT / 16) : 0;
-    const int hl = n_long > 0 ? grid_for(n_long, SPMV_NT / 64) : 0;
-    const int hl2 = n_long > 0 ? grid_for(n_long, SPMV_NT / 16) : 0;    // long rows in the two-stage (segment) mode
+    const int hs = n_short > 0 ? grid_blocks(n_short, SPMV_NT / 16, CG_MAX_PART / 2) : 0;
+    const int hl = n_long > 0 ? grid_blocks(n_long, SPMV_NT / 64, CG_MAX_PART / 2) : 0;
+    const int hl2 = n_long > 0 ? grid_blocks(n_long, SPMV_NT / 16, CG_MAX_PART / 2) : 0;    // long rows in the two-stage (segment) mode
     int np_ap = hs + hl;
 
 #define SPMV(MODE, vin, vout, a0, a1, partp)                                                                          \
@@ -589,7 +580,7 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
     e.stats.xt_subblocks = 0; e.stats.xt_local_subblocks = 0; e.stats.xt_items = 0;
     // blocks of k_spmv_segs: segments (a wave each), then the short rows (16 lanes each)
     const int nsb = (nseg_loc + SEGK_NT / 64 - 1) / (SEGK_NT / 64);
-    const int hsA = (use_runs && n_short > 0) ? grid_for(n_short, SEGK_NT / 16) : 0;
+    const int hsA = (use_runs && n_short > 0) ? grid_blocks(n_short, SEGK_NT / 16, CG_MAX_PART / 2) : 0;
     if (use_runs) np_ap = hsA + hl2;
     // ---- Jacobi scaling ----
     SPMV(M_DIAG, (const double *)nullptr, s, x, y, (double *)nullptr);
@@ -602,10 +593,10 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
 
     // ---- optional kernel profile: HIP events around every A*p launch (bench.py roofline) ----
     const bool prof = e.profiling && !uniform_rows;
-    static hipEvent_t evs[4 * 64], evc[64 / PROF_STRIDE]; static bool evs_ready = false;
-    double prof_short_ms = 0.0, prof_long_ms = 0.0, prof_comm_ms = 0.0; int prof_short_n = 0, prof_long_n = 0, prof_comm_n = 0;
+    EventSampler &pf = g_loop_events;
     if (prof) {
-        if (!evs_ready) { for (auto &ev : evs) HIPCHK(hipEventCreate(&ev)); for (auto &ev : evc) HIPCHK(hipEventCreate(&ev)); evs_ready = true; }
+        // without the run view one launch does the whole product: its interval alone; the exchange's only in a sharded solve
+        if (int rc = pf.begin(use_runs ? EventSampler::LONG | EventSampler::SHORT | (sharded ? EventSampler::COMM : 0) : EventSampler::LONG)) return rc;
         std::vector<RP> hrp((size_t)m + 1);
         HIPCHK(hipMemcpy(hrp.data(), rp, ((size_t)m + 1) * sizeof(RP), hipMemcpyDeviceToHost));
         long long nl = 0, nsh = 0;
@@ -619,38 +610,15 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
             e.stats.spmv_segment_entries = tot;
         }
     }
-    // ---- iterations, launched in batches; the host polls the control block between batches ----
-    // Batch plan: the iteration count of consecutive solves of the same system changes slowly (X: 666 +- 10 at 85 k sites), so
-    // the first batch is sized just below the previous count; after it, short batches keep the no-op tail small.
-    int it = 0, launched = 0;
-    int batch = 8;
-    if (iter_hint && *iter_hint > 24) batch = *iter_hint - 8;
+    // ---- iterations, launched in batches; the host polls the control block between batches (batch plan: launch_plan.h) ----
     // matrix stream: default cache policy while the values of one sweep fit the 256 MiB Infinity Cache (they are re-read
     // every iteration), non-temporal beyond that (measured: 45 vs 53 us at 240 MB, 478 vs 456 us at 1.86 GB); a rank of a
     // sharded solve streams only its share
     const int seg_nt = nnz * 8 / (sharded ? comm_nranks() : 1) > (300ll << 20);
     CgCtrl h{};
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (prof && launched) {       // only launches that did work (iteration index below the final count) are counted
-            for (int b = 0; b < launched && b < 64; b += PROF_STRIDE) {
-                if (it - launched + b >= h.iters) break;
-                float ms = 0.f;
-                if (use_runs) {
-                    HIPCHK(hipEventElapsedTime(&ms, evs[4 * b], evs[4 * b + 1])); prof_long_ms += ms; ++prof_long_n;
-                    if (sharded) { HIPCHK(hipEventElapsedTime(&ms, evs[4 * b + 1], evc[b / PROF_STRIDE])); prof_comm_ms += ms; ++prof_comm_n; }
-                    HIPCHK(hipEventElapsedTime(&ms, evs[4 * b + 2], evs[4 * b + 3])); prof_short_ms += ms; ++prof_short_n;
-                } else { HIPCHK(hipEventElapsedTime(&ms, evs[4 * b], evs[4 * b + 1])); prof_long_ms += ms; ++prof_long_n; }
-            }
-        }
-        if (h.done) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int b = 0; b < batch; ++b, ++it) {
-            // sampled launches (1 in 8 of the first 64 of a batch) carry start/stop events of the dispatch itself
-            // (hipExtLaunchKernelGGL): the kernel's own begin/end timestamps, no extra marker packets in the stream
-            const bool pb = prof && b < 64 && (b % PROF_STRIDE == 0);
-            hipEvent_t e0 = pb ? evs[4 * b] : nullptr, e1 = pb ? evs[4 * b + 1] : nullptr, e2 = pb ? evs[4 * b + 2] : nullptr, e3 = pb ? evs[4 * b + 3] : nullptr;
+    if (int rc = cg_poll_loop(ctrl, h, iter_hint ? LaunchPlan::hinted_minus8(*iter_hint) : LaunchPlan::doubling(8), st, "CG: no convergence after 200000 iterations",
+                              prof ? &pf : nullptr, [&](int it, const hipEvent_t *ev) -> int {
+            hipEvent_t e0 = ev[0], e1 = ev[1], e2 = ev[2], e3 = ev[3];
             if (use_runs) {
 #define SEG_ARGS nseg_loc, (const RunDesc *)segs + seg_lo, (const double *)a, (const double *)pS, seg_part + seg_lo, (const CgCtrl *)ctrl, (const int *)rem, ci, \
                  (const double *)p, nsb, n_short, short_rows, rp, long_rows, t, part_pAp
@@ -663,10 +631,10 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
                     // exactly the same sequence of collectives (the batch plan and the stop decisions depend only on values
                     // that are identical on all ranks).
                     const int me = comm_rank(), r0 = parts.lo[me], r1 = parts.lo[me + 1];
-                    if (r1 > r0) hipLaunchKernelGGL(k_rowsum_owner, dim3(grid_for(r1 - r0, SPMV_NT / 16)), dim3(SPMV_NT), 0, st, r0, r1, (const int *)nruns,
+                    if (r1 > r0) hipLaunchKernelGGL(k_rowsum_owner, dim3(grid_blocks(r1 - r0, SPMV_NT / 16, CG_MAX_PART / 2)), dim3(SPMV_NT), 0, st, r0, r1, (const int *)nruns,
                                                     (const int *)seg_off, (const double *)seg_part, xbuf + (size_t)me * parts.chunk, ctrl);
                     if (int rc = comm_allgather_f64(xbuf, (size_t)parts.chunk)) return rc;
-                    if (pb) HIPCHK(hipEventRecord(evc[b / PROF_STRIDE], st));
+                    if (ev[4]) HIPCHK(hipEventRecord(ev[4], st));
                     hipExtLaunchKernelGGL(k_rowsum_apply, dim3(hl2), dim3(SPMV_NT), 0, st, e2, e3, 0, n_long, long_rows, (const RowParts *)dparts, (const double *)xbuf,
                                           (const double *)p, t, part_pAp + hsA, (const CgCtrl *)ctrl);
                 } else
@@ -679,18 +647,10 @@ static int cg_solve_jacobi_t(double *a, const RP *rp, const int *ci, long long n
                                        (const int *)rem, (const int *)nrem, (const double *)pS, (const int *)seg_off);
             hipLaunchKernelGGL(k_cg_update, dim3(gv), dim3(CG_NT), 0, st, m, it, part_pAp, np_ap, p, t, y, r, part_rr, ctrl);
             hipLaunchKernelGGL(k_cg_direction, dim3(gv), dim3(CG_NT), 0, st, m, it, part_rr, gv, r, p, ctrl, tol2, use_runs ? srank : (const int *)nullptr, pS);
-        }
-        launched = batch;
-        KCHK();
-        if (iter_hint && *iter_hint > 24) batch = 8;           // after the sized first batch: short ones
-        else if (batch < 64) batch *= 2;
-    }
+            return 0;
+        })) return rc;
 #undef SPMV
-    if (prof) {
-        e.stats.spmv_long_ms = prof_long_ms; e.stats.spmv_short_ms = prof_short_ms;
-        e.stats.spmv_long_launches = prof_long_n; e.stats.spmv_short_launches = prof_short_n;
-        e.stats.comm_ms = prof_comm_ms; e.stats.comm_launches = prof_comm_n;
-    }
+    if (prof) pf.to_stats(e.stats, true);
     // ---- un-scale the solution (:459) ----
     hipLaunchKernelGGL(k_vec_mul, dim3(gv), dim3(CG_NT), 0, st, m, y, s);
     KCHK();

@@ -194,6 +194,14 @@ int dkmc_fail(int code, const char *what, const char *file, int line);
 void *scratch(int slot, size_t bytes);
 // the same for a buffer the caller can do without: null and NO error recorded when the allocation fails
 void *scratch_try(int slot, size_t bytes);
+// blocks for `work` items at `per_block` each, at least 1 and at most `cap`
+static inline int grid_blocks(long long work, int per_block, int cap)
+{
+    long long b = (work + per_block - 1) / per_block;
+    if (b < 1) b = 1;
+    if (b > cap) b = cap;
+    return (int)b;
+}
 inline MetalSet load_metals(const int *d_metals, int num_metals) { MetalSet ms; ms.n = num_metals; ms.e = d_metals; return ms; }
 
 #define HIPCHK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return dkmc_fail((int)e__, hipGetErrorString(e__), __FILE__, __LINE__); } while (0)

@@ -1,6 +1,7 @@
 // heat.hip -- global temperature update; local temperature model.
 #include "common.h"
 #include "kcg_run.h"
+#include "launch_plan.h"
 
 #define HT_NT 256
 __global__ __launch_bounds__(HT_NT) void k_power_partials(int N, const double *__restrict__ p, double *__restrict__ part)
@@ -305,14 +306,6 @@ __global__ void k_heat_arm(KCtrl *ctrl, const HeatChain *ch)
     *ctrl = ch->start;
 }
 
-// polls the batch plan of cg.hip makes for a solve of `iters` iterations (8, 16, 32, then 64 at a time, one poll before each batch)
-static int heat_csr_polls(int iters)
-{
-    int n = 1, launched = 0, batch = 8;
-    while (launched < iters) { launched += batch; ++n; if (batch < 64) batch *= 2; }
-    return n;
-}
-
 // the update on the forms of kcg.hip.  syncs / resumes: host synchronisations of the solves, sub-steps that took the resume path
 static int heat_update_forms(dkmc_gpubuf *buf, HeatPat &h, int nsolve, int steady, double s, double T0, double pv, double pn, int *iters_total, int *syncs, int *resumes,
                              long long *bytes)
@@ -411,7 +404,7 @@ extern "C" int dkmc_update_temperature_local(dkmc_gpubuf *buf, double step_time,
                            (const int *)buf->site_element, (const double *)buf->site_temperature, (const double *)buf->site_power, s, steady, T0, pv, pn, a, b, y);
         int it = 0;
         rc = cg_solve_jacobi(a, h.rp, h.ci, h.nnz, m, b, y, 1, nullptr, 0, &it, nullptr);
-        iters_total += it; syncs += heat_csr_polls(it);
+        iters_total += it; syncs += LaunchPlan::doubling(8).polls(it);       // the plan cg.hip runs without a hint
         if (!rc) hipLaunchKernelGGL(k_heat_store, dim3((m + 255) / 256), dim3(256), 0, st, m, h.lo, (const double *)y, T0, buf->site_temperature);
     }
     e.cg_tol = saved_tol;

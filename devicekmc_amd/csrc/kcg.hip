@@ -20,9 +20,9 @@
 //   assembly   k_link (the rule of one entry), k_word (what is stored for it), k_contacts (the two contact sums), k_assemble_tail (diagonal and rhs)
 //   product    kb_rows: the pass loop of k_kb_apply and k_kbw_apply (k_kc_apply: 8 lanes per row, no LDS -- another algorithm, on its own)
 //   vectors    kc_check0 / kc_update / kc_direction / kc_q<LIST>: all rows (k_kc_*) or the rows of a list (k_ks_*)
-//   host       kc_with_cb, kb_raise_lds_limit, kpattern_download, kblocked_upload, kcg_poll (the poll loop of both host loops),
+//   host       kc_with_cb, kb_raise_lds_limit, kpattern_download, kblocked_upload, cg_poll_loop (cg_host.h: the poll loop of both host loops),
 //              kcg_run_* (kcg_run.h: the one-GPU loop without K's assembly; K's solve and the local heat model of heat.hip run on it)
-#include "common.h"
+#include "cg_host.h"
 #include "slab.h"
 #include "kbw_plan.h"
 #include "kcg_run.h"
@@ -633,14 +633,6 @@ __global__ void k_kc_unscale(int m, double *__restrict__ y, const double *__rest
     if (i < m) y[i] = y[i] * s[i];
 }
 
-static inline int kc_grid(long long work, int per_block, int cap)
-{
-    long long b = (work + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
-}
-
 // cb (0 potential rule, 1 CB-edge rule, 2 CB-edge rule on atoms only) as the CB template argument: f(std::integral_constant<int, CB>)
 template <class F> static void kc_with_cb(int cb, F &&f)
 {
@@ -653,27 +645,6 @@ template <class K> static int kb_raise_lds_limit(K apply0, K apply1, bool *set)
     HIPCHK(hipFuncSetAttribute((const void *)apply0, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
     HIPCHK(hipFuncSetAttribute((const void *)apply1, hipFuncAttributeMaxDynamicSharedMemorySize, KB_MAXWIN * 8));
     *set = true;
-    return 0;
-}
-// The host's poll loop of both K-CG loops: reads *ctrl_d into h, stops on done, on iter_cap (> 0: the emulation's cap) or after 200 000 iterations
-// (recorded as a failure), else enqueues a batch of iterations (8, 16, 32, then 64 at a time) through enqueue(it), whose error code ends the loop at once.
-// first > 0: that many iterations are enqueued before the first poll (a caller that knows what the solve will need); syncs: counts the polls.
-template <class F> static int kcg_poll(const KCtrl *ctrl_d, KCtrl &h, int iter_cap, hipStream_t st, F &&enqueue, int first = 0, int *syncs = nullptr)
-{
-    int it = 0, batch = 8;
-    for (; it < first; ++it) if (int rc = enqueue(it)) return rc;
-    if (first > 0) KCHK();
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl_d, sizeof(KCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (syncs) ++*syncs;
-        if (h.done) break;
-        if (iter_cap > 0 && it >= iter_cap) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int b = 0; b < batch; ++b, ++it) if (int rc = enqueue(it)) return rc;
-        KCHK();
-        if (batch < 64) batch *= 2;
-    }
     return 0;
 }
 // a K pattern on the host: row pointers, columns, x and (y_d, z_d not null) y, z of its rows
@@ -817,8 +788,8 @@ int kcg_run_setup(KcgRun &c, int m, const int *rp, int nnz, const KBlocked *kb, 
         if (int rc = c.kbw2 ? kb_raise_lds_limit(k_kbw_apply<0, 2>, k_kbw_apply<1, 2>, &lds_set[2]) : c.kbw ? kb_raise_lds_limit(k_kbw_apply<0, 4>, k_kbw_apply<1, 4>, &lds_set[1])
                                                                                                             : kb_raise_lds_limit(k_kb_apply<0>, k_kb_apply<1>, &lds_set[0])) return rc;
     }
-    c.ga = kb ? kb->nb : kc_grid(m, KC_NT / 8, KC_NPA);         // product: one block of the blocked form, or 32 rows, per workgroup and pass
-    c.gv = kc_grid(m, KC_NT, KC_NP);
+    c.ga = kb ? kb->nb : grid_blocks(m, KC_NT / 8, KC_NPA);         // product: one block of the blocked form, or 32 rows, per workgroup and pass
+    c.gv = grid_blocks(m, KC_NT, KC_NP);
     c.npa = (c.ga + KC_NT - 1) / KC_NT * KC_NT;
     return 0;
 }
@@ -860,7 +831,8 @@ int kcg_run_iterate(KcgRun &c, int it)
 #undef KC_APPLY
 int kcg_run_poll(KcgRun &c, KCtrl &h, int first)
 {
-    return kcg_poll(c.ctrl, h, 0, eng().stream, [&](int it) -> int { return kcg_run_iterate(c, it); }, first, &c.syncs);
+    return cg_poll_loop(c.ctrl, h, LaunchPlan::doubling(8), eng().stream, "CG: no convergence after 200000 iterations", nullptr,
+                        [&](int it, const hipEvent_t *) -> int { return kcg_run_iterate(c, it); }, 0, first, &c.syncs);
 }
 int kcg_run_unscale(KcgRun &c)
 {
@@ -1168,7 +1140,7 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
     // ---- r = A y - b, p = -r, q = S p ----
     for (int iv = 0; iv < nv; ++iv) {
         KsRank &K = RK[iv];
-        const int ga = kc_grid(K.n_own, KC_NT / 8, KC_NPA);
+        const int ga = grid_blocks(K.n_own, KC_NT / 8, KC_NPA);
         if (K.n_own > 0) {
             hipLaunchKernelGGL((k_kc_apply<1>), dim3(ga), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G, (const double *)nullptr, K.t,
                                K.xa + (size_t)K.v * KC_NPA, (const KCtrl *)K.ctrl, b, K.r, K.p, (const int *)K.own);
@@ -1180,13 +1152,13 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
     if (int rcx = halo(false)) return rcx;
     KCHK();
     KCtrl h{};
-    if (int rc = kcg_poll(RK[0].ctrl, h, emu ? g_ks_iter_cap : 0, st, [&](int it) -> int {
+    if (int rc = cg_poll_loop(RK[0].ctrl, h, LaunchPlan::doubling(8), st, "CG: no convergence after 200000 iterations", nullptr, [&](int it, const hipEvent_t *) -> int {
         const bool on = timing && it >= 2 && tcount < 24;
         for (int iv = 0; iv < nv; ++iv) {
             KsRank &K = RK[iv];
             if (K.n_own <= 0) continue;
             int rc = timed(iv, 0, on, [&]() {
-                hipLaunchKernelGGL((k_kc_apply<2>), dim3(kc_grid(K.n_own, KC_NT / 8, KC_NPA)), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G,
+                hipLaunchKernelGGL((k_kc_apply<2>), dim3(grid_blocks(K.n_own, KC_NT / 8, KC_NPA)), dim3(KC_NT), 0, st, K.n_own, rp, cf, diag, s, (const double *)K.q, high_G, low_G,
                                    (const double *)K.p, K.t, K.xa + (size_t)K.v * KC_NPA, (const KCtrl *)K.ctrl, (const double *)nullptr, K.r, (double *)nullptr, (const int *)K.own);
             }); if (rc) return rc;
         }
@@ -1194,7 +1166,7 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
         for (int iv = 0; iv < nv; ++iv) {
             KsRank &K = RK[iv];
             int rc = timed(iv, 1, on, [&]() {
-                hipLaunchKernelGGL(k_ks_update, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xa, nr * KC_NPA,
+                hipLaunchKernelGGL(k_ks_update, dim3(grid_blocks(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xa, nr * KC_NPA,
                                    (const double *)K.p, (const double *)K.t, K.y, K.r, K.xb + (size_t)K.v * KC_NP, (const KCtrl *)K.ctrl);
             }); if (rc) return rc;
         }
@@ -1202,14 +1174,14 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
         for (int iv = 0; iv < nv; ++iv) {
             KsRank &K = RK[iv];
             int rc = timed(iv, 2, on, [&]() {
-                hipLaunchKernelGGL(k_ks_direction, dim3(kc_grid(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xb, nr * KC_NP,
+                hipLaunchKernelGGL(k_ks_direction, dim3(grid_blocks(std::max(K.n_own, 1), KC_NT, KC_NP)), dim3(KC_NT), 0, st, K.n_own, (const int *)K.own, it, (const double *)K.xb, nr * KC_NP,
                                    (const double *)K.r, K.p, s, K.q, K.ctrl, tol2);
             }); if (rc) return rc;
         }
         if (int rcx = halo(on)) return rcx;
         if (on) ++tcount;
         return 0;
-    })) return rc;
+    }, emu ? g_ks_iter_cap : 0)) return rc;
     if (e.err_code) return e.err_code;
     if (emu) {
         for (int iv = 1; iv < nv; ++iv) {

@@ -12,7 +12,7 @@
 // Here: one workgroup per 32 rows of M; the gathered sub-vector p[idx] is staged through LDS in chunks of 1024 columns, every
 // wave streams 8 rows with 16-byte loads, row sums are combined in a fixed order; each row of M is summed by exactly one
 // workgroup, so the result is added to t without atomics.  HBM-bound: 8 B per entry of M per iteration.
-#include "common.h"
+#include "cg_host.h"
 
 #define SP_NT 256
 struct SCtrl { double rr; double pad; int done; int iters; };
@@ -162,14 +162,6 @@ __global__ void k_sp_publish(const double *part_rr, int n, SCtrl *ctrl, double t
     if (threadIdx.x == 0) { ctrl->rr = rr; ctrl->iters = it + 1; if (!(sqrt(rr) > tol)) ctrl->done = 1; }
 }
 
-static inline int sp_grid(long long work, int per_block, int cap)
-{
-    long long b = (work + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
-}
-
 // A (CSR, m rows, int32) and M (msub x msub dense, row-major) are read only; x: right-hand side; y: start vector in, solution out.
 // index_offset: the reference adds 2 to every insertion index (node = atom + 2, :646); pass 0 for plain row indices.
 extern "C" int dkmc_solve_sparse_CG_splitmatrix(const double *M, int msub, const double *A_data, const int *A_row_ptr, const int *A_col_indices,
@@ -186,7 +178,7 @@ extern "C" int dkmc_solve_sparse_CG_splitmatrix(const double *M, int msub, const
     SCtrl *ctrl = (SCtrl *)scratch(S_CG_CTRL, 64);
     if (!r || !p || !t || !tsub || !part || !ctrl) return e.err_code;
     double *part_pt = part, *part_rr = part + 4096;
-    const int nab = sp_grid(m, SP_NT / 8, 4096), nmb = (msub + 31) / 32, gv = sp_grid(m, SP_NT * 4, 512);
+    const int nab = grid_blocks(m, SP_NT / 8, 4096), nmb = (msub + 31) / 32, gv = grid_blocks(m, SP_NT * 4, 512);
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(SCtrl), st));
     auto matvec = [&](const double *v) {
         hipLaunchKernelGGL(k_sp_apply, dim3(nab + nmb), dim3(SP_NT), 0, st, m, A_row_ptr, A_col_indices, A_data, v, t, nab, msub, M, insertion_indices,
@@ -197,23 +189,15 @@ extern "C" int dkmc_solve_sparse_CG_splitmatrix(const double *M, int msub, const
     hipLaunchKernelGGL(k_sp_init, dim3(gv), dim3(SP_NT), 0, st, m, (const double *)t, x, r, p, part_rr);
     hipLaunchKernelGGL(k_sp_check, dim3(1), dim3(SP_NT), 0, st, (const double *)part_rr, gv, ctrl, tol, 0);
     KCHK();
-    int it = 0, batch = 8;
     SCtrl h{};
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(SCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (h.done) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int b = 0; b < batch; ++b, ++it) {
+    if (int rc = cg_poll_loop(ctrl, h, LaunchPlan::doubling(8), st, "CG: no convergence after 200000 iterations", nullptr, [&](int it, const hipEvent_t *) -> int {
             matvec(p);
             hipLaunchKernelGGL(k_sp_dot, dim3(gv), dim3(SP_NT), 0, st, m, (const double *)p, (const double *)t, part_pt, (const SCtrl *)ctrl);
             hipLaunchKernelGGL(k_sp_update, dim3(gv), dim3(SP_NT), 0, st, m, (const double *)part_pt, gv, (const double *)p, (const double *)t, y, r, part_rr, (const SCtrl *)ctrl);
             hipLaunchKernelGGL(k_sp_direction, dim3(gv), dim3(SP_NT), 0, st, m, it, (const double *)part_rr, gv, (const double *)r, p, ctrl, tol);
             hipLaunchKernelGGL(k_sp_publish, dim3(1), dim3(SP_NT), 0, st, (const double *)part_rr, gv, ctrl, tol, it);
-        }
-        KCHK();
-        if (batch < 64) batch *= 2;
-    }
+            return 0;
+        })) return rc;
     if (iters_out) *iters_out = h.iters;
     if (rnorm_out) *rnorm_out = sqrt(h.rr);
     return e.err_code;

@@ -829,7 +829,7 @@ extern "C" int dkmc_debug_step_stop_word(int m, int it, int done_word, int *upda
     double *p = buf, *t = p + m, *y = t + m, *r = y + m, *sc = r + m, *q = sc + m, *part3 = q + m, *prr = part3 + 3 * XT_PSTRIDE, *qS = prr + 2 * 512;
     int *nsrank = ibuf, *cnt = ibuf + m;
     XCtrl *ctrl = reinterpret_cast<XCtrl *>(ibuf + m + 4);
-    const int gv = xt_grid((m + XT_NT - 1) / XT_NT, 4, 512);
+    const int gv = grid_blocks((m + XT_NT - 1) / XT_NT, 4, 512);
     hipLaunchKernelGGL(k_xt_dbg_fill, dim3((m + 255) / 256), dim3(256), 0, st, m, p, t, y, r, sc, nsrank);
     // p.t = m, r.t = -m / 2, t.t = m, r.r = m: alpha = 1, r'.r' = m: no convergence at any tolerance below m
     const double h_part[3] = {(double)m, -0.5 * (double)m, (double)m}, h_rr = (double)m;
@@ -980,22 +980,7 @@ static int xt_build_items(int nK, int nW, int kc, int ntiles, long long nsub_tot
 // Second stream of the sharded solve: the neighbour part of the product (replicated on every rank, ~0.3 GB at 9.4e5 sites) runs
 // here, beside the tile pass, the partial row sums and the all-reduce on the engine's stream; the two meet again before the rows
 // are finished.  Events from a ring: a wait refers to the record that preceded it, the host may run a whole batch ahead.
-#define XT_SIDE_RING 64
-struct XSide { hipStream_t st = nullptr; hipEvent_t a[XT_SIDE_RING], b[XT_SIDE_RING]; int device = -1; unsigned seq = 0; bool ready = false; };
-static XSide g_side;
-static int xt_side_init()
-{
-    XSide &S = g_side; const int dev = eng().device;
-    if (S.ready && S.device == dev) return 0;
-    if (S.ready) { (void)hipStreamDestroy(S.st); for (int i = 0; i < XT_SIDE_RING; ++i) { (void)hipEventDestroy(S.a[i]); (void)hipEventDestroy(S.b[i]); } S.ready = false; }
-    HIPCHK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-    for (int i = 0; i < XT_SIDE_RING; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&S.a[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&S.b[i], hipEventDisableTiming));
-    }
-    S.device = dev; S.seq = 0; S.ready = true;
-    return 0;
-}
+static SideStream g_side;
 
 // Assemble Xs + tiles and solve X m = rhs with the Jacobi-scaled CG.  aneigh/ancnt/aflag/srank/S/atom_site: current.hip steps 1-2.
 int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEntry *S, const int *aneigh, const int *ancnt, const int *aflag,
@@ -1032,7 +1017,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     double *xbuf = nullptr;
     auto assemble = [&]() -> int {
         if (g_fault_phase == 1) { g_fault_phase = 0; return dkmc_fail(90, "injected fault (assembly of X)", __FILE__, __LINE__); }
-        if (sharded) { xbuf = (double *)scratch(S_CG_XCHG, ((size_t)ns * (e.x_block > 1 ? 16 : 1) + 2) * (e.x_block > 1 ? comm_nranks() : 1) * 8); if (!xbuf) return e.err_code; if (ns > 0) { rc = xt_side_init(); if (rc) return rc; } }
+        if (sharded) { xbuf = (double *)scratch(S_CG_XCHG, ((size_t)ns * (e.x_block > 1 ? 16 : 1) + 2) * (e.x_block > 1 ? comm_nranks() : 1) * 8); if (!xbuf) return e.err_code; if (ns > 0) { rc = side_stream_init(g_side); if (rc) return rc; } }
         // ---- sparse part Xs: neighbour pattern of every row + values (same kernels as the CSR path, all rows) ----
         cnt = (int *)scratch(S_X_CNT, (size_t)(Nsub + 4) * 4);
         rp = (xrp_t *)scratch(S_X_ROWPTR, (size_t)(Nsub + 4) * sizeof(xrp_t));
@@ -1179,8 +1164,8 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     const int ntb = (X.item_n + 3) / 4;
     const int nsb = (std::max(m - 2, 1) + XT_NT / 8 * XT_RPG_FUSED - 1) / (XT_NT / 8 * XT_RPG_FUSED);     // neighbour role inside k_xt_apply
     const int nsb1 = (std::max(m - 2, 1) + XT_NT / 8 - 1) / (XT_NT / 8);                                    // k_xt_neigh
-    const int n2b = xt_grid(std::max(std::max(nK, (m + 4095) / 4096), 1), 1, 1024);    // row kernel: S row blocks + its share of the p.t dot
-    const int gv = xt_grid(m, XT_NT * 4, 256);
+    const int n2b = grid_blocks(std::max(std::max(nK, (m + 4095) / 4096), 1), 1, 1024);    // row kernel: S row blocks + its share of the p.t dot
+    const int gv = grid_blocks(m, XT_NT * 4, 256);
     const int np_pt = n2b;
     const bool nt_loads = (size_t)X.sub_n * XT_SUB * 8 > ((size_t)200 << 20);
 
@@ -1193,7 +1178,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
                       rowpart, colpart, (const XCtrl *)ctrl, NTB, NSB, m, (const xrp_t *)rp, (const int *)col, (const double *)val, (const double *)q, \
                       (const double *)sc, (const int *)nsrank, t
         if (split) {
-            XSide &S = g_side; const int sl = (int)(S.seq++ % XT_SIDE_RING);
+            SideStream &S = g_side; const int sl = (int)(S.seq++ % SideStream::RING);
             // Host-side failures between two collectives must not leave the peers in the all-reduce: the local part runs in `local`;
             // if it fails, this rank still joins the all-reduce, with the abort word set, and every rank leaves the loop together.
             auto local = [&]() -> int {
@@ -1248,7 +1233,6 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     // single-vector loop below continues from the last good iterate ----
     XCtrl h{};
     bool solved = false;
-    double prof_long_ms = 0.0, prof_short_ms = 0.0, prof_comm_ms = 0.0; int prof_long_n = 0, prof_short_n = 0, prof_comm_n = 0;
     e.stats.xb_width = 1; e.stats.xb_fallback = 0; e.stats.xb_poly_used = 0;
     if (e.x_block > 1 && ns > 0) {
         XtbArgs B{};
@@ -1280,41 +1264,19 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     KCHK();
 
     // ---- optional kernel profile: start/stop events of sampled apply launches (bench.py roofline) ----
-    static hipEvent_t evs[4 * 64], evc[64 / XT_PROF_STRIDE]; static bool evs_ready = false;
-    if (prof && !evs_ready) { for (auto &ev : evs) HIPCHK(hipEventCreate(&ev)); for (auto &ev : evc) HIPCHK(hipEventCreate(&ev)); evs_ready = true; }
+    EventSampler &pf = g_loop_events;
+    if (prof) if (int prc = pf.begin(EventSampler::LONG | EventSampler::SHORT | (sharded && ns > 0 ? EventSampler::COMM : 0))) return prc;
 
-    // ---- iterations in batches; the host polls the control block between batches (batch plan: see cg.hip) ----
-    int it = 0, launched = 0, batch = 8;
-    if (e.x_iter_hint > 24) batch = e.x_iter_hint - 8;
-    int loop_rc = 0;
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (prof && launched) {
-            for (int b = 0; b < launched && b < 64; b += XT_PROF_STRIDE) {
-                if (it - launched + b >= h.iters) break;
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * b], evs[4 * b + 1])); prof_long_ms += ms; ++prof_long_n;
-                HIPCHK(hipEventElapsedTime(&ms, evs[4 * b + 2], evs[4 * b + 3])); prof_short_ms += ms; ++prof_short_n;
-                if (sharded && ns > 0) { HIPCHK(hipEventElapsedTime(&ms, evs[4 * b + 1], evc[b / XT_PROF_STRIDE])); prof_comm_ms += ms; ++prof_comm_n; }
-            }
-        }
-        if (h.done || loop_rc) break;
-        if (it >= 200000) { dkmc_fail(4, "CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int b = 0; b < batch; ++b, ++it) {
+    // ---- iterations in batches; the host polls the control block between batches (batch plan: launch_plan.h) ----
+    const int loop_rc = cg_poll_loop(ctrl, h, LaunchPlan::hinted_minus8(e.x_iter_hint), st, "CG: no convergence after 200000 iterations", prof ? &pf : nullptr,
+                                     [&](int it, const hipEvent_t *ev) -> int {
             cur_it = it;
-            const bool pb = prof && b < 64 && (b % XT_PROF_STRIDE == 0);
-            loop_rc = matvec(pb ? evs[4 * b] : nullptr, pb ? evs[4 * b + 1] : nullptr, pb ? evs[4 * b + 2] : nullptr, pb ? evs[4 * b + 3] : nullptr,
-                             pb ? evc[b / XT_PROF_STRIDE] : nullptr);
-            if (loop_rc) break;
+            if (int mrc = matvec(ev[0], ev[1], ev[2], ev[3], ev[4])) return mrc;
             hipLaunchKernelGGL(k_xt_step, dim3(gv), dim3(XT_NT), 0, st, m, it, (const double *)part_pt, np_pt, (const double *)(part_rr + 512 * (it & 1)), gv,
                                part_rr + 512 * ((it + 1) & 1), p, (const double *)t, y, r, (const double *)sc, q, (const int *)nsrank, qS, ctrl, tol2);
-        }
-        launched = batch;
-        KCHK();
-        if (e.x_iter_hint > 24) batch = 8; else if (batch < 64) batch *= 2;
-    }
-    if (loop_rc) return loop_rc;
+            return 0;
+        });
+    if (loop_rc) { HIPCHK(hipStreamSynchronize(st)); return loop_rc; }       // (what the ended batch left in the stream has drained when the caller sees the failure)
     if (local_fail) return local_fail;                                                     // this rank failed between two collectives: the peers were told (abort word)
     if (h.aborted) return dkmc_fail(46, "a peer rank aborted the sharded current solve", __FILE__, __LINE__);
     }
@@ -1344,11 +1306,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     e.stats.xt_sparse_nnz = xs_nnz; e.stats.xt_ns = ns;
     e.stats.spmv_segments = 0; e.stats.spmv_segment_entries = 0;
     e.stats.spmv_long_rows = ns; e.stats.spmv_short_rows = m - ns; e.stats.spmv_long_nnz = 2 * t_upper; e.stats.spmv_short_nnz = xs_nnz;
-    if (prof && !solved) {
-        e.stats.spmv_long_ms = prof_long_ms; e.stats.spmv_short_ms = prof_short_ms;
-        e.stats.spmv_long_launches = prof_long_n; e.stats.spmv_short_launches = prof_short_n;
-        e.stats.comm_ms = prof_comm_ms; e.stats.comm_launches = prof_comm_n;
-    }
+    if (prof && !solved) g_loop_events.to_stats(e.stats, true);
     return e.err_code;
 }
 
@@ -1429,7 +1387,7 @@ extern "C" int dkmc_xt_time_share(int nranks, int rank, int reps, double *apply_
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
     HIPCHK(hipMemsetAsync(ytmp, 0, (size_t)(m + ns + 8) * 8, st));
     const int ntb = (item_n + 3) / 4, nsb = (std::max(m - 2, 1) + XT_NT / 8 * XT_RPG_FUSED - 1) / (XT_NT / 8 * XT_RPG_FUSED), nsb1 = (std::max(m - 2, 1) + XT_NT / 8 - 1) / (XT_NT / 8);
-    const int n2b = xt_grid(std::max(std::max(nK, (m + 4095) / 4096), 1), 1, 1024), gv = xt_grid(m, XT_NT * 4, 256);
+    const int n2b = grid_blocks(std::max(std::max(nK, (m + 4095) / 4096), 1), 1, 1024), gv = grid_blocks(m, XT_NT * 4, 256);
     const bool nt_loads = (size_t)sh.sub_n * XT_SUB * 8 > ((size_t)200 << 20);
     // one GPU: the whole product in one launch.  nranks > 1: the tile pass alone, as the sharded solve launches it; the neighbour part
     // (which that solve runs on a second stream beside the exchange) is timed on its own as the fourth side kernel.

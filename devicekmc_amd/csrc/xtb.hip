@@ -1168,19 +1168,7 @@ __global__ void k_xtb_zero(long long n, double *__restrict__ p)
 // Second stream of the block loop on large systems: the neighbour part (an L2 / Infinity-Cache gather, 0.3 ms per sweep at 9.4e5 sites) runs
 // BESIDE the tile x panel kernel (one wave per SIMD on the matrix pipe) instead of behind it.  Events from a ring: the host runs a whole
 // batch ahead.  On small systems the two cross-stream edges cost more than the overlap gains (xt.hip measured ~15 us per iteration).
-#define XB_SIDE_RING 64
-struct XbSide { hipStream_t st = nullptr; hipEvent_t a[XB_SIDE_RING], b[XB_SIDE_RING]; int device = -1; unsigned seq = 0; bool ready = false; };
-static XbSide g_xb_side;
-static int xtb_side_init()
-{
-    XbSide &S = g_xb_side; const int dev = eng().device;
-    if (S.ready && S.device == dev) return 0;
-    if (S.ready) { (void)hipStreamDestroy(S.st); for (int i = 0; i < XB_SIDE_RING; ++i) { (void)hipEventDestroy(S.a[i]); (void)hipEventDestroy(S.b[i]); } S.ready = false; }
-    HIPCHK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-    for (int i = 0; i < XB_SIDE_RING; ++i) { HIPCHK(hipEventCreateWithFlags(&S.a[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&S.b[i], hipEventDisableTiming)); }
-    S.device = dev; S.seq = 0; S.ready = true;
-    return 0;
-}
+static SideStream g_xb_side;
 
 // test aid: make this rank fail once on the host side of block-CG iteration `iteration` of a sharded solve (dkmc_debug_inject_fault(3, it))
 int g_xtb_fault_iter = -1;
@@ -1272,58 +1260,17 @@ static void xtb_rows_launch(bool init, int ng, hipStream_t st, hipEvent_t e0, hi
     if (init) hipLaunchKernelGGL((k_xtb_rows<1, SH, NF>), dim3(ng), dim3(XT_NT), 0, st, a...);
     else hipExtLaunchKernelGGL((k_xtb_rows<0, SH, NF>), dim3(ng), dim3(XT_NT), 0, st, e0, e1, 0, a...);
 }
-// profiling (dkmc_set_profiling): the tile and the row kernel of the first sweep of every XT_PROF_STRIDE of a batch (up to 8) between events of one set
-struct XbProf { double long_ms = 0.0, short_ms = 0.0; int long_n = 0, short_n = 0; };
-static hipEvent_t g_xb_evs[4 * 8]; static bool g_xb_evs_ready = false;
-static const hipEvent_t g_xb_noev[4] = {nullptr, nullptr, nullptr, nullptr};
-// Launch plan of a block loop: batches of sweeps, one read-back of the control words (into h) per batch.  The first batch covers three quarters of the
-// previous solve's sweeps -- with the warm start the count moves by +-30 per cent from step to step (9.4e5 sites: 268 ... 505), and a batch sized to the
-// previous count left up to a quarter of its launches as no-ops --, then batches of 8; without a hint batches of 4, 8, ... 64.
-// sweep(it, ev) issues sweep `it`; ev: its four events (tile kernel, row kernel) or none.  hint: plan from e.x_iter_hint; cap > 0: stop after cap sweeps;
-// prof: harvest the events into pf; fault: the test aid g_xtb_fault_iter applies (it fails this rank on the host side, local_fail).
-template <class Sweep>
-static int xtb_sweeps(const XCtrl *ctrl, XCtrl &h, bool hint, int cap, bool prof, bool fault, int &local_fail, XbProf &pf, Sweep sweep)
-{
-    Engine &e = eng(); hipStream_t st = e.stream;
-    if (prof && !g_xb_evs_ready) { for (auto &ev : g_xb_evs) HIPCHK(hipEventCreate(&ev)); g_xb_evs_ready = true; }
-    int it = 0, launched = 0, batch = 4;
-    if (hint && e.x_iter_hint > 12) batch = std::max(4, e.x_iter_hint * 3 / 4);
-    for (;;) {
-        HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (prof && launched) {
-            for (int bq = 0; bq < 8 && bq * XT_PROF_STRIDE < launched; ++bq) {
-                if (it - launched + bq * XT_PROF_STRIDE >= h.iters) break;
-                float ms = 0.f;
-                HIPCHK(hipEventElapsedTime(&ms, g_xb_evs[4 * bq], g_xb_evs[4 * bq + 1])); pf.long_ms += ms; ++pf.long_n;
-                HIPCHK(hipEventElapsedTime(&ms, g_xb_evs[4 * bq + 2], g_xb_evs[4 * bq + 3])); pf.short_ms += ms; ++pf.short_n;
-            }
-        }
-        if (h.done) break;
-        if (cap > 0 && it >= cap) break;
-        if (it >= 200000) { dkmc_fail(4, "block-CG: no convergence after 200000 iterations", __FILE__, __LINE__); break; }
-        for (int bq = 0; bq < batch; ++bq, ++it) {
-            const bool pb = prof && bq < 8 * XT_PROF_STRIDE && (bq % XT_PROF_STRIDE == 0);
-            if (fault && g_xtb_fault_iter >= 0 && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
-            if (int rc = sweep(it, pb ? g_xb_evs + 4 * (bq / XT_PROF_STRIDE) : g_xb_noev)) return rc;
-        }
-        launched = batch;
-        KCHK();
-        if (hint && e.x_iter_hint > 12) batch = 8; else if (batch < 64) batch *= 2;
-    }
-    return 0;
-}
+// A block loop runs on cg_poll_loop (cg_host.h) with the plan LaunchPlan::hinted_three_quarters of e.x_iter_hint (an emulation: of no hint) and the
+// message below.  profiling (dkmc_set_profiling): the tile and the row kernel of the sampled sweeps run between the events of one slot of g_loop_events.
+static const char *const XTB_NO_CONVERGENCE = "block-CG: no convergence after 200000 iterations";
 // end of a block loop: sweeps and residual to the caller, the profile to the stats; hint: the sweeps size the next solve's first batch
-static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, const XbProf &pf, int *iters_out, double *rr_out)
+static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, int *iters_out, double *rr_out)
 {
     Engine &e = eng();
     if (hint) e.x_iter_hint = h.iters;
     if (iters_out) *iters_out = h.iters;
     if (rr_out) *rr_out = h.rr[h.iters & 1];
-    if (prof) {
-        e.stats.spmv_long_ms = pf.long_ms; e.stats.spmv_short_ms = pf.short_ms;
-        e.stats.spmv_long_launches = pf.long_n; e.stats.spmv_short_launches = pf.short_n;
-    }
+    if (prof) g_loop_events.to_stats(e.stats, false);
     if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
     return again ? DKMC_XTB_AGAIN : 0;
 }
@@ -1450,19 +1397,19 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     const XbView *vw = &full;
     const int ntb = (A.item_n + 3) / 4;
     const int nnb = 2 * XB_DSPLIT + (std::max(m - 2, 1) + 15) / 16;
-    const int gs = xt_grid((m + 15) / 16, 4, 2048);
+    const int gs = grid_blocks((m + 15) / 16, 4, 2048);
     const bool prof = e.profiling != 0;
-    XbProf pf;
-    // neighbour part beside the tile kernel (see XbSide): only in a sharded solve, where a rank's tile pass is 1 / N of the sweep and the
+    if (prof) if (int prc = g_loop_events.begin(EventSampler::LONG | EventSampler::SHORT)) return prc;
+    // neighbour part beside the tile kernel (see g_xb_side): only in a sharded solve, where a rank's tile pass is 1 / N of the sweep and the
     // (replicated) neighbour part would otherwise be a serial 0.3 ms behind it.  On ONE GPU the overlap was measured and does not pay: the two
     // kernels share the memory system, the tile pass slows by what the neighbour part takes (9.4e5 sites: 3.95 + 0 against 3.65 + 0.32 ms; 85 k sites,
     // where both are latency-bound: 15.0 against 13.5 ms per superstep -- the two event hand-overs per sweep cost more than the overlap gains).
-    const bool side = sharded && m > 20000 && ntb > 0 && xtb_side_init() == 0;
+    const bool side = sharded && m > 20000 && ntb > 0 && side_stream_init(g_xb_side) == 0;
     const float *t32 = nullptr;                                               // the tile launch of product() streams the fp32 image (product_pre) or the fp64 store
     auto product = [&](hipEvent_t e0, hipEvent_t e1) {
         int sl = 0;
         if (side) {
-            XbSide &S = g_xb_side; sl = (int)(S.seq++ % XB_SIDE_RING);
+            SideStream &S = g_xb_side; sl = (int)(S.seq++ % SideStream::RING);
             (void)hipEventRecord(S.a[sl], st);                                 // P of the previous step (and the stop word) are final
             (void)hipStreamWaitEvent(S.st, S.a[sl], 0);
             hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, S.st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
@@ -1536,7 +1483,9 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
                        (const int *)nullptr, Ypanel);
     KCHK();
     XCtrl h{};
-    if (int rcx = xtb_sweeps(A.ctrl, h, true, 0, prof && ntb > 0 && live.item_n > 0, sharded, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {     // (no tile launch: no events)
+    if (int rcx = cg_poll_loop(A.ctrl, h, LaunchPlan::hinted_three_quarters(e.x_iter_hint), st, XTB_NO_CONVERGENCE, prof && ntb > 0 && live.item_n > 0 ? &g_loop_events : nullptr,     // (no tile launch: no events)
+                               [&](int it, const hipEvent_t *ev) -> int {
+            if (sharded && g_xtb_fault_iter >= 0 && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
             if (pd > 0) product_pre(ev[0], ev[1]);
             else product(ev[0], ev[1]);
             if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
@@ -1577,7 +1526,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     } else
     HIPCHK(hipMemcpyAsync(A.y, y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     if (keep_aux) hipLaunchKernelGGL(k_xtb_yaux_out, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const int *)nullptr, (const double *)Ypanel, A.sc, A.yaux);
-    return xtb_finish(h, true, again, prof, pf, iters_out, rr_out);
+    return xtb_finish(h, true, again, prof, iters_out, rr_out);
 }
 
 #include "xtb_slab.inc"

@@ -587,7 +587,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     };
     const int nnb_of = 2 * XB_DSPLIT;
     const bool prof = e.profiling != 0 && !emu;
-    XbProf pf;
+    if (prof) if (int prc = g_loop_events.begin(EventSampler::LONG | EventSampler::SHORT)) return prc;
     int local_fail = 0;
 
     // panels of a rank by member: the preconditioned loop runs the same passes on Vp / Zp that the plain one runs on P / T
@@ -720,7 +720,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             }); if (rc) return rc;
             if (itn < 0) hipLaunchKernelGGL(k_xtb_zero, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, (long long)pan, K.P);
             rc = timed(iv, 6, on, [&]() {
-                hipLaunchKernelGGL(k_xtb_step, dim3(xt_grid((K.n_own + 2 + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, K.n_own + 2, itn, (const double *)K.mats, K.y0, K.R, K.P,
+                hipLaunchKernelGGL(k_xtb_step, dim3(grid_blocks((K.n_own + 2 + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, K.n_own + 2, itn, (const double *)K.mats, K.y0, K.R, K.P,
                                    (const double *)K.T, A.sc, A.nsrank, K.QS, (const XCtrl *)K.ctrl, (const int *)K.steplist, K.Ypanel);
             }); if (rc) return rc;
         }
@@ -760,7 +760,9 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     KCHK();
     // the launch plan of xtb_cg_body; an emulation starts without the hint and leaves it unset
     XCtrl h{};
-    if (int rcx = xtb_sweeps(RK[0].ctrl, h, !emu, emu ? g_slab_sweep_cap : 0, prof, !emu, local_fail, pf, [&](int it, const hipEvent_t *ev) -> int {
+    if (int rcx = cg_poll_loop(RK[0].ctrl, h, LaunchPlan::hinted_three_quarters(emu ? 0 : e.x_iter_hint), st, XTB_NO_CONVERGENCE, prof ? &g_loop_events : nullptr,
+                               [&](int it, const hipEvent_t *ev) -> int {
+            if (!emu && g_xtb_fault_iter >= 0 && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
             const bool on = timing && it >= 2 && tphase < 24;            // sweeps 2 ... 25 of the emulation are timed, kernel by kernel
             if (pd > 0) {
                 if (int rcx = sweep_pre(it, on, ev[0], ev[1], ev[2], ev[3])) return rcx;
@@ -771,7 +773,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             }
             if (on) ++tphase;
             return 0;
-        })) return rcx;
+        }, emu ? g_slab_sweep_cap : 0)) return rcx;
     if (local_fail) return local_fail;
     if (h.aborted) return dkmc_fail(46, "a peer rank aborted the sharded current solve", __FILE__, __LINE__);
     if (e.err_code) return e.err_code;
@@ -862,5 +864,5 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         TM.nmul_us = nmul_n ? sum[8] * 1e3 / nmul_n : 0.0;
         g_slab_last.nmul_us = TM.nmul_us;
     }
-    return xtb_finish(h, !emu, again, prof, pf, iters_out, rr_out);
+    return xtb_finish(h, !emu, again, prof, iters_out, rr_out);
 }

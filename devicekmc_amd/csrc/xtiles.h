@@ -2,6 +2,7 @@
 // the MFMA tile x panel product).  See the head of xt.hip for the storage scheme.
 #pragma once
 #include "xshared.h"
+#include "cg_host.h"
 
 #define XT_R 32                      // S-rows per tile
 #define XT_C 256                     // S-columns per tile
@@ -9,7 +10,6 @@
 #define XT_SUB (XT_R * XT_SBW)       // doubles per sub-block (8 KiB)
 #define XT_NT 256
 #define XT_MAXKC 32                   // largest nominal run length (tiles) of a wave: min(XT_MAXKC, tiles / ranks / 4096); 16 until round 5 (profiles/r05_ab_tile_run_lists.jsonl)
-#define XT_PROF_STRIDE 8
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 // fp32 image of the tile values (dkmc_set_x_tile_f32): the sub-block layout at half width.  A sub-block is 4 consecutive 1-KiB wave loads; lane
@@ -66,14 +66,6 @@ extern XLive g_xlive;                // the last solve's
 int xt_live_build(double theta, int unit, const double *sS, XLive *lv);
 void xt_live_zero_dead(const XLive &lv, double *rowpartB, int so);
 int xt_live_for_test(XLive *lv);
-
-static inline int xt_grid(long long work, int per_block, int cap)
-{
-    long long b = (work + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    if (b > cap) b = cap;
-    return (int)b;
-}
 
 // ---- block-CG on the tiled X (xtb.hip) ----
 #define DKMC_XTB_AGAIN 1001          // xtb_cg_body (preconditioned solve): the true residual does not meet the stop test yet; y holds the iterate reached
