@@ -175,6 +175,7 @@ struct Engine {
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
     int x_block = 16;              // block-CG width of the current solve on the tiled X (dkmc_set_x_block; xtb.hip): 16 by default, 1 = the reference's single-vector loop (its iterate sequence)
     int x_format = 1;              // 1: tiled X (xt.hip, default); 0: CSR X as the reference stores it (current.hip + cg.hip)
+    int current_map = 0;           // 1: every current solve also leaves the atom-resolved current map of its GPUBuffers (dkmc_set_current_map; current.hip step 6 1/2)
     int x_iter_hint = 0;           // iteration count of the previous CG solve of X (sizes the first launch batch)
     dkmc_stats stats{};
     char err[512] = {0};
@@ -230,6 +231,7 @@ enum {
     // test aids of the preconditioner (xtb_precond.h: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
     S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,
     S_XTB_TEST_W1, S_XTB_TEST_W2, S_XTB_TEST_QS, S_XTB_TEST_CTRL, S_XTB_TEST_NPCNT, S_XTB_TEST_NPOFF, S_XTB_TEST_NPCOL, S_XTB_TEST_NPW,
+    S_P_CMAP,       // current map (dkmc_set_current_map): tile sums of S and the row kernel's partials
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

@@ -18,6 +18,8 @@
 int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEntry *S, const int *aneigh, const int *ancnt, const int *aflag,
                           const int *srank, const int *atom_site, double *rhs, double *y, int *iters_out, double *rr_out, double *yaux, int yaux_valid);
 int xt_power(dkmc_gpubuf *buf, const XParams &P, const int *aflag, const int *atom_site, const double *m, double Vd, double alpha);
+int xt_current_map_blocks(int Nsub);
+int xt_current_map(const int *atom_site, const double *m, int N, double *map, double *sums, double *part, int *passes_out);
 const xrp_t *xt_xs_rp(); const int *xt_xs_col(); const double *xt_xs_val(); bool xt_valid();
 int xt_export_csr(int *rows_out, long long *nnz_out, int *h_rp, int *h_col, double *h_data);
 
@@ -122,6 +124,7 @@ struct TCacheState {
 // buffers, least recently used one evicted.  The engine's scratch buffers are shared: they carry nothing across calls.
 struct XBufState { const void *key = nullptr; TCacheState tc; double *warm = nullptr; int warm_n = 0; unsigned long long stamp = 0;
                    double *warm_aux = nullptr; int warm_aux_n = 0, warm_aux_valid = 0;      // [warm_aux_n][16]: unscaled solutions of the block-CG's auxiliary columns (dkmc_set_x_aux_warm)
+                   double *cmap = nullptr; int cmap_n = 0, cmap_valid = 0;                  // [3 cmap_n + 8]: thr_all | thr_tun | net_tun | info of the last solve with dkmc_set_current_map(1); allocated by the first one
                    double lat[3] = {0, 0, 0}; bool lat_ok = false; };       // lattice: constant per GPUBuffers, fetched once
 static XBufState g_states[8];
 static XBufState *g_cur = &g_states[0];
@@ -146,6 +149,7 @@ void xstate_reset(const void *key)
     tc_release();
     if (st->warm) (void)hipFree(st->warm);
     if (st->warm_aux) (void)hipFree(st->warm_aux);
+    if (st->cmap) (void)hipFree(st->cmap);
     *st = XBufState();
     g_cur = save;
 }
@@ -396,6 +400,63 @@ __global__ void k_iota_rows(int n, int *rows)
     if (i < n) rows[i] = i;
 }
 
+// ---- current map (dkmc_set_current_map; no counterpart in the reference; definitions: include/devicekmc_hip.h) ----------------------------
+// CSR form of X: per atom row the bond currents J_ic = x_ic (m_i - m_c) over every column but the row's own.  An entry belongs to the tunnelling
+// block T when both ends are in S and the pair is no neighbour pair (site_dist >= nn_dist: the test x_entry makes, same operands, same bits).
+// LPR lanes per row.  Per workgroup: part[b] = max |sum_c J_ic|, part[nb + b] = sum thr_all, part[2 nb + b] = sum thr_tun (nb = gridDim.x).
+// The tiled form's twin is k_xt_current_rows (xt.hip).
+template <int LPR>
+__global__ __launch_bounds__(256) void k_current(XParams P, int Nsub, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ xv,
+                                                 const double *__restrict__ m, const int *__restrict__ node_srank, const double *__restrict__ ax,
+                                                 const double *__restrict__ ay, const double *__restrict__ az, const int *__restrict__ atom_site,
+                                                 double *__restrict__ thr_all, double *__restrict__ thr_tun, double *__restrict__ net_tun, double *__restrict__ part)
+{
+    constexpr int gpb = 256 / LPR;
+    __shared__ double red[gpb][3];
+    const int g = threadIdx.x / LPR, l = threadIdx.x % LPR;
+    const int i = 2 + blockIdx.x * gpb + g;
+    const bool ok = i < Nsub;                                       // (no early return: the workgroup's partials need every row group)
+    const double mi = ok ? m[i] : 0.0;
+    const xrp_t p0 = ok ? rp[i] : 0, p1 = ok ? rp[i + 1] : 0;
+    const bool inS = ok && node_srank[i] >= 0;
+    const double xa = ok ? ax[i - 2] : 0.0, ya = ok ? ay[i - 2] : 0.0, za = ok ? az[i - 2] : 0.0;
+    double sa = 0.0, sn = 0.0, ta = 0.0, tn = 0.0;
+    for (xrp_t q = p0 + l; q < p1; q += LPR) {
+        const int c = ci[q];
+        if (c == i) continue;
+        const double j = __dmul_rn(xv[q], mi - m[c]);
+        sa += fabs(j); sn += j;
+        if (inS && c >= 2 && node_srank[c] >= 0 && !(site_dist(xa, ya, za, ax[c - 2], ay[c - 2], az[c - 2], P.laty, P.latz, P.pbc) < P.nn_dist)) { ta += fabs(j); tn += j; }
+    }
+    sa = group_sum<LPR>(sa); sn = group_sum<LPR>(sn); ta = group_sum<LPR>(ta); tn = group_sum<LPR>(tn);
+    if (l == 0) {
+        red[g][0] = ok ? fabs(sn) : 0.0; red[g][1] = ok ? 0.5 * sa : 0.0; red[g][2] = ok ? 0.5 * ta : 0.0;
+        if (ok) { const int site = atom_site[i - 2]; thr_all[site] = 0.5 * sa; thr_tun[site] = 0.5 * ta; net_tun[site] = tn; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double mx = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int w = 0; w < gpb; ++w) { mx = fmax(mx, red[w][0]); s1 += red[w][1]; s2 += red[w][2]; }
+        part[blockIdx.x] = mx; part[gridDim.x + blockIdx.x] = s1; part[2 * gridDim.x + blockIdx.x] = s2;
+    }
+}
+// the summary of the map, one workgroup, fixed order: info[0] = I_macro (the bits k_imacro wrote), [1] = the driver-0 side current by k_imacro's
+// rule on row 0, [2 .. 4] = the fold of the row kernel's np partials (max, sum thr_all, sum thr_tun), [5] = rows covered, [6] = tile passes, [7] = 0
+__global__ __launch_bounds__(256) void k_current_info(int np, const double *__restrict__ part, const double *__restrict__ xv, const xrp_t *__restrict__ rp,
+                                                      const int *__restrict__ ci, const double *__restrict__ m, const double *__restrict__ imacro,
+                                                      double rows, double passes, double *__restrict__ info)
+{
+    __shared__ double red[4], redm[256];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, mx = 0.0;
+    const double m0 = m[0];
+    for (xrp_t p = rp[0] + threadIdx.x; p < rp[1]; p += 256) { const int c = ci[p]; if (c >= 2) s0 += xv[p] * (m[c] - m0); }
+    for (int b = threadIdx.x; b < np; b += 256) { mx = fmax(mx, part[b]); s1 += part[np + b]; s2 += part[2 * np + b]; }
+    s0 = block_sum_all<256>(s0, red); s1 = block_sum_all<256>(s1, red); s2 = block_sum_all<256>(s2, red);
+    redm[threadIdx.x] = mx; __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) redm[threadIdx.x] = fmax(redm[threadIdx.x], redm[threadIdx.x + s]); __syncthreads(); }
+    if (threadIdx.x == 0) { info[0] = *imacro; info[1] = s0; info[2] = redm[0]; info[3] = s1; info[4] = s2; info[5] = rows; info[6] = passes; info[7] = 0.0; }
+}
+
 // state of the last call (for dkmc_get_last_X and the private warm start)
 static int g_last_rows = 0; static long long g_last_nnz = 0; static bool g_last_tiled = false;
 
@@ -561,6 +622,35 @@ static int update_power_body(dkmc_gpubuf *buf, int n_src, int n_gnd, int nlc, do
                                alpha_disp, buf->site_power);
         }
     }
+    // ---- 6 1/2. current map (dkmc_set_current_map): from the potentials as they stay in the buffer -- scaled, and shifted when heating is on ----
+    if (e.current_map) {
+        if (g_cur->cmap_n != N) {
+            if (g_cur->cmap) (void)hipFree(g_cur->cmap);
+            g_cur->cmap = nullptr; g_cur->cmap_n = 0;
+            HIPCHK(hipMalloc((void **)&g_cur->cmap, ((size_t)3 * N + 8) * 8));
+            g_cur->cmap_n = N;
+        }
+        g_cur->cmap_valid = 0;                                  // (a call that fails leaves no map)
+        double *map = g_cur->cmap, *info = map + (size_t)3 * N;
+        HIPCHK(hipMemsetAsync(map, 0, (size_t)3 * N * 8, st));  // sites without a row
+        const int nbm = e.x_format != 0 ? xt_current_map_blocks(Nsub) : std::max(1, (Nsub - 2 + 3) / 4);
+        double *work = (double *)scratch(S_P_CMAP, ((size_t)2 * ns + (size_t)3 * nbm + 8) * 8);     // tile sums of S (sum |J|, sum J) | the row kernel's partials
+        if (!work) return e.err_code;
+        double *part = work + (size_t)2 * ns;
+        int passes = 0;
+        if (e.x_format != 0) { rc = xt_current_map(atom_site, m, N, map, work, part, &passes); if (rc) return rc; }
+        else {
+            hipLaunchKernelGGL((k_current<64>), dim3(nbm), dim3(256), 0, st, P, Nsub, rp, col, data, (const double *)m, (const int *)e.buf[S_X_SCB],      // (node_srank: filled before the solve)
+                               (const double *)buf->atom_x, (const double *)buf->atom_y, (const double *)buf->atom_z, (const int *)atom_site,
+                               map, map + N, map + (size_t)2 * N, part);
+        }
+        hipLaunchKernelGGL(k_current_info, dim3(1), dim3(256), 0, st, nbm, (const double *)part, data, rp, col, (const double *)m, (const double *)d_im,
+                           (double)(Nsub - 2), (double)passes, info);
+        KCHK();
+        HIPCHK(hipStreamSynchronize(st));
+        if (e.err_code) return e.err_code;
+        g_cur->cmap_valid = 1;
+    }
     KCHK();
     HIPCHK(hipStreamSynchronize(st));
     return e.err_code;
@@ -620,6 +710,35 @@ extern "C" int dkmc_set_current_warm_aux(const dkmc_gpubuf *buf, const double *h
     }
     g_cur->warm_aux_valid = 0;
     if (rows > 0) { HIPCHK(hipMemcpy(g_cur->warm_aux, h_in, (size_t)n * 8, hipMemcpyHostToDevice)); g_cur->warm_aux_valid = 1; }
+    return 0;
+}
+
+// ---- the current map of the last solve with dkmc_set_current_map(1), per GPUBuffers (include/devicekmc_hip.h) ----------------------------
+static XBufState *cmap_state(const dkmc_gpubuf *buf)
+{
+    XBufState *st = buf ? xstate_find(buf->site_x) : nullptr;
+    return (st && st->cmap && st->cmap_valid) ? st : nullptr;
+}
+extern "C" int dkmc_copy_current_map_from_gpu(const dkmc_gpubuf *buf, double *h_thr_all, double *h_thr_tun, double *h_net_tun)
+{
+    Engine &e = eng();
+    XBufState *st = cmap_state(buf);
+    if (!st) return dkmc_fail(15, "dkmc_copy_current_map_from_gpu: this GPUBuffers has had no current solve with dkmc_set_current_map(1)", __FILE__, __LINE__);
+    HIPCHK(hipStreamSynchronize(e.stream));
+    const size_t n = (size_t)st->cmap_n;
+    if (h_thr_all) HIPCHK(hipMemcpy(h_thr_all, st->cmap, n * 8, hipMemcpyDeviceToHost));
+    if (h_thr_tun) HIPCHK(hipMemcpy(h_thr_tun, st->cmap + n, n * 8, hipMemcpyDeviceToHost));
+    if (h_net_tun) HIPCHK(hipMemcpy(h_net_tun, st->cmap + 2 * n, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int dkmc_get_current_map_info(const dkmc_gpubuf *buf, double *info8)
+{
+    Engine &e = eng();
+    XBufState *st = cmap_state(buf);
+    if (!st) return dkmc_fail(15, "dkmc_get_current_map_info: this GPUBuffers has had no current solve with dkmc_set_current_map(1)", __FILE__, __LINE__);
+    if (!info8) return dkmc_fail(14, "dkmc_get_current_map_info: bad arguments", __FILE__, __LINE__);
+    HIPCHK(hipStreamSynchronize(e.stream));
+    HIPCHK(hipMemcpy(info8, st->cmap + (size_t)3 * st->cmap_n, 8 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

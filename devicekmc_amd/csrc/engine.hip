@@ -59,6 +59,8 @@ int dkmc_get_current_warm_start(void) { return eng().current_warm_start; }
 void dkmc_set_profiling(int on) { eng().profiling = on; }
 void dkmc_set_x_format(int tiled) { eng().x_format = tiled ? 1 : 0; }
 int dkmc_get_x_format(void) { return eng().x_format; }
+void dkmc_set_current_map(int on) { eng().current_map = on ? 1 : 0; }
+int dkmc_get_current_map(void) { return eng().current_map; }
 void dkmc_set_tcache_budget(long long bytes) { eng().tcache_budget = bytes; }
 void dkmc_set_pair_cutoff(double x_cut) { eng().pair_cut = x_cut > 0.0 ? x_cut : 0.0; }
 void dkmc_set_pair_form(int form) { eng().pair_form = form == 1 ? 1 : 0; }

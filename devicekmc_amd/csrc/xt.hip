@@ -255,6 +255,14 @@ template <int OP>
 __device__ __forceinline__ void xt_acc(const dbl2 v, const double pcx, const double pcy, const double pr, double &ra, double &cax, double &cay, bool vpos)
 {
     if (OP == 0) { ra += v.x * pcx + v.y * pcy; cax += v.x * pr; cay += v.y * pr; }
+    else if (OP == 2 || OP == 3) {
+        // current map (dkmc_set_current_map): bond current J = x (m_i - m_j) of the entry, seen from its row node i; its column node j sees -J.
+        // OP 2: |J| to both ends; OP 3: J to the row, -J to the column.  The product is rounded once (no contraction into the sums), so that
+        // both ends add the same bits and a stored zero adds exactly zero
+        const double jx = __dmul_rn(v.x, pr - pcx), jy = __dmul_rn(v.y, pr - pcy);
+        if (OP == 2) { const double bx = fabs(jx), by = fabs(jy); ra += bx + by; cax += bx; cay += by; }
+        else { ra += jx + jy; cax -= jx; cay -= jy; }
+    }
     else {
         // entry x between row node i (potential pr) and column node j (pcx / pcy): ical = x (m_i - m_j); the pair heats the
         // node the current flows INTO: row i when ical has the sign opposite to Vd, column j otherwise; amount x (m_i - m_j)^2
@@ -914,6 +922,50 @@ __global__ __launch_bounds__(XT_NT) void k_xt_power_rows(int Nsub, const xrp_t *
         site_power[atom_site[a]] = -1 * alpha * p;
     }
 }
+// current map of every atom row (dkmc_set_current_map): the bond currents J_ic = x_ic (m_i - m_c) of the sparse part (8 lanes per row, every
+// column but the row's own, the drivers' included) + the two tile sums of S rows (absS: sum |J|, netS: sum J over the row's pairs of T; null
+// without S).  Writes the three site values of the row's atom and, per workgroup, part[b] = max |sum_c J_ic|, part[nb + b] = sum thr_all,
+// part[2 nb + b] = sum thr_tun (nb = gridDim.x; folded in a fixed order by k_current_info, current.hip)
+__global__ __launch_bounds__(XT_NT) void k_xt_current_rows(int Nsub, const xrp_t *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
+                                                           const double *__restrict__ m, const int *__restrict__ nsrank, const double *__restrict__ absS,
+                                                           const double *__restrict__ netS, const int *__restrict__ atom_site, double *__restrict__ thr_all,
+                                                           double *__restrict__ thr_tun, double *__restrict__ net_tun, double *__restrict__ part)
+{
+    __shared__ double red[XT_NT / 64][4];
+    const int g = threadIdx.x >> 3, l = threadIdx.x & 7;
+    const int i = 2 + blockIdx.x * (XT_NT / 8) + g;
+    const bool ok = i < Nsub;                                       // (no early return: the block sums below need every thread)
+    const double mi = ok ? m[i] : 0.0;
+    const xrp_t p0 = ok ? rp[i] : 0, p1 = ok ? rp[i + 1] : 0;
+    double sa = 0.0, sn = 0.0;
+    for (xrp_t q = p0 + l; q < p1; q += 8) {
+        const int c = ci[q];
+        if (c == i) continue;
+        const double j = __dmul_rn(val[q], mi - m[c]);
+        sa += fabs(j); sn += j;
+    }
+    sa = group_sum<8>(sa); sn = group_sum<8>(sn);
+    double v[3] = {0.0, 0.0, 0.0};                                  // |net current of the row|, thr_all, thr_tun
+    if (ok && l == 0) {
+        const int sr = nsrank[i];
+        double at = 0.0, nt = 0.0;
+        if (sr >= 0 && absS) { at = absS[sr]; nt = netS[sr]; }
+        const int site = atom_site[i - 2];
+        v[0] = fabs(sn + nt); v[1] = 0.5 * (sa + at); v[2] = 0.5 * at;
+        thr_all[site] = v[1]; thr_tun[site] = v[2]; net_tun[site] = nt;
+    }
+    double mx = v[0];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, WAVE));
+    double s2[2] = {v[1], v[2]};
+    xt_block_sums<2>(s2, red);                                      // (two barriers: red[w][3] below is written after the first, read after a third)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][3] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < XT_NT / 64; ++w) mx = fmax(mx, red[w][3]);
+        part[blockIdx.x] = mx; part[gridDim.x + blockIdx.x] = s2[0]; part[2 * gridDim.x + blockIdx.x] = s2[1];
+    }
+}
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 XTState g_xt;
@@ -1325,6 +1377,32 @@ int xt_power(dkmc_gpubuf *buf, const XParams &P, const int *aflag, const int *at
                        m, Vd, (const int *)g_xb.nsrank, (const double *)pS, aflag, atom_site, alpha, buf->site_power);
     KCHK();
     (void)P;
+    return 0;
+}
+
+// current map from the same potentials (dkmc_set_current_map; definitions: include/devicekmc_hip.h): gather m onto S, one tile pass per rule
+// (OP 2: sum |J|, OP 3: sum J) on the fp64 store, each folded by k_xt_rows<1> (sharded: completed by the all-reduce, rank 0's bits for everyone),
+// then one row kernel.  map: [thr_all N | thr_tun N | net_tun N], zeroed by the caller.  part: 3 x xt_current_map_blocks(Nsub) partials for k_current_info.
+int xt_current_map_blocks(int Nsub) { return (std::max(Nsub - 2, 1) + XT_NT / 8 - 1) / (XT_NT / 8); }
+int xt_current_map(const int *atom_site, const double *m, int N, double *map, double *sums, double *part, int *passes_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
+    if (!X.valid) return dkmc_fail(13, "xt_current_map: no assembled X", __FILE__, __LINE__);
+    double *mS = (double *)e.buf[S_CG_PS];
+    double *absS = nullptr, *netS = nullptr;
+    int passes = 0;
+    if (X.ns > 0) {
+        absS = sums; netS = sums + X.ns;
+        hipLaunchKernelGGL(k_xt_gather_S, dim3((X.ns + 255) / 256), dim3(256), 0, st, X.ns, (const int *)g_xb.srow, m, mS);
+        int rc = xt_tile_sums<2>(mS, absS, 0); if (rc) return rc;
+        rc = xt_tile_sums<3>(mS, netS, 0); if (rc) return rc;
+        passes = 2;
+    }
+    const int nb = xt_current_map_blocks(X.Nsub);
+    hipLaunchKernelGGL(k_xt_current_rows, dim3(nb), dim3(XT_NT), 0, st, X.Nsub, (const xrp_t *)g_xb.rp, (const int *)g_xb.ci, (const double *)g_xb.val,
+                       m, (const int *)g_xb.nsrank, (const double *)absS, (const double *)netS, atom_site, map, map + N, map + 2 * (size_t)N, part);
+    KCHK();
+    *passes_out = passes;
     return 0;
 }
 

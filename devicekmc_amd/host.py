@@ -224,7 +224,27 @@ class Device:
                                                        len(p.metals), C.byref(imacro), int(p.solve_heating_local),
                                                        int(p.solve_heating_global), 1.0))
         self.imacro = imacro.value
+        if _lib.load().dkmc_get_current_map():
+            self._fetch_current_map(gpubuf)
         return {"Current [uA]": self.imacro * 1e6, "Z - calculation time - dissipated power [s]": time.perf_counter() - t0}
+
+    CURRENT_MAP_INFO = ("I_macro", "I_driver0", "max_node_defect", "sum_current", "sum_current_tunnel", "rows", "tile_passes", "reserved")
+
+    def _fetch_current_map(self, gpubuf: GPUBuffers):
+        """dkmc_set_current_map(1): the atom-resolved current map of the solve just done (definitions: include/devicekmc_hip.h).
+        site_current = thr_all, site_current_tunnel = thr_tun, site_tunnel_outflow = net_tun, per site, in amperes."""
+        L = _lib.load()
+        a, t, o, info = np.empty(self.N), np.empty(self.N), np.empty(self.N), (C.c_double * 8)()
+        check(L.dkmc_copy_current_map_from_gpu(C.byref(gpubuf.c), _np_ptr(a), _np_ptr(t), _np_ptr(o)))
+        check(L.dkmc_get_current_map_info(C.byref(gpubuf.c), info))
+        self.site_current, self.site_current_tunnel, self.site_tunnel_outflow = a, t, o
+        self.current_map_info = dict(zip(self.CURRENT_MAP_INFO, list(info)))
+
+    def tunnel_current_profile(self, cuts):
+        """Tunnelling current crossing the plane x = cut, for every cut: the sum of site_tunnel_outflow over the sites with site_x <= cut
+        (the tunnelling block is symmetric, so the pairs inside that set cancel).  Divide by imacro for the tunnelling share."""
+        x, out = np.asarray(self.site_x), np.asarray(self.site_tunnel_outflow)
+        return np.array([out[x <= c].sum() for c in np.atleast_1d(np.asarray(cuts, dtype=np.float64))])
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

@@ -24,13 +24,14 @@ def _g6(v: float) -> str:
     return "%g" % v
 
 
-def write_snapshot(path, element, x, y, z, potential, power, full_precision=False):
+def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None):
+    """current: optional per-site array (e.g. Device.site_current) appended as one more column; read_xyz ignores it.  None: the reference's file."""
     fmt = (lambda v: repr(float(v))) if full_precision else _g6
     with open(path, "w") as f:
         f.write("%d\n\n" % len(element))
         for i in range(len(element)):
-            f.write("%s   %s   %s   %s   %s   %s\n" % (ELEMENT_NAMES[int(element[i])], fmt(x[i]), fmt(y[i]), fmt(z[i]),
-                                                    fmt(potential[i]), fmt(power[i])))
+            f.write("%s   %s   %s   %s   %s   %s%s\n" % (ELEMENT_NAMES[int(element[i])], fmt(x[i]), fmt(y[i]), fmt(z[i]),
+                                                      fmt(potential[i]), fmt(power[i]), "" if current is None else "   " + fmt(current[i])))
 
 
 def read_xyz(path) -> Structure:

@@ -141,6 +141,10 @@ SYMBOLS = {
     "dkmc_update_power_gpu_sparse": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I,
                                           c_dbl_p, _I, _I, _D]),
     "dkmc_get_last_X": (_I, [c_int_p, C.POINTER(C.c_longlong), vp, vp, vp]),
+    "dkmc_set_current_map": (None, [_I]),
+    "dkmc_get_current_map": (_I, []),
+    "dkmc_copy_current_map_from_gpu": (_I, [C.POINTER(dkmc_gpubuf), vp, vp, vp]),
+    "dkmc_get_current_map_info": (_I, [C.POINTER(dkmc_gpubuf), c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

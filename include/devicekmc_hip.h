@@ -394,6 +394,28 @@ int dkmc_update_power_gpu_sparse(dkmc_gpubuf *buf, int num_source_inj, int num_g
 /* Assemble_X_sparsity + Assemble_X2 of the last update_power call, copied to host for inspection
  * (dump_csr_matrix_txt twin, iterative_solvers_gpu.cu:142-169).  Pass NULL pointers to query sizes. */
 int dkmc_get_last_X(int *rows_out, long long *nnz_out, int *h_row_ptr, int *h_col, double *h_data);
+/* Atom-resolved current map from the solved current system (opt-in, default 0; no counterpart in the reference).  With the switch on, every
+ * dkmc_update_power_gpu_sparse call also computes, on the device and from the potentials m exactly as they stay in atom_virtual_potentials when
+ * the call returns (G0-scaled, and shifted when heating is on), on both layouts of X and whether or not heating is on:
+ *   bond current   J_ic = x_ic (m_i - m_c) for every off-diagonal entry of a row i >= 2 (node i = atom i - 2; nodes 0, 1 are the drivers;
+ *                  Nsub = N_atom + 1 rows, the last atom is dropped), site = the atom's site;
+ *   thr_all[site]  = 1/2 sum_{c != i} |J_ic| over all columns, the driver columns 0 and 1 included: the current passing through the atom;
+ *   thr_tun[site]  = 1/2 sum_{c in T} |J_ic| over the tunnelling block T only (the non-neighbour pairs of S: what the tiles hold; on the CSR
+ *                  layout the entries with both ends in S and site_dist >= nn_dist);
+ *   net_tun[site]  = sum_{c in T} J_ic, signed.  T is symmetric and has no driver columns, so the sum of net_tun over an atom set A is the
+ *                  tunnelling current leaving A (e.g. all sites with x below a plane: the tunnelling current crossing it).
+ * Three fp64 arrays of N sites; every entry is written by every call, sites without a row are 0, metal atoms are included (unlike site_power).
+ * info8: [0] I_macro (the bits h_imacro received); [1] sum_{c >= 2} x_0c (m_c - m_0), the driver-0 side current; [2] max_i |sum_{c != i} J_ic|
+ * over the atom rows (the continuity defect of the solve in amperes); [3] sum thr_all; [4] sum thr_tun; [5] rows covered; [6] tile passes run
+ * (2 on the tiled layout with a non-empty S, else 0: one per rule over the fp64 tile store); [7] 0.  All sums are added in a fixed order (no
+ * floating-point atomics): two calls on the same state give the same bits; in a sharded solve every rank ends with the same arrays.  Nothing
+ * else changes: with the switch off no launch and no allocation is added.  The arrays are kept per GPUBuffers (freed with its solver state);
+ * the two getters fail (dkmc_last_error names the call) for a buffer that has had no solve with the switch on.  Any pointer of
+ * dkmc_copy_current_map_from_gpu may be NULL. */
+void dkmc_set_current_map(int on);
+int dkmc_get_current_map(void);
+int dkmc_copy_current_map_from_gpu(const dkmc_gpubuf *buf, double *h_thr_all, double *h_thr_tun, double *h_net_tun);
+int dkmc_get_current_map_info(const dkmc_gpubuf *buf, double *info8);
 
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
