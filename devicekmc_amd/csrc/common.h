@@ -232,6 +232,8 @@ enum {
     S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,
     S_XTB_TEST_W1, S_XTB_TEST_W2, S_XTB_TEST_QS, S_XTB_TEST_CTRL, S_XTB_TEST_NPCNT, S_XTB_TEST_NPOFF, S_XTB_TEST_NPCOL, S_XTB_TEST_NPW,
     S_P_CMAP,       // current map (dkmc_set_current_map): tile sums of S and the row kernel's partials
+    // test aids of the sweep's Gram, s x s and panel-step kernels (xtb.hip: dkmc_xtb_test_gram / _small / _step): their own buffers, as above
+    S_XTB_ALG_PANELS, S_XTB_ALG_INTS, S_XTB_ALG_GRAM, S_XTB_ALG_QS, S_XTB_ALG_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

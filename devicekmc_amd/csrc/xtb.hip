@@ -1632,6 +1632,166 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     return e.err_code;
 }
 
+// ---- test aids (tests/test_gpu_block_cg_algebra.py; devicekmc_hip_debug.h) -----------------------------------------------------------------
+// The last four launches of a preconditioned sweep -- k_xtb_rows<0, 0, 1>, k_xtb_gred, k_xtb_small, k_xtb_step -- as production launches them, on
+// data the caller supplies.  Buffers of their own (S_XTB_ALG_*) and an XCtrl of their own: the resident X, the solver's XCtrl, the warm start and the
+// launch batch of the next solve are not touched.  Every argument is checked before anything is launched.
+#define XTB_ALG_MAXROWS (1 << 21)
+static_assert(sizeof(dkmc_xtb_ctrl) == sizeof(XCtrl) && offsetof(dkmc_xtb_ctrl, pad) == offsetof(XCtrl, pad) && offsetof(dkmc_xtb_ctrl, done) == offsetof(XCtrl, done),
+              "dkmc_xtb_ctrl mirrors XCtrl");
+static size_t xtb_alg_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// nsrank[m]: -1 or an S rank 0 ... ns - 1, each rank once; srow (may be null): the row of every rank
+static bool xtb_alg_sranks(int m, const int *nsrank, int ns, std::vector<int> *srow)
+{
+    if (ns < 0 || ns > m) return false;
+    std::vector<int> sr((size_t)ns, -1);
+    for (int i = 0; i < m; ++i) {
+        const int r = nsrank[i];
+        if (r < -1 || r >= ns) return false;
+        if (r >= 0) { if (sr[r] >= 0) return false; sr[r] = i; }
+    }
+    for (int r = 0; r < ns; ++r) if (sr[r] < 0) return false;
+    if (srow) srow->swap(sr);
+    return true;
+}
+// [ns][16] -> QS (interleaved, xtb_qs_pos); the inverse of k_xtb_test_qs_decode
+__global__ void k_xtb_test_qs_encode(int ns, const double *__restrict__ in, double *__restrict__ QS)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ns * XB_SP) QS[xtb_qs_pos(i >> 4, i & 15)] = in[i];
+}
+// Gram stage: k_xtb_rows<0, 0, 1> over ng workgroups, then k_xtb_gred, on host panels P, T, R of [m][16].  gfin [6 * 256] is uploaded first and read back
+// afterwards (a preset stop word leaves it as it came); the row kernel's partials start as NaN, so a partial nobody wrote shows.
+extern "C" int dkmc_xtb_test_gram(int m, const double *P, const double *T, const double *R, const int *nsrank, int ns, int ng, int done_word, double *gfin,
+                                  dkmc_xtb_ctrl *ctrl_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || m > XTB_ALG_MAXROWS || !P || !T || !R || !nsrank || ng < 1 || ng > 4096 || !gfin) return dkmc_fail(13, "xtb_test_gram: bad arguments", __FILE__, __LINE__);
+    std::vector<int> srow;
+    if (!xtb_alg_sranks(m, nsrank, ns, &srow)) return dkmc_fail(13, "xtb_test_gram: bad S ranks", __FILE__, __LINE__);
+    // the row blocks of the S rows; the NF form folds nothing but still reads wrange[k], nitem_w[k / 8], nitem_w[nW + 2 + k / 8] and nitem_w[2 (nW + 2)]: zeros
+    const int nK = (ns + XT_R - 1) / XT_R, nW = std::max(1, (nK + XT_C / XT_R - 1) / (XT_C / XT_R));
+    const size_t pan = (size_t)m * XB_SP * 8, pan_up = xtb_alg_up(pan);
+    const size_t b_nsr = xtb_alg_up((size_t)m * 4), b_srow = xtb_alg_up((size_t)std::max(ns, 1) * 4), b_wr = xtb_alg_up((size_t)std::max(nK, 1) * sizeof(int2));
+    const size_t b_nit = xtb_alg_up((size_t)(2 * (nW + 2) + 1) * 4);
+    const size_t b_gpart = (size_t)ng * XB_NG * 256 * 8;
+    char *panels = (char *)scratch(S_XTB_ALG_PANELS, 3 * pan_up);
+    char *ints = (char *)scratch(S_XTB_ALG_INTS, b_nsr + b_srow + b_wr + b_nit);
+    char *gram = (char *)scratch(S_XTB_ALG_GRAM, b_gpart + (size_t)XB_NG * 256 * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
+    if (!panels || !ints || !gram || !ctrl) return e.err_code;
+    double *dP = (double *)panels, *dT = (double *)(panels + pan_up), *dR = (double *)(panels + 2 * pan_up);
+    int *dnsr = (int *)ints, *dsrow = (int *)(ints + b_nsr);
+    int2 *dwr = (int2 *)(ints + b_nsr + b_srow);
+    int *dnit = (int *)(ints + b_nsr + b_srow + b_wr);
+    double *gpart = (double *)gram, *dgfin = (double *)(gram + b_gpart);
+    XCtrl h{}; h.done = done_word;
+    HIPCHK(hipMemcpyAsync(dP, P, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dT, T, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dR, R, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dnsr, nsrank, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    if (ns > 0) HIPCHK(hipMemcpyAsync(dsrow, srow.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(dwr, 0, b_wr + b_nit, st));
+    HIPCHK(hipMemsetAsync(gpart, 0xff, b_gpart, st));
+    HIPCHK(hipMemcpyAsync(dgfin, gfin, (size_t)XB_NG * 256 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctrl, &h, sizeof(XCtrl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                          // (the uploads read pageable host memory, srow and h among it)
+    xtb_rows_launch<0, 1>(false, ng, st, nullptr, nullptr, ns, nK, nW, m, 16, 16, (const int2 *)dwr, (const int *)dnit, (const double *)nullptr, (const double *)nullptr,
+                          (const int *)dsrow, (const double *)nullptr, (const int *)dnsr, (const double *)nullptr, (const double *)nullptr, dT, (const double *)dP, dR,
+                          (const double *)nullptr, gpart, ctrl, (const double *)nullptr, 0, 1, (const XbAux *)nullptr, (const double *)nullptr, (const double *)nullptr,
+                          (const double *)nullptr);
+    hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, dgfin, (const XCtrl *)ctrl);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(gfin, dgfin, (size_t)XB_NG * 256 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&h, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ctrl_out) memcpy(ctrl_out, &h, sizeof(XCtrl));
+    return e.err_code;
+}
+// Small stage: ONE launch of k_xtb_small (256 threads) on caller-given Gram blocks [nrg][6 * 256 + 2] (a block's last word: that rank's abort word), the
+// caller's XCtrl and the caller's pre-filled mats [4 * 256]; mats and the XCtrl come back.
+extern "C" int dkmc_xtb_test_small(int it, int s, int nrg, const double *gblocks, double tol2, const dkmc_xtb_ctrl *ctrl_in, double *mats, dkmc_xtb_ctrl *ctrl_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (it < -1 || it > 0x3fffffff || s < 1 || s > XB_SP || nrg < 1 || nrg > 64 || !gblocks || !ctrl_in || !mats || !ctrl_out)
+        return dkmc_fail(13, "xtb_test_small: bad arguments", __FILE__, __LINE__);
+    const size_t gstr = (size_t)XB_NG * 256 + 2, b_g = xtb_alg_up((size_t)nrg * gstr * 8);
+    char *gram = (char *)scratch(S_XTB_ALG_GRAM, b_g + 4 * 256 * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
+    if (!gram || !ctrl) return e.err_code;
+    double *dg = (double *)gram, *dmats = (double *)(gram + b_g);
+    HIPCHK(hipMemcpyAsync(dg, gblocks, (size_t)nrg * gstr * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dmats, mats, 4 * 256 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctrl, ctrl_in, sizeof(XCtrl), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, it, s, (const double *)dg, dmats, ctrl, tol2, nrg, (int)gstr);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(mats, dmats, 4 * 256 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ctrl_out, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+// Step stage: ONE launch of k_xtb_step with the grid of a solve.  Panels of [m][16] and y0 [m] go up, and come back afterwards; rowlist (nlist distinct
+// rows, may be null): the row-list form of the slab-distributed loop; Ypanel may be null.  qs [ns][16] in natural order goes up as the pre-fill of QS and
+// comes back decoded (null only with ns = 0).
+extern "C" int dkmc_xtb_test_step(int m, int it, const double *mats, int done_word, double *y0, double *R, double *P, const double *T, const double *sc,
+                                  const int *nsrank, int ns, const int *rowlist, int nlist, double *Ypanel, double *qs)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || m > XTB_ALG_MAXROWS || it < -1 || it > 0x3fffffff || !mats || !y0 || !R || !P || !T || !sc || !nsrank || (ns > 0 && !qs))
+        return dkmc_fail(13, "xtb_test_step: bad arguments", __FILE__, __LINE__);
+    if (!xtb_alg_sranks(m, nsrank, ns, nullptr)) return dkmc_fail(13, "xtb_test_step: bad S ranks", __FILE__, __LINE__);
+    if (rowlist) {
+        if (nlist < 1 || nlist > m) return dkmc_fail(13, "xtb_test_step: bad row list", __FILE__, __LINE__);
+        std::vector<char> seen((size_t)m, 0);
+        for (int i = 0; i < nlist; ++i) {
+            if (rowlist[i] < 0 || rowlist[i] >= m || seen[rowlist[i]]) return dkmc_fail(13, "xtb_test_step: bad row list", __FILE__, __LINE__);
+            seen[rowlist[i]] = 1;
+        }
+    }
+    const int n = rowlist ? nlist : m;
+    const size_t pan = (size_t)m * XB_SP * 8, pan_up = xtb_alg_up(pan), vec_up = xtb_alg_up((size_t)m * 8);
+    const size_t b_nsr = xtb_alg_up((size_t)m * 4), b_list = xtb_alg_up((size_t)n * 4);
+    const size_t b_qs = xtb_alg_up((size_t)(ns + 2) * XB_SP * 8);
+    char *panels = (char *)scratch(S_XTB_ALG_PANELS, 4 * pan_up + 2 * vec_up);
+    char *ints = (char *)scratch(S_XTB_ALG_INTS, b_nsr + b_list);
+    char *gram = (char *)scratch(S_XTB_ALG_GRAM, 4 * 256 * 8);
+    char *qsb = (char *)scratch(S_XTB_ALG_QS, 2 * b_qs);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
+    if (!panels || !ints || !gram || !qsb || !ctrl) return e.err_code;
+    double *dR = (double *)panels, *dP = (double *)(panels + pan_up), *dT = (double *)(panels + 2 * pan_up), *dY = (double *)(panels + 3 * pan_up);
+    double *dy0 = (double *)(panels + 4 * pan_up), *dsc = (double *)(panels + 4 * pan_up + vec_up);
+    int *dnsr = (int *)ints, *dlist = rowlist ? (int *)(ints + b_nsr) : nullptr;
+    double *dmats = (double *)gram, *QS = (double *)qsb, *dq = (double *)(qsb + b_qs);
+    XCtrl h{}; h.done = done_word;
+    HIPCHK(hipMemcpyAsync(dR, R, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dP, P, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dT, T, pan, hipMemcpyHostToDevice, st));
+    if (Ypanel) HIPCHK(hipMemcpyAsync(dY, Ypanel, pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dy0, y0, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dsc, sc, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dnsr, nsrank, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    if (dlist) HIPCHK(hipMemcpyAsync(dlist, rowlist, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dmats, mats, 4 * 256 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(QS, 0, b_qs, st));
+    if (ns > 0) {
+        HIPCHK(hipMemcpyAsync(dq, qs, (size_t)ns * XB_SP * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_xtb_test_qs_encode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, (const double *)dq, QS);
+    }
+    HIPCHK(hipMemcpyAsync(ctrl, &h, sizeof(XCtrl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                          // (h is read by the upload)
+    hipLaunchKernelGGL(k_xtb_step, dim3(grid_blocks((n + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, n, it, (const double *)dmats, dy0, dR, dP, (const double *)dT,
+                       (const double *)dsc, (const int *)dnsr, QS, (const XCtrl *)ctrl, (const int *)dlist, Ypanel ? dY : (double *)nullptr);
+    if (ns > 0) hipLaunchKernelGGL(k_xtb_test_qs_decode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, (const double *)QS, dq);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(R, dR, pan, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(P, dP, pan, hipMemcpyDeviceToHost, st));
+    if (Ypanel) HIPCHK(hipMemcpyAsync(Ypanel, dY, pan, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(y0, dy0, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    if (ns > 0) HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+
 // Test aid (tests/test_gpu_tile_f32.py): the tile sums of the 16 test vectors of k_xtb_test_panel on the X left resident by the last single-GPU solve,
 // from the fp64 store (stored_bytes = 8) or its fp32 image (4): k_xtb_apply + the fold of the partial sums (k_xtb_fold_local), before any row scaling.
 // -4 (tests/test_gpu_tile_drop.py, test_gpu_tile_drop_unit.py): the compact image of the live tiles (or live sub-blocks) at the current

@@ -43,6 +43,12 @@ class dkmc_stats(C.Structure):
                 ("kcg_ms", C.c_double), ("kcg_iters_timed", C.c_int), ("kcg_blocked", C.c_int), ("pair_ms", C.c_double), ("pair_evaluated", C.c_longlong), ("pair_tested", C.c_longlong), ("xt_records", C.c_longlong), ("tcache_bytes", C.c_longlong), ("kcg_bytes", C.c_longlong), ("xb_aux", C.c_int), ("xb_poly_used", C.c_int), ("xb_width", C.c_int), ("xb_fallback", C.c_int), ("x_tile_stream", C.c_int), ("x_tile_f64_rounds", C.c_int), ("x_tile_f32_bytes", C.c_longlong)]
 
 
+class dkmc_xtb_ctrl(C.Structure):
+    """Mirror of struct dkmc_xtb_ctrl (include/devicekmc_hip_debug.h): the control words of the block-CG (csrc/xtiles.h: XCtrl)."""
+    _fields_ = [("rr", C.c_double * 2), ("done_local", C.c_int), ("sharded", C.c_int), ("done", C.c_int), ("iters", C.c_int),
+                ("abort_local", C.c_int), ("aborted", C.c_int), ("pad", C.c_int * 2), ("xchg_timeout", C.c_int), ("pad2", C.c_int)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p)
 
 
@@ -166,6 +172,9 @@ SYMBOLS = {
     "dkmc_xtb_poly_rule": (_I, [_I]),
     "dkmc_xtb_test_nstep": (_I, [_I, vp, vp, vp, vp, vp, vp, _D, _D, _I, vp, _I, vp, _I, vp, vp]),
     "dkmc_xtb_check_poly": (_I, [_I, _I, vp, vp, vp]),
+    "dkmc_xtb_test_gram": (_I, [_I, vp, vp, vp, vp, _I, _I, _I, vp, C.POINTER(dkmc_xtb_ctrl)]),
+    "dkmc_xtb_test_small": (_I, [_I, _I, _I, vp, _D, C.POINTER(dkmc_xtb_ctrl), vp, C.POINTER(dkmc_xtb_ctrl)]),
+    "dkmc_xtb_test_step": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, vp, vp, _I, vp, _I, vp, vp]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),
     "dkmc_xtb_emulate_slabs": (_I, [_I, _I, _D, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong), c_int_p]),
     "dkmc_xtb_slab_last": (_I, [c_int_p, C.POINTER(C.c_longlong), c_dbl_p]),

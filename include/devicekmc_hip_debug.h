@@ -43,6 +43,32 @@ void dkmc_set_x_poly_auto_rows(int n0, int n1);
 int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
                         double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs);
 int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs);
+/* Test aids of the last four launches of a preconditioned block-CG sweep (csrc/xtb.hip): the PRODUCTION kernels, with production's launch shapes, on data
+ * the caller supplies.  They keep buffers and an XCtrl of their own: the resident X, the solver's XCtrl, the warm start and the launch batch of the next
+ * solve are left alone.  Every argument is checked first; a bad one returns non-zero and launches nothing.  Panels are host arrays of [m][16] doubles.
+ * dkmc_xtb_ctrl (below) mirrors the XCtrl of csrc/xtiles.h; ctrl_out receives the aid's own XCtrl after the launches.
+ *
+ * dkmc_xtb_test_gram: k_xtb_rows<0, 0, 1> (the form of a preconditioned sweep: T final in every row) over ng workgroups (1 ... 4096), then k_xtb_gred.
+ *   nsrank[m]: -1, or an S rank 0 ... ns - 1 (each once); the aid builds srow from it, nK = ceil(ns / 32), and zeroed wrange / nitem_w arrays.
+ *   done_word presets the stop word (non-zero: nothing is written).  gfin [6 * 256] is read (the pre-fill) and written: six 16 x 16 matrices in the order
+ *   P'T, P'R, T'R, T'T, R'R, P'P (X'Z = sum over the rows of x_i z_j).  Entry (i, j) of matrix g sits at
+ *       gfin[g * 256 + 64 * (i / 4) + 16 * (i % 4) + j]
+ *   -- the row kernel's accumulator map: word 64 u + l of a matrix is register u of lane l, and that is entry (i, j) = (l / 16 + 4 u, l % 16).
+ *   k_xtb_small reads its Gram blocks in the same map.
+ * dkmc_xtb_test_small: ONE launch of k_xtb_small for iteration `it` (-1: the set-up pass) and block width s (1 ... 16).  gblocks [nrg][6 * 256 + 2]
+ *   (nrg 1 ... 64): per rank the six matrices in the map above, a spare word, and the rank's abort word (read only when nrg > 1).  tol2: the stop bound
+ *   (on rr for it >= 0, on sqrt(rr) for it = -1).  ctrl_in: the XCtrl the kernel starts from (sharded, done, pad[1] ...).  mats [4 * 256] is read (the
+ *   pre-fill) and written: c | M1 = -W | M2 = beta W | M3 = c M1, each row-major [i * 16 + j].
+ * dkmc_xtb_test_step: ONE launch of k_xtb_step for iteration `it` with the stop word preset to done_word, on the grid a solve gives it (at most 2048
+ *   workgroups of four 16-row groups).  y0 [m], R, P and (may be null) Ypanel are read and written, T, sc [m], nsrank [m] (as above), mats are read.
+ *   rowlist (nlist distinct rows, may be null): the row-list form of the slab-distributed loop -- only those rows are touched.  qs [ns][16] (null only with
+ *   ns = 0): the pre-fill of QS and, afterwards, QS, both in natural order (the aid applies and undoes the kernel's interleaving of row pairs). */
+typedef struct dkmc_xtb_ctrl { double rr[2]; int done_local, sharded; int done; int iters; int abort_local, aborted; int pad[2]; int xchg_timeout, pad2; } dkmc_xtb_ctrl;
+int dkmc_xtb_test_gram(int m, const double *P, const double *T, const double *R, const int *nsrank, int ns, int ng, int done_word, double *gfin,
+                       dkmc_xtb_ctrl *ctrl_out);
+int dkmc_xtb_test_small(int it, int s, int nrg, const double *gblocks, double tol2, const dkmc_xtb_ctrl *ctrl_in, double *mats, dkmc_xtb_ctrl *ctrl_out);
+int dkmc_xtb_test_step(int m, int it, const double *mats, int done_word, double *y0, double *R, double *P, const double *T, const double *sc,
+                       const int *nsrank, int ns, const int *rowlist, int nlist, double *Ypanel, double *qs);
 /* Measurement aid: average duration [us] of the tile x panel kernel of the block-CG over the X left resident by the last single-GPU solve
  * (`reps` launches).  variant 0: as a solve runs it; on the round-4 form of the loop: 1: without its matrix instructions (tile stream + LDS
  * traffic); 2: without re-reading the tile stream (matrix instructions + LDS traffic); 3: operand stages of one k-pair; 4: without LDS
