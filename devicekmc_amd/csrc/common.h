@@ -170,6 +170,10 @@ struct Engine {
     int x_tile_f32 = 1;            // tile values of the block-CG's sweeps: 1 (auto) = the fp32 image inside the one-GPU preconditioned loop at cg_tol >= 1e-8, when the copy could be made; 0 = always the fp64 store (dkmc_set_x_tile_f32; xtb.hip)
     double x_tile_drop = 0.0;      // > 0: where the sweeps stream the fp32 image they stream a compacted one of the LIVE tiles only -- stored 32 x 256 tiles with a scaled entry sc_i |v_ij| sc_j >= this threshold (dkmc_set_x_tile_drop; xt_live.h); 0 (default) = off
     int x_tile_drop_unit = 0;      // what x_tile_drop drops: 0 (default) whole tiles, 1 the sub-blocks (32 x 32) without such an entry inside the live tiles too (dkmc_set_x_tile_drop_unit; xt_live.h)
+    int x_tile_drop_auto = 1;      // 1 (default): with x_tile_drop at 0 a WARM-STARTED solve whose stored X reaches the measured size gate runs its sweeps on the live tiles at 1e-10 (xtl_drop_rule, xt_live.h; dkmc_set_x_tile_drop_auto); an explicit x_tile_drop > 0 applies as it is, cold starts included
+    long long x_tile_drop_gate = 0;     // test aid (dkmc_set_x_tile_drop_auto_subblocks): stored sub-blocks at and above which that rule switches the live view on; 0 = the measured gate
+    double x_tile_drop_used = 0.0;      // the threshold the sweeps of the last current solve ran on, 0 = the full view (dkmc_get_x_tile_drop_used)
+    int xtl_census_form = 1;       // census of the live view: 1 (default; 0.87 of form 0's time per solve at 9.4e5 sites, profiles/x_tile_census_forms_tile10.jsonl) = from the fp32 image with a guard band and an fp64 re-read of the undecided sub-blocks, 0 = from the fp64 store; same result (dkmc_debug_xtl_census_form; xt_live.h)
     int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)

@@ -16,7 +16,7 @@
 
 // tiled X (xt.hip)
 int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEntry *S, const int *aneigh, const int *ancnt, const int *aflag,
-                          const int *srank, const int *atom_site, double *rhs, double *y, int *iters_out, double *rr_out, double *yaux, int yaux_valid);
+                          const int *srank, const int *atom_site, double *rhs, double *y, int *iters_out, double *rr_out, double *yaux, int yaux_valid, int warm);
 int xt_power(dkmc_gpubuf *buf, const XParams &P, const int *aflag, const int *atom_site, const double *m, double Vd, double alpha);
 int xt_current_map_blocks(int Nsub);
 int xt_current_map(const int *atom_site, const double *m, int N, double *map, double *sums, double *part, int *passes_out);
@@ -534,12 +534,14 @@ static int update_power_body(dkmc_gpubuf *buf, int n_src, int n_gnd, int nlc, do
     double *m = buf->atom_virtual_potentials;
     const xrp_t *rp = nullptr; const int *col = nullptr; const double *data = nullptr;
     g_last_tiled = e.x_format != 0;
+    e.x_tile_drop_used = 0.0;                                   // (the block loop sets it where its sweeps run on the live view)
     if (e.x_format != 0) {
         // ---- 3-5 (tiled X, xt.hip): neighbour part as a small CSR, tunnelling block straight into symmetric tiles, solve ----
         // (the coefficient cache is brought up to date inside, once this rank's share of the tiles is known: tc_prepare_tiled)
         hipLaunchKernelGGL(k_set_rhs, dim3((Na + 2 + 255) / 256), dim3(256), 0, st, rhs, Na + 2, loop_G, Vd);
+        int warm = 0;                                           // the solve starts from the previous solution (auto mode of the live view applies to such solves only: xt_live.h)
         if (e.current_warm_start == 1) {
-            if (g_warm && g_warm_n == Nsub) HIPCHK(hipMemcpyAsync(m, g_warm, (size_t)Nsub * 8, hipMemcpyDeviceToDevice, st));
+            if (g_warm && g_warm_n == Nsub) { HIPCHK(hipMemcpyAsync(m, g_warm, (size_t)Nsub * 8, hipMemcpyDeviceToDevice, st)); warm = 1; }
         }
         // the auxiliary columns of the block-CG start from the previous solve's solutions too (kept per GPUBuffers like the start vector itself)
         double *yaux = nullptr; int yaux_valid = 0;
@@ -553,7 +555,7 @@ static int update_power_body(dkmc_gpubuf *buf, int n_src, int n_gnd, int nlc, do
             yaux = g_cur->warm_aux; yaux_valid = g_cur->warm_aux_valid;
         }
         if (yaux) g_cur->warm_aux_valid = 0;                    // (a solve that fails leaves nothing to start from)
-        rc = xt_assemble_and_solve(buf, P, ns, S, aneigh, ancnt, aflag, srank, atom_site, rhs, m, &e.stats.cg_iters_X, &e.stats.cg_rr_X, yaux, yaux_valid);
+        rc = xt_assemble_and_solve(buf, P, ns, S, aneigh, ancnt, aflag, srank, atom_site, rhs, m, &e.stats.cg_iters_X, &e.stats.cg_rr_X, yaux, yaux_valid, warm);
         if (rc) return rc;
         if (yaux && e.stats.xb_width > 1 && !e.stats.xb_fallback) g_cur->warm_aux_valid = 1;
         rp = xt_xs_rp(); col = xt_xs_col(); data = xt_xs_val();

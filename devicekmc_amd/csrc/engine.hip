@@ -83,6 +83,10 @@ void dkmc_set_x_tile_drop(double theta) { eng().x_tile_drop = theta > 0.0 ? (the
 double dkmc_get_x_tile_drop(void) { return eng().x_tile_drop; }
 void dkmc_set_x_tile_drop_unit(int unit) { eng().x_tile_drop_unit = unit == 1 ? 1 : 0; }
 int dkmc_get_x_tile_drop_unit(void) { return eng().x_tile_drop_unit; }
+void dkmc_set_x_tile_drop_auto(int on) { eng().x_tile_drop_auto = on ? 1 : 0; }
+int dkmc_get_x_tile_drop_auto(void) { return eng().x_tile_drop_auto; }
+void dkmc_set_x_tile_drop_auto_subblocks(long long gate) { eng().x_tile_drop_gate = gate > 0 ? gate : 0; }
+double dkmc_get_x_tile_drop_used(void) { return eng().x_tile_drop_used; }
 void dkmc_debug_fail_true_residual_once(void) { eng().x_tile_f32_fail_once = 1; }
 void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }

@@ -1036,7 +1036,7 @@ static SideStream g_side;
 
 // Assemble Xs + tiles and solve X m = rhs with the Jacobi-scaled CG.  aneigh/ancnt/aflag/srank/S/atom_site: current.hip steps 1-2.
 int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEntry *S, const int *aneigh, const int *ancnt, const int *aflag,
-                          const int *srank, const int *atom_site, double *rhs, double *y, int *iters_out, double *rr_out, double *yaux, int yaux_valid)
+                          const int *srank, const int *atom_site, double *rhs, double *y, int *iters_out, double *rr_out, double *yaux, int yaux_valid, int warm)
 {
     TCacheView TC{};                     // brought up to date for this rank's share inside assemble() (tc_prepare_tiled, current.hip)
     Engine &e = eng(); hipStream_t st = e.stream;
@@ -1294,6 +1294,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         B.srow = srow; B.sS = sS; B.nsrank = nsrank; B.rp = rp; B.ci = col; B.val = val; B.sc = sc; B.ax = buf->atom_x; B.ay = buf->atom_y; B.az = buf->atom_z; B.b = rhs; B.y = y;
         B.yaux = yaux; B.yaux_valid = yaux_valid;
         B.ctrl = ctrl; B.tol2 = tol2; B.nt_loads = nt_loads; B.sharded = sharded; B.w_lo = X.w_lo; B.w_hi = X.w_hi;
+        B.warm = warm != 0; B.stored_subblocks = X.nsub_total;
         int bi = 0; double brr = 0.0;
         rc = xtb_cg(B, &bi, &brr);
         e.stats.xb_width = e.x_block;
@@ -1355,6 +1356,12 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     e.stats.X_nnz = xs_nnz + 2 * t_upper;
     e.stats.spmv_tiles = ntiles; e.stats.spmv_tile_entries = t_upper;
     e.stats.xt_subblocks = X.nsub_total; e.stats.xt_local_subblocks = X.sub_n; e.stats.xt_items = X.nitems; e.stats.xt_kc = X.kc; e.stats.xt_records = X.nitems >> X.rec_shift;
+    // sweeps on the live view (xt_live.h): the four counts that price a sampled tile launch (bench.py) are those of the view the sampled launches ran on
+    // -- streamed sub-blocks, live tiles, its runs and its records; xt_subblocks, spmv_tile_entries and X_nnz always describe the stored X
+    if (solved && e.x_tile_drop_used > 0.0 && g_xlive.state == 1) {
+        const XLive &lv = g_xlive;
+        e.stats.xt_local_subblocks = lv.info[e.x_tile_drop_unit == 1 ? 5 : 4]; e.stats.spmv_tiles = (int)lv.info[2]; e.stats.xt_items = lv.nitems; e.stats.xt_records = lv.nrecords;
+    }
     e.stats.xt_sparse_nnz = xs_nnz; e.stats.xt_ns = ns;
     e.stats.spmv_segments = 0; e.stats.spmv_segment_entries = 0;
     e.stats.spmv_long_rows = ns; e.stats.spmv_short_rows = m - ns; e.stats.spmv_long_nnz = 2 * t_upper; e.stats.spmv_short_nnz = xs_nnz;

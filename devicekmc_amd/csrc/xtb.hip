@@ -1320,10 +1320,14 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
     e.stats.x_tile_f64_rounds = f32 ? 0 : 1;
     // live tiles only (dkmc_set_x_tile_drop, xt_live.h): where the sweeps stream the image, and a live view of the resident X is worth having and fits,
     // they stream its compact image on its own launch view; everything else of the solve -- and every re-entry round -- keeps the full view
+    // The threshold of this solve: the explicit one where it is set (cold starts included); else, in auto mode, the size rule's -- for a solve that
+    // starts from the previous solution only (from a zero start the dropped part acts on the whole solution: an fp64 re-entry round, not a gain)
     XLive *lv = nullptr;
-    if (f32 && e.x_tile_drop > 0.0 && A.item_n > 0 && A.tiles == g_xb.tiles && A.tval32 == g_xb.tval32) {
-        if (int rcl = xt_live_build(e.x_tile_drop, e.x_tile_drop_unit, A.sS, &g_xlive)) return rcl;
-        if (g_xlive.state == 1) lv = &g_xlive;
+    const double theta = e.x_tile_drop > 0.0 ? e.x_tile_drop : (e.x_tile_drop_auto && A.warm ? xtl_drop_rule(A.stored_subblocks, e.x_tile_drop_gate) : 0.0);
+    e.x_tile_drop_used = 0.0;
+    if (f32 && theta > 0.0 && A.item_n > 0 && A.tiles == g_xb.tiles && A.tval32 == g_xb.tval32) {
+        if (int rcl = xt_live_build(theta, e.x_tile_drop_unit, A.sS, &g_xlive)) return rcl;
+        if (g_xlive.state == 1) { lv = &g_xlive; e.x_tile_drop_used = theta; }
     }
     int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32, lv);
     rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false, nullptr); });

@@ -58,12 +58,14 @@ extern XTBuffers g_xb;
 struct XLive {
     int state = 0;                   // 0 off or not applicable, 1 usable, -1 no buffer for the compact image, -2 nothing to drop
     const XTile *tiles = nullptr; const XItem *items = nullptr; int item_n = 0; const int2 *wrange = nullptr; const int *nitem_w = nullptr; int nrecords = 0;
+    int nitems = 0;                  // runs of the live view (what dkmc_stats.xt_items reports after a solve whose sweeps ran on it)
     const float *tval32 = nullptr;   // the compact image (sub-block slot = the live tile's soff; with dkmc_set_x_tile_drop_unit(1) only the live sub-blocks of a tile, its mask reduced to them)
     const int *tflag = nullptr;      // per STORED tile: 1 live, 0 dead
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double ms[2] = {0.0, 0.0};
 };
 extern XLive g_xlive;                // the last solve's
 int xt_live_build(double theta, int unit, const double *sS, XLive *lv);
+double xtl_drop_rule(long long stored_subblocks, long long gate_override);      // auto mode's threshold for a stored X of that many sub-blocks (xt_live.h)
 void xt_live_zero_dead(const XLive &lv, double *rowpartB, int so);
 int xt_live_for_test(XLive *lv);
 
@@ -86,6 +88,8 @@ struct XtbArgs {
     double *yaux; int yaux_valid;                 // UNSCALED solutions of the auxiliary columns, [m][16] (may be null): in (if valid) the previous solve's, out this solve's
     XCtrl *ctrl; double tol2; bool nt_loads;
     bool sharded; int w_lo, w_hi;                 // sharded solve (comm.hip): windows of this rank's tiles
+    bool warm;                                    // y holds the previous solve's solution (current.hip: the warm-start copy was loaded); auto mode of the live view needs it
+    long long stored_subblocks;                   // sub-blocks of the stored X, all ranks (the size auto mode's gate is stated in)
 };
 int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out);
 // one rank's share of the work items of an nranks-way split (xt.hip: xt_build_items)

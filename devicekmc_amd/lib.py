@@ -81,6 +81,9 @@ SYMBOLS = {
     "dkmc_get_x_tile_drop": (_D, []),
     "dkmc_set_x_tile_drop_unit": (None, [_I]),
     "dkmc_get_x_tile_drop_unit": (_I, []),
+    "dkmc_set_x_tile_drop_auto": (None, [_I]),
+    "dkmc_get_x_tile_drop_auto": (_I, []),
+    "dkmc_get_x_tile_drop_used": (_D, []),
     "dkmc_get_x_tile_live_info": (_I, [C.POINTER(C.c_longlong), c_dbl_p]),
     "dkmc_xt_get_live": (_I, [_D, vp, vp]),
     "dkmc_xt_get_live_masks": (_I, [_D, vp]),
@@ -170,6 +173,10 @@ SYMBOLS = {
     "dkmc_xt_get_tiles": (_I, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp]),
     "dkmc_xtb_poly_coeffs": (_I, [_I, c_dbl_p]),
     "dkmc_xtb_poly_rule": (_I, [_I]),
+    "dkmc_xtl_drop_rule": (_D, [C.c_longlong]),
+    "dkmc_debug_xtl_census_form": (_I, [_I]),
+    "dkmc_debug_xtl_census_reread": (C.c_longlong, []),
+    "dkmc_set_x_tile_drop_auto_subblocks": (None, [C.c_longlong]),
     "dkmc_xtb_test_nstep": (_I, [_I, vp, vp, vp, vp, vp, vp, _D, _D, _I, vp, _I, vp, _I, vp, vp]),
     "dkmc_xtb_check_poly": (_I, [_I, _I, vp, vp, vp]),
     "dkmc_xtb_test_gram": (_I, [_I, vp, vp, vp, vp, _I, _I, _I, vp, C.POINTER(dkmc_xtb_ctrl)]),

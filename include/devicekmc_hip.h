@@ -211,6 +211,18 @@ double dkmc_get_x_tile_drop(void);
  * than 1 / 64 of the stored sub-blocks would go" rule counts the sub-blocks this unit would drop.  What it is worth: DESIGN.md section 6. */
 void dkmc_set_x_tile_drop_unit(int unit);
 int dkmc_get_x_tile_drop_unit(void);
+/* AUTO MODE of the live view, on by default.  While dkmc_set_x_tile_drop is 0 (an explicit threshold applies as described there, cold starts
+ * included), a current solve runs its sweeps on the live tiles at 1e-10 when (a) it starts from the previous solution (dkmc_set_current_warm_start(1)
+ * and the copy of matching size was loaded: from a zero start the dropped part acts on the whole solution and costs an fp64 re-entry round) and (b) the
+ * stored X has at least the measured number of sub-blocks from which the live view pays for its per-solve census and compaction
+ * (profiles/x_tile_drop_by_size.jsonl).  Below the gate, from a zero start and wherever dkmc_set_x_tile_drop is ignored every
+ * solve is as with auto mode off, bit for bit.  dkmc_set_x_tile_drop_auto(0) switches it off: the full view everywhere unless a threshold is set.
+ * dkmc_get_x_tile_drop_used: the threshold the sweeps of the LAST current solve ran on, 0.0 for the full view.  After a solve on the live view the
+ * dkmc_stats fields xt_local_subblocks, spmv_tiles, xt_items and xt_records carry the live view's counts (what a sampled tile launch streamed);
+ * xt_subblocks, spmv_tile_entries and X_nnz always describe the stored X. */
+void dkmc_set_x_tile_drop_auto(int on);
+int dkmc_get_x_tile_drop_auto(void);
+double dkmc_get_x_tile_drop_used(void);
 /* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
  * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */

@@ -108,6 +108,16 @@ int dkmc_xtb_time_apply_stored(int width, int stored_bytes, int reps, double *us
  * it); [6] bytes of the compact image: 4096 x ([4] + 4) with unit 0, 4096 x ([5] + 4) with unit 1; [7] sweeps run on it.  [1]-[5] and [7] mean the
  * same in both units.  ms2 (written only with dkmc_set_profiling on): census + scan, compaction + view build. */
 int dkmc_get_x_tile_live_info(long long *info8, double *ms2);
+/* The size rule of dkmc_set_x_tile_drop_auto (csrc/xt_live.h: xtl_drop_rule).  dkmc_xtl_drop_rule: the threshold it gives a stored X of that many
+ * sub-blocks -- 1e-10 at or above the gate, 0.0 below it and for sizes <= 0; host code only, no GPU needed.  dkmc_set_x_tile_drop_auto_subblocks: test
+ * aid -- moves the gate so that a small workload reaches the live view; 0 (or less) selects the measured gate. */
+/* The census of the live view (csrc/xt_live.h).  Form 1: from the fp32 image, with a guard band of 2^-22 around the threshold and an fp64 re-read of the
+ * sub-blocks inside it -- the same flags, masks and counts as form 0, the census on the fp64 store, at half the bytes; taken only where there is an
+ * image and theta >= 1e-290; the call returns the form that was set before.  dkmc_debug_xtl_census_reread: sub-blocks the last census read again from the fp64 store (0 with form 0). */
+int dkmc_debug_xtl_census_form(int form);
+long long dkmc_debug_xtl_census_reread(void);
+double dkmc_xtl_drop_rule(long long stored_subblocks);
+void dkmc_set_x_tile_drop_auto_subblocks(long long gate);
 /* Test aid: for the X left by the last one-GPU solve, the live flag (1 / 0) of every stored tile at threshold theta, in dkmc_xt_get_tiles order, and
  * that solve's scaling by S rank (sS_out[xt_ns]).  Either array may be null. */
 int dkmc_xt_get_live(double theta, int *live_per_tile, double *sS_out);

@@ -39,6 +39,7 @@ def run(name, theta, steps, warmup, unit=None):
     from devicekmc_amd import host, lib
     L = lib.load()
     L.dkmc_set_x_tile_drop(theta); L.dkmc_set_x_tile_drop_unit(unit or 0)
+    L.dkmc_set_x_tile_drop_auto(0)                    # the cases are explicit thresholds: theta = 0 is the full view at every size
     try:
         sim = Sim(name, "cuda:0")
         for _ in range(warmup):
@@ -69,7 +70,7 @@ def run(name, theta, steps, warmup, unit=None):
         sim.close()
         return rec, (im, power, logs)
     finally:
-        L.dkmc_set_x_tile_drop(0.0); L.dkmc_set_x_tile_drop_unit(0); L.dkmc_set_profiling(0)
+        L.dkmc_set_x_tile_drop(0.0); L.dkmc_set_x_tile_drop_unit(0); L.dkmc_set_x_tile_drop_auto(1); L.dkmc_set_profiling(0)
 
 
 def child(name, steps, warmup, out_dir, units):

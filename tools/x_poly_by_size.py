@@ -48,7 +48,7 @@ def best(record, same_size=0.001):
     within the spread of the fastest.  Workloads whose rows differ by less than `same_size` are ONE size to a rule on the rows: their best degree is the
     one with the largest geometric mean, over those workloads, of steps/s relative to degree 8 (each workload's own result stays in the record)."""
     import statistics
-    runs = [r for r in map(json.loads, open(record)) if "steps_per_s" in r and isinstance(r.get("degree"), int)]
+    runs = [r for r in map(json.loads, open(record)) if "steps_per_s" in r and isinstance(r.get("degree"), int) and not r.get("with_live_view")]      # (the lines recorded with the live view on are a record beside the rule, not part of it)
     wls = {}
     for r in runs:
         wls.setdefault(r["workload"], []).append(r)
