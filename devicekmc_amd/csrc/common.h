@@ -177,6 +177,9 @@ struct Engine {
     int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
+    int x_nmul_window = 2;         // panel operands of the packed 16-byte N products from LDS row windows (k_xtb_nmulw, nwin_plan.h): 0 = off, 1 = on, 2 = by size (xb_nwin_rows); same results (dkmc_set_x_nmul_window)
+    int x_nmul_window_cap = 76 * 1024;   // test aid (dkmc_debug_set_x_nmul_window): LDS bytes of a window at most (0: every slot gathers from memory) ...
+    int x_nmul_window_block = 320;       // ... and the rows of a block
     int x_block = 16;              // block-CG width of the current solve on the tiled X (dkmc_set_x_block; xtb.hip): 16 by default, 1 = the reference's single-vector loop (its iterate sequence)
     int x_format = 1;              // 1: tiled X (xt.hip, default); 0: CSR X as the reference stores it (current.hip + cg.hip)
     int current_map = 0;           // 1: every current solve also leaves the atom-resolved current map of its GPUBuffers (dkmc_set_current_map; current.hip step 6 1/2)

@@ -92,6 +92,14 @@ void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
 void dkmc_set_x_nmul_lane_bytes(int bytes) { eng().x_nmul_lane_bytes = bytes == 8 ? 8 : 16; }
 int dkmc_get_x_nmul_lane_bytes(void) { return eng().x_nmul_lane_bytes; }
+void dkmc_set_x_nmul_window(int mode) { eng().x_nmul_window = (mode == 0 || mode == 1) ? mode : 2; }
+int dkmc_get_x_nmul_window(void) { return eng().x_nmul_window; }
+void dkmc_debug_set_x_nmul_window(int cap_bytes, int block_rows)
+{
+    Engine &e = eng();
+    e.x_nmul_window_cap = cap_bytes < 0 ? 76 * 1024 : (cap_bytes > 76 * 1024 ? 76 * 1024 : cap_bytes);
+    e.x_nmul_window_block = (block_rows >= 16 && block_rows <= 1024 && block_rows % 16 == 0) ? block_rows : 320;
+}
 void dkmc_set_x_slab(int on) { eng().x_slab = on ? 1 : 0; }
 int dkmc_get_x_slab(void) { return eng().x_slab; }
 void dkmc_set_x_slab_poly(int on) { eng().x_slab_poly = on ? 1 : 0; }

@@ -7,6 +7,7 @@
 // sparse part, and 2 d sparse panel products per sweep buy 2-3x fewer passes over the tiles (tools/precond_block_proto.py).  The loop's algebra
 // is untouched: it sees another SPD operator.  A start vector y0 enters as the right-hand side: A d = b - A y0, d = L dh, dh from zero.
 #pragma once
+#include "nwin_plan.h"
 // ---- the row gather: 16 lanes per row (one per vector), batches of 16 entries ----------------------------------------------------------------
 // Lane v of a row's group holds entry v of a batch (column c, weight w); every entry is handed round the group and the 16 panel reads of the batch
 // are issued together; entry u goes to accumulator u % 4 in increasing u.  k_xtb_neigh (atom rows), k_xtb_nmul and k_xtb_nmulp are built from these
@@ -227,6 +228,94 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_nmulp16(int m, const long long *_
         if (QSF) { const int sr = nsrank[R.row]; if (sr >= 0) { const double sq = sc[R.row]; QS[xtb_qs_pos(sr, 2 * v8)] = sq * o0; QS[xtb_qs_pos(sr, 2 * v8 + 1)] = sq * o1; } }
     }
 }
+// k_xtb_nmulp16 with the panel operands served from LDS (dkmc_set_x_nmul_window; the plan: nwin_plan.h).  What bounds k_xtb_nmulp16 is the address rate of
+// the vector-memory path: every padded slot sends a 128-byte panel row through it, four times the launch's compulsory bytes.  Here a workgroup owns a
+// block of B consecutive rows, copies the block's window -- the block and a halo on either side, where structure order keeps an atom's neighbours -- from
+// `in` into LDS once, with coalesced 16-byte loads, and then runs k_xtb_nmulp16's loop over its slices: same slots, same order, same accumulators, same
+// result formation, the same bits.  Only the operand's source differs: ds_read_b128 for a slot whose column lies in the window, the global gather for a
+// flagged one (nwin_code < 0: far columns, the cross-cell neighbours of a lateral tiling).  The code is formed from the packed column in registers;
+// the packed N is read as it is.
+// 16 waves, 64 rows per pass over the block.  Two workgroups share a CU (LDS), so a SIMD holds 8 waves and a wave 64 registers: what hides the latency of the
+// slot loads and of the flagged gathers is the number of waves -- with 8 and 12 waves per workgroup (80 registers) the kernel lost to, then tied with, k_xtb_nmulp16
+#define XN_WIN_NT 1024
+// the operand of pair J: the code goes round as the column does (xn_bc2 -- here, in front of the branch: a DPP move reads nothing from a lane that is
+// switched off, so it must not stand inside it); every lane reads LDS (a flagged one row 0 of the window), the flagged ones then gather
+// The window is read through a pointer of the LDS address space: through a generic one the compiler folds the two loads into ONE flat load of a
+// selected address, and a flat load goes down the vector-memory path again.
+typedef const __attribute__((address_space(3))) char *xn_lds_t;
+typedef double xn_d2 __attribute__((ext_vector_type(2)));
+template <int J> __device__ __forceinline__ double2 xn_operand2(const double *panel, xn_lds_t win, int v8, int code)
+{
+    const int cu = xn_bc2<J>(code);
+    const xn_d2 l = *reinterpret_cast<const __attribute__((address_space(3))) xn_d2 *>(win + ((unsigned)max(cu, 0) * (unsigned)NWIN_ROW_BYTES + (unsigned)(v8 * 16)));
+    double2 x = make_double2(l.x, l.y);
+    if (cu < 0) x = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(panel) + ((unsigned)~cu * (unsigned)(XB_SP * 8) + (unsigned)(v8 * 16)));
+    return x;
+}
+// head of a slice of the block: its offset and width from the block's offsets in LDS (one global load less in front of the slots), and lane v's slot of
+// the first batch of row r
+struct XnHeadW { long long o0; int w; XnSlot n; };
+__device__ __forceinline__ XnHeadW xn_head_w(const long long *boff, const int *pcol, const double *pw, int sl, int r, int v)
+{
+    const long long o0 = boff[sl]; const int w = (int)((boff[sl + 1] - o0) >> 2);
+    return {o0, w, xn_slot({0, w, pcol + o0 + r, pw + o0 + r}, v)};
+}
+template <bool QSF>
+__global__ __launch_bounds__(XN_WIN_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_xtb_nmulw(int m, const long long *__restrict__ off, const int *__restrict__ pcol, const double *__restrict__ pw,
+                                                         const double *__restrict__ sc, const double *__restrict__ in, const double *__restrict__ add,
+                                                         double ca, double cb, double *__restrict__ out, const XCtrl *ctrl, const int *__restrict__ nsrank, double *__restrict__ QS,
+                                                         int B, int cap_rows)
+{
+    extern __shared__ double2 xn_win[];
+    __shared__ long long xn_boff[NWIN_BLOCK_MAX / 4 + 1];
+    if (ctrl->done) return;
+    const int blk = xtb_xcd_block((int)gridDim.x, (int)blockIdx.x);
+    const NwinWindow W = nwin_window(m, B, cap_rows, blk);
+    const int q0 = blk * (B / 4), nq = min(B / 4, (m + 3) / 4 - q0);             // the block's slices (the last block: those that exist)
+    for (int i = threadIdx.x; i <= nq; i += XN_WIN_NT) xn_boff[i] = off[q0 + i];
+    {   // the window: W.n rows of eight 16-byte pieces
+        const double2 *src = reinterpret_cast<const double2 *>(in + (size_t)W.lo * XB_SP);
+        const int n16 = W.n * 8;
+#pragma unroll 4
+        for (int i = threadIdx.x; i < n16; i += XN_WIN_NT) xn_win[i] = src[i];
+    }
+    __syncthreads();
+    const xn_lds_t win = (xn_lds_t)xn_win;
+    const int v = threadIdx.x & 15, r = (threadIdx.x >> 4) & 3, v8 = v & 7;
+    // a wave takes every (XN_WIN_NT / 64)-th slice of the block; the offsets come from LDS
+    for (int sl = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); sl < nq; sl += XN_WIN_NT / 64) {
+        const XnHeadW C = xn_head_w(xn_boff, pcol, pw, sl, r, v);
+        const int q = q0 + sl;
+        const bool ok = 4 * q + r < m, wr = ok && v < 8;
+        const XnRow R = {4 * q + r, C.w, pcol + C.o0 + r, pw + C.o0 + r};
+        const double scr = ok ? sc[R.row] : 0.0;
+        // (the QS-writing form reads `add` behind the loop: it has no registers to hold it across)
+        double2 av = (!QSF && wr) ? *reinterpret_cast<const double2 *>(add + (size_t)R.row * XB_SP + 2 * v8) : make_double2(0.0, 0.0);
+        XnSums2 s = {0.0, 0.0, 0.0, 0.0}; XnSlot n = C.n;
+        for (int k0 = 0; k0 < R.w; k0 += 16) {
+            const int t = R.w - k0; const XnEntry e = xn_entry(nwin_code(n.c, W), n.w);
+            if (t > 16) n = xn_slot(R, k0 + 16 + v);                           // next batch in flight
+            double2 x[4];                                                      // two halves of the batch: LDS answers soon, and four operands in flight keep the kernel at 64 registers
+            x[0] = xn_operand2<0>(in, win, v8, e.c); x[1] = xn_operand2<1>(in, win, v8, e.c);
+            if (t > 4) { x[2] = xn_operand2<2>(in, win, v8, e.c); x[3] = xn_operand2<3>(in, win, v8, e.c); }
+            s = xn_acc2<0>(e, x[0], x[1], s);
+            if (t > 4) s = xn_acc2<2>(e, x[2], x[3], s);
+            if (t > 8) {
+                x[0] = xn_operand2<4>(in, win, v8, e.c); x[1] = xn_operand2<5>(in, win, v8, e.c);
+                if (t > 12) { x[2] = xn_operand2<6>(in, win, v8, e.c); x[3] = xn_operand2<7>(in, win, v8, e.c); }
+                s = xn_acc2<4>(e, x[0], x[1], s);
+                if (t > 12) s = xn_acc2<6>(e, x[2], x[3], s);
+            }
+        }
+        if (QSF && wr) av = *reinterpret_cast<const double2 *>(add + (size_t)R.row * XB_SP + 2 * v8);
+        const double tA0 = xor_lane<8>(s.A0), tA1 = xor_lane<8>(s.A1), tB0 = xor_lane<8>(s.B0), tB1 = xor_lane<8>(s.B1);
+        if (wr) {
+            const double o0 = xn_result(ca, av.x, cb, scr, {s.A0, tA0, s.B0, tB0}), o1 = xn_result(ca, av.y, cb, scr, {s.A1, tA1, s.B1, tB1});
+            *reinterpret_cast<double2 *>(out + (size_t)R.row * XB_SP + 2 * v8) = make_double2(o0, o1);
+            if (QSF) { const int sr = nsrank[R.row]; if (sr >= 0) { QS[xtb_qs_pos(sr, 2 * v8)] = scr * o0; QS[xtb_qs_pos(sr, 2 * v8 + 1)] = scr * o1; } }      // (scr is sc[row] here)
+        }
+    }
+}
 // QS (the compact, interleaved copy of the S rows the tile kernel reads) of an arbitrary panel
 __global__ void k_xtb_qs_from(int m, const double *__restrict__ V, const double *__restrict__ sc, const int *__restrict__ nsrank, double *__restrict__ QS, const XCtrl *ctrl)
 {
@@ -286,7 +375,13 @@ __global__ __launch_bounds__(256) void k_xtb_pre_rr(int np, const double *__rest
 
 // ---- host side: the packed N of a solve, one Horner step, L = p(N) and its coefficients -----------------------------------------------------
 // the packed N of one solve (k_xtb_npack): slice offsets, columns, weights
-struct XbNPack { const long long *off; const int *col; const double *w; int lane_bytes; };      // lane_bytes: 16 = k_xtb_nmulp16, 8 = k_xtb_nmulp (dkmc_set_x_nmul_lane_bytes)
+// win_B > 0: the products run k_xtb_nmulw on blocks of win_B rows with windows of at most win_rows panel rows (dkmc_set_x_nmul_window; nwin_plan.h)
+struct XbNPack { const long long *off; const int *col; const double *w; int lane_bytes; int win_B, win_rows; };      // lane_bytes: 16 = k_xtb_nmulp16, 8 = k_xtb_nmulp (dkmc_set_x_nmul_lane_bytes)
+// Where the windowed form runs by size (dkmc_set_x_nmul_window(2)): rows from which it paid.  One N product, k_xtb_nmulp16 -> k_xtb_nmulw, median of 8 alternating
+// timings (tools/time_nmul_window.py, profiles/nmul_window_by_size.jsonl): 57 782 rows 11.1 -> 16.7 us, 160 526 rows 23.1 -> 23.3 us (the panel fits the L2s,
+// a launch is short against the window copy), 642 101 rows 119.0 -> 106.3 us.  Nothing was measured in between, so the gate is the degree rule's last
+// breakpoint (xb_poly_rows[1]): the sizes that run degree 16.
+static const int xb_nwin_rows = 450000;
 // N packed over n rows: rows 0 ... n - 1, or the entries of rowlist (a rank of the slab loop).  alloc(slot, bytes) provides the buffers (scratch, or a
 // virtual rank's own); pad: spare slots behind the packed ones
 template <class Alloc>
@@ -308,6 +403,10 @@ static int xtb_npack(const XtbArgs &A, int n, const int *rowlist, Alloc alloc, l
     hipLaunchKernelGGL(k_xtb_npack, dim3((nsl + 3) / 4), dim3(256), 0, st, n, A.rp, A.ci, A.val, A.sc, (const long long *)off, col, w, rowlist);
     KCHK();
     np->off = off; np->col = col; np->w = w; np->lane_bytes = e.x_nmul_lane_bytes;
+    // the window plan of the solve is arithmetic of (n, block, cap): nothing to build (nwin_plan.h); row lists keep k_xtb_nmulp16
+    const bool win = !rowlist && np->lane_bytes == 16 && nwin_use(e.x_nmul_window, n, xb_nwin_rows);
+    np->win_B = win ? nwin_block_rows(e.x_nmul_window_block) : 0;
+    np->win_rows = win ? nwin_cap_rows(std::min(std::max(e.x_nmul_window_cap, 0), NWIN_CAP_BYTES)) : 0;
     return 0;
 }
 // one rank's N for the preconditioner's products: n rows (rowlist: the entries of a rank's list, the slab loop), packed (np) or CSR (np null), the
@@ -319,6 +418,19 @@ static void xtb_nstep(hipStream_t st, const XtbArgs &A, const XbNRank &R, const 
 {
     const dim3 g((R.n + 15) / 16), b(XT_NT);
     if (!R.np) { hipLaunchKernelGGL(k_xtb_nmul<LIST>, g, b, 0, st, R.n, A.rp, A.ci, A.val, A.sc, in, add, ca, cb, out, R.ctrl, R.rowlist); return; }
+    if (!LIST && R.np->win_B > 0) {
+        const int B = R.np->win_B, lds = nwin_lds_bytes(R.n, B, R.np->win_rows);
+        const auto kw = qsf ? k_xtb_nmulw<true> : k_xtb_nmulw<false>;
+        static bool big_lds = false;                                           // more than 64 KiB of dynamic LDS: once per process
+        if (!big_lds) {
+            (void)hipFuncSetAttribute((const void *)k_xtb_nmulw<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NWIN_CAP_BYTES);
+            (void)hipFuncSetAttribute((const void *)k_xtb_nmulw<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NWIN_CAP_BYTES);
+            big_lds = true;
+        }
+        hipLaunchKernelGGL(kw, dim3(nwin_blocks(R.n, B)), dim3(XN_WIN_NT), lds, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl,
+                           qsf ? A.nsrank : (const int *)nullptr, qsf ? R.QS : (double *)nullptr, B, R.np->win_rows);
+        return;
+    }
     const bool b16 = R.np->lane_bytes == 16;
     const auto k = qsf ? (b16 ? k_xtb_nmulp16<true, LIST> : k_xtb_nmulp<true, LIST>) : (b16 ? k_xtb_nmulp16<false, LIST> : k_xtb_nmulp<false, LIST>);
     hipLaunchKernelGGL(k, g, b, 0, st, R.n, R.np->off, R.np->col, R.np->w, A.sc, in, add, ca, cb, out, R.ctrl, qsf ? A.nsrank : (const int *)nullptr,
@@ -523,5 +635,44 @@ extern "C" int dkmc_xtb_check_poly(int degree, int form, const double *in, doubl
     HIPCHK(hipMemcpyAsync(out, dout, pan, hipMemcpyDeviceToHost, st));
     if (int rc = xtb_test_qs_out(st, X.ns, QS, qs)) return rc;
     HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+// Measurement aid (tools/time_nmul_window.py): mean duration of one N product inside L = p(N), `reps` applications of L back to back on the resident X
+// (dkmc_xtb_check_poly's set-up, packed form, the current switches); the input panel is whatever the test buffers hold -- timing does not depend on it
+extern "C" int dkmc_xtb_time_poly(int degree, int reps, double *us)
+{
+    Engine &e = eng(); hipStream_t st = e.stream; const XTState &X = g_xt;
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || X.ns <= 0) return dkmc_fail(13, "xtb_time_poly: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    if (degree < 1 || degree > XB_MAXPOLY || reps < 1 || !us) return dkmc_fail(13, "xtb_time_poly: bad arguments", __FILE__, __LINE__);
+    const int m = X.Nsub;
+    const size_t pan = (size_t)m * XB_SP * 8;
+    double *sc = (double *)e.buf[S_CG_S];
+    double *din = (double *)scratch(S_XTB_TEST_IN, pan), *dout = (double *)scratch(S_XTB_TEST_OUT, pan);
+    double *W1 = (double *)scratch(S_XTB_TEST_W1, pan), *W2 = (double *)scratch(S_XTB_TEST_W2, pan);
+    double *QS = (double *)scratch(S_XTB_TEST_QS, (size_t)X.ns_pad * XB_SP * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_TEST_CTRL, sizeof(XCtrl));
+    if (!din || !dout || !W1 || !W2 || !QS || !ctrl) return e.err_code;
+    if (!sc || !g_xb.rp || !g_xb.ci || !g_xb.val || !g_xb.nsrank) return dkmc_fail(13, "xtb_time_poly: no solver state", __FILE__, __LINE__);
+    HIPCHK(hipMemsetAsync(din, 0, pan, st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(XCtrl), st));
+    XtbArgs A{};
+    A.m = m; A.ns = X.ns; A.ns_pad = X.ns_pad; A.rp = g_xb.rp; A.ci = g_xb.ci; A.val = g_xb.val; A.sc = sc; A.nsrank = g_xb.nsrank;
+    XbNPack npk{};
+    if (int rc = xtb_npack(A, m, nullptr, xtb_test_alloc, 0, &npk)) return rc;
+    const XbNRank nk{m, nullptr, &npk, QS, ctrl};
+    double pc[XB_MAXPOLY + 1] = {1.0};
+    xtb_poly_coeffs(degree, pc);
+    hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    for (int r = -1; r < reps; ++r) {
+        if (r == 0) HIPCHK(hipEventRecord(e0, st));
+        if (int rc = xtb_applyL(st, A, degree, pc, din, dout, W1, W2, true, [](int, double *) { return 0; },
+                                [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; })) return rc;
+    }
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    KCHK();
+    *us = (double)ms * 1e3 / ((double)reps * degree);
     return e.err_code;
 }

@@ -92,6 +92,9 @@ SYMBOLS = {
     "dkmc_get_x_nmul_form": (_I, []),
     "dkmc_set_x_nmul_lane_bytes": (None, [_I]),
     "dkmc_get_x_nmul_lane_bytes": (_I, []),
+    "dkmc_set_x_nmul_window": (None, [_I]),
+    "dkmc_get_x_nmul_window": (_I, []),
+    "dkmc_debug_set_x_nmul_window": (None, [_I, _I]),
     "dkmc_set_x_apply_form": (None, [_I]),
     "dkmc_get_x_apply_form": (_I, []),
     "dkmc_set_x_slab": (None, [_I]),
@@ -169,6 +172,7 @@ SYMBOLS = {
     "dkmc_xtb_check_product": (_I, [_I, c_dbl_p, c_dbl_p]),
     "dkmc_xtb_time_apply": (_I, [_I, _I, _I, c_dbl_p]),
     "dkmc_xtb_time_apply_stored": (_I, [_I, _I, _I, c_dbl_p]),
+    "dkmc_xtb_time_poly": (_I, [_I, _I, c_dbl_p]),
     "dkmc_xtb_tile_product": (_I, [_I, _I, vp]),
     "dkmc_xt_get_tiles": (_I, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp]),
     "dkmc_xtb_poly_coeffs": (_I, [_I, c_dbl_p]),

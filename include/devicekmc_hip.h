@@ -228,6 +228,14 @@ double dkmc_get_x_tile_drop_used(void);
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */
 void dkmc_set_x_nmul_lane_bytes(int bytes);
 int dkmc_get_x_nmul_lane_bytes(void);
+/* Where the packed 16-byte N products (k_xtb_nmulp16) take their panel operands from.  The windowed form (k_xtb_nmulw; csrc/nwin_plan.h) cuts the rows
+ * into blocks of 320, copies a block's window -- the block and a halo on either side, at most 76 KiB, so that two workgroups share a CU -- from the
+ * input panel into LDS once and serves every slot whose column lies inside it from there; the other slots gather from memory as before.  Every
+ * element is formed by the same sequence of fp64 operations on the same operands: the same bits.  0 = off, 1 = on wherever the packed 16-byte form
+ * runs on one GPU (the row-list products of the slab-distributed loop keep k_xtb_nmulp16), 2 (default) = by size: systems of at least the measured
+ * number of rows (csrc/xtb_precond.h: xb_nwin_rows).  Any other value selects 2.  Read when a solve packs N. */
+void dkmc_set_x_nmul_window(int mode);
+int dkmc_get_x_nmul_window(void);
 void dkmc_set_x_slab(int on);
 int dkmc_get_x_slab(void);
 /* Opt-in: 1 runs the slab-distributed block-CG (dkmc_set_x_slab(1), more than one rank) on L A L with the degree and the coefficients of the one-GPU

@@ -43,6 +43,13 @@ void dkmc_set_x_poly_auto_rows(int n0, int n1);
 int dkmc_xtb_test_nstep(int m, const long long *rp, const int *ci, const double *val, const double *sc, const double *in, const double *add,
                         double ca, double cb, int form, const int *rowlist, int nlist, const int *nsrank, int ns, double *out, double *qs);
 int dkmc_xtb_check_poly(int degree, int form, const double *in, double *out, double *qs);
+/* Test aid of dkmc_set_x_nmul_window: the LDS bytes a window may take (0 ... 77824; 0: every slot gathers from memory, a small value: both operand
+ * paths inside one row) and the rows of a block (a multiple of 16 in 16 ... 1024).  Out-of-range values restore 77824 and 320.  Same bits at any setting.
+ * dkmc_xtb_check_poly and dkmc_xtb_test_nstep (form 1, no row list) follow dkmc_set_x_nmul_window and this aid as a solve does. */
+void dkmc_debug_set_x_nmul_window(int cap_bytes, int block_rows);
+/* Measurement aid: mean duration [us] of ONE N product inside L = p(N) of the given degree (1 ... 16), `reps` applications of L back to back on the X
+ * left resident by the last single-GPU solve, packed form, under the current dkmc_set_x_nmul_lane_bytes / dkmc_set_x_nmul_window. */
+int dkmc_xtb_time_poly(int degree, int reps, double *us);
 /* Test aids of the last four launches of a preconditioned block-CG sweep (csrc/xtb.hip): the PRODUCTION kernels, with production's launch shapes, on data
  * the caller supplies.  They keep buffers and an XCtrl of their own: the resident X, the solver's XCtrl, the warm start and the launch batch of the next
  * solve are left alone.  Every argument is checked first; a bad one returns non-zero and launches nothing.  Panels are host arrays of [m][16] doubles.
