@@ -1,0 +1,351 @@
+// clusters.hip -- filament analysis: connected components of the "member" sites over a padded neighbour index, their summaries, contact flags
+// and the bridging verdict (dkmc_find_clusters; definitions: include/devicekmc_hip.h).  No counterpart in the reference.  A pure function of its
+// arguments: nothing of GPUBuffers, no engine state a later phase reads and no other kernel is touched.
+//
+// Labelling: min-hooking + compression in rounds, the kernel boundary is the only synchronisation point.
+//   label[] (the caller's array) holds, between rounds, the ROOT of every member's tree (-1: not a member); it is read-only inside a hook launch.
+//   parent[] holds the forest.  A hook launch does atomicMin(parent[max(ru, rv)], min(ru, rv)) for every index entry between two members whose
+//   roots differ; only root entries are targets, and the result of a set of atomicMin on one word does not depend on their order, so the forest
+//   after the launch is a function of label[] alone.  The compress launch walks parent[] from every member to its root (parents strictly
+//   decrease: the walk is bounded; a walker that sees an older value of a word sees an older ANCESTOR, never a wrong one, so the path halving
+//   it does on the way may race freely) and writes the root -- the same value whatever the walkers did to each other -- into label[] and
+//   parent[].  A round whose atomicMins lowered nothing ends the loop: "rounds" is the number of rounds run, that last one included, and is the
+//   number the synchronous host model (tests/cluster_ref.py) needs: the same on every call.
+// Work shape: the hook kernel skips non-members in place (no member list: one 4-byte read per site decides, and the summaries need the per-site
+//   pass anyway); a member row is read by LPR lanes, 16 up to 128 entries per row and the whole wave above.
+#include "common.h"
+
+#define CL_NT 256
+#define CL_BATCH 8                   // rounds enqueued per read-back; a round after the one that changed nothing returns at once
+#define CL_CAP_DEFAULT 64
+#define CL_CAP_MAX 4096
+
+namespace {
+
+struct ClInfoDev {
+    int n_members, n_components, bridged, bridge_root, largest_free_size, pad[3];
+    double tip_left_x, tip_right_x, gap_x;
+};
+struct ClusterState {
+    int valid = 0, N = 0, rounds = 0;
+    ClInfoDev info{};
+    double ms_label = 0.0, ms_sum = 0.0;
+    hipEvent_t ev[3]; bool ev_ready = false;
+} g_cl;
+int g_round_cap = CL_CAP_DEFAULT;
+
+// order-preserving 64-bit key of a double (unsigned compare): negative values flip every bit, the others the sign bit.  -0.0 orders below +0.0.
+__device__ __forceinline__ unsigned long long dbl_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_dbl(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)b);
+}
+__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// 1. membership: member flag as the initial root / parent (the site itself, -1 for a non-member), and the identities of the per-root summaries
+__global__ __launch_bounds__(CL_NT) void k_cl_members(int N, const int *el, const int *charge, MetalSet ms, int members,
+                                                      int *label, int *parent, int *csize, int *cvac, int *cflags,
+                                                      unsigned long long *kmin, unsigned long long *kmax)
+{
+    const int i = blockIdx.x * CL_NT + threadIdx.x;
+    if (i >= N) return;
+    const int e = el[i];
+    bool m = (members & 1) && is_metal(e, ms);
+    if ((members & 2) && e == VACANCY) m = m || !(members & 4) || charge[i] == 0;
+    label[i] = parent[i] = m ? i : -1;
+    csize[i] = 0; cvac[i] = 0; cflags[i] = 0;
+    kmin[i] = ~0ull; kmax[i] = 0ull;
+}
+
+// 2a. hook: LPR lanes per member row
+template <int LPR>
+__global__ __launch_bounds__(CL_NT) void k_cl_hook(int N, int nn, const int *__restrict__ idx, const int *__restrict__ label, int *parent,
+                                                   int *ctrl, int round)
+{
+    if (round > 0 && ctrl[round - 1] == 0) return;            // the round before changed nothing: the labelling is finished
+    const int lane = threadIdx.x % LPR;
+    const long long groups = (long long)gridDim.x * (CL_NT / LPR);
+    int changed = 0;
+    for (long long u = (long long)blockIdx.x * (CL_NT / LPR) + threadIdx.x / LPR; u < N; u += groups) {
+        const int ru = label[u];
+        if (ru < 0) continue;
+        const int *row = idx + (size_t)u * nn;
+        for (int k = lane; k < nn; k += LPR) {
+            const int v = row[k];
+            if (v < 0 || v >= N) continue;                    // padding, anywhere in the row
+            const int rv = label[v];
+            if (rv < 0 || rv == ru) continue;
+            const int hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
+            if (atomicMin(&parent[hi], lo) > lo) changed = 1;
+        }
+    }
+    if (changed) atomicOr(&ctrl[round], 1);
+}
+
+// 2b. compress: every member to its root, with path halving on the way
+__global__ __launch_bounds__(CL_NT) void k_cl_compress(int N, int *label, int *parent, const int *ctrl, int round)
+{
+    if (ctrl[round] == 0) return;                             // nothing was hooked: label[] and parent[] hold the roots already
+    const int i = blockIdx.x * CL_NT + threadIdx.x;
+    if (i >= N || label[i] < 0) return;
+    int c = i;
+    for (;;) {
+        const int p = ld_agent(&parent[c]);
+        if (p >= c || p < 0) break;                           // c is a root (a parent is smaller than its child: the walk ends)
+        const int gp = ld_agent(&parent[p]);
+        if (gp >= p || gp < 0) { c = p; break; }
+        st_agent(&parent[c], gp);
+        c = gp;
+    }
+    label[i] = c;
+    st_agent(&parent[i], c);
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
+    return v;
+}
+
+// 3a. summaries per root: integer atomics only (counts, OR, min / max of the keys), so the order of arrival does not matter.  A wave whose
+// members all carry one root -- the rule inside a contact slab -- combines them first and sends one set of atomics.
+__global__ __launch_bounds__(CL_NT) void k_cl_summaries(int N, const int *label, const int *el, const double *x, int n_left, int n_right,
+                                                        int *csize, int *cvac, int *cflags, unsigned long long *kmin, unsigned long long *kmax,
+                                                        int *isroot)
+{
+    const int i = blockIdx.x * CL_NT + threadIdx.x;
+    const int r = i < N ? label[i] : -1;
+    const bool mem = r >= 0;
+    if (i < N) isroot[i] = (r == i) ? 1 : 0;
+    const bool vac = mem && el[i] == VACANCY;
+    const int f = mem ? ((i < n_left ? 1 : 0) | (i >= N - n_right ? 2 : 0)) : 0;
+    const unsigned long long key = mem ? dbl_key(x[i]) : 0ull;
+    const unsigned long long bm = __ballot(mem);
+    if (bm == 0ull) return;
+    const int first = __ffsll((long long)bm) - 1;
+    const int r0 = __shfl(r, first, WAVE);
+    if (__all(!mem || r == r0)) {
+        const int cnt = __popcll(bm), nv = __popcll(__ballot(vac));
+        const int ff = (__ballot(f & 1) ? 1 : 0) | (__ballot(f & 2) ? 2 : 0);
+        const unsigned long long lo = wave_min_u64(mem ? key : ~0ull), hi = wave_max_u64(mem ? key : 0ull);
+        if ((int)(threadIdx.x & 63) == first) {
+            atomicAdd(&csize[r0], cnt);
+            if (nv) atomicAdd(&cvac[r0], nv);
+            if (ff) atomicOr(&cflags[r0], ff);
+            atomicMin(&kmin[r0], lo); atomicMax(&kmax[r0], hi);
+        }
+    } else if (mem) {
+        atomicAdd(&csize[r], 1);
+        if (vac) atomicAdd(&cvac[r], 1);
+        if (f) atomicOr(&cflags[r], f);
+        atomicMin(&kmin[r], key); atomicMax(&kmax[r], key);
+    }
+}
+
+// 3b. the table: one row per root, ascending (pos = exclusive scan of the root flags)
+__global__ __launch_bounds__(CL_NT) void k_cl_table(int N, const int *isroot, const int *pos, const int *csize, const int *cvac, const int *cflags,
+                                                    const unsigned long long *kmin, const unsigned long long *kmax,
+                                                    int *t_root, int *t_size, int *t_vac, int *t_flags, double *t_xmin, double *t_xmax)
+{
+    const int i = blockIdx.x * CL_NT + threadIdx.x;
+    if (i >= N || !isroot[i]) return;
+    const int p = pos[i];
+    t_root[p] = i; t_size[p] = csize[i]; t_vac[p] = cvac[i]; t_flags[p] = cflags[i];
+    t_xmin[p] = key_dbl(kmin[i]); t_xmax[p] = key_dbl(kmax[i]);
+}
+
+// 3c. the info block, one workgroup: sums, minima and maxima only (no order dependence)
+__global__ __launch_bounds__(CL_NT) void k_cl_info(const int *d_ncomp, const int *t_root, const int *t_size, const int *t_flags,
+                                                   const double *t_xmin, const double *t_xmax, ClInfoDev *out)
+{
+    __shared__ int s_mem[CL_NT], s_broot[CL_NT], s_free[CL_NT];
+    __shared__ double s_tl[CL_NT], s_tr[CL_NT];
+    const int nc = *d_ncomp, t = threadIdx.x;
+    int mem = 0, broot = 0x7fffffff, fre = 0;
+    double tl = -INFINITY, tr = INFINITY;
+    for (int j = t; j < nc; j += CL_NT) {
+        const int f = t_flags[j], s = t_size[j];
+        mem += s;
+        if (f == 3) broot = min(broot, t_root[j]);
+        if (f == 0) fre = max(fre, s);
+        if (f == 1) tl = fmax(tl, t_xmax[j]);
+        if (f == 2) tr = fmin(tr, t_xmin[j]);
+    }
+    s_mem[t] = mem; s_broot[t] = broot; s_free[t] = fre; s_tl[t] = tl; s_tr[t] = tr;
+    __syncthreads();
+    for (int off = CL_NT / 2; off > 0; off >>= 1) {
+        if (t < off) {
+            s_mem[t] += s_mem[t + off]; s_broot[t] = min(s_broot[t], s_broot[t + off]); s_free[t] = max(s_free[t], s_free[t + off]);
+            s_tl[t] = fmax(s_tl[t], s_tl[t + off]); s_tr[t] = fmin(s_tr[t], s_tr[t + off]);
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int bridged = s_broot[0] != 0x7fffffff;
+        out->n_members = s_mem[0]; out->n_components = nc; out->bridged = bridged; out->bridge_root = bridged ? s_broot[0] : -1;
+        out->largest_free_size = s_free[0]; out->pad[0] = out->pad[1] = out->pad[2] = 0;
+        out->tip_left_x = s_tl[0]; out->tip_right_x = s_tr[0];
+        out->gap_x = bridged ? 0.0 : s_tr[0] - s_tl[0];
+    }
+}
+
+struct ClTable { int *root, *size, *vac, *flags; double *xmin, *xmax; };
+ClTable table_of(void *base, size_t N)
+{
+    ClTable t;
+    t.xmin = (double *)base; t.xmax = t.xmin + N;
+    t.root = (int *)(t.xmax + N); t.size = t.root + N; t.vac = t.size + N; t.flags = t.vac + N;
+    return t;
+}
+
+}   // namespace
+
+extern "C" {
+
+void dkmc_debug_set_cluster_round_cap(int cap) { g_round_cap = cap <= 0 ? CL_CAP_DEFAULT : (cap > CL_CAP_MAX ? CL_CAP_MAX : cap); }
+
+int dkmc_debug_get_cluster_times(double *ms2)
+{
+    if (!g_cl.valid) return dkmc_fail(3, "dkmc_debug_get_cluster_times: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    if (ms2) { ms2[0] = g_cl.ms_label; ms2[1] = g_cl.ms_sum; }
+    return 0;
+}
+
+int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_element, const int *d_site_charge, const double *d_site_x,
+                       const int *d_metals, int num_metals, int members, int n_left_sites, int n_right_sites, int *d_label)
+{
+    g_cl.valid = 0;
+    if (N < 0 || nn < 1 || (N > 0 && (!d_index || !d_site_element || !d_site_x || !d_label)) || ((members & 4) && N > 0 && !d_site_charge)
+        || ((members & 1) && num_metals > 0 && !d_metals) || num_metals < 0)
+        return dkmc_fail(3, "dkmc_find_clusters: bad arguments (N >= 0, nn >= 1, device arrays of N sites; site_charge with members bit 2)", __FILE__, __LINE__);
+    if (n_left_sites < 0) n_left_sites = 0;
+    if (n_right_sites < 0) n_right_sites = 0;
+    if (n_left_sites > N) n_left_sites = N;
+    if (n_right_sites > N) n_right_sites = N;
+    hipStream_t st = eng().stream;
+    const int cap = g_round_cap;
+    g_cl.N = N; g_cl.rounds = 0; g_cl.ms_label = g_cl.ms_sum = 0.0;
+    if (N == 0) {
+        g_cl.info = ClInfoDev{}; g_cl.info.bridge_root = -1; g_cl.info.tip_left_x = -INFINITY; g_cl.info.tip_right_x = INFINITY; g_cl.info.gap_x = INFINITY;
+        g_cl.valid = 1;
+        return 0;
+    }
+    const size_t n = (size_t)N;
+    int *parent = (int *)scratch(S_CL_PARENT, n * sizeof(int));
+    char *sums = (char *)scratch(S_CL_SUMS, n * (2 * sizeof(unsigned long long) + 3 * sizeof(int)));
+    int *flagpos = (int *)scratch(S_CL_POS, 2 * n * sizeof(int));
+    void *tab = scratch(S_CL_TABLE, n * (2 * sizeof(double) + 4 * sizeof(int)));
+    int *ctrl = (int *)scratch(S_CL_CTRL, (size_t)(CL_CAP_MAX + 2) * sizeof(int) + sizeof(ClInfoDev));
+    if (!parent || !sums || !flagpos || !tab || !ctrl) return eng().err_code;
+    unsigned long long *kmin = (unsigned long long *)sums, *kmax = kmin + n;
+    int *csize = (int *)(kmax + n), *cvac = csize + n, *cflags = cvac + n;
+    int *isroot = flagpos, *pos = flagpos + n;
+    int *d_ncomp = ctrl + CL_CAP_MAX;
+    ClInfoDev *d_info = (ClInfoDev *)(ctrl + CL_CAP_MAX + 2);
+    const ClTable T = table_of(tab, n);
+    const bool timed = eng().profiling != 0;
+    if (timed && !g_cl.ev_ready) { for (auto &e : g_cl.ev) HIPCHK(hipEventCreate(&e)); g_cl.ev_ready = true; }
+
+    const int site_blocks = (N + CL_NT - 1) / CL_NT;
+    if (timed) HIPCHK(hipEventRecord(g_cl.ev[0], st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, (size_t)(CL_CAP_MAX + 2) * sizeof(int), st));
+    hipLaunchKernelGGL(k_cl_members, dim3(site_blocks), dim3(CL_NT), 0, st, N, d_site_element, d_site_charge, load_metals(d_metals, (members & 1) ? num_metals : 0),
+                       members, d_label, parent, csize, cvac, cflags, kmin, kmax);
+    KCHK();
+    // rounds: CL_BATCH of them per read-back of their change words
+    const int lpr = nn <= 128 ? 16 : 64;
+    const int hook_blocks = grid_blocks((long long)N * lpr, CL_NT, 8192);
+    int rounds = 0, launched = 0;
+    static int h_changed[CL_CAP_MAX];
+    while (!rounds && launched < cap) {
+        const int b = cap - launched < CL_BATCH ? cap - launched : CL_BATCH;
+        for (int r = launched; r < launched + b; ++r) {
+            if (lpr == 16) hipLaunchKernelGGL(k_cl_hook<16>, dim3(hook_blocks), dim3(CL_NT), 0, st, N, nn, d_index, (const int *)d_label, parent, ctrl, r);
+            else hipLaunchKernelGGL(k_cl_hook<64>, dim3(hook_blocks), dim3(CL_NT), 0, st, N, nn, d_index, (const int *)d_label, parent, ctrl, r);
+            hipLaunchKernelGGL(k_cl_compress, dim3(site_blocks), dim3(CL_NT), 0, st, N, d_label, parent, (const int *)ctrl, r);
+        }
+        KCHK();
+        HIPCHK(hipMemcpyAsync(h_changed + launched, ctrl + launched, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int r = launched; r < launched + b && !rounds; ++r) if (!h_changed[r]) rounds = r + 1;
+        launched += b;
+    }
+    if (!rounds) {
+        // not finished: no partial labels go out as valid
+        HIPCHK(hipMemsetAsync(d_label, 0xff, n * sizeof(int), st));
+        HIPCHK(hipStreamSynchronize(st));
+        char msg[200];
+        snprintf(msg, sizeof(msg), "dkmc_find_clusters: labelling not finished after %d rounds (the cap: dkmc_debug_set_cluster_round_cap); labels set to -1", cap);
+        return dkmc_fail(4, msg, __FILE__, __LINE__);
+    }
+    if (timed) HIPCHK(hipEventRecord(g_cl.ev[1], st));
+    // summaries, table, info
+    hipLaunchKernelGGL(k_cl_summaries, dim3(site_blocks), dim3(CL_NT), 0, st, N, (const int *)d_label, d_site_element, d_site_x, n_left_sites, n_right_sites,
+                       csize, cvac, cflags, kmin, kmax, isroot);
+    KCHK();
+    if (int rc = dkmc_exclusive_scan_i32(isroot, pos, N, d_ncomp)) return rc;
+    hipLaunchKernelGGL(k_cl_table, dim3(site_blocks), dim3(CL_NT), 0, st, N, (const int *)isroot, (const int *)pos, (const int *)csize, (const int *)cvac,
+                       (const int *)cflags, (const unsigned long long *)kmin, (const unsigned long long *)kmax, T.root, T.size, T.vac, T.flags, T.xmin, T.xmax);
+    hipLaunchKernelGGL(k_cl_info, dim3(1), dim3(CL_NT), 0, st, (const int *)d_ncomp, (const int *)T.root, (const int *)T.size, (const int *)T.flags,
+                       (const double *)T.xmin, (const double *)T.xmax, d_info);
+    KCHK();
+    if (timed) HIPCHK(hipEventRecord(g_cl.ev[2], st));
+    HIPCHK(hipMemcpyAsync(&g_cl.info, d_info, sizeof(ClInfoDev), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (timed) {
+        float a = 0.f, b = 0.f;
+        HIPCHK(hipEventElapsedTime(&a, g_cl.ev[0], g_cl.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_cl.ev[1], g_cl.ev[2]));
+        g_cl.ms_label = a; g_cl.ms_sum = b;
+    }
+    g_cl.rounds = rounds;
+    g_cl.valid = 1;
+    return 0;
+}
+
+int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vacancy, int *h_flags, double *h_xmin, double *h_xmax, int *rows_out)
+{
+    if (!g_cl.valid) return dkmc_fail(3, "dkmc_copy_cluster_table: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    int rows = g_cl.info.n_components;
+    if (rows > capacity) rows = capacity;
+    if (rows < 0) rows = 0;
+    if (rows_out) *rows_out = rows;
+    if (rows == 0) return 0;
+    hipStream_t st = eng().stream;
+    const ClTable T = table_of(eng().buf[S_CL_TABLE], (size_t)g_cl.N);
+    const size_t r = (size_t)rows;
+    if (h_root) HIPCHK(hipMemcpyAsync(h_root, T.root, r * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (h_size) HIPCHK(hipMemcpyAsync(h_size, T.size, r * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (h_n_vacancy) HIPCHK(hipMemcpyAsync(h_n_vacancy, T.vac, r * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (h_flags) HIPCHK(hipMemcpyAsync(h_flags, T.flags, r * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (h_xmin) HIPCHK(hipMemcpyAsync(h_xmin, T.xmin, r * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (h_xmax) HIPCHK(hipMemcpyAsync(h_xmax, T.xmax, r * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int dkmc_get_cluster_info(int *info8, double *x3)
+{
+    if (!g_cl.valid) return dkmc_fail(3, "dkmc_get_cluster_info: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    const ClInfoDev &I = g_cl.info;
+    if (info8) {
+        info8[0] = I.n_members; info8[1] = I.n_components; info8[2] = I.bridged; info8[3] = I.bridge_root; info8[4] = I.largest_free_size;
+        info8[5] = g_cl.rounds; info8[6] = 0; info8[7] = 0;
+    }
+    if (x3) { x3[0] = I.tip_left_x; x3[1] = I.tip_right_x; x3[2] = I.gap_x; }
+    return 0;
+}
+
+}   // extern "C"

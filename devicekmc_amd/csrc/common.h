@@ -241,6 +241,8 @@ enum {
     S_P_CMAP,       // current map (dkmc_set_current_map): tile sums of S and the row kernel's partials
     // test aids of the sweep's Gram, s x s and panel-step kernels (xtb.hip: dkmc_xtb_test_gram / _small / _step): their own buffers, as above
     S_XTB_ALG_PANELS, S_XTB_ALG_INTS, S_XTB_ALG_GRAM, S_XTB_ALG_QS, S_XTB_ALG_CTRL,
+    // filament analysis (clusters.hip: dkmc_find_clusters): the forest, the per-root summaries, root flags + positions, the component table, change words + info
+    S_CL_PARENT, S_CL_SUMS, S_CL_POS, S_CL_TABLE, S_CL_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

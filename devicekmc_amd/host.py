@@ -137,6 +137,33 @@ def _use_stream(dev):
     check(_lib.load().dkmc_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
 
+# member sets of the filament analysis (include/devicekmc_hip.h: dkmc_find_clusters); NEUTRAL_ONLY restricts the vacancies to site_charge == 0
+METAL, VACANCY, NEUTRAL_ONLY = 1, 2, 4
+CLUSTER_INFO = ("n_members", "n_components", "bridged", "bridge_root", "largest_free_size", "rounds")
+CLUSTER_TABLE = ("root", "size", "n_vacancy", "flags", "xmin", "xmax")
+
+
+def find_clusters(index, nn, element, charge, x, metal_types, members, n_left, n_right, capacity=None):
+    """dkmc_find_clusters on device tensors (index: N * nn int32; element, charge: N int32; x: N float64; metal_types: int32; charge may be
+    None without NEUTRAL_ONLY).  Returns (label: int32 device tensor of N, table: dict of host arrays with min(capacity, n_components) rows --
+    capacity None: all of them --, info: dict of CLUSTER_INFO + tip_left_x, tip_right_x, gap_x).  Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(element.numel())
+    _use_stream(element.device)
+    label = torch.empty(N, dtype=torch.int32, device=element.device)
+    check(L.dkmc_find_clusters(N, int(nn), _ptr(index), _ptr(element), _ptr(charge) if charge is not None else None, _ptr(x), _ptr(metal_types),
+                               int(metal_types.numel()), int(members), int(n_left), int(n_right), _ptr(label)))
+    i8, x3 = (C.c_int * 8)(), (C.c_double * 3)()
+    check(L.dkmc_get_cluster_info(i8, x3))
+    info = dict(zip(CLUSTER_INFO, (int(v) for v in i8)))
+    info.update(tip_left_x=x3[0], tip_right_x=x3[1], gap_x=x3[2])
+    cap = info["n_components"] if capacity is None else int(capacity)
+    cols = [np.empty(max(cap, 0), dtype=np.int32) for _ in range(4)] + [np.empty(max(cap, 0)) for _ in range(2)]
+    rows = C.c_int(0)
+    check(L.dkmc_copy_cluster_table(cap, *[_np_ptr(c) for c in cols], C.byref(rows)))
+    return label, {k: c[:rows.value] for k, c in zip(CLUSTER_TABLE, cols)}, info
+
+
 class Device:
     """Device.h:61-231 (USE_CUDA build): host copy of the site fields + the thin callers of the GPU path."""
 
@@ -245,6 +272,23 @@ class Device:
         (the tunnelling block is symmetric, so the pairs inside that set cancel).  Divide by imacro for the tunnelling share."""
         x, out = np.asarray(self.site_x), np.asarray(self.site_tunnel_outflow)
         return np.array([out[x <= c].sum() for c in np.atleast_1d(np.asarray(cuts, dtype=np.float64))])
+
+    def find_clusters(self, gpubuf: GPUBuffers, members=METAL | VACANCY, link_index=None, n_left=None, n_right=None, capacity=None):
+        """Filament analysis on the device (dkmc_find_clusters; definitions: include/devicekmc_hip.h): the connected components of the member
+        sites of gpubuf's CURRENT site_element (and site_charge, with NEUTRAL_ONLY) over gpubuf.neigh_idx, or over link_index = (int32 device
+        tensor of N * nn, nn) -- e.g. build_neighbor_index_gpu at a larger radius, moved to the device -- for a gap-tolerant filament.  n_left /
+        n_right: sites of the contact seeds, by default get_num_in_contacts(num_atoms_first_layer) on either side.  Changes nothing in gpubuf.
+        Returns (labels: host int32 array, table, info) and keeps them as site_cluster, cluster_table, cluster_info."""
+        p = self.p
+        if n_left is None:
+            n_left = self.get_num_in_contacts(p.num_atoms_first_layer, "left")
+        if n_right is None:
+            n_right = self.get_num_in_contacts(p.num_atoms_first_layer, "right")
+        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        label, table, info = find_clusters(index, nn, gpubuf.site_element, gpubuf.site_charge, gpubuf.site_x, gpubuf.metal_types, members,
+                                           n_left, n_right, capacity)
+        self.site_cluster, self.cluster_table, self.cluster_info = label.cpu().numpy(), table, info
+        return self.site_cluster, table, info
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

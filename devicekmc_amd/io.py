@@ -24,14 +24,17 @@ def _g6(v: float) -> str:
     return "%g" % v
 
 
-def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None):
-    """current: optional per-site array (e.g. Device.site_current) appended as one more column; read_xyz ignores it.  None: the reference's file."""
+def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None, cluster=None):
+    """current: optional per-site array (e.g. Device.site_current) appended as one more column; read_xyz ignores it.  None: the reference's file.
+    cluster: optional per-site integer array (Device.site_cluster: the label of the site's conducting cluster, -1 for none) appended as the last
+    column, after current when both are given; read_xyz ignores it too.  None: the file as without it, byte for byte."""
     fmt = (lambda v: repr(float(v))) if full_precision else _g6
     with open(path, "w") as f:
         f.write("%d\n\n" % len(element))
         for i in range(len(element)):
-            f.write("%s   %s   %s   %s   %s   %s%s\n" % (ELEMENT_NAMES[int(element[i])], fmt(x[i]), fmt(y[i]), fmt(z[i]),
-                                                      fmt(potential[i]), fmt(power[i]), "" if current is None else "   " + fmt(current[i])))
+            f.write("%s   %s   %s   %s   %s   %s%s%s\n" % (ELEMENT_NAMES[int(element[i])], fmt(x[i]), fmt(y[i]), fmt(z[i]),
+                                                        fmt(potential[i]), fmt(power[i]), "" if current is None else "   " + fmt(current[i]),
+                                                        "" if cluster is None else "   %d" % int(cluster[i])))
 
 
 def read_xyz(path) -> Structure:

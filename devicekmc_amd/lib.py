@@ -157,6 +157,11 @@ SYMBOLS = {
     "dkmc_get_current_map": (_I, []),
     "dkmc_copy_current_map_from_gpu": (_I, [C.POINTER(dkmc_gpubuf), vp, vp, vp]),
     "dkmc_get_current_map_info": (_I, [C.POINTER(dkmc_gpubuf), c_dbl_p]),
+    "dkmc_find_clusters": (_I, [_I, _I, vp, vp, vp, vp, vp, _I, _I, _I, _I, vp]),
+    "dkmc_copy_cluster_table": (_I, [_I, vp, vp, vp, vp, vp, vp, c_int_p]),
+    "dkmc_get_cluster_info": (_I, [c_int_p, c_dbl_p]),
+    "dkmc_debug_set_cluster_round_cap": (None, [_I]),
+    "dkmc_debug_get_cluster_times": (_I, [c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

@@ -437,6 +437,38 @@ int dkmc_get_current_map(void);
 int dkmc_copy_current_map_from_gpu(const dkmc_gpubuf *buf, double *h_thr_all, double *h_thr_tun, double *h_net_tun);
 int dkmc_get_current_map_info(const dkmc_gpubuf *buf, double *info8);
 
+/* ---- filament analysis: conducting clusters and contact bridging (csrc/clusters.hip; no counterpart in the reference) ----
+ * Connected components of the MEMBER sites over a padded neighbour index, with per-component summaries, contact flags and a bridging verdict, all
+ * computed on the device.  A pure function of its arguments: no field of GPUBuffers, no engine state a later phase reads and no other kernel changes.
+ *   members     bit mask.  bit 0: metal sites (site_element in d_metals[num_metals]); bit 1: VACANCY sites; bit 2: of the vacancies only the
+ *               neutral ones, site_charge == 0 (the set the current solve links with its high conductance).  d_site_charge is read only with bit 2.
+ *   link        members u, v are linked when v occurs in row u of the index OR u occurs in row v: symmetric even where the index is not.
+ *   index       d_index[N][nn] int32, any nn >= 1, an ARGUMENT: gpubuf.neigh_idx gives the nearest-neighbour filament, an index built by
+ *               dkmc_build_neighbor_index at a larger radius a gap-tolerant one.  Entries < 0 (and >= N) are padding, anywhere in a row.
+ *   label       d_label[site] (device, N ints, written by the call) = the smallest site index of the site's component, -1 for a non-member:
+ *               canonical, independent of the algorithm, its races and the launch geometry.
+ *   table       one row per component in ascending order of label: root (= label), size, n_vacancy, flags (bit 0: touches the left contact, bit 1:
+ *               the right), xmin, xmax = min / max of d_site_x over the component -- the input doubles themselves (compared through an
+ *               order-preserving integer key: -0.0 orders below +0.0; NaN coordinates are not supported).
+ *   seeds       left: the members with index < n_left_sites; right: the members with index >= N - n_right_sites (both clamped to 0 ... N).
+ *   info8       [0] n_members, [1] n_components, [2] bridged (1: some component has both flag bits), [3] bridge_root (the smallest such root, or
+ *               -1), [4] largest_free_size (largest component touching neither contact), [5] rounds (hook + compress rounds the labelling ran,
+ *               the one that changed nothing included: what the synchronous model needs, the same on every call), [6], [7] 0.
+ *   x3          [0] tip_left_x = max of xmax over the components that touch left and not right (-inf: none), [1] tip_right_x = min of xmin over
+ *               those that touch right and not left (+inf: none), [2] gap_x = tip_right_x - tip_left_x, exactly 0.0 when bridged.  (The Euclidean
+ *               gap between the two clusters is not computed.)
+ * dkmc_find_clusters labels, summarises and keeps table and info of the LAST call in the library; it returns after they are complete.  The
+ * labelling runs min-hooking + pointer jumping in rounds from the host, at most 64 rounds (7.5 nm device: 5; a randomly numbered chain of 200 000
+ * sites: 12); at the cap the call fails (dkmc_last_error), d_label is set to -1 everywhere and the two getters fail until a call succeeds.
+ * dkmc_copy_cluster_table copies the first min(capacity, n_components) rows to host arrays (any may be NULL) and reports them in *rows_out; the
+ * true count is info8[1].  Every output is an integer or one of the input doubles: the same inputs give the same bytes on every call. */
+enum { DKMC_MEMBERS_METAL = 1, DKMC_MEMBERS_VACANCY = 2, DKMC_MEMBERS_NEUTRAL_ONLY = 4 };
+int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_element, const int *d_site_charge, const double *d_site_x,
+                       const int *d_metals, int num_metals, int members, int n_left_sites, int n_right_sites, int *d_label);
+int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vacancy, int *h_flags, double *h_xmin, double *h_xmax,
+                            int *rows_out);
+int dkmc_get_cluster_info(int *info8, double *x3);
+
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
 int dkmc_update_temperatureglobal_gpu(const double *d_site_power, double *d_T_bg, int N, double a_coeff,

@@ -191,6 +191,12 @@ int dkmc_get_pair_sum_info(long long *info /* [6] */, double *ms /* [2] */);
  * batch, then the largest count seen, rounded up to a multiple of 8, plus 8), so that a budget below what a solve needs forces the resume path.
  * The temperatures are the same bits either way. */
 void dkmc_debug_heat_chain(int on, int budget);
+/* Test aid of dkmc_find_clusters (csrc/clusters.hip): the cap on the labelling's rounds, 1 ... 4096; cap <= 0 restores the default 64.  A labelling
+ * that needs more rounds than the cap fails with a message instead of delivering labels.
+ * Measurement aid: with dkmc_set_profiling(1), ms2 = HIP-event time of the last call's membership pass + labelling rounds (the host's read-backs
+ * between them included) and of its summaries (per-root atomics, scan, table, info); both 0 with profiling off. */
+void dkmc_debug_set_cluster_round_cap(int cap);
+int dkmc_debug_get_cluster_times(double *ms2);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Forming run gated by the filament analysis: current-off supersteps (charge, potential, KMC events) with Device.find_clusters after every
+step, until a conducting cluster bridges the two contacts or the step cap is reached; then ONE superstep with the current solve.  The X solve,
+which dominates a superstep, is paid only from the moment the filament has closed.
+Prints one JSON line: steps run current-off, the step at which the verdict turned to bridged (null: never), gap_x after every step (null where
+one of the tips does not exist), members of the analysis, and I_macro of the closing step with the current solve.
+usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0]"""
+import argparse
+import json
+import math
+import os
+import sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("workload", nargs="?", default="2.5nm")
+    ap.add_argument("--max-steps", type=int, default=50)
+    ap.add_argument("--vd", type=float, default=5.0)
+    ap.add_argument("--members", type=int, default=3, help="bit mask: 1 metal, 2 vacancies, 4 neutral vacancies only")
+    ap.add_argument("--wide-radius", type=float, default=0.0, help="> 0: link members within this distance (gap-tolerant filament) instead of nearest neighbours")
+    a = ap.parse_args()
+    import torch
+    from bench import Sim
+    from devicekmc_amd import host
+    sim = Sim(a.workload, "cuda:0", solve_current=False, Vd=a.vd)
+    dev, gb, p = sim.dev, sim.gb, sim.p
+    link = None
+    if a.wide_radius > 0:
+        wide, nn = host.build_neighbor_index_gpu(dev.site_x, dev.site_y, dev.site_z, p.lattice, p.pbc, a.wide_radius)
+        link = (torch.as_tensor(wide.reshape(-1)).to("cuda:0"), nn)
+    gaps, bridged_at, info = [], None, None
+    for k in range(a.max_steps):
+        sim.step(False)
+        _, _, info = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
+        gaps.append(info["gap_x"] if math.isfinite(info["gap_x"]) else None)
+        if info["bridged"]:
+            bridged_at = k + 1
+            break
+    p.solve_current = True
+    sim.step(False)
+    print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
+                          bridged_at_step=bridged_at, bridge_root=None if info is None else info["bridge_root"], gap_x=gaps,
+                          n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro)), flush=True)
+    sim.close()
+
+
+if __name__ == "__main__":
+    main()
