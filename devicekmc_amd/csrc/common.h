@@ -184,6 +184,10 @@ struct Engine {
     int x_format = 1;              // 1: tiled X (xt.hip, default); 0: CSR X as the reference stores it (current.hip + cg.hip)
     int current_map = 0;           // 1: every current solve also leaves the atom-resolved current map of its GPUBuffers (dkmc_set_current_map; current.hip step 6 1/2)
     int x_iter_hint = 0;           // iteration count of the previous CG solve of X (sizes the first launch batch)
+    int event_temperature = 0;     // rate model of the event table (dkmc_set_event_temperature; events.hip): 0 the reference as compiled (one global T_bg), 1 the reference authors' kinetic term on the local site temperature, 2 Arrhenius on it
+    int event_census = 0;          // 1: every dkmc_execute_kmc_step_gpu that builds a table also takes its rate census (dkmc_set_event_census; ev_census.hip)
+    int event_census_valid = 0;    // ... and the last one taken (dkmc_get_event_census)
+    double event_census_info[16] = {0};
     dkmc_stats stats{};
     char err[512] = {0};
     int err_code = 0;
@@ -243,6 +247,8 @@ enum {
     S_XTB_ALG_PANELS, S_XTB_ALG_INTS, S_XTB_ALG_GRAM, S_XTB_ALG_QS, S_XTB_ALG_CTRL,
     // filament analysis (clusters.hip: dkmc_find_clusters): the forest, the per-root summaries, root flags + positions, the component table, change words + info
     S_CL_PARENT, S_CL_SUMS, S_CL_POS, S_CL_TABLE, S_CL_CTRL,
+    // event rates on the local temperature (events.hip): the bad-temperature word of a build; rate census (ev_census.hip): workgroup partials, info
+    S_EV_NBAD, S_EV_CENSUS_PART, S_EV_CENSUS_INFO,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");
@@ -261,6 +267,9 @@ double *comm_peer_slots(int parity);
 void comm_peer_drop();                                  // after a failed solve: the peers' sequence counters may have drifted (comm.hip)
 int comm_peer_exchange(int parity, size_t count, int *ctrl_done, int *ctrl_aborted, int *ctrl_timeout, int stamp);
 int comm_bcast0_f64(double *buf, size_t count);        // in place; every rank ends with rank 0's bits
+
+// rate census of an event table (ev_census.hip): enqueues the two kernels on the engine's stream; *d_info16 = the device copy of the 16 doubles
+int ev_census_enqueue(int N, int nn, const int *neigh, const int *element, const double *temperature, const double *ev_prob, double **d_info16);
 
 // shared primitives (scan.hip)
 // exclusive prefix sum of n ints (in -> out, out may alias in); total written to d_total (device int) if non-null

@@ -10,6 +10,11 @@
 // node is a fixed-order sum of its children, so selection is run-to-run deterministic; it equals the
 // sequential-prefix definition of the host engine (utils.h:91-99, KMCProcess.cpp:303-311) except for
 // draws that land within rounding distance of a bucket edge.
+//
+// Event rates on the local site temperature (dkmc_set_event_temperature; include/devicekmc_hip.h): slot_rate and k_ev_build are templates on the
+// mode.  0 is the reference as compiled (Ekin = 0, one global T_bg) and never dereferences the temperature; 1 puts the reference's commented-out
+// kinetic term back (Ekin = kB (T_s - T_bg)); 2 is Arrhenius on T_s.  T_s is the temperature of the site those commented-out lines name: j for
+// generation, i for the three other classes.  The temperature enters at build time only: the event loop never recomputes a rate.
 #include "common.h"
 
 struct LayerEnergies { double gen[DKMC_MAX_LAYERS], rec[DKMC_MAX_LAYERS], vdiff[DKMC_MAX_LAYERS], odiff[DKMC_MAX_LAYERS]; };
@@ -20,16 +25,21 @@ __constant__ LayerEnergies c_layerE;
 struct EvOut {                 // device -> host mailbox
     double event_time, psum_last;
     int n_events, exhausted, bad, n_charged;
+    int n_bad_T, pad;          // modes 1, 2: event-class slots of the build with a temperature that is not finite or not > 0 (the loop then ran no event)
 };
 
 // rate of slot (i, j): kmc_events.cu:52-122.  Returns the event type, P through *prob.
+// MODE 1, 2: T_i = temperature[i] (read once per row by the caller), temperature[j] is gathered for generation slots only; a slot whose T_s is
+// not finite or not > 0 keeps its type, gets P = 0 and adds 1 to *n_bad.  With T_s == T_bg both modes form mode 0's P bit for bit: Ekin is +0.0
+// (x - (+0.0) is x - 0), and kB * T_s is the same product.
+template <int MODE>
 __device__ __forceinline__ int slot_rate(int i, int j, int N, const int *__restrict__ layer, double laty, double latz, int pbc,
                                          double T_bg, double freq, double sigma, double kk,
                                          const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
                                          const double *__restrict__ pb, const double *__restrict__ pc,
                                          const int *__restrict__ element, const int *__restrict__ charge,
                                          int ei, int qi, double xi, double yi, double zi, double phii,
-                                         double *prob)
+                                         const double *__restrict__ temperature, double T_i, int *n_bad, double *prob)
 {
     int type = EV_NULL; double P = 0.0;
     if (j >= 0 && j < N) {
@@ -56,8 +66,21 @@ __device__ __forceinline__ int slot_rate(int i, int j, int N, const int *__restr
                 En = (qi - qj) * (dphi - self);
                 E0 = c_layerE.odiff[lj]; type = EV_IDIFF;
             }
-            const double EA = E0 - En - 0;
-            P = exp(-1 * EA / (DKMC_KB * T_bg)) * freq;
+            if constexpr (MODE == 0) {
+                const double EA = E0 - En - 0;
+                P = exp(-1 * EA / (DKMC_KB * T_bg)) * freq;
+            } else {
+                const double T_s = gen ? temperature[j] : T_i;
+                if (!(T_s > 0.0) || isinf(T_s)) { P = 0.0; ++*n_bad; }
+                else if constexpr (MODE == 1) {
+                    const double Ekin = DKMC_KB * (T_s - T_bg);          // kmc_events.cu:65,81,99,118, as the authors left it in the comments
+                    const double EA = E0 - En - Ekin;
+                    P = exp(-1 * EA / (DKMC_KB * T_bg)) * freq;
+                } else {
+                    const double EA = E0 - En - 0;
+                    P = exp(-1 * EA / (DKMC_KB * T_s)) * freq;
+                }
+            }
         }
     }
     *prob = P;
@@ -78,7 +101,8 @@ __device__ __forceinline__ double group_sum(const double *__restrict__ v, int ba
     return wave_sum_all(k < n ? v[k] : 0.0);
 }
 
-// one wave per site row: rates of its nn slots + row sum
+// one wave per site row: rates of its nn slots + row sum (MODE 1, 2: + the row's bad-temperature slots added to *n_bad_out, one atomic per wave that has any)
+template <int MODE>
 __global__ __launch_bounds__(256) void k_ev_build(int N, int nn, const int *__restrict__ neigh, const int *__restrict__ layer,
                                                   const double *__restrict__ lattice, int pbc, const double *__restrict__ T_bg_p,
                                                   const double *__restrict__ freq_p, const double *__restrict__ sigma_p,
@@ -86,7 +110,8 @@ __global__ __launch_bounds__(256) void k_ev_build(int N, int nn, const int *__re
                                                   const double *__restrict__ y, const double *__restrict__ z,
                                                   const double *__restrict__ pb, const double *__restrict__ pc,
                                                   const int *__restrict__ element, const int *__restrict__ charge,
-                                                  int *__restrict__ ev_type, double *__restrict__ ev_prob, double *__restrict__ rowsum)
+                                                  int *__restrict__ ev_type, double *__restrict__ ev_prob, double *__restrict__ rowsum,
+                                                  const double *__restrict__ temperature, int *__restrict__ n_bad_out)
 {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -94,18 +119,24 @@ __global__ __launch_bounds__(256) void k_ev_build(int N, int nn, const int *__re
     const double laty = lattice[1], latz = lattice[2], T_bg = *T_bg_p, freq = *freq_p, sigma = *sigma_p, kk = *k_p;
     const int ei = element[i], qi = charge[i];
     const double xi = x[i], yi = y[i], zi = z[i], phii = pb[i] + pc[i];
+    double T_i = 0.0; int n_bad = 0;
+    if constexpr (MODE != 0) T_i = temperature[i];
     double s = 0.0;
     for (int c = lane; c < nn; c += WAVE) {
         const size_t idx = (size_t)i * nn + c;
         double P;
-        const int type = slot_rate(i, neigh[idx], N, layer, laty, latz, pbc, T_bg, freq, sigma, kk, x, y, z, pb, pc, element, charge,
-                                   ei, qi, xi, yi, zi, phii, &P);
+        const int type = slot_rate<MODE>(i, neigh[idx], N, layer, laty, latz, pbc, T_bg, freq, sigma, kk, x, y, z, pb, pc, element, charge,
+                                         ei, qi, xi, yi, zi, phii, temperature, T_i, &n_bad, &P);
         ev_prob[idx] = P;
         if (ev_type) ev_type[idx] = type;
         s += P;
     }
     s = wave_sum_all(s);
     if (lane == 0 && rowsum) rowsum[i] = s;
+    if constexpr (MODE != 0) {
+        n_bad = wave_sum_all_i(n_bad);
+        if (lane == 0 && n_bad && n_bad_out) atomicAdd(n_bad_out, n_bad);
+    }
 }
 
 // one wave per tree node: out[k] = sum of in[64k .. 64k+63]
@@ -154,11 +185,19 @@ __global__ __launch_bounds__(EVL_NT) void k_ev_loop(int N, int nn, const int *__
                                                     int ng2, int ng3, int *__restrict__ element, int *__restrict__ charge,
                                                     const double *__restrict__ uniform, int n_uniform,
                                                     const double *__restrict__ freq_p, EvOut *__restrict__ out,
-                                                    int *__restrict__ evlog, int max_log, const int *__restrict__ ncharged_p)
+                                                    int *__restrict__ evlog, int max_log, const int *__restrict__ ncharged_p,
+                                                    const int *__restrict__ n_bad_T_p)
 {
     __shared__ int sh_i, sh_j, sh_stop;
     __shared__ double sh_psum;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // modes 1, 2 of the rate model: the build met a temperature it cannot use -- no selection, no event (the word is the same for every thread)
+    const int n_bad_T = n_bad_T_p ? *n_bad_T_p : 0;
+    if (n_bad_T) {
+        if (tid == 0) { out->event_time = 0.0; out->psum_last = 0.0; out->n_events = 0; out->exhausted = 0; out->bad = 0;
+                        out->n_charged = ncharged_p ? *ncharged_p : -1; out->n_bad_T = n_bad_T; out->pad = 0; }
+        return;
+    }
     const double inv_freq = 1 / (*freq_p);
     int n_events = 0, exhausted = 0, bad = 0;
     double event_time = 0.0, psum_last = 0.0;
@@ -245,7 +284,8 @@ __global__ __launch_bounds__(EVL_NT) void k_ev_loop(int N, int nn, const int *__
         if (!(event_time < inv_freq)) break;
     }
     if (tid == 0) { out->event_time = event_time; out->psum_last = psum_last; out->n_events = n_events; out->exhausted = exhausted; out->bad = bad;
-                    out->n_charged = ncharged_p ? *ncharged_p : -1; }     // charged-site count of the last pair sum rides along in the mailbox
+                    out->n_charged = ncharged_p ? *ncharged_p : -1;       // charged-site count of the last pair sum rides along in the mailbox
+                    out->n_bad_T = 0; out->pad = 0; }
 }
 
 // called by dkmc_copy_to_const_memory (engine.hip)
@@ -257,14 +297,76 @@ int events_upload_layers()
     return 0;
 }
 
+// ---- rate model switch (include/devicekmc_hip.h) ----
+extern "C" void dkmc_set_event_temperature(int mode) { eng().event_temperature = (mode == 1 || mode == 2) ? mode : 0; }
+extern "C" int dkmc_get_event_temperature(void) { return eng().event_temperature; }
+extern "C" void dkmc_set_event_census(int on) { eng().event_census = on ? 1 : 0; }
+extern "C" int dkmc_get_event_census_on(void) { return eng().event_census; }
+extern "C" int dkmc_get_event_census(double *info16)
+{
+    Engine &e = eng();
+    if (!info16) return dkmc_fail(13, "get_event_census: bad arguments", __FILE__, __LINE__);
+    if (!e.event_census_valid) return dkmc_fail(17, "get_event_census: no census has been taken (dkmc_set_event_census(1), then a step)", __FILE__, __LINE__);
+    memcpy(info16, e.event_census_info, sizeof(e.event_census_info));
+    return 0;
+}
+
+// k_ev_build of the engine's mode on the engine's stream
+static void ev_build_launch(int mode, int N, int nn, const int *neigh, const int *layer, const double *lattice, int pbc,
+                            const double *T_bg, const double *freq, const double *sigma, const double *k,
+                            const double *x, const double *y, const double *z, const double *pb, const double *pc,
+                            const int *element, const int *charge, int *ev_type, double *ev_prob, double *rowsum,
+                            const double *temperature, int *n_bad)
+{
+    const dim3 grid((N + 3) / 4), block(256);
+    hipStream_t st = eng().stream;
+    if (mode == 1)
+        hipLaunchKernelGGL(k_ev_build<1>, grid, block, 0, st, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge,
+                           ev_type, ev_prob, rowsum, temperature, n_bad);
+    else if (mode == 2)
+        hipLaunchKernelGGL(k_ev_build<2>, grid, block, 0, st, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge,
+                           ev_type, ev_prob, rowsum, temperature, n_bad);
+    else
+        hipLaunchKernelGGL(k_ev_build<0>, grid, block, 0, st, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge,
+                           ev_type, ev_prob, rowsum, (const double *)nullptr, (int *)nullptr);
+}
+
+extern "C" int dkmc_build_event_list_T(int N, int nn, const int *neigh, const int *layer, const double *lattice, int pbc,
+                                       const double *T_bg, const double *freq, const double *sigma, const double *k,
+                                       const double *x, const double *y, const double *z, const double *pb, const double *pc,
+                                       const int *element, const int *charge, int *ev_type, double *ev_prob,
+                                       const double *temperature, int *n_bad)
+{
+    const int mode = eng().event_temperature;
+    if (N <= 0 || nn <= 0 || !ev_prob) return dkmc_fail(13, "build_event_list: bad arguments", __FILE__, __LINE__);
+    if (mode != 0 && !temperature)
+        return dkmc_fail(13, "build_event_list: dkmc_set_event_temperature is 1 or 2 and there is no site_temperature (bad arguments)", __FILE__, __LINE__);
+    ev_build_launch(mode, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge, ev_type, ev_prob,
+                    (double *)nullptr, temperature, n_bad);
+    KCHK();
+    return 0;
+}
+
 extern "C" int dkmc_build_event_list(int N, int nn, const int *neigh, const int *layer, const double *lattice, int pbc,
                                      const double *T_bg, const double *freq, const double *sigma, const double *k,
                                      const double *x, const double *y, const double *z, const double *pb, const double *pc,
                                      const int *element, const int *charge, int *ev_type, double *ev_prob)
 {
-    hipLaunchKernelGGL(k_ev_build, dim3((N + 3) / 4), dim3(256), 0, eng().stream, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k,
-                       x, y, z, pb, pc, element, charge, ev_type, ev_prob, (double *)nullptr);
+    if (eng().event_temperature != 0)
+        return dkmc_fail(13, "build_event_list: dkmc_set_event_temperature is 1 or 2 and this call has no site_temperature: use dkmc_build_event_list_T (bad arguments)",
+                         __FILE__, __LINE__);
+    ev_build_launch(0, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge, ev_type, ev_prob,
+                    (double *)nullptr, (const double *)nullptr, (int *)nullptr);
     KCHK();
+    return 0;
+}
+
+// measurement aid (dkmc_set_profiling(1)): HIP-event time of the last step's k_ev_build and of its census
+static hipEvent_t g_ev_t[4]; static bool g_ev_t_ready = false; static double g_ev_ms[2] = {0.0, 0.0};
+extern "C" int dkmc_debug_get_event_times(double *ms2)
+{
+    if (!ms2) return dkmc_fail(13, "debug_get_event_times: bad arguments", __FILE__, __LINE__);
+    ms2[0] = g_ev_ms[0]; ms2[1] = g_ev_ms[1];
     return 0;
 }
 
@@ -275,8 +377,11 @@ extern "C" int dkmc_execute_kmc_step_gpu(int N, int nn, const int *neigh, const 
                                          const double *h_uniform, int n_uniform, int resume,
                                          int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out)
 {
-    (void)temperature;     // unused by the reference kernel as well (Ekin = 0, kmc_events.cu:65)
+    // mode 0: the temperature is unused, as by the reference kernel (Ekin = 0, kmc_events.cu:65), and may be null
     Engine &e = eng(); hipStream_t st = e.stream;
+    const int mode = e.event_temperature;
+    if (mode != 0 && !temperature)
+        return dkmc_fail(13, "execute_kmc_step: dkmc_set_event_temperature is 1 or 2 and site_temperature is null (bad arguments)", __FILE__, __LINE__);
     const size_t total = (size_t)N * nn;
     const int ng2 = (N + 63) / 64, ng3 = (ng2 + 63) / 64;
     const int max_log = n_uniform / 2;
@@ -287,25 +392,50 @@ extern "C" int dkmc_execute_kmc_step_gpu(int N, int nn, const int *neigh, const 
     int *evlog = (int *)scratch(S_EV_LOG, (size_t)(max_log > 0 ? max_log : 1) * 16);
     EvOut *out = (EvOut *)scratch(S_EV_CTRL, sizeof(EvOut));
     if (!ev_prob || !rowsum || !g2 || !g3 || !uni || !evlog || !out) return e.err_code;
+    const bool build = !resume, census = build && e.event_census != 0, timed = build && e.profiling != 0;
+    int *n_bad = nullptr; double *census_info = nullptr;
+    if (build && mode != 0) { n_bad = (int *)scratch(S_EV_NBAD, sizeof(int)); if (!n_bad) return e.err_code; }
+    if (timed && !g_ev_t_ready) { for (auto &t : g_ev_t) HIPCHK(hipEventCreate(&t)); g_ev_t_ready = true; }
     if (n_uniform > 0) HIPCHK(hipMemcpyAsync(uni, h_uniform, (size_t)n_uniform * 8, hipMemcpyHostToDevice, st));
-    if (!resume) {
-        hipLaunchKernelGGL(k_ev_build, dim3((N + 3) / 4), dim3(256), 0, st, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k,
-                           x, y, z, pb, pc, element, charge, (int *)nullptr, ev_prob, rowsum);
+    if (build) {
+        if (n_bad) HIPCHK(hipMemsetAsync(n_bad, 0, sizeof(int), st));
+        if (timed) HIPCHK(hipEventRecord(g_ev_t[0], st));
+        ev_build_launch(mode, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge, (int *)nullptr, ev_prob, rowsum,
+                        temperature, n_bad);
+        if (timed) HIPCHK(hipEventRecord(g_ev_t[1], st));
         hipLaunchKernelGGL(k_ev_level, dim3((ng2 + 3) / 4), dim3(256), 0, st, N, rowsum, ng2, g2);
         hipLaunchKernelGGL(k_ev_level, dim3((ng3 + 3) / 4), dim3(256), 0, st, ng2, g2, ng3, g3);
+        if (census) {       // on the step's own table, before the loop zeroes any of it
+            if (timed) HIPCHK(hipEventRecord(g_ev_t[2], st));
+            if (ev_census_enqueue(N, nn, neigh, element, temperature, ev_prob, &census_info)) return e.err_code;
+            if (timed) HIPCHK(hipEventRecord(g_ev_t[3], st));
+        }
     }
     hipLaunchKernelGGL(k_ev_loop, dim3(1), dim3(EVL_NT), 0, st, N, nn, neigh, ev_prob, rowsum, g2, g3, ng2, ng3, element, charge,
-                       uni, n_uniform, freq, out, h_event_log ? evlog : (int *)nullptr, max_log, (const int *)e.buf[S_PW_CNT]);
+                       uni, n_uniform, freq, out, h_event_log ? evlog : (int *)nullptr, max_log, (const int *)e.buf[S_PW_CNT], (const int *)n_bad);
     KCHK();
     EvOut h;
     HIPCHK(hipMemcpyAsync(&h, out, sizeof(EvOut), hipMemcpyDeviceToHost, st));
+    if (census) HIPCHK(hipMemcpyAsync(e.event_census_info, census_info, sizeof(e.event_census_info), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (census) e.event_census_valid = 1;
+    if (timed) {
+        float a = 0.0f, b = 0.0f;
+        HIPCHK(hipEventElapsedTime(&a, g_ev_t[0], g_ev_t[1]));
+        if (census) HIPCHK(hipEventElapsedTime(&b, g_ev_t[2], g_ev_t[3]));
+        g_ev_ms[0] = a; g_ev_ms[1] = b;
+    }
     if (h_event_log && h.n_events > 0) HIPCHK(hipMemcpy(h_event_log, evlog, (size_t)h.n_events * 16, hipMemcpyDeviceToHost));
     e.stats.n_events = h.n_events; e.stats.psum_last = h.psum_last;
     if (h.n_charged >= 0) e.stats.n_charged = h.n_charged;
     if (n_events_out) *n_events_out = h.n_events;
     if (exhausted_out) *exhausted_out = h.exhausted;
     if (event_time_out) *event_time_out = h.event_time;
+    if (h.n_bad_T) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "execute_kmc_step: %d event slots have a site temperature that is not finite or not > 0; no event ran", h.n_bad_T);
+        return dkmc_fail(16, msg, __FILE__, __LINE__);
+    }
     if (h.bad) return dkmc_fail(7, "execute_kmc_step: no event with a positive rate", __FILE__, __LINE__);
     return 0;
 }

@@ -164,6 +164,33 @@ def find_clusters(index, nn, element, charge, x, metal_types, members, n_left, n
     return label, {k: c[:rows.value] for k, c in zip(CLUSTER_TABLE, cols)}, info
 
 
+# rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
+EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
+
+
+def _census_dict(info):
+    """The 16 doubles of the census as named entries + the per-class rate-weighted mean temperature (NaN for a class without rate)."""
+    v = [float(x) for x in info]
+    d = {"n_slots": {c: int(v[k]) for k, c in enumerate(EVENT_CLASSES)},
+         "rate": {c: v[4 + k] for k, c in enumerate(EVENT_CLASSES)},
+         "rate_temperature": {c: v[8 + k] for k, c in enumerate(EVENT_CLASSES)},
+         "max_rate": v[12], "max_rate_slot": int(v[13]), "n_nonfinite": int(v[14]), "n_live": int(v[15]), "info16": v}
+    d["rate_total"] = v[4] + v[5] + v[6] + v[7]
+    d["mean_temperature"] = {c: (v[8 + k] / v[4 + k] if v[4 + k] > 0 else float("nan")) for k, c in enumerate(EVENT_CLASSES)}
+    return d
+
+
+def event_rate_census(neigh_idx, nn, element, ev_prob, temperature=None):
+    """dkmc_event_rate_census on device tensors (neigh_idx: N * nn int32; element: N int32; ev_prob: N * nn float64, e.g. the table of
+    dkmc_build_event_list_T; temperature: N float64 or None).  Returns the dict of _census_dict.  Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    _use_stream(element.device)
+    info = (C.c_double * 16)()
+    check(L.dkmc_event_rate_census(int(element.numel()), int(nn), _ptr(neigh_idx), _ptr(element),
+                                   _ptr(temperature) if temperature is not None else None, _ptr(ev_prob), info))
+    return _census_dict(info)
+
+
 class Device:
     """Device.h:61-231 (USE_CUDA build): host copy of the site fields + the thin callers of the GPU path."""
 
@@ -348,6 +375,7 @@ class KMCProcess:
         self.site_layer = device.site_layer
         self.batch = 64            # events worth of random numbers handed to the device per launch
         self.last_event_log = None
+        self.last_event_census = None     # device.p.event_census: the rate census of the last step's table (host._census_dict)
 
     # KMCProcess.cpp:259-373 (USE_CUDA branch) -> execute_kmc_step_gpu (kmc_events.cu:146-365)
     def executeKMCStep(self, gpubuf: GPUBuffers, device: Device, want_log=False):
@@ -355,7 +383,12 @@ class KMCProcess:
         t0 = time.perf_counter()
         _use_stream(gpubuf.dev)
         g = gpubuf
+        # the parameters are authoritative for the rate model on every call (the engine's switches are process-wide)
+        L.dkmc_set_event_temperature(int(device.p.event_temperature))
+        L.dkmc_set_event_census(1 if device.p.event_census else 0)
         total_events, logs, resume = 0, [], 0
+        self.last_n_events = 0
+        self.last_event_census = None
         while True:
             probe = self.random_generator.copy()
             u = np.ascontiguousarray(probe.uniform_batch(2 * self.batch))
@@ -377,6 +410,10 @@ class KMCProcess:
         if want_log:
             self.last_event_log = np.concatenate(logs) if logs else np.zeros((0, 4), dtype=np.int32)
         self.last_n_events = total_events
+        if L.dkmc_get_event_census_on():
+            info = (C.c_double * 16)()
+            check(L.dkmc_get_event_census(info))
+            self.last_event_census = _census_dict(info)
         return {"Z - calculation time - kmc events [s]": time.perf_counter() - t0}, et.value
 
 

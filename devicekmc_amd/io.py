@@ -107,10 +107,18 @@ class StepLog:
     def bias_header(self, Vd, folder):
         self.buf.append("--------------------------------\nApplied Voltage = %s V\n--------------------------------\nCreated folder: %s\n" % (_g6(Vd), folder))
 
-    def step(self, kmc_step_count, V_vcm, kmc_time, result_map, t_fields=None, t_log=None, t_superstep=None):
+    def step(self, kmc_step_count, V_vcm, kmc_time, result_map, t_fields=None, t_log=None, t_superstep=None, census=None):
+        """census: optional rate census of the step's event table (KMCProcess.last_event_census): adds the total rate and the shares of the four
+        event classes to the block, in key order with the rest (no counterpart in the reference's logs; None: the reference's block, byte for byte)."""
         out = ["--------------\n", "KMC step count: %d\n" % kmc_step_count, "V_vcm: %s\n" % _g6(V_vcm), "KMC time is: %s\n" % _g6(kmc_time)]
-        for key in sorted(result_map):                       # std::map iterates in key order
-            out.append("%s: %s\n" % (key, _g6(result_map[key])))
+        lines = {key: _g6(result_map[key]) for key in result_map}
+        if census is not None:
+            total = census["rate_total"]
+            lines["Event rate total [1/s]"] = _g6(total)
+            lines["Event rate share gen/rec/vdiff/idiff"] = "/".join(_g6(census["rate"][c] / total if total > 0 else 0.0)
+                                                                     for c in ("gen", "rec", "vdiff", "idiff"))
+        for key in sorted(lines):                            # std::map iterates in key order
+            out.append("%s: %s\n" % (key, lines[key]))
         if t_fields is not None:
             out.append("Z - calculation time - all fields [s]: %s\n" % _g6(t_fields))
         if t_log is not None:

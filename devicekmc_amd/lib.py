@@ -150,6 +150,14 @@ SYMBOLS = {
     "dkmc_execute_kmc_step_gpu": (_I, [_I, _I, vp, vp, vp, _I, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                        vp, _I, _I, c_int_p, c_int_p, vp, c_dbl_p]),
     "dkmc_build_event_list": (_I, [_I, _I, vp, vp, vp, _I, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dkmc_set_event_temperature": (None, [_I]),
+    "dkmc_get_event_temperature": (_I, []),
+    "dkmc_build_event_list_T": (_I, [_I, _I, vp, vp, vp, _I, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "dkmc_event_rate_census": (_I, [_I, _I, vp, vp, vp, vp, c_dbl_p]),
+    "dkmc_set_event_census": (None, [_I]),
+    "dkmc_get_event_census_on": (_I, []),
+    "dkmc_get_event_census": (_I, [c_dbl_p]),
+    "dkmc_debug_get_event_times": (_I, [c_dbl_p]),
     "dkmc_update_power_gpu_sparse": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I,
                                           c_dbl_p, _I, _I, _D]),
     "dkmc_get_last_X": (_I, [c_int_p, C.POINTER(C.c_longlong), vp, vp, vp]),

@@ -77,6 +77,11 @@ class KMCParameters:
     # snapshot's source (potential_solver_gpu.cu:595-694: every site, interstitials included); "atoms" = interstitial sites (DEFECT /
     # OXYGEN_DEFECT) carry no link -- the revision that wrote the reference's CSR dump and its current log (`log_revision()`).
     cb_edge_domain: str = "sites"
+    # Rate model of the event table (dkmc_set_event_temperature, include/devicekmc_hip.h): 0 = the reference as compiled (every rate at T_bg),
+    # 1 = the reference authors' commented-out kinetic term on the local site temperature, 2 = Arrhenius on it.  Only meaningful with
+    # solve_heating_local, which maintains site_temperature.  event_census: every KMC step also takes the rate census of its table.
+    event_temperature: int = 0
+    event_census: bool = False
     # local temperature model (parameters.txt:76-91)
     k_th_metal: float = 29.0
     k_th_non_vacancy: float = 0.5

@@ -406,6 +406,53 @@ int dkmc_build_event_list(int N, int nn, const int *d_neigh_idx, const int *d_si
                           const int *d_site_element, const int *d_site_charge,
                           int *d_event_type, double *d_event_prob);
 
+/* ---- event rates on the local site temperature (opt-in, default 0; csrc/events.hip) ----
+ * The reference computes every rate at the one global temperature T_bg: its kinetic term is commented out (Ekin = 0, kmc_events.cu:65,81,99,118;
+ * KMCProcess.cpp:99,116,135,156), and so does mode 0, bit for bit.  Modes 1 and 2 let the local heat model reach the vacancy and ion kinetics.
+ *   deciding site  For every slot (i, j) that has an event class one site s supplies T_s = d_site_temperature[s]; s is the site the reference's
+ *                  commented-out lines name: j for GENERATION, i for RECOMBINATION, VACANCY DIFFUSION and ION DIFFUSION.
+ *   mode 0         (default) EA = E0 - En - 0, P = exp(-EA / (kB T_bg)) freq: today's table.  d_site_temperature is never dereferenced and may be NULL.
+ *   mode 1         "kinetic", the reference authors' term: Ekin = kB (T_s - T_bg), EA = E0 - En - Ekin, P = exp(-EA / (kB T_bg)) freq.
+ *   mode 2         "Arrhenius": EA = E0 - En, P = exp(-EA / (kB T_s)) freq.
+ *   identities     Where T_s equals T_bg as a double, modes 1 and 2 give mode 0's P bit for bit, whatever the rest of the field holds.
+ *   bad values     Modes 1, 2: an event-class slot whose T_s is not finite or not > 0 gets P = 0 (its type is still written) and is counted in a
+ *                  device word.  dkmc_execute_kmc_step_gpu then runs NO event: it returns error 16, the message names the count, site_element and
+ *                  site_charge are untouched, *n_events_out = 0 and no random number was consumed.  Modes 1, 2 with d_site_temperature == NULL
+ *                  fail with the bad-argument code (13) before any launch.
+ *   when           The temperature enters when the table is built; invalidation after an event never recomputes a rate, and a resume call
+ *                  (resume != 0) needs nothing new.
+ * Values outside 0 ... 2 are taken as 0.  The mode is read at every dkmc_execute_kmc_step_gpu and dkmc_build_event_list(_T).  Modes 1 and 2 are
+ * only meaningful where site_temperature is maintained, i.e. with the local heat model (dkmc_update_temperature_local); with global heating only
+ * T_bg moves and site_temperature keeps what the host put there.  The library does not second-guess the caller.
+ * dkmc_build_event_list_T: dkmc_build_event_list + the temperature and an optional device word d_n_bad, zeroed by the caller, that receives the
+ * count of bad-temperature slots (modes 1, 2).  dkmc_build_event_list itself has no temperature: it fails (13) while the mode is not 0. */
+void dkmc_set_event_temperature(int mode);
+int dkmc_get_event_temperature(void);
+int dkmc_build_event_list_T(int N, int nn, const int *d_neigh_idx, const int *d_site_layer,
+                            const double *d_lattice, int pbc, const double *d_T_bg, const double *d_freq,
+                            const double *d_sigma, const double *d_k,
+                            const double *d_posx, const double *d_posy, const double *d_posz,
+                            const double *d_site_potential_boundary, const double *d_site_potential_charge,
+                            const int *d_site_element, const int *d_site_charge,
+                            int *d_event_type, double *d_event_prob, const double *d_site_temperature, int *d_n_bad);
+/* Rate census of an event table (csrc/ev_census.hip; no counterpart in the reference): which class carries the total rate and how hot the sites
+ * that fire are, computed on the device.  A pure function of the caller's table d_ev_prob[N * nn] (e.g. of dkmc_build_event_list_T).  A LIVE slot
+ * has a finite P > 0; its class is recomputed from (site_element[i], site_element[j]) exactly as the table's builder does, s as above.
+ *   info16   [0..3]   live slots per class (GENERATION, RECOMBINATION, VACANCY DIFFUSION, ION DIFFUSION), exact integers in doubles;
+ *            [4..7]   sum of P per class;
+ *            [8..11]  sum of P T_s per class, all 0 when d_site_temperature is NULL: [8 + c] / [4 + c] is the rate-weighted temperature of class c;
+ *            [12]     the largest finite P > 0 (0 when there is none), [13] its slot index i nn + c, the smallest among ties, -1 when no slot is live;
+ *            [14]     slots with a non-finite P (inf, NaN): excluded from every other entry;
+ *            [15]     the total of [0..3].
+ * Every sum is added in a fixed order (no floating-point atomics): the same table gives the same bits on every call.
+ * dkmc_set_event_census(1) (default 0): every dkmc_execute_kmc_step_gpu with resume == 0 also takes the census of its own table right after the build,
+ * before the first event (dkmc_get_event_census_on: the switch); dkmc_get_event_census returns the last one and fails (17) when none has been taken. */
+int dkmc_event_rate_census(int N, int nn, const int *d_neigh_idx, const int *d_site_element, const double *d_site_temperature,
+                           const double *d_ev_prob, double *h_info16);
+void dkmc_set_event_census(int on);
+int dkmc_get_event_census_on(void);
+int dkmc_get_event_census(double *info16);
+
 /* ---- current / power: update_power_gpu_sparse (current_solver_gpu.cu:854-1147) --------------- */
 int dkmc_update_power_gpu_sparse(dkmc_gpubuf *buf, int num_source_inj, int num_ground_ext, int num_layers_contact,
                                  double Vd, int pbc, double high_G, double low_G, double loop_G, double G0,

@@ -197,6 +197,9 @@ void dkmc_debug_heat_chain(int on, int budget);
  * between them included) and of its summaries (per-root atomics, scan, table, info); both 0 with profiling off. */
 void dkmc_debug_set_cluster_round_cap(int cap);
 int dkmc_debug_get_cluster_times(double *ms2);
+/* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
+ * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
+int dkmc_debug_get_event_times(double *ms2);
 
 #ifdef __cplusplus
 }

@@ -155,3 +155,15 @@ DKMC_SHIM_API double update_temperature_local_gpu(GPUBuffers &gpubuf, const doub
                                                      nn_dist, num_atoms_contact, nullptr, nullptr, nullptr, &T_bg));
     return T_bg;
 }
+
+// Event rates on the local site temperature: execute_kmc_step_gpu above already passes site_temperature, so the reference side needs this ONE
+// call (0: the reference as compiled, every rate at T_bg; 1: its authors' commented-out kinetic term; 2: Arrhenius on the site temperature;
+// devicekmc_hip.h).  Meaningful where site_temperature is maintained, i.e. with update_temperature_local_gpu.
+DKMC_SHIM_API void set_event_temperature(const int mode) { dkmc_set_event_temperature(mode); }
+
+// Rate census of an event table (devicekmc_hip.h: dkmc_event_rate_census): 16 doubles to the host.  site_temperature may be null.
+DKMC_SHIM_API void event_rate_census(const int N, const int nn, const int *neigh_idx, const ELEMENT *site_element, const double *site_temperature,
+                                     const double *event_prob, double *info16)
+{
+    GPUBuffers::report(dkmc_event_rate_census(N, nn, neigh_idx, reinterpret_cast<const int *>(site_element), site_temperature, event_prob, info16));
+}
