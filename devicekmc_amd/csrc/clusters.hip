@@ -34,20 +34,6 @@ struct ClusterState {
 } g_cl;
 int g_round_cap = CL_CAP_DEFAULT;
 
-// order-preserving 64-bit key of a double (unsigned compare): negative values flip every bit, the others the sign bit.  -0.0 orders below +0.0.
-__device__ __forceinline__ unsigned long long dbl_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_dbl(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // 1. membership: member flag as the initial root / parent (the site itself, -1 for a non-member), and the identities of the per-root summaries
 __global__ __launch_bounds__(CL_NT) void k_cl_members(int N, const int *el, const int *charge, MetalSet ms, int members,
                                                       int *label, int *parent, int *csize, int *cvac, int *cflags,

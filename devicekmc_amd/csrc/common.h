@@ -126,6 +126,21 @@ __device__ __forceinline__ double block_sum_all(double v, double *red)
     return s;
 }
 
+// ---- integer forms of doubles and relaxed agent-scope words (clusters.hip, gaps.hip) ----------
+// order-preserving 64-bit key of a double (unsigned compare): negative values flip every bit, the others the sign bit.  -0.0 orders below +0.0.
+__device__ __forceinline__ unsigned long long dbl_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_dbl(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)b);
+}
+__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 // blocked form of a K pattern (kcg.hip: kblocked_build, once per pattern; device arrays)
 struct KBlocked {
     int m, R, nb, total, maxwin, maxints;      // maxints: ints of the largest block's padded rows
@@ -195,7 +210,7 @@ struct Engine {
     double E_gen[DKMC_MAX_LAYERS] = {0}, E_rec[DKMC_MAX_LAYERS] = {0}, E_Vdiff[DKMC_MAX_LAYERS] = {0}, E_Odiff[DKMC_MAX_LAYERS] = {0};
     int num_layers = 0;
     // named persistent device buffers (grown on demand, never shrunk)
-    static const int NBUF = 160;
+    static const int NBUF = 176;
     void *buf[NBUF] = {nullptr};
     size_t bufsz[NBUF] = {0};
 };
@@ -249,6 +264,9 @@ enum {
     S_CL_PARENT, S_CL_SUMS, S_CL_POS, S_CL_TABLE, S_CL_CTRL,
     // event rates on the local temperature (events.hip): the bad-temperature word of a build; rate census (ev_census.hip): workgroup partials, info
     S_EV_NBAD, S_EV_CENSUS_PART, S_EV_CENSUS_INFO,
+    // gap analysis (gaps.hip: dkmc_find_gaps): per-site words (component flags, cell, node), control block + box partials, the cell list, the members
+    // in cell order, the per-node picks and pointers, the forest's edges
+    S_GAP_SITE, S_GAP_CTRL, S_GAP_CELLS, S_GAP_SORTED, S_GAP_NODES, S_GAP_EDGES,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

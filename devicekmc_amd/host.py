@@ -164,6 +164,37 @@ def find_clusters(index, nn, element, charge, x, metal_types, members, n_left, n
     return label, {k: c[:rows.value] for k, c in zip(CLUSTER_TABLE, cols)}, info
 
 
+GAP_EDGES = ("site_a", "site_b", "root_a", "root_b")
+GAP_CHAIN = ("from_site", "to_site")
+
+
+def find_gaps(label, x, y, z, lattice, pbc, n_left, n_right, r_max):
+    """dkmc_find_gaps on device tensors (label: N int32, e.g. the first return value of find_clusters; x, y, z: N float64; lattice: 3 host numbers,
+    read with pbc).  Returns (edges: dict of host arrays GAP_EDGES + d2 + dist, one row per edge of the island graph in key order; chain: dict of
+    GAP_CHAIN + d2 + dist, the hops from the left contact node to the right one; info: dict of n_components, n_edges, status (0 none, 1 chain,
+    2 bridged), n_hops, rounds, pairs_tested, direct = (a, b, dist) or None, bottleneck_d2, bottleneck).  dist = np.sqrt(d2).
+    Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(label.numel())
+    _use_stream(label.device)
+    lat = np.ascontiguousarray(lattice, dtype=np.float64)
+    check(L.dkmc_find_gaps(N, _ptr(x), _ptr(y), _ptr(z), _np_ptr(lat), int(bool(pbc)), _ptr(label), int(n_left), int(n_right), float(r_max)))
+    i8, d2 = (C.c_longlong * 8)(), (C.c_double * 2)()
+    check(L.dkmc_get_gap_info(i8, d2))
+    rows = C.c_int(0)
+    cols = [np.empty(i8[1], dtype=np.int32) for _ in GAP_EDGES] + [np.empty(i8[1])]
+    check(L.dkmc_copy_gap_edges(int(i8[1]), *[_np_ptr(c) for c in cols], C.byref(rows)))
+    edges = {k: c[:rows.value] for k, c in zip(GAP_EDGES + ("d2",), cols)}
+    cols = [np.empty(i8[3], dtype=np.int32) for _ in GAP_CHAIN] + [np.empty(i8[3])]
+    check(L.dkmc_copy_gap_chain(int(i8[3]), *[_np_ptr(c) for c in cols], C.byref(rows)))
+    chain = {k: c[:rows.value] for k, c in zip(GAP_CHAIN + ("d2",), cols)}
+    edges["dist"], chain["dist"] = np.sqrt(edges["d2"]), np.sqrt(chain["d2"])
+    info = dict(n_components=int(i8[0]), n_edges=int(i8[1]), status=int(i8[2]), n_hops=int(i8[3]), rounds=int(i8[4]), pairs_tested=int(i8[5]),
+                direct=(int(i8[6]), int(i8[7]), float(np.sqrt(d2[1]))) if i8[6] >= 0 else None,
+                bottleneck_d2=float(d2[0]), bottleneck=float(np.sqrt(d2[0])))
+    return edges, chain, info
+
+
 # rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
 EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
 
@@ -314,8 +345,27 @@ class Device:
         index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
         label, table, info = find_clusters(index, nn, gpubuf.site_element, gpubuf.site_charge, gpubuf.site_x, gpubuf.metal_types, members,
                                            n_left, n_right, capacity)
+        self._cluster_label = label                # the device tensor, for find_gaps
         self.site_cluster, self.cluster_table, self.cluster_info = label.cpu().numpy(), table, info
         return self.site_cluster, table, info
+
+    def find_gaps(self, gpubuf: GPUBuffers, r_max=10.0, label=None, n_left=None, n_right=None):
+        """Gap analysis on the device (dkmc_find_gaps; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- one with
+        the default members is run if there is none -- or over label (int32 device tensor of N): the island graph within r_max, the tunnelling
+        chain between the contact clusters with its bottleneck hop, and the direct tip-to-tip gap, with this device's pbc and lattice and the
+        contact seeds of find_clusters.  Changes nothing in gpubuf.  Returns (edges, chain, info) and keeps them as gap_edges, gap_chain, gap_info."""
+        p = self.p
+        if label is None:
+            if getattr(self, "_cluster_label", None) is None:
+                self.find_clusters(gpubuf, n_left=n_left, n_right=n_right)
+            label = self._cluster_label
+        if n_left is None:
+            n_left = self.get_num_in_contacts(p.num_atoms_first_layer, "left")
+        if n_right is None:
+            n_right = self.get_num_in_contacts(p.num_atoms_first_layer, "right")
+        self.gap_edges, self.gap_chain, self.gap_info = find_gaps(label, gpubuf.site_x, gpubuf.site_y, gpubuf.site_z, self.lattice, self.pbc,
+                                                                  n_left, n_right, r_max)
+        return self.gap_edges, self.gap_chain, self.gap_info
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

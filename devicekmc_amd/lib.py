@@ -170,6 +170,11 @@ SYMBOLS = {
     "dkmc_get_cluster_info": (_I, [c_int_p, c_dbl_p]),
     "dkmc_debug_set_cluster_round_cap": (None, [_I]),
     "dkmc_debug_get_cluster_times": (_I, [c_dbl_p]),
+    "dkmc_find_gaps": (_I, [_I, vp, vp, vp, vp, _I, vp, _I, _I, _D]),
+    "dkmc_get_gap_info": (_I, [C.POINTER(C.c_longlong), c_dbl_p]),
+    "dkmc_copy_gap_edges": (_I, [_I, vp, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_gap_chain": (_I, [_I, vp, vp, vp, c_int_p]),
+    "dkmc_debug_set_gap_cell_skip": (None, [_I]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

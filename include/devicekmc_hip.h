@@ -503,7 +503,7 @@ int dkmc_get_current_map_info(const dkmc_gpubuf *buf, double *info8);
  *               the one that changed nothing included: what the synchronous model needs, the same on every call), [6], [7] 0.
  *   x3          [0] tip_left_x = max of xmax over the components that touch left and not right (-inf: none), [1] tip_right_x = min of xmin over
  *               those that touch right and not left (+inf: none), [2] gap_x = tip_right_x - tip_left_x, exactly 0.0 when bridged.  (The Euclidean
- *               gap between the two clusters is not computed.)
+ *               gap between the two clusters, and the chain of islands between them: dkmc_find_gaps below.)
  * dkmc_find_clusters labels, summarises and keeps table and info of the LAST call in the library; it returns after they are complete.  The
  * labelling runs min-hooking + pointer jumping in rounds from the host, at most 64 rounds (7.5 nm device: 5; a randomly numbered chain of 200 000
  * sites: 12); at the cap the call fails (dkmc_last_error), d_label is set to -1 everywhere and the two getters fail until a call succeeds.
@@ -515,6 +515,46 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
 int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vacancy, int *h_flags, double *h_xmin, double *h_xmax,
                             int *rows_out);
 int dkmc_get_cluster_info(int *info8, double *x3);
+
+/* ---- gap analysis: closest pairs, island graph, tunnelling chain (csrc/gaps.hip; no counterpart in the reference) ----
+ * Where the filament is not bridged: the Euclidean gap between the two contact clusters, the graph of the islands between them and the chain of
+ * hops whose widest one is as narrow as possible, all from per-site work on the device.  A pure function of its arguments: no field of GPUBuffers,
+ * no engine state a later phase reads and no other kernel changes.
+ *   members     site i is a member when 0 <= d_label[i] < N; its component is the label value (any other value: not a member).  The labels are
+ *               those of dkmc_find_clusters, but nothing else of that call is used.
+ *   nodes       a component touches the left contact when it has a member with index < n_left_sites, the right one when it has a member with
+ *               index >= N - n_right_sites (both clamped to 0 ... N): the rule of the cluster table's flags, recomputed from the labels.  Node L
+ *               is the union of the left-touching components, node R of the right-touching ones; a component that touches both makes the device
+ *               bridged, and L and R are then one node.  Every other component is a node of its own.
+ *   distance    for sites u != v, a = min(u, v), b = max(u, v): dx = x[a] - x[b]; with pbc fy = (y[a] - y[b]) / lattice[1], fy -= round(fy),
+ *               dy = fy * lattice[1], and the same for z with lattice[2] (the arithmetic of the reference's site_dist); without pbc the plain
+ *               differences.  d2 = (dx * dx + dy * dy) + dz * dz with every product and every sum rounded on its own (no contraction), so that
+ *               numpy reproduces the bits.  The library reports d2; the square root is the caller's.  h_lattice (host, 3 doubles) is read with pbc.
+ *   edge order  strictly by the key (d2, a, b), lexicographically: crystalline inputs hold exact ties of d2, the tie-break is part of the contract.
+ *   candidates  the member pairs whose nodes differ and whose d2 <= r_max * r_max (one rounded product).
+ *   island graph  the minimum spanning forest of the nodes over the candidates under that order: unique, whatever computes it.  One row per forest
+ *               edge in ascending key order: site_a < site_b, root_a = d_label[site_a], root_b = d_label[site_b], d2.
+ *   chain       present when neither contact set is empty, the device is not bridged and L and R lie in one tree: the tree path from L to R, whose
+ *               largest hop is the smallest possible over all L -> R paths of the candidate graph.  Rows in order from L to R: from_site (the
+ *               end nearer to L), to_site, d2.  Consecutive hops need not share a site: a hop lands anywhere on an island.
+ *   direct gap  the smallest candidate between L and R themselves, if one lies within r_max: the Euclidean tip-to-tip gap.
+ *   info8       (long long) [0] number of components (distinct labels), [1] forest edges, [2] status: 0 = no chain within r_max or a contact set is
+ *               empty, 1 = chain found, 2 = bridged, [3] hops in the chain, [4] rounds (below), [5] distance tests made (a diagnostic: it depends
+ *               on the cell grid), [6] direct_a, [7] direct_b (-1, -1: none).
+ *   d2x2        [0] bottleneck d2 = the largest hop of the chain; exactly 0.0 when bridged, +inf at status 0.  [1] direct d2, +inf if none.
+ * dkmc_find_gaps bins the members into cells of edge >= r_max (a periodic axis may have fewer than 3 cells, r_max may exceed the box: every distinct
+ * neighbour cell is visited once) and runs Boruvka rounds: every node picks its smallest candidate by integer atomic minima, the picks are
+ * recorded and contracted; a round in which no node has a candidate ends the loop, and rounds counts the rounds run, that one included -- a function
+ * of the input alone, at most 32.  It keeps the results of the LAST call in the library and returns after they are complete; the three getters
+ * fail (dkmc_last_error) before any successful call.  Any output pointer may be NULL; capacity truncates and *rows_out reports the rows copied (the
+ * true counts are info8[1] and info8[3]).  N == 0, or no member at all, succeeds with empty tables and status 0.  N < 0, a null array with N > 0,
+ * r_max not finite or <= 0 fail with code 3 before any launch.  No floating-point atomics, no order-dependent sums: the same inputs give the same
+ * bytes on every call. */
+int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_z, const double *h_lattice, int pbc,
+                   const int *d_label, int n_left_sites, int n_right_sites, double r_max);
+int dkmc_get_gap_info(long long *info8, double *d2x2);
+int dkmc_copy_gap_edges(int capacity, int *h_site_a, int *h_site_b, int *h_root_a, int *h_root_b, double *h_d2, int *rows_out);
+int dkmc_copy_gap_chain(int capacity, int *h_from, int *h_to, double *h_d2, int *rows_out);
 
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */

@@ -197,6 +197,11 @@ void dkmc_debug_heat_chain(int on, int budget);
  * between them included) and of its summaries (per-root atomics, scan, table, info); both 0 with profiling off. */
 void dkmc_debug_set_cluster_round_cap(int cap);
 int dkmc_debug_get_cluster_times(double *ms2);
+/* Test and measurement aid of dkmc_find_gaps (csrc/gaps.hip): on != 0 (default) a searching member skips every neighbour cell whose members all
+ * carry its own node (a per-cell word, recomputed every round: inside the contact slabs whole cells are one node); 0: every cell is scanned.  What
+ * it saves are the reads of those members' node words -- a pair of one node is never distance-tested --, so the results, info8[5] included, are
+ * the same bytes either way. */
+void dkmc_debug_set_gap_cell_skip(int on);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);

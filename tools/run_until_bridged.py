@@ -4,7 +4,9 @@ step, until a conducting cluster bridges the two contacts or the step cap is rea
 which dominates a superstep, is paid only from the moment the filament has closed.
 Prints one JSON line: steps run current-off, the step at which the verdict turned to bridged (null: never), gap_x after every step (null where
 one of the tips does not exist), members of the analysis, and I_macro of the closing step with the current solve.
-usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0]"""
+With --gaps R every check also runs Device.find_gaps at r_max = R and the line carries, per step, the bottleneck hop of the tunnelling chain and the
+direct tip-to-tip gap (null: none within R): distances that close smoothly where the verdict only flips.
+usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0]"""
 import argparse
 import json
 import math
@@ -21,6 +23,7 @@ def main():
     ap.add_argument("--vd", type=float, default=5.0)
     ap.add_argument("--members", type=int, default=3, help="bit mask: 1 metal, 2 vacancies, 4 neutral vacancies only")
     ap.add_argument("--wide-radius", type=float, default=0.0, help="> 0: link members within this distance (gap-tolerant filament) instead of nearest neighbours")
+    ap.add_argument("--gaps", type=float, default=0.0, metavar="R", help="> 0: log the bottleneck and the direct gap of Device.find_gaps(r_max=R) at every check")
     a = ap.parse_args()
     import torch
     from bench import Sim
@@ -32,18 +35,24 @@ def main():
         wide, nn = host.build_neighbor_index_gpu(dev.site_x, dev.site_y, dev.site_z, p.lattice, p.pbc, a.wide_radius)
         link = (torch.as_tensor(wide.reshape(-1)).to("cuda:0"), nn)
     gaps, bridged_at, info = [], None, None
+    bottleneck, direct = [], []
     for k in range(a.max_steps):
         sim.step(False)
         _, _, info = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
         gaps.append(info["gap_x"] if math.isfinite(info["gap_x"]) else None)
+        if a.gaps > 0:
+            _, _, ginfo = dev.find_gaps(gb, r_max=a.gaps)
+            bottleneck.append(ginfo["bottleneck"] if math.isfinite(ginfo["bottleneck"]) else None)
+            direct.append(None if ginfo["direct"] is None else ginfo["direct"][2])
         if info["bridged"]:
             bridged_at = k + 1
             break
     p.solve_current = True
     sim.step(False)
+    more = dict(gaps_r_max=a.gaps, bottleneck=bottleneck, direct=direct) if a.gaps > 0 else {}
     print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
                           bridged_at_step=bridged_at, bridge_root=None if info is None else info["bridge_root"], gap_x=gaps,
-                          n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro)), flush=True)
+                          n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro, **more)), flush=True)
     sim.close()
 
 
