@@ -117,7 +117,7 @@ __global__ __launch_bounds__(CL_NT) void k_cl_summaries(int N, const int *label,
     const bool mem = r >= 0;
     if (i < N) isroot[i] = (r == i) ? 1 : 0;
     const bool vac = mem && el[i] == VACANCY;
-    const int f = mem ? ((i < n_left ? 1 : 0) | (i >= N - n_right ? 2 : 0)) : 0;
+    const int f = mem ? seed_bits(i, N, n_left, n_right) : 0;
     const unsigned long long key = mem ? dbl_key(x[i]) : 0ull;
     const unsigned long long bm = __ballot(mem);
     if (bm == 0ull) return;
@@ -217,10 +217,7 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
     if (N < 0 || nn < 1 || (N > 0 && (!d_index || !d_site_element || !d_site_x || !d_label)) || ((members & 4) && N > 0 && !d_site_charge)
         || ((members & 1) && num_metals > 0 && !d_metals) || num_metals < 0)
         return dkmc_fail(3, "dkmc_find_clusters: bad arguments (N >= 0, nn >= 1, device arrays of N sites; site_charge with members bit 2)", __FILE__, __LINE__);
-    if (n_left_sites < 0) n_left_sites = 0;
-    if (n_right_sites < 0) n_right_sites = 0;
-    if (n_left_sites > N) n_left_sites = N;
-    if (n_right_sites > N) n_right_sites = N;
+    clamp_seeds(N, n_left_sites, n_right_sites);
     hipStream_t st = eng().stream;
     const int cap = g_round_cap;
     g_cl.N = N; g_cl.rounds = 0; g_cl.ms_label = g_cl.ms_sum = 0.0;

@@ -126,20 +126,26 @@ __device__ __forceinline__ double block_sum_all(double v, double *red)
     return s;
 }
 
-// ---- integer forms of doubles and relaxed agent-scope words (clusters.hip, gaps.hip) ----------
+// ---- integer forms of doubles, relaxed agent-scope words, contact seeds (clusters.hip, gaps.hip)
 // order-preserving 64-bit key of a double (unsigned compare): negative values flip every bit, the others the sign bit.  -0.0 orders below +0.0.
-__device__ __forceinline__ unsigned long long dbl_key(double v)
+__host__ __device__ __forceinline__ unsigned long long dbl_key(double v)
 {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-__device__ __forceinline__ double key_dbl(unsigned long long k)
+__host__ __device__ __forceinline__ double key_dbl(unsigned long long k)
 {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
+    return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
 }
 __device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// contact seeds: site i is a left seed (bit 0) iff i < n_left, a right seed (bit 1) iff i >= N - n_right; the entry points clamp both to [0, N]
+__device__ __forceinline__ int seed_bits(int i, int N, int n_left, int n_right) { return (i < n_left ? 1 : 0) | (i >= N - n_right ? 2 : 0); }
+inline void clamp_seeds(int N, int &n_left, int &n_right)
+{
+    n_left = n_left < 0 ? 0 : (n_left > N ? N : n_left);
+    n_right = n_right < 0 ? 0 : (n_right > N ? N : n_right);
+}
 
 // blocked form of a K pattern (kcg.hip: kblocked_build, once per pattern; device arrays)
 struct KBlocked {

@@ -5,8 +5,9 @@
 //
 // Nodes: the left-touching components together are node N, the right-touching ones node N + 1 (N too when one component touches both), every
 //   other component is the node of its label.  node_site[] holds the current node of every member, snode[] the same in cell order.
-// Cell list over the members only, cells of edge >= r_max (a hair more, so that rounding in the binning cannot put a pair within r_max two cells
-//   apart); the members' coordinates, sites and nodes are stored in cell order, so the lanes of a wave scan the same neighbour cells.
+// Cell list over the members only (binning and walk: cellgrid.h), cells of edge >= r_max (a hair more, so that rounding in the binning cannot put a
+//   pair within r_max two cells apart); the members' coordinates, sites and nodes are stored in cell order, so the lanes of a wave scan the same
+//   neighbour cells.
 // Boruvka rounds, the kernel boundary is the only synchronisation point:
 //   search   every member scans its neighbour cells and keeps its best pair by the key (d2, a, b) among the members of another node, then
 //            atomicMin(best_d2[node], key of d2);
@@ -20,23 +21,17 @@
 //   candidate, so 32 rounds suffice for any N.
 // The picked edges of all rounds are the forest; their rows (labels and contact flags of both ends) are gathered on the device, the at most
 // n_components - 1 rows are sorted by key and the L -> R tree path is walked on the host.
-#include "common.h"
+#include "cellgrid.h"
 #include <algorithm>
 #include <vector>
 
-#define GP_NT 256
+#define GP_NT CELL_NT
 #define GP_BATCH 4                   // rounds enqueued per read-back of the control block
 #define GP_ROUND_CAP 34
-#define GP_MM_BLOCKS 256
 #define GP_MAX_CELLS (1 << 24)
 
 namespace {
 
-struct GpGrid {
-    double x0, y0, z0, hx, hy, hz;   // origin and cell edge per axis
-    int nx, ny, nz, pbc;
-    double laty, latz;
-};
 struct GpCtrl {
     int any[GP_ROUND_CAP + 2];       // per round: some node had a candidate
     int n_components, n_edges, flags, pad;   // flags: bit 0 a left-touching component exists, bit 1 a right-touching one, bit 2 one touches both
@@ -70,17 +65,6 @@ __device__ __forceinline__ double gp_d2(double xa, double ya, double za, double 
     return (xx + yy) + zz;
 }
 
-__device__ __forceinline__ void gp_cell_of(const GpGrid &G, double x, double y, double z, int &cx, int &cy, int &cz)
-{
-    cx = (int)((x - G.x0) / G.hx);
-    if (G.pbc) {                        // y, z are periodic: bin the wrapped coordinate (neighbors.hip)
-        double fy = y / G.laty; fy -= floor(fy);
-        double fz = z / G.latz; fz -= floor(fz);
-        cy = (int)(fy * G.ny); cz = (int)(fz * G.nz);
-    } else { cy = (int)((y - G.y0) / G.hy); cz = (int)((z - G.z0) / G.hz); }
-    cx = min(max(cx, 0), G.nx - 1); cy = min(max(cy, 0), G.ny - 1); cz = min(max(cz, 0), G.nz - 1);
-}
-
 __device__ __forceinline__ bool gp_member(int r, int N) { return r >= 0 && r < N; }
 
 // 1. per component (indexed by its label): contact flags (bits 0, 1) and presence (bit 2); the components are counted as they appear
@@ -90,7 +74,7 @@ __global__ __launch_bounds__(GP_NT) void k_gp_flags(int N, const int *__restrict
     if (i >= N) return;
     const int r = label[i];
     if (!gp_member(r, N)) return;
-    const int want = 4 | (i < n_left ? 1 : 0) | (i >= N - n_right ? 2 : 0);
+    const int want = 4 | seed_bits(i, N, n_left, n_right);
     if ((ld_agent(&cflags[r]) & want) == want) return;        // an older value only costs the atomic
     const int old = atomicOr(&cflags[r], want);
     if (!(old & 4)) atomicAdd(&ctrl->n_components, 1);
@@ -100,7 +84,6 @@ __global__ __launch_bounds__(GP_NT) void k_gp_flags(int N, const int *__restrict
 __global__ __launch_bounds__(GP_NT) void k_gp_census(int N, const int *__restrict__ label, const int *__restrict__ cflags, const double *__restrict__ x,
                                                      const double *__restrict__ y, const double *__restrict__ z, double *box, int *cnt, GpCtrl *ctrl)
 {
-    __shared__ double red[6][GP_NT];
     __shared__ int s_cnt[GP_NT], s_fl[GP_NT];
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     int n = 0, fl = 0;
@@ -114,36 +97,19 @@ __global__ __launch_bounds__(GP_NT) void k_gp_census(int N, const int *__restric
         mn[1] = fmin(mn[1], y[i]); mx[1] = fmax(mx[1], y[i]);
         mn[2] = fmin(mn[2], z[i]); mx[2] = fmax(mx[2], z[i]);
     }
+    block_box(mn, mx, box + blockIdx.x * 6);
     const int t = threadIdx.x;
-    for (int k = 0; k < 3; ++k) { red[k][t] = mn[k]; red[3 + k][t] = mx[k]; }
     s_cnt[t] = n; s_fl[t] = fl;
     __syncthreads();
     for (int s = GP_NT / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            for (int k = 0; k < 3; ++k) { red[k][t] = fmin(red[k][t], red[k][t + s]); red[3 + k][t] = fmax(red[3 + k][t], red[3 + k][t + s]); }
-            s_cnt[t] += s_cnt[t + s]; s_fl[t] |= s_fl[t + s];
-        }
+        if (t < s) { s_cnt[t] += s_cnt[t + s]; s_fl[t] |= s_fl[t + s]; }
         __syncthreads();
     }
-    if (t < 6) box[blockIdx.x * 6 + t] = red[t][0];
     if (t == 0) { cnt[blockIdx.x] = s_cnt[0]; if (s_fl[0]) atomicOr(&ctrl->flags, s_fl[0]); }
 }
 
-// 3. cell list of the members
-__global__ __launch_bounds__(GP_NT) void k_gp_cell_count(int N, GpGrid G, const int *__restrict__ label, const double *__restrict__ x,
-                                                         const double *__restrict__ y, const double *__restrict__ z, int *cell_id, int *cell_cnt)
-{
-    const int i = blockIdx.x * GP_NT + threadIdx.x;
-    if (i >= N) return;
-    if (!gp_member(label[i], N)) { cell_id[i] = -1; return; }
-    int cx, cy, cz; gp_cell_of(G, x[i], y[i], z[i], cx, cy, cz);
-    const int c = (cx * G.ny + cy) * G.nz + cz;
-    cell_id[i] = c;
-    atomicAdd(&cell_cnt[c], 1);
-}
-
-// the members in cell order (the order inside a cell is the atomics': every result is a minimum over a cell, so it does not matter) and the
-// initial node of every site
+// 3. cell list of the members: k_cell_count (cellgrid.h) with the labels, then the members in cell order (the order inside a cell is the
+// atomics': every result is a minimum over a cell, so it does not matter) and the initial node of every site
 __global__ __launch_bounds__(GP_NT) void k_gp_scatter(int N, int M, const int *__restrict__ cell_id, const int *__restrict__ cell_start, int *cell_fill,
                                                       const int *__restrict__ label, const int *__restrict__ cflags, const GpCtrl *ctrl,
                                                       const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
@@ -186,7 +152,7 @@ __global__ __launch_bounds__(GP_NT) void k_gp_cell_uniform(int ncell, const int 
 // 4a. search.  DIRECT = 0: a round's search, every member against the members of the other nodes.  DIRECT = 1: the members of node L against
 // those of node R only (the direct gap).  A periodic axis with fewer than 3 cells is scanned whole, so every distinct neighbour cell is visited once.
 template <int DIRECT>
-__global__ __launch_bounds__(GP_NT) void k_gp_search(int M, int N, GpGrid G, double r2max, const double *__restrict__ sx, const double *__restrict__ sy,
+__global__ __launch_bounds__(GP_NT) void k_gp_search(int M, int N, CellGrid G, double r2max, const double *__restrict__ sx, const double *__restrict__ sy,
                                                      const double *__restrict__ sz, const int *__restrict__ ssite, const int *__restrict__ snode,
                                                      const int *__restrict__ cell_start, const int *__restrict__ cell_cnt,
                                                      const int *__restrict__ cell_node, int skip, unsigned long long *best_d2,
@@ -201,37 +167,27 @@ __global__ __launch_bounds__(GP_NT) void k_gp_search(int M, int N, GpGrid G, dou
         if (!DIRECT || mynode == N) {
             const int i = ssite[s];
             const double xi = sx[s], yi = sy[s], zi = sz[s];
-            int cx, cy, cz; gp_cell_of(G, xi, yi, zi, cx, cy, cz);
-            const bool wy = G.pbc && G.ny < 3, wz = G.pbc && G.nz < 3;
-            const int y0 = wy ? 0 : cy - 1, y1 = wy ? G.ny - 1 : cy + 1, z0 = wz ? 0 : cz - 1, z1 = wz ? G.nz - 1 : cz + 1;
-            for (int ax = max(cx - 1, 0); ax <= min(cx + 1, G.nx - 1); ++ax)
-                for (int qy = y0; qy <= y1; ++qy) {
-                    int ay = qy;
-                    if (G.pbc) ay = (ay + G.ny) % G.ny; else if (ay < 0 || ay >= G.ny) continue;
-                    for (int qz = z0; qz <= z1; ++qz) {
-                        int az = qz;
-                        if (G.pbc) az = (az + G.nz) % G.nz; else if (az < 0 || az >= G.nz) continue;
-                        const int c = (ax * G.ny + ay) * G.nz + az;
-                        if (skip) {
-                            const int u = cell_node[c];
-                            if (DIRECT ? (u >= 0 && u != N + 1) : (u == mynode)) continue;
-                        }
-                        const int t0 = cell_start[c], t1 = t0 + cell_cnt[c];
-                        for (int t = t0; t < t1; ++t) {
-                            const int other = snode[t];
-                            if (DIRECT ? (other != N + 1) : (other == mynode)) continue;
-                            const int j = ssite[t];
-                            const double xj = sx[t], yj = sy[t], zj = sz[t];
-                            const bool lo = i < j;
-                            const double d2 = lo ? gp_d2(xi, yi, zi, xj, yj, zj, G.laty, G.latz, G.pbc) : gp_d2(xj, yj, zj, xi, yi, zi, G.laty, G.latz, G.pbc);
-                            ++tests;
-                            if (!(d2 <= r2max)) continue;
-                            const unsigned long long k = dbl_key(d2);
-                            const unsigned long long p = ((unsigned long long)(unsigned)(lo ? i : j) << 32) | (unsigned)(lo ? j : i);
-                            if (k < bk || (k == bk && p < bp)) { bk = k; bp = p; }
-                        }
-                    }
+            int cx, cy, cz; cell_of(G, xi, yi, zi, cx, cy, cz);
+            for_each_neighbor_cell(G, cx, cy, cz, [&](int c) {
+                if (skip) {
+                    const int u = cell_node[c];
+                    if (DIRECT ? (u >= 0 && u != N + 1) : (u == mynode)) return;
                 }
+                const int t0 = cell_start[c], t1 = t0 + cell_cnt[c];
+                for (int t = t0; t < t1; ++t) {
+                    const int other = snode[t];
+                    if (DIRECT ? (other != N + 1) : (other == mynode)) continue;
+                    const int j = ssite[t];
+                    const double xj = sx[t], yj = sy[t], zj = sz[t];
+                    const bool lo = i < j;
+                    const double d2 = lo ? gp_d2(xi, yi, zi, xj, yj, zj, G.laty, G.latz, G.pbc) : gp_d2(xj, yj, zj, xi, yi, zi, G.laty, G.latz, G.pbc);
+                    ++tests;
+                    if (!(d2 <= r2max)) continue;
+                    const unsigned long long k = dbl_key(d2);
+                    const unsigned long long p = ((unsigned long long)(unsigned)(lo ? i : j) << 32) | (unsigned)(lo ? j : i);
+                    if (k < bk || (k == bk && p < bp)) { bk = k; bp = p; }
+                }
+            });
             if (bk != GP_NONE && bk < __hip_atomic_load(&best_d2[mynode], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&best_d2[mynode], bk);
         }
         mykey[s] = bk; mypair[s] = bp;
@@ -341,14 +297,6 @@ void gap_reset()
     g_gap.e_d2.clear(); g_gap.c_d2.clear();
 }
 
-// key_dbl on the host
-double gp_key_value(unsigned long long k)
-{
-    const unsigned long long bits = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v; memcpy(&v, &bits, sizeof(v));
-    return v;
-}
-
 // cells along an extent at edge h; -1 where they would be too many
 int gp_cells(double ext, double h)
 {
@@ -410,10 +358,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
     if (N < 0 || N > 0x7ffffff0 || (N > 0 && (!d_x || !d_y || !d_z || !d_label)) || !(r_max > 0.0) || !isfinite(r_max)
         || (pbc && (!h_lattice || !(h_lattice[1] > 0.0) || !(h_lattice[2] > 0.0) || !isfinite(h_lattice[1]) || !isfinite(h_lattice[2]))))
         return dkmc_fail(3, "dkmc_find_gaps: bad arguments (N >= 0, device arrays of N sites, r_max finite and > 0, a positive lattice with pbc)", __FILE__, __LINE__);
-    if (n_left_sites < 0) n_left_sites = 0;
-    if (n_right_sites < 0) n_right_sites = 0;
-    if (n_left_sites > N) n_left_sites = N;
-    if (n_right_sites > N) n_right_sites = N;
+    clamp_seeds(N, n_left_sites, n_right_sites);
     gap_reset();
     if (N == 0) { g_gap.valid = 1; return 0; }
     hipStream_t st = eng().stream;
@@ -422,30 +367,28 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
 
     // components, their contact flags, the members' box
     int *persite = (int *)scratch(S_GAP_SITE, 3 * n * sizeof(int));
-    char *ctrl_raw = (char *)scratch(S_GAP_CTRL, sizeof(GpCtrl) + (size_t)GP_MM_BLOCKS * (6 * sizeof(double) + sizeof(int)));
+    char *ctrl_raw = (char *)scratch(S_GAP_CTRL, sizeof(GpCtrl) + (size_t)CELL_BOX_BLOCKS * (6 * sizeof(double) + sizeof(int)));
     if (!persite || !ctrl_raw) return eng().err_code;
     int *cflags = persite, *cell_id = persite + n, *node_site = persite + 2 * n;
     GpCtrl *ctrl = (GpCtrl *)ctrl_raw;
     double *box = (double *)(ctrl_raw + sizeof(GpCtrl));
-    int *cnt = (int *)(box + GP_MM_BLOCKS * 6);
+    int *cnt = (int *)(box + CELL_BOX_BLOCKS * 6);
     HIPCHK(hipMemsetAsync(ctrl, 0, sizeof(GpCtrl), st));
     HIPCHK(hipMemsetAsync(cflags, 0, n * sizeof(int), st));
     hipLaunchKernelGGL(k_gp_flags, dim3(site_blocks), dim3(GP_NT), 0, st, N, d_label, n_left_sites, n_right_sites, cflags, ctrl);
-    hipLaunchKernelGGL(k_gp_census, dim3(GP_MM_BLOCKS), dim3(GP_NT), 0, st, N, d_label, (const int *)cflags, d_x, d_y, d_z, box, cnt, ctrl);
+    hipLaunchKernelGGL(k_gp_census, dim3(CELL_BOX_BLOCKS), dim3(GP_NT), 0, st, N, d_label, (const int *)cflags, d_x, d_y, d_z, box, cnt, ctrl);
     KCHK();
-    static double h_box[GP_MM_BLOCKS * 6];
-    static int h_cnt[GP_MM_BLOCKS];
+    static double h_box[CELL_BOX_BLOCKS * 6];
+    static int h_cnt[CELL_BOX_BLOCKS];
     GpCtrl h_ctrl;
     HIPCHK(hipMemcpyAsync(h_box, box, sizeof(h_box), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&h_ctrl, ctrl, sizeof(GpCtrl), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    double mn[3], mx[3];
+    fold_boxes(h_box, mn, mx);
     long long members = 0;
-    for (int b = 0; b < GP_MM_BLOCKS; ++b) {
-        members += h_cnt[b];
-        for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], h_box[b * 6 + k]); mx[k] = fmax(mx[k], h_box[b * 6 + 3 + k]); }
-    }
+    for (int b = 0; b < CELL_BOX_BLOCKS; ++b) members += h_cnt[b];
     if (members == 0) { g_gap.valid = 1; return 0; }
     if (!isfinite(mn[0]) || !isfinite(mx[0]) || !isfinite(mn[1]) || !isfinite(mx[1]) || !isfinite(mn[2]) || !isfinite(mx[2]))
         return dkmc_fail(3, "dkmc_find_gaps: a member site has a coordinate that is not finite", __FILE__, __LINE__);
@@ -453,7 +396,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
     const bool has_l = h_ctrl.flags & 1, has_r = h_ctrl.flags & 2, bridged = h_ctrl.flags & 4;
 
     // the grid: cells of edge >= r_max (2^-30 more), doubled until the cells are few enough
-    GpGrid G; G.pbc = pbc ? 1 : 0; G.laty = pbc ? h_lattice[1] : 1.0; G.latz = pbc ? h_lattice[2] : 1.0;
+    CellGrid G; G.pbc = pbc ? 1 : 0; G.laty = pbc ? h_lattice[1] : 1.0; G.latz = pbc ? h_lattice[2] : 1.0;
     G.x0 = mn[0]; G.y0 = mn[1]; G.z0 = mn[2];
     long long ncell = 0;
     for (double h = r_max * (1.0 + 0x1p-30);; h *= 2.0) {
@@ -493,7 +436,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
 
     HIPCHK(hipMemsetAsync(cells, 0, 3 * nc * sizeof(int), st));
     HIPCHK(hipMemsetAsync(best_d2[0], 0xff, 4 * nnode * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_gp_cell_count, dim3(site_blocks), dim3(GP_NT), 0, st, N, G, d_label, d_x, d_y, d_z, cell_id, cell_cnt);
+    hipLaunchKernelGGL(k_cell_count, dim3(site_blocks), dim3(GP_NT), 0, st, N, G, d_label, d_x, d_y, d_z, cell_id, cell_cnt);
     KCHK();
     if (int rc = dkmc_exclusive_scan_i32(cell_cnt, cell_start, (int)ncell, nullptr)) return rc;
     hipLaunchKernelGGL(k_gp_scatter, dim3(site_blocks), dim3(GP_NT), 0, st, N, M, (const int *)cell_id, (const int *)cell_start, cell_fill, d_label,
@@ -565,7 +508,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
     for (int k = 0; k < E; ++k) {
         const int e = order[k];
         g_gap.e_a.push_back((int)(h_pair[e] >> 32)); g_gap.e_b.push_back((int)(h_pair[e] & 0xffffffffull));
-        g_gap.e_d2.push_back(gp_key_value(h_key[e]));
+        g_gap.e_d2.push_back(key_dbl(h_key[e]));
         node_a[k] = node_of(h_row[4 * e], h_row[4 * e + 2]); node_b[k] = node_of(h_row[4 * e + 1], h_row[4 * e + 3]);
         g_gap.e_ra.push_back(h_row[4 * e]); g_gap.e_rb.push_back(h_row[4 * e + 1]);
     }
@@ -574,7 +517,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
     else if (has_l && has_r) {
         gap_chain(node_a, node_b);
         if (h_ctrl.direct_key != GP_NONE) {
-            g_gap.d2x2[1] = gp_key_value(h_ctrl.direct_key);
+            g_gap.d2x2[1] = key_dbl(h_ctrl.direct_key);
             g_gap.info[6] = (long long)(h_ctrl.direct_pair >> 32); g_gap.info[7] = (long long)(h_ctrl.direct_pair & 0xffffffffull);
         }
     }

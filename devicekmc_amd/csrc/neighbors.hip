@@ -3,57 +3,17 @@
 // row i holds every j != i with site_dist(i, j) < nn_dist in ascending j, padded with -1 to the global maximum nn.
 // Cell list with cells of edge >= nn_dist: O(N) work, same distance arithmetic as gpu_solvers.h:225-257, so the
 // result is identical to the reference's (asserted against the oracle in tests/test_gpu_parity.py).
-#include "common.h"
-#include <vector>
-
-struct CellGrid {
-    double x0, y0, z0, hx, hy, hz;     // origin and cell edge per axis
-    int nx, ny, nz, pbc;
-    double laty, latz;
-};
-
-__device__ __forceinline__ void cell_of(const CellGrid &G, double x, double y, double z, int &cx, int &cy, int &cz)
-{
-    cx = (int)((x - G.x0) / G.hx);
-    if (G.pbc) {                        // y, z are periodic: bin the wrapped coordinate
-        double fy = y / G.laty; fy -= floor(fy);
-        double fz = z / G.latz; fz -= floor(fz);
-        cy = (int)(fy * G.ny); cz = (int)(fz * G.nz);
-    } else { cy = (int)((y - G.y0) / G.hy); cz = (int)((z - G.z0) / G.hz); }
-    cx = min(max(cx, 0), G.nx - 1); cy = min(max(cy, 0), G.ny - 1); cz = min(max(cz, 0), G.nz - 1);
-}
+#include "cellgrid.h"
 
 __global__ void k_minmax(int N, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z, double *out)
 {
-    __shared__ double red[6][256];
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
+    for (int i = blockIdx.x * CELL_NT + threadIdx.x; i < N; i += gridDim.x * CELL_NT) {
         mn[0] = fmin(mn[0], x[i]); mx[0] = fmax(mx[0], x[i]);
         mn[1] = fmin(mn[1], y[i]); mx[1] = fmax(mx[1], y[i]);
         mn[2] = fmin(mn[2], z[i]); mx[2] = fmax(mx[2], z[i]);
     }
-    for (int k = 0; k < 3; ++k) { red[k][threadIdx.x] = mn[k]; red[3 + k][threadIdx.x] = mx[k]; }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s)
-            for (int k = 0; k < 3; ++k) {
-                red[k][threadIdx.x] = fmin(red[k][threadIdx.x], red[k][threadIdx.x + s]);
-                red[3 + k][threadIdx.x] = fmax(red[3 + k][threadIdx.x], red[3 + k][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 6) out[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-__global__ void k_cell_count(int N, CellGrid G, const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ z,
-                             int *__restrict__ cell_id, int *__restrict__ cell_cnt)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    int cx, cy, cz; cell_of(G, x[i], y[i], z[i], cx, cy, cz);
-    const int c = (cx * G.ny + cy) * G.nz + cz;
-    cell_id[i] = c;
-    atomicAdd(&cell_cnt[c], 1);
+    block_box(mn, mx, out + blockIdx.x * 6);
 }
 
 __global__ void k_cell_scatter(int N, const int *__restrict__ cell_id, const int *__restrict__ cell_start, int *__restrict__ cell_fill,
@@ -77,28 +37,17 @@ __global__ __launch_bounds__(128) void k_neigh(int N, CellGrid G, double nn_dist
     int cx, cy, cz; cell_of(G, xi, yi, zi, cx, cy, cz);
     int n = 0;
     int *row = FILL ? neigh + (size_t)i * nn : nullptr;
-    for (int dx = -1; dx <= 1; ++dx) {
-        const int ax = cx + dx;
-        if (ax < 0 || ax >= G.nx) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            int ay = cy + dy;
-            if (G.pbc) ay = (ay + G.ny) % G.ny; else if (ay < 0 || ay >= G.ny) continue;
-            for (int dz = -1; dz <= 1; ++dz) {
-                int az = cz + dz;
-                if (G.pbc) az = (az + G.nz) % G.nz; else if (az < 0 || az >= G.nz) continue;
-                const int c = (ax * G.ny + ay) * G.nz + az;
-                const int s0 = cell_start[c], s1 = s0 + cell_cnt[c];
-                for (int s = s0; s < s1; ++s) {
-                    const int j = cell_sites[s];
-                    if (j == i) continue;
-                    if (site_dist(xi, yi, zi, x[j], y[j], z[j], G.laty, G.latz, G.pbc) < nn_dist) {
-                        if (FILL) { if (n < nn) row[n] = j; }
-                        ++n;
-                    }
-                }
+    for_each_neighbor_cell(G, cx, cy, cz, [&](int c) {
+        const int s0 = cell_start[c], s1 = s0 + cell_cnt[c];
+        for (int s = s0; s < s1; ++s) {
+            const int j = cell_sites[s];
+            if (j == i) continue;
+            if (site_dist(xi, yi, zi, x[j], y[j], z[j], G.laty, G.latz, G.pbc) < nn_dist) {
+                if (FILL) { if (n < nn) row[n] = j; }
+                ++n;
             }
         }
-    }
+    });
     if (!FILL) { atomicMax(max_nn, n); return; }
     const int cnt = min(n, nn);
     for (int a = 1; a < cnt; ++a) {                       // insertion sort of the thread's own row (<= nn entries)
@@ -117,16 +66,15 @@ extern "C" int dkmc_build_neighbor_index(int N, const double *d_x, const double 
     Engine &e = eng(); hipStream_t st = e.stream;
     if (N <= 0) return dkmc_fail(13, "build_neighbor_index: no sites", __FILE__, __LINE__);
     // bounding box
-    const int nb = 256;
-    double *mm = (double *)scratch(S_MISC0, (size_t)nb * 6 * 8);
+    double *mm = (double *)scratch(S_MISC0, sizeof(double) * CELL_BOX_BLOCKS * 6);
     if (!mm) return e.err_code;
-    hipLaunchKernelGGL(k_minmax, dim3(nb), dim3(256), 0, st, N, d_x, d_y, d_z, mm);
-    std::vector<double> h((size_t)nb * 6);
-    HIPCHK(hipMemcpyAsync(h.data(), mm, h.size() * 8, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_minmax, dim3(CELL_BOX_BLOCKS), dim3(CELL_NT), 0, st, N, d_x, d_y, d_z, mm);
+    double h[CELL_BOX_BLOCKS * 6], mn[3], mx[3];
+    HIPCHK(hipMemcpyAsync(h, mm, sizeof(h), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = 0; b < nb; ++b) for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], h[b * 6 + k]); mx[k] = fmax(mx[k], h[b * 6 + 3 + k]); }
-    CellGrid G; G.pbc = pbc; G.laty = h_lattice[1]; G.latz = h_lattice[2];
+    fold_boxes(h, mn, mx);
+    // the non-periodic distance and binning never read laty, latz
+    CellGrid G; G.pbc = pbc; G.laty = pbc ? h_lattice[1] : 1.0; G.latz = pbc ? h_lattice[2] : 1.0;
     G.x0 = mn[0]; G.y0 = mn[1]; G.z0 = mn[2];
     G.nx = (int)((mx[0] - mn[0]) / nn_dist) + 1; G.hx = nn_dist;
     if (pbc) {
@@ -146,10 +94,10 @@ extern "C" int dkmc_build_neighbor_index(int N, const double *d_x, const double 
     int *cell_start = cell_cnt + (ncell + 4), *cell_fill = cell_start + (ncell + 4);
     HIPCHK(hipMemsetAsync(cell_cnt, 0, (size_t)(ncell + 4) * 4 * 3, st));
     HIPCHK(hipMemsetAsync(mx_nn, 0, 16, st));
-    const int gb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_cell_count, dim3(gb), dim3(256), 0, st, N, G, d_x, d_y, d_z, cell_id, cell_cnt);
+    const int gb = (N + CELL_NT - 1) / CELL_NT;
+    hipLaunchKernelGGL(k_cell_count, dim3(gb), dim3(CELL_NT), 0, st, N, G, (const int *)nullptr, d_x, d_y, d_z, cell_id, cell_cnt);
     int rc = dkmc_exclusive_scan_i32(cell_cnt, cell_start, (int)ncell, nullptr); if (rc) return rc;
-    hipLaunchKernelGGL(k_cell_scatter, dim3(gb), dim3(256), 0, st, N, (const int *)cell_id, (const int *)cell_start, cell_fill, cell_sites);
+    hipLaunchKernelGGL(k_cell_scatter, dim3(gb), dim3(CELL_NT), 0, st, N, (const int *)cell_id, (const int *)cell_start, cell_fill, cell_sites);
     const int gn = (N + 127) / 128;
     if (!d_neigh_out) {
         hipLaunchKernelGGL((k_neigh<0>), dim3(gn), dim3(128), 0, st, N, G, nn_dist, d_x, d_y, d_z, (const int *)cell_start, (const int *)cell_cnt,

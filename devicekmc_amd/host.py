@@ -337,11 +337,7 @@ class Device:
         tensor of N * nn, nn) -- e.g. build_neighbor_index_gpu at a larger radius, moved to the device -- for a gap-tolerant filament.  n_left /
         n_right: sites of the contact seeds, by default get_num_in_contacts(num_atoms_first_layer) on either side.  Changes nothing in gpubuf.
         Returns (labels: host int32 array, table, info) and keeps them as site_cluster, cluster_table, cluster_info."""
-        p = self.p
-        if n_left is None:
-            n_left = self.get_num_in_contacts(p.num_atoms_first_layer, "left")
-        if n_right is None:
-            n_right = self.get_num_in_contacts(p.num_atoms_first_layer, "right")
+        n_left, n_right = self.contact_seeds(n_left, n_right)
         index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
         label, table, info = find_clusters(index, nn, gpubuf.site_element, gpubuf.site_charge, gpubuf.site_x, gpubuf.metal_types, members,
                                            n_left, n_right, capacity)
@@ -354,15 +350,11 @@ class Device:
         the default members is run if there is none -- or over label (int32 device tensor of N): the island graph within r_max, the tunnelling
         chain between the contact clusters with its bottleneck hop, and the direct tip-to-tip gap, with this device's pbc and lattice and the
         contact seeds of find_clusters.  Changes nothing in gpubuf.  Returns (edges, chain, info) and keeps them as gap_edges, gap_chain, gap_info."""
-        p = self.p
         if label is None:
             if getattr(self, "_cluster_label", None) is None:
                 self.find_clusters(gpubuf, n_left=n_left, n_right=n_right)
             label = self._cluster_label
-        if n_left is None:
-            n_left = self.get_num_in_contacts(p.num_atoms_first_layer, "left")
-        if n_right is None:
-            n_right = self.get_num_in_contacts(p.num_atoms_first_layer, "right")
+        n_left, n_right = self.contact_seeds(n_left, n_right)
         self.gap_edges, self.gap_chain, self.gap_info = find_gaps(label, gpubuf.site_x, gpubuf.site_y, gpubuf.site_z, self.lattice, self.pbc,
                                                                   n_left, n_right, r_max)
         return self.gap_edges, self.gap_chain, self.gap_info
@@ -403,6 +395,13 @@ class Device:
         if contact_name == "left":
             return 0 if num_atoms_contact <= 0 else int(nondef[num_atoms_contact - 1]) + 1
         return 0 if num_atoms_contact <= 0 else N - int(nondef[len(nondef) - num_atoms_contact])
+
+    def contact_seeds(self, n_left=None, n_right=None):
+        """(n_left, n_right) of the contact seeds of find_clusters / find_gaps: a given value as it is, otherwise
+        get_num_in_contacts(num_atoms_first_layer) on that side."""
+        k = self.p.num_atoms_first_layer
+        return (self.get_num_in_contacts(k, "left") if n_left is None else n_left,
+                self.get_num_in_contacts(k, "right") if n_right is None else n_right)
 
     # heat_solver.cpp:40-246 (kmc_main.cpp:90-94: once, when solve_heating_local is set)
     def constructLaplacian(self, gpubuf: GPUBuffers, p: KMCParameters):

@@ -526,6 +526,34 @@ def test_neighbor_index_gpu(cell_2p5, dev_7p5, hip):
     assert d1.max_num_neighbors == d2.max_num_neighbors and np.array_equal(d1.neigh_idx, d2.neigh_idx)
 
 
+def _small_grid(case):
+    """(x, y, z, lattice, pbc) of the small grids of the neighbour index, nn_dist = 3.5: a = exactly 3 x 3 periodic cells in y, z, the smallest
+    grid the index accepts (every wrap goes to a distinct cell); b = 4 x 3 periodic cells and one cell along x; c = one cell in all, no pbc."""
+    d = 3.5
+    N, ext, pbc = {"a": (257, (2.4 * d, 3 * d + 0.01, 3 * d + 0.01), 1), "b": (257, (1.0 * d, 4.2 * d, 3.3 * d), 1),
+                   "c": (65, (0.9 * d, 0.9 * d, 0.9 * d), 0)}[case]
+    rng = np.random.default_rng(7)
+    x, y, z = (rng.uniform(0.0, e, N) for e in ext)        # nn = 64 in all three; the pair nearest the cut is 1.3e-5 from it (case a)
+    return x, y, z, np.array(ext), pbc
+
+
+@pytest.mark.parametrize("case", ["a", "b", "c", "refused"])
+def test_neighbor_index_small_grids(hip, case):
+    """The index on the smallest grids its cell walk meets, rows and nn equal to the oracle's; "refused": a periodic box narrower than 3 cells
+    is still an error, and the call after it is not affected."""
+    from devicekmc_amd.lib import DeviceKMCError
+    from oracle import oracle as oc
+    host, L = hip
+    x, y, z, lat, pbc = _small_grid("a" if case == "refused" else case)
+    if case == "refused":
+        narrow = lat.copy(); narrow[1] = 2.9 * 3.5
+        with pytest.raises(DeviceKMCError, match="narrower than 3 cells"):
+            host.build_neighbor_index_gpu(x, y, z, narrow, True, 3.5)
+    neigh, nn = host.build_neighbor_index_gpu(x, y, z, lat, bool(pbc), 3.5)
+    on, onn = oc.build_neighbors(x, y, z, lat, bool(pbc), 3.5)
+    assert nn == onn and np.array_equal(neigh, on)
+
+
 def test_superstep_pbc_and_heating(cell_2p5, hip):
     """The 2.5 nm cell is periodic in y,z with the period of parameters.txt: run it with pbc = 1 (wrapped distances in the
     neighbour list, pair sum, event table and X) and global heating on; same events, T_bg and current as the oracle."""

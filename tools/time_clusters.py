@@ -40,7 +40,7 @@ def child(name, calls, warmup_calls, steps, warmup, out_dir):
         sim.step(False)
     step_ms = [1e3 * sim.step(True) for _ in range(steps)]
     dev, gb, p = sim.dev, sim.gb, sim.p
-    nl, nr = dev.get_num_in_contacts(p.num_atoms_first_layer, "left"), dev.get_num_in_contacts(p.num_atoms_first_layer, "right")
+    nl, nr = dev.contact_seeds()
     members = host.METAL | host.VACANCY
 
     def analyse():

@@ -36,7 +36,7 @@ def child(name, radii, calls, warmup_calls, steps, warmup, route_max_gib, out_di
         sim.step(False)
     step_ms = [1e3 * sim.step(True) for _ in range(steps)]
     dev, gb, p = sim.dev, sim.gb, sim.p
-    nl, nr = dev.get_num_in_contacts(p.num_atoms_first_layer, "left"), dev.get_num_in_contacts(p.num_atoms_first_layer, "right")
+    nl, nr = dev.contact_seeds()
     members = host.METAL | host.VACANCY
     label, _, cinfo = host.find_clusters(gb.neigh_idx, gb.nn_, gb.site_element, gb.site_charge, gb.site_x, gb.metal_types, members, nl, nr, capacity=0)
     lat = np.ascontiguousarray(p.lattice, dtype=np.float64)
