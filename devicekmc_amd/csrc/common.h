@@ -184,6 +184,9 @@ struct Engine {
     int x_poly = X_POLY_DEFAULT;                // degree d of the split polynomial preconditioner of the block-CG (dkmc_set_x_poly; xtb_precond.h): the loop runs on L A L, L = the degree-d Chebyshev interpolant of (1 - x)^(-1/2) in N (neighbour part); 0 = off.  With x_poly_auto it is the base degree: on (> 0) or off, the one-GPU loop takes its degree from the system size
     int x_poly_auto = 1;           // 1 (default): the one-GPU preconditioned loop takes its degree from the rows of the system (xtb_poly_rule, xtb_precond.h); dkmc_set_x_poly(d) pins d and clears it, dkmc_set_x_poly_auto(1) sets it again
     int x_poly_rows[2] = {0, 0};   // test aid (dkmc_set_x_poly_auto_rows): breakpoints of that rule; {0, 0} = the measured ones
+    int x_poly_form = 2;           // form of the one-GPU preconditioned loop (dkmc_set_x_poly_form; xtb.hip): 0 = split, CG on L A L (2 d N products per sweep); 1 = one polynomial q(N) ~ (I - N)^-1 as M^-1, in transformed variables (n(d) products); 2 = one polynomial where the degree comes from the rule (x_poly_auto), split where a degree is pinned
+    int x_poly1_degree = 0;        // measurement aid (dkmc_debug_set_x_poly1_degree): > 0 overrides the degree n(d) of the one-polynomial form
+    int x_poly_form_used = 0, x_poly_products = 0;      // the last one-GPU block solve: 1 = it ran the one-polynomial form; its N products per sweep (dkmc_get_x_poly_form_used / _products)
     int x_slab_poly = 0;           // 1: the slab-distributed block-CG (> 1 rank, x_slab) runs on L A L too (dkmc_set_x_slab_poly; xtb_slab.inc); 0 (default): plain
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
@@ -256,7 +259,7 @@ enum {
     S_XT_T_NITEMW, S_XT_T_ITEMS, S_XT_T_SPLIT, S_XT_T_COLPART, S_XT_T_MISC,
     S_XTB_PANELS, S_XTB_QS, S_XTB_ROWPART, S_XTB_COLPART, S_XTB_GRAM, S_XTB_SMALL, S_XTB_XI,
     S_XTB_SLAB_BOX, S_XTB_SLAB_TAB, S_XTB_SLAB_OWNER, S_XTB_SLAB_LISTS, S_XTB_SLAB_SDST, S_XTB_SLAB_FLAG, S_XTB_SLAB_RLISTS, S_XTB_SLAB_GX, S_XTB_SLAB_S1, S_XTB_SLAB_S3, S_XTB_SLAB_R3,
-    S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z,
+    S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z, S_XTB_PRE_U,
     S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
     S_XTL_CELLS, S_XTL_TFLAG, S_XTL_TVAL32, S_XTL_TILES, S_XTL_WRANGE, S_XTL_NITEMW, S_XTL_ITEMS, S_XTL_SPLIT,      // live view of the tile list (xt_live.h)
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,

@@ -74,6 +74,11 @@ void dkmc_set_x_poly(int degree) { eng().x_poly = degree < 0 ? 0 : (degree > 16 
 int dkmc_get_x_poly(void) { return eng().x_poly; }
 void dkmc_set_x_poly_auto(int on) { Engine &e = eng(); e.x_poly_auto = on ? 1 : 0; if (on && e.x_poly <= 0) e.x_poly = X_POLY_DEFAULT; }
 int dkmc_get_x_poly_auto(void) { return eng().x_poly_auto; }
+void dkmc_set_x_poly_form(int form) { eng().x_poly_form = form == 1 ? 1 : (form == 2 ? 2 : 0); }
+int dkmc_get_x_poly_form(void) { return eng().x_poly_form; }
+int dkmc_get_x_poly_form_used(void) { return eng().x_poly_form_used; }
+int dkmc_get_x_poly_products(void) { return eng().x_poly_products; }
+void dkmc_debug_set_x_poly1_degree(int n) { eng().x_poly1_degree = n < 0 ? 0 : (n > 20 ? 20 : n); }
 void dkmc_set_x_poly_auto_rows(int n0, int n1) { Engine &e = eng(); e.x_poly_rows[0] = n0 > 0 ? n0 : 0; e.x_poly_rows[1] = n1 > e.x_poly_rows[0] ? n1 : e.x_poly_rows[0]; }
 void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }
 int dkmc_get_x_apply_form(void) { return eng().x_apply_form; }

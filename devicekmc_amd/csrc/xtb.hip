@@ -36,7 +36,8 @@
 // combined record; row sums (32 x s) go to a grid-indexed array per tile.
 // Only column 0 of Y is kept (a vector): the auxiliary solutions are never needed.  The neighbour part gathers P and the scaling, so no
 // scaled full-length copy of P exists; the compact scaled copy over S (QS) feeds the tiles.
-// The split polynomial preconditioner (dkmc_set_x_poly) and the row gather the neighbour part shares with it: xtb_precond.h.
+// The split polynomial preconditioner (dkmc_set_x_poly) and the row gather the neighbour part shares with it: xtb_precond.h.  Its one-polynomial form
+// (dkmc_set_x_poly_form: the same loop in transformed variables, one q(N) per sweep): k_xtb_gram1, k_xtb_step1 and the `one` branches of xtb_cg_body.
 #include "xtiles.h"
 #include "slab.h"
 #include <hip/hip_ext.h>
@@ -47,6 +48,7 @@
 
 #define XB_SP 16                      // vectors per panel row (padded block width)
 #define XB_MAXPOLY 16                 // largest degree of the split polynomial preconditioner (dkmc_set_x_poly)
+#define XB_MAXPOLY1 20                // largest degree of the one-polynomial form (dkmc_set_x_poly_form): what monomial Horner carries
 #define XB_DSPLIT 8                   // workgroups per driver row of Xs
 #define XB_NG 6                       // Gram matrices per pass: P'T, P'R, T'R, T'T, R'R, P'P
 typedef double dbl4 __attribute__((ext_vector_type(4)));
@@ -1131,6 +1133,126 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_step(int m, int it, const double 
         }
     }
 }
+// ---- one-polynomial form (dkmc_set_x_poly_form): M^-1 = q(N) ~ (I - N)^-1 in the place of L^2, the loop in the variables Pt = L P, Rt = L^-1 R ------
+// so that L is never applied: Q = A Pt (tiles + neighbour part + fold), U = q(N) Q, Z = M^-1 Rt and Pi = M Pt kept by recurrence.  The six Gram matrices
+// of the split form are then  P'T = Pt'Q, P'R = Pt'Rt, T'R = Q'Z, T'T = Q'U, R'R = Rt'Z, P'P = Pt'Pi  -- k_xtb_gred and k_xtb_small take them as they are.
+// Gram pass over [m][16] panels: four rows per matrix instruction with the ROW on the k index, a wave's rows of its workgroup's chunk in one chain, the
+// four waves and then k_xtb_gred in a fixed order -- the grouping of the non-S rows of k_xtb_rows.  Q'U, Rt'Z and Pt'Pi are symmetric only to rounding:
+// every workgroup stores (G + G') / 2 of its partial, so their sums are symmetric bit for bit.
+__global__ __launch_bounds__(XT_NT) void k_xtb_gram1(int m, const double *__restrict__ Pt, const double *__restrict__ Pi, const double *__restrict__ Q,
+                                                     const double *__restrict__ U, const double *__restrict__ Rt, const double *__restrict__ Z,
+                                                     double *__restrict__ gpart, const XCtrl *ctrl)
+{
+    __shared__ double lg[4][XB_NG / 2][4][64];
+    if (ctrl->done) return;                                                    // uniform over the launch
+    const int v = threadIdx.x & 15, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    dbl4 G[XB_NG];
+#pragma unroll
+    for (int g = 0; g < XB_NG; ++g) G[g] = (dbl4)(0.0);
+    const int chunk = ((m + (int)gridDim.x - 1) / (int)gridDim.x + 3) & ~3;
+    const long long i0l = (long long)blockIdx.x * chunk;
+    const int i0 = (int)(i0l < m ? i0l : m), i1 = (int)(i0l + chunk < m ? i0l + chunk : m);
+    for (int r0 = i0 + 4 * wv; r0 < i1; r0 += 64) {
+        double pv[4], iv[4], qv[4], uv[4], rv[4], zv[4]; bool in[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int row = r0 + 16 * u + (lane >> 4);
+            in[u] = row < i1;
+            const size_t o = (size_t)(in[u] ? row : i0) * XB_SP + v;               // (i0 < i1 <= m inside the loop)
+            pv[u] = Pt[o]; iv[u] = Pi[o]; qv[u] = Q[o]; uv[u] = U[o]; rv[u] = Rt[o]; zv[u] = Z[o];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (r0 + 16 * u >= i1) break;                                     // uniform over the wave
+            const double p_ = in[u] ? pv[u] : 0.0, i_ = in[u] ? iv[u] : 0.0, q_ = in[u] ? qv[u] : 0.0, u_ = in[u] ? uv[u] : 0.0, r_ = in[u] ? rv[u] : 0.0,
+                         z_ = in[u] ? zv[u] : 0.0;
+            G[0] = XB_MFMA(p_, q_, G[0]); G[1] = XB_MFMA(p_, r_, G[1]); G[2] = XB_MFMA(q_, z_, G[2]);
+            G[3] = XB_MFMA(q_, u_, G[3]); G[4] = XB_MFMA(r_, z_, G[4]); G[5] = XB_MFMA(p_, i_, G[5]);
+        }
+    }
+    // one partial per workgroup: the four waves added in a fixed order; entry (register u, lane l) is (i = l / 16 + 4 u, j = l % 16), that is 16 i + j
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        __syncthreads();
+#pragma unroll
+        for (int g = 0; g < XB_NG / 2; ++g)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) lg[wv][g][u][lane] = G[h * (XB_NG / 2) + g][u];
+        __syncthreads();
+        for (int e = threadIdx.x; e < (XB_NG / 2) * 256; e += XT_NT) {
+            const int g = e >> 8, x = e & 255, u = x >> 6, l = x & 63;
+            double a = (lg[0][g][u][l] + lg[1][g][u][l]) + (lg[2][g][u][l] + lg[3][g][u][l]);
+            if (h == 1) {                                                     // matrices 3, 4, 5: the symmetric ones
+                const int xt = ((x & 15) << 4) | (x >> 4), ut = xt >> 6, lt = xt & 63;
+                a = 0.5 * (a + ((lg[0][g][ut][lt] + lg[1][g][ut][lt]) + (lg[2][g][ut][lt] + lg[3][g][ut][lt])));
+            }
+            gpart[(size_t)blockIdx.x * (XB_NG * 256) + h * (XB_NG / 2) * 256 + e] = a;
+        }
+    }
+}
+// Panel step: Y += Pt c (column 0) ; Rt += Q c ; Z += U c ; Pt = Z M1 + U M3 + Pt M2 ; Pi = Rt M1 + Q M3 + Pi M2 ; QS = S Pt -- the products of k_xtb_step
+// (16 rows per wave and step, panels as A operands, the 16 x 16 matrices as B operands), everything from the ORIGINAL panels.
+__global__ __launch_bounds__(XT_NT) void k_xtb_step1(int m, int it, const double *__restrict__ mats, double *__restrict__ y0, double *__restrict__ Rt,
+                                                     double *__restrict__ Z, double *__restrict__ Pt, double *__restrict__ Pi, const double *__restrict__ Q,
+                                                     const double *__restrict__ U, const double *__restrict__ sc, const int *__restrict__ nsrank,
+                                                     double *__restrict__ QS, const XCtrl *ctrl)
+{
+    __shared__ int sdone;
+    if (threadIdx.x == 0) { const int d = ctrl->done; sdone = d != 0 && it + 1 >= d; }
+    __syncthreads();
+    if (sdone) return;
+    const int lane = threadIdx.x & 63, a = lane & 15, b = lane >> 4;
+    const int wv = threadIdx.x >> 6;
+    double cB[4], m1B[4], m2B[4], m3B[4], c0[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        const int o = (4 * kk + b) * 16 + a;
+        cB[kk] = mats[o]; m1B[kk] = mats[256 + o]; m2B[kk] = mats[512 + o]; m3B[kk] = mats[768 + o];
+        c0[kk] = mats[(4 * kk + b) * 16];
+    }
+    const int ngroups = (m + 15) / 16;
+    for (int g = (int)blockIdx.x * 4 + wv; g < ngroups; g += (int)gridDim.x * 4) {
+        const int row0 = 16 * g;
+        double pa[4], ia[4], qa[4], ua[4], ra[4], za[4];
+        const bool oka = row0 + a < m;
+        const int rowa = oka ? row0 + a : 0;
+        const size_t oa = (size_t)rowa * XB_SP + b;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            pa[kk] = oka ? Pt[oa + 4 * kk] : 0.0; ia[kk] = oka ? Pi[oa + 4 * kk] : 0.0; qa[kk] = oka ? Q[oa + 4 * kk] : 0.0;
+            ua[kk] = oka ? U[oa + 4 * kk] : 0.0; ra[kk] = oka ? Rt[oa + 4 * kk] : 0.0; za[kk] = oka ? Z[oa + 4 * kk] : 0.0;
+        }
+        dbl4 rN, zN, pN = (dbl4)(0.0), iN = (dbl4)(0.0);
+        const double yold = (b == 0 && oka) ? y0[rowa] : 0.0;
+        int rowu[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int li = row0 + b + 4 * u;
+            rowu[u] = li < m ? li : -1;
+            rN[u] = rowu[u] >= 0 ? Rt[(size_t)rowu[u] * XB_SP + a] : 0.0;
+            zN[u] = rowu[u] >= 0 ? Z[(size_t)rowu[u] * XB_SP + a] : 0.0;
+        }
+        double yacc = (pa[0] * c0[0] + pa[1] * c0[1]) + (pa[2] * c0[2] + pa[3] * c0[3]);
+        yacc += __shfl_xor(yacc, 16, WAVE); yacc += __shfl_xor(yacc, 32, WAVE);
+        if (b == 0 && oka) y0[rowa] = yold + yacc;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            rN = XB_MFMA(qa[kk], cB[kk], rN); zN = XB_MFMA(ua[kk], cB[kk], zN);
+            pN = XB_MFMA(za[kk], m1B[kk], pN); pN = XB_MFMA(ua[kk], m3B[kk], pN); pN = XB_MFMA(pa[kk], m2B[kk], pN);
+            iN = XB_MFMA(ra[kk], m1B[kk], iN); iN = XB_MFMA(qa[kk], m3B[kk], iN); iN = XB_MFMA(ia[kk], m2B[kk], iN);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int row = rowu[u];
+            if (row >= 0) {
+                const size_t o = (size_t)row * XB_SP + a;
+                Rt[o] = rN[u]; Z[o] = zN[u]; Pt[o] = pN[u]; Pi[o] = iN[u];
+                const int sr = nsrank[row];
+                if (sr >= 0) QS[xtb_qs_pos(sr, a)] = sc[row] * pN[u];
+            }
+        }
+    }
+}
 // before the first product: P = Y0 stands in for Y0 (the product below is A Y0), QS = S Y0 over S; y0 = column 0.  Column 0 starts from y;
 // the auxiliary columns from zero, or -- yaux != nullptr: columns hs ... s - 1, the hash set -- from the UNSCALED solutions the previous solve left
 // (their right-hand sides are the same in every solve): their residuals then carry what the previous solve had not yet resolved, which is what
@@ -1356,17 +1478,28 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     // behind Vp: m zeros (the right-hand side of column 0 once the start vector has gone into it) and one double for the true residual
     const int pd = xtb_poly_degree(e, A);                                     // pinned (dkmc_set_x_poly) or from the rows of the system (xtb_poly_rule)
     e.stats.xb_poly_used = pd;
-    double *Vp = nullptr, *W1 = nullptr, *W2 = nullptr, *Zp = nullptr, *bz = nullptr;
+    // one-polynomial form (dkmc_set_x_poly_form; k_xtb_gram1): P, T, R are Pt, Q, Rt; Vp holds Pi, Zp holds Z, Up holds U = q(N) Q; pn products per sweep
+    const bool one = pd > 0 && xtb_poly_one(e);
+    const int pn = one ? xtb_poly1_degree(e, pd) : pd;
+    e.x_poly_form_used = one ? 1 : 0; e.x_poly_products = one ? pn : 2 * pd;
+    double *Vp = nullptr, *W1 = nullptr, *W2 = nullptr, *Zp = nullptr, *bz = nullptr, *Up = nullptr;
     if (pd > 0) {
         Vp = (double *)scratch(S_XTB_PRE_V, (pan + m + 16) * 8); W1 = (double *)scratch(S_XTB_PRE_W1, pan * 8); W2 = (double *)scratch(S_XTB_PRE_W2, pan * 8);
         Zp = (double *)scratch(S_XTB_PRE_Z, pan * 8);
         if (!Vp || !W1 || !W2 || !Zp) return e.err_code;
         bz = Vp + pan;
         HIPCHK(hipMemsetAsync(bz, 0, (size_t)(m + 16) * 8, st));
+        if (one) {
+            Up = (double *)scratch(S_XTB_PRE_U, pan * 8);
+            if (!Up) return e.err_code;
+            HIPCHK(hipMemsetAsync(Vp, 0, pan * 8, st));                       // Pi and U of the set-up pass: its Gram pass reads them, its step multiplies them by zero
+            HIPCHK(hipMemsetAsync(Up, 0, pan * 8, st));
+        }
     }
-    double pc[XB_MAXPOLY + 1] = {1.0};
-    xtb_poly_coeffs(pd, pc);
-    const double tol2_loop = pd > 0 ? A.tol2 / 2.25 : A.tol2;                 // ||r|| <= 1.42 ||L r||: the loop stops a little early, the true residual is checked at the end
+    double pc[XB_MAXPOLY1 + 1] = {1.0}, qmin = 1.0;
+    if (one) xtb_poly1_coeffs(pn, pc, &qmin); else xtb_poly_coeffs(pd, pc);
+    // split form: ||r|| <= 1.42 ||L r||, the loop stops a little early; one polynomial: the loop tests rt'q(N)rt >= min q ||rt||^2.  The true residual is checked at the end
+    const double tol2_loop = one ? A.tol2 * qmin : (pd > 0 ? A.tol2 / 2.25 : A.tol2);
     HIPCHK(hipMemsetAsync(QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
     HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
     HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(nrec + 1) * XT_C * so * 8, st));
@@ -1426,7 +1559,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     // dst = L src (xtb_applyL)
     const XbNRank nk{m, nullptr, np, QS, A.ctrl};
     auto applyL = [&](double *src, double *dst, bool qs) {
-        xtb_applyL(st, A, pd, pc, src, dst, W1, W2, qs, [](int, double *) { return 0; }, [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; });
+        xtb_applyL(st, A, pn, pc, src, dst, W1, W2, qs, [](int, double *) { return 0; }, [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; });
     };
     auto fold_rows = [&](double *Tt) {
         hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, vw->wrange, vw->nitem_w, (const double *)rowpartB, (const double *)colpartB,
@@ -1444,6 +1577,26 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         fold_rows(Zp);
         vw = &full;
         applyL(Zp, T, false);
+    };
+    // one polynomial: Q = A Pt (into T), U = q(N) Q
+    auto product_one = [&](hipEvent_t e0, hipEvent_t e1) {
+        t32 = f32 ? A.tval32 : nullptr;
+        if (lv) { vw = &live; t32 = lv->tval32; }
+        product(e0, e1);
+        t32 = nullptr;
+        fold_rows(T);
+        vw = &full;
+        applyL(T, Up, false);
+    };
+    auto gram_one = [&](hipEvent_t e2, hipEvent_t e3) {
+        hipExtLaunchKernelGGL(k_xtb_gram1, dim3(ng), dim3(XT_NT), 0, st, e2, e3, 0, m, (const double *)P, (const double *)Vp, (const double *)T, (const double *)Up,
+                              (const double *)R, (const double *)Zp, gpart, (const XCtrl *)A.ctrl);
+    };
+    auto step = [&](int it) {
+        if (one) hipLaunchKernelGGL(k_xtb_step1, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, Zp, P, Vp, (const double *)T, (const double *)Up, A.sc,
+                                    A.nsrank, QS, (const XCtrl *)A.ctrl);
+        else hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
+                                (const int *)nullptr, Ypanel);
     };
     const double *bsel = A.b;
 #define XB_ROWS_ARGS(IT_) A.ns, A.nK, A.nW, m, s, so, (lv && !init ? live : full).wrange, (lv && !init ? live : full).nitem_w, (const double *)rowpartB, (const double *)colpartB, A.srow, A.sS, A.nsrank, A.sc, \
@@ -1470,7 +1623,14 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     };
     // ---- R = A Y0 - B ; first directions ----
     product(nullptr, nullptr);
-    if (pd > 0) {
+    if (one) {
+        // Rt = A Y0 - B in every column (column 0 from the start vector, the auxiliary columns from zero: their right-hand sides are those of A), Z = q(N) Rt
+        fold_rows(T);
+        if (lv) xt_live_zero_dead(*lv, rowpartB, so);
+        if (int rcx = rows(true, -1, nullptr, nullptr)) return rcx;
+        applyL(R, Zp, false);
+        gram_one(nullptr, nullptr);
+    } else if (pd > 0) {
         // the start vector goes into the right-hand side: column 0 solves L A L dh = L (b - A y0) from zero, the auxiliary columns keep their own
         fold_rows(T);                                                         // T = A Y0
         if (lv) xt_live_zero_dead(*lv, rowpartB, so);                         // the sweeps fold on the live view: the dead tiles' row sums of this launch must not be added
@@ -1479,24 +1639,25 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         bsel = bz;                                                            // R = T - [0 | auxiliary right-hand sides]
         HIPCHK(hipMemsetAsync(y0, 0, (size_t)m * 8, st));
     }
-    if (int rcx = rows(true, -1, nullptr, nullptr)) return rcx;
+    if (!one) if (int rcx = rows(true, -1, nullptr, nullptr)) return rcx;
     hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, gfin, (const XCtrl *)A.ctrl);
     hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, -1, s, (const double *)gfin, mats, A.ctrl, tol2_loop);
     hipLaunchKernelGGL(k_xtb_zero, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, (long long)pan, P);          // Y0 has served: P_{-1} = 0
-    hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, -1, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
-                       (const int *)nullptr, Ypanel);
+    step(-1);
     KCHK();
     XCtrl h{};
     if (int rcx = cg_poll_loop(A.ctrl, h, LaunchPlan::hinted_three_quarters(e.x_iter_hint), st, XTB_NO_CONVERGENCE, prof && ntb > 0 && live.item_n > 0 ? &g_loop_events : nullptr,     // (no tile launch: no events)
                                [&](int it, const hipEvent_t *ev) -> int {
             if (sharded && g_xtb_fault_iter >= 0 && it >= g_xtb_fault_iter) { g_xtb_fault_iter = -1; local_fail = dkmc_fail(91, "injected fault (block-CG iteration)", __FILE__, __LINE__); }
-            if (pd > 0) product_pre(ev[0], ev[1]);
-            else product(ev[0], ev[1]);
-            if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
+            if (one) { product_one(ev[0], ev[1]); gram_one(ev[2], ev[3]); }
+            else {
+                if (pd > 0) product_pre(ev[0], ev[1]);
+                else product(ev[0], ev[1]);
+                if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
+            }
             hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, gfin, (const XCtrl *)A.ctrl);
             hipLaunchKernelGGL(k_xtb_small, dim3(1), dim3(256), 0, st, it, s, (const double *)gfin, mats, A.ctrl, tol2_loop);
-            hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
-                               (const int *)nullptr, Ypanel);
+            step(it);
             return 0;
         })) return rcx;
 #undef XB_ROWS_ARGS
@@ -1509,9 +1670,12 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     if (pd > 0) {
         // y = y0 + L dh, then the TRUE residual of column 0 in the unpreconditioned system: one more pass over the tiles
         HIPCHK(hipMemsetAsync(A.ctrl, 0, sizeof(XCtrl), st));                 // (the kernels below are gated by `done`)
-        hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)y0, Zp);
-        applyL(Zp, Vp, false);
-        hipLaunchKernelGGL(k_xtb_pre_add, dim3((m + 255) / 256), dim3(256), 0, st, m, (const double *)Vp, A.y);
+        if (one) HIPCHK(hipMemcpyAsync(A.y, y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));      // Y += Pt c ran in the unpreconditioned space, from the start vector
+        else {
+            hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)y0, Zp);
+            applyL(Zp, Vp, false);
+            hipLaunchKernelGGL(k_xtb_pre_add, dim3((m + 255) / 256), dim3(256), 0, st, m, (const double *)Vp, A.y);
+        }
         if (!h.pad[0]) {
             hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, P);
             hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)P, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
@@ -1790,6 +1954,80 @@ extern "C" int dkmc_xtb_test_step(int m, int it, const double *mats, int done_wo
     HIPCHK(hipMemcpyAsync(R, dR, pan, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(P, dP, pan, hipMemcpyDeviceToHost, st));
     if (Ypanel) HIPCHK(hipMemcpyAsync(Ypanel, dY, pan, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(y0, dy0, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    if (ns > 0) HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+
+// The same two stages of the one-polynomial form (tests/test_gpu_x_poly_form_kernels.py).  panels: six host panels of [m][16] in the order Pt, Pi, Q, U, Rt, Z.
+// Gram stage: k_xtb_gram1 over ng workgroups, then k_xtb_gred; gfin as in dkmc_xtb_test_gram.
+extern "C" int dkmc_xtb_test_gram1(int m, const double *const *panels, int ng, int done_word, double *gfin)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || m > XTB_ALG_MAXROWS || !panels || ng < 1 || ng > 4096 || !gfin) return dkmc_fail(13, "xtb_test_gram1: bad arguments", __FILE__, __LINE__);
+    for (int k = 0; k < 6; ++k) if (!panels[k]) return dkmc_fail(13, "xtb_test_gram1: bad arguments", __FILE__, __LINE__);
+    const size_t pan = (size_t)m * XB_SP * 8, pan_up = xtb_alg_up(pan), b_gpart = (size_t)ng * XB_NG * 256 * 8;
+    char *dp = (char *)scratch(S_XTB_ALG_PANELS, 6 * pan_up);
+    char *gram = (char *)scratch(S_XTB_ALG_GRAM, b_gpart + (size_t)XB_NG * 256 * 8);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
+    if (!dp || !gram || !ctrl) return e.err_code;
+    double *gpart = (double *)gram, *dgfin = (double *)(gram + b_gpart);
+    XCtrl h{}; h.done = done_word;
+    for (int k = 0; k < 6; ++k) HIPCHK(hipMemcpyAsync(dp + k * pan_up, panels[k], pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(gpart, 0xff, b_gpart, st));
+    HIPCHK(hipMemcpyAsync(dgfin, gfin, (size_t)XB_NG * 256 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ctrl, &h, sizeof(XCtrl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+#define XB_DP(k_) (const double *)(dp + (k_) * pan_up)
+    hipLaunchKernelGGL(k_xtb_gram1, dim3(ng), dim3(XT_NT), 0, st, m, XB_DP(0), XB_DP(1), XB_DP(2), XB_DP(3), XB_DP(4), XB_DP(5), gpart, (const XCtrl *)ctrl);
+#undef XB_DP
+    hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, dgfin, (const XCtrl *)ctrl);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(gfin, dgfin, (size_t)XB_NG * 256 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+// Step stage: ONE launch of k_xtb_step1 with the grid of a solve.  Pt, Pi, Rt, Z and y0 [m] go up and come back, Q and U go up; qs [ns][16] as in
+// dkmc_xtb_test_step.
+extern "C" int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
+                                   double *qs)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || m > XTB_ALG_MAXROWS || it < -1 || it > 0x3fffffff || !mats || !y0 || !panels || !sc || !nsrank || (ns > 0 && !qs))
+        return dkmc_fail(13, "xtb_test_step1: bad arguments", __FILE__, __LINE__);
+    for (int k = 0; k < 6; ++k) if (!panels[k]) return dkmc_fail(13, "xtb_test_step1: bad arguments", __FILE__, __LINE__);
+    if (!xtb_alg_sranks(m, nsrank, ns, nullptr)) return dkmc_fail(13, "xtb_test_step1: bad S ranks", __FILE__, __LINE__);
+    const size_t pan = (size_t)m * XB_SP * 8, pan_up = xtb_alg_up(pan), vec_up = xtb_alg_up((size_t)m * 8);
+    const size_t b_qs = xtb_alg_up((size_t)(ns + 2) * XB_SP * 8);
+    char *dp = (char *)scratch(S_XTB_ALG_PANELS, 6 * pan_up + 2 * vec_up);
+    int *dnsr = (int *)scratch(S_XTB_ALG_INTS, xtb_alg_up((size_t)m * 4));
+    double *dmats = (double *)scratch(S_XTB_ALG_GRAM, 4 * 256 * 8);
+    char *qsb = (char *)scratch(S_XTB_ALG_QS, 2 * b_qs);
+    XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
+    if (!dp || !dnsr || !dmats || !qsb || !ctrl) return e.err_code;
+    double *dy0 = (double *)(dp + 6 * pan_up), *dsc = (double *)(dp + 6 * pan_up + vec_up);
+    double *QS = (double *)qsb, *dq = (double *)(qsb + b_qs);
+    XCtrl h{}; h.done = done_word;
+    for (int k = 0; k < 6; ++k) HIPCHK(hipMemcpyAsync(dp + k * pan_up, panels[k], pan, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dy0, y0, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dsc, sc, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dnsr, nsrank, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dmats, mats, 4 * 256 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(QS, 0, b_qs, st));
+    if (ns > 0) {
+        HIPCHK(hipMemcpyAsync(dq, qs, (size_t)ns * XB_SP * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_xtb_test_qs_encode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, (const double *)dq, QS);
+    }
+    HIPCHK(hipMemcpyAsync(ctrl, &h, sizeof(XCtrl), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+#define XB_DP(k_) (double *)(dp + (k_) * pan_up)
+    hipLaunchKernelGGL(k_xtb_step1, dim3(grid_blocks((m + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, m, it, (const double *)dmats, dy0, XB_DP(4), XB_DP(5), XB_DP(0), XB_DP(1),
+                       (const double *)XB_DP(2), (const double *)XB_DP(3), (const double *)dsc, (const int *)dnsr, QS, (const XCtrl *)ctrl);
+#undef XB_DP
+    if (ns > 0) hipLaunchKernelGGL(k_xtb_test_qs_decode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, (const double *)QS, dq);
+    KCHK();
+    for (int k = 0; k < 6; ++k) if (k != 2 && k != 3) HIPCHK(hipMemcpyAsync(panels[k], dp + k * pan_up, pan, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(y0, dy0, (size_t)m * 8, hipMemcpyDeviceToHost, st));
     if (ns > 0) HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

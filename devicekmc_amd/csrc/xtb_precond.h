@@ -460,37 +460,70 @@ static int xtb_applyL(hipStream_t st, const XtbArgs &A, int pd, const double *pc
                                       R.QS, R.ctrl);
     });
 }
+// Chebyshev interpolant of degree d of f on [-1, b] in the monomial basis (Horner): pc[0 ... d]
+template <class F>
+static void xtb_cheb_monomial(int d, double b, F f, double *pc)
+{
+    const int n = d + 1;
+    const double a = -1.0;
+    double fx[XB_MAXPOLY1 + 1], c[XB_MAXPOLY1 + 1], pt[XB_MAXPOLY1 + 1] = {0}, Tm2[XB_MAXPOLY1 + 1] = {0}, Tm1[XB_MAXPOLY1 + 1] = {0};
+    for (int k = 0; k < n; ++k) { const double t = cos(M_PI * (k + 0.5) / n), x = 0.5 * (b - a) * t + 0.5 * (b + a); fx[k] = f(x); }
+    for (int j = 0; j < n; ++j) { double acc = 0.0; for (int k = 0; k < n; ++k) acc += fx[k] * cos(M_PI * j * (k + 0.5) / n); c[j] = acc * 2.0 / n; }
+    c[0] *= 0.5;
+    Tm2[0] = 1.0; Tm1[1] = 1.0;                                               // T_0, T_1 in powers of t
+    pt[0] += c[0]; pt[1] += c[1];
+    for (int j = 2; j <= d; ++j) {
+        double Tj[XB_MAXPOLY1 + 1];
+        for (int i = 0; i <= XB_MAXPOLY1; ++i) Tj[i] = (i >= 1 ? 2.0 * Tm1[i - 1] : 0.0) - Tm2[i];
+        for (int i = 0; i <= XB_MAXPOLY1; ++i) { pt[i] += c[j] * Tj[i]; Tm2[i] = Tm1[i]; Tm1[i] = Tj[i]; }
+    }
+    const double al = 2.0 / (b - a), be = -(a + b) / (b - a);                 // t = al x + be
+    double res[XB_MAXPOLY1 + 2] = {0}; res[0] = pt[d]; int deg = 0;
+    for (int i = d - 1; i >= 0; --i) {
+        double nr[XB_MAXPOLY1 + 2] = {0};
+        for (int q = 0; q <= deg; ++q) { nr[q] += res[q] * be; nr[q + 1] += res[q] * al; }
+        ++deg; nr[0] += pt[i];
+        for (int q = 0; q <= XB_MAXPOLY1 + 1; ++q) res[q] = nr[q];
+    }
+    for (int q = 0; q <= d; ++q) pc[q] = res[q];
+}
 // coefficients pc[0 ... pd] of the preconditioner L = p(N) (dkmc_set_x_poly; shared by the one-GPU and the slab-distributed loop)
 static void xtb_poly_coeffs(int pd, double *pc)
 {
     // coefficients of L = p(N), p ~ (1 - x)^(-1/2): the Chebyshev interpolant of degree d on [-1, 1 - delta], delta = min(0.5, 1.6 / d^2), in the monomial
     // basis (Horner).  Against the Taylor series of the same degree -- which is exact at 0 and weakest where it matters, towards x -> 1 (the largest
     // eigenvalue of N is 0.99994 at 9.4 k sites) -- the block loop needs a third fewer sweeps (85 k sites, d = 4: 34 -> 24, 95 without preconditioner).
-    if (pd > 0) {
-        const int d = pd, n = d + 1;
-        const double a = -1.0, b = 1.0 - std::min(0.5, 1.6 / (double)(d * d));
-        double fx[XB_MAXPOLY + 1], c[XB_MAXPOLY + 1], pt[XB_MAXPOLY + 1] = {0}, Tm2[XB_MAXPOLY + 1] = {0}, Tm1[XB_MAXPOLY + 1] = {0};
-        for (int k = 0; k < n; ++k) { const double t = cos(M_PI * (k + 0.5) / n), x = 0.5 * (b - a) * t + 0.5 * (b + a); fx[k] = 1.0 / sqrt(1.0 - x); }
-        for (int j = 0; j < n; ++j) { double acc = 0.0; for (int k = 0; k < n; ++k) acc += fx[k] * cos(M_PI * j * (k + 0.5) / n); c[j] = acc * 2.0 / n; }
-        c[0] *= 0.5;
-        Tm2[0] = 1.0; Tm1[1] = 1.0;                                           // T_0, T_1 in powers of t
-        pt[0] += c[0]; pt[1] += c[1];
-        for (int j = 2; j <= d; ++j) {
-            double Tj[XB_MAXPOLY + 1];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) Tj[i] = (i >= 1 ? 2.0 * Tm1[i - 1] : 0.0) - Tm2[i];
-            for (int i = 0; i <= XB_MAXPOLY; ++i) { pt[i] += c[j] * Tj[i]; Tm2[i] = Tm1[i]; Tm1[i] = Tj[i]; }
-        }
-        const double al = 2.0 / (b - a), be = -(a + b) / (b - a);             // t = al x + be
-        double res[XB_MAXPOLY + 2] = {0}; res[0] = pt[d]; int deg = 0;
-        for (int i = d - 1; i >= 0; --i) {
-            double nr[XB_MAXPOLY + 2] = {0};
-            for (int q = 0; q <= deg; ++q) { nr[q] += res[q] * be; nr[q + 1] += res[q] * al; }
-            ++deg; nr[0] += pt[i];
-            for (int q = 0; q <= XB_MAXPOLY + 1; ++q) res[q] = nr[q];
-        }
-        for (int q = 0; q <= d; ++q) pc[q] = res[q];
-    }
+    if (pd > 0) xtb_cheb_monomial(pd, 1.0 - std::min(0.5, 1.6 / (double)(pd * pd)), [](double x) { return 1.0 / sqrt(1.0 - x); }, pc);
 }
+// One-polynomial form (dkmc_set_x_poly_form): coefficients pc[0 ... n] of M^-1 = q(N), q ~ (1 - x)^-1 fitted directly -- the Chebyshev interpolant of
+// degree n on [-1, 1 - min(0.5, 3.2 / n^2)].  The split form pays 2 d products for p^2, a polynomial of degree 2 d with d free parameters; q reaches its
+// conditioning at n ~ 1.25 d.  Monomial Horner loses digits with the degree (relative error 1.3e-11 at 20, 1e-9 at 24): the cap is 20.
+// *qmin: the smallest q over 4001 equidistant points of [-1, 1] (q > 0 there: q(N) is positive definite; r'q(N)r >= qmin r'r scales the loop's stop test)
+static void xtb_poly1_coeffs(int n, double *pc, double *qmin)
+{
+    xtb_cheb_monomial(n, 1.0 - std::min(0.5, 3.2 / (double)(n * n)), [](double x) { return 1.0 / (1.0 - x); }, pc);
+    double lo = 1e300;
+    for (int k = 0; k <= 4000; ++k) {
+        const double x = -1.0 + (double)k / 2000.0;
+        double q = pc[n];
+        for (int j = n - 1; j >= 0; --j) q = q * x + pc[j];
+        lo = std::min(lo, q);
+    }
+    if (qmin) *qmin = lo;
+}
+// degree n(d) of the one-polynomial form at the level d (pinned or from xtb_poly_rule): ceil(1.25 d), at most XB_MAXPOLY1, except where a level of the
+// rule was measured (profiles/x_poly_form_by_size.jsonl, steady warm-started steps; the fastest n of the level's size, or its lower neighbour inside the
+// size's spread): level 8 -> 10 (7.5nm: n = 8 / 10 / 12 take 4.46 / 4.38 / 4.62 ms, tile:5: 20.9 / 19.3 / 19.9 ms), level 10 -> 10 (tile:7: n = 10 / 13 / 16 take
+// 55.1 / 55.5 / 56.0 ms, a tie inside the spread of 1.6 %), level 16 -> 18 (tile:10: n = 12 / 14 / 16 / 18 / 20 take 212.4 / 204.8 / 206.3 / 204.1 / 210.4 ms)
+static int xtb_poly1_degree(const Engine &e, int d)
+{
+    if (e.x_poly1_degree > 0) return std::min(e.x_poly1_degree, XB_MAXPOLY1);
+    if (d == 10) return 10;
+    if (d == 16) return 18;
+    return std::min((5 * d + 3) / 4, XB_MAXPOLY1);
+}
+// which form a preconditioned one-GPU solve runs (dkmc_set_x_poly_form): a pinned degree is a statement about L and keeps the split form under 2
+static bool xtb_poly_one(const Engine &e) { return e.x_poly_form == 1 || (e.x_poly_form == 2 && e.x_poly_auto != 0); }
 // ---- the degree a solve runs ---------------------------------------------------------------------------------------------------------------
 // A sweep costs (tile pass + row passes) + 2 d N products and the sweep count falls with d, so the best degree grows with the share of the tile pass,
 // that is with the rows m of the system.  Step function of m from profiles/x_poly_degree_by_size.jsonl (steady warm-started steps, degrees 6 ... 16,
@@ -520,6 +553,13 @@ extern "C" int dkmc_xtb_poly_coeffs(int degree, double *pc)
 {
     if (degree < 1 || degree > XB_MAXPOLY || !pc) return dkmc_fail(13, "xtb_poly_coeffs: degree outside 1 ... 16", __FILE__, __LINE__);
     xtb_poly_coeffs(degree, pc);
+    return 0;
+}
+// coefficients pc[0 ... n] of the one-polynomial form and the smallest q on [-1, 1]; host code only (no HIP call)
+extern "C" int dkmc_xtb_poly1_coeffs(int n, double *pc, double *qmin)
+{
+    if (n < 1 || n > XB_MAXPOLY1 || !pc) return dkmc_fail(13, "xtb_poly1_coeffs: degree outside 1 ... 20", __FILE__, __LINE__);
+    xtb_poly1_coeffs(n, pc, qmin);
     return 0;
 }
 // the degree the rule gives a one-GPU solve of m rows (breakpoints of dkmc_set_x_poly_auto_rows included); host code only (no HIP call)

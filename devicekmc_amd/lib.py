@@ -75,6 +75,11 @@ SYMBOLS = {
     "dkmc_set_x_poly_auto": (None, [_I]),
     "dkmc_get_x_poly_auto": (_I, []),
     "dkmc_set_x_poly_auto_rows": (None, [_I, _I]),
+    "dkmc_set_x_poly_form": (None, [_I]),
+    "dkmc_get_x_poly_form": (_I, []),
+    "dkmc_get_x_poly_form_used": (_I, []),
+    "dkmc_get_x_poly_products": (_I, []),
+    "dkmc_debug_set_x_poly1_degree": (None, [_I]),
     "dkmc_set_x_tile_f32": (None, [_I]),
     "dkmc_get_x_tile_f32": (_I, []),
     "dkmc_set_x_tile_drop": (None, [_D]),
@@ -195,6 +200,7 @@ SYMBOLS = {
     "dkmc_xt_get_tiles": (_I, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp]),
     "dkmc_xtb_poly_coeffs": (_I, [_I, c_dbl_p]),
     "dkmc_xtb_poly_rule": (_I, [_I]),
+    "dkmc_xtb_poly1_coeffs": (_I, [_I, c_dbl_p, c_dbl_p]),
     "dkmc_xtl_drop_rule": (_D, [C.c_longlong]),
     "dkmc_debug_xtl_census_form": (_I, [_I]),
     "dkmc_debug_xtl_census_reread": (C.c_longlong, []),
@@ -204,6 +210,8 @@ SYMBOLS = {
     "dkmc_xtb_test_gram": (_I, [_I, vp, vp, vp, vp, _I, _I, _I, vp, C.POINTER(dkmc_xtb_ctrl)]),
     "dkmc_xtb_test_small": (_I, [_I, _I, _I, vp, _D, C.POINTER(dkmc_xtb_ctrl), vp, C.POINTER(dkmc_xtb_ctrl)]),
     "dkmc_xtb_test_step": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, vp, vp, _I, vp, _I, vp, vp]),
+    "dkmc_xtb_test_gram1": (_I, [_I, vp, _I, _I, vp]),
+    "dkmc_xtb_test_step1": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, _I, vp]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),
     "dkmc_xtb_emulate_slabs": (_I, [_I, _I, _D, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong), c_int_p]),
     "dkmc_xtb_slab_last": (_I, [c_int_p, C.POINTER(C.c_longlong), c_dbl_p]),

@@ -172,6 +172,18 @@ void dkmc_set_x_poly(int degree);
 int dkmc_get_x_poly(void);
 void dkmc_set_x_poly_auto(int on);
 int dkmc_get_x_poly_auto(void);
+/* Form of the one-GPU preconditioned loop.  The split form pays 2 d N products per sweep for p^2, a polynomial of degree 2 d with d free parameters.
+ * The one-polynomial form takes M^-1 = q(N), q the degree-n Chebyshev interpolant of (1 - x)^-1 on [-1, 1 - min(0.5, 3.2 / n^2)], n = n(d) ~ 1.25 d
+ * (at most 20), and runs the same block-CG in the variables Pt = L P, Rt = L^-1 R, so that no L is ever applied: n N products per sweep, the iterate
+ * already in the unpreconditioned space, the same true-residual check and re-entry (csrc/xtb.hip: k_xtb_gram1, k_xtb_step1).
+ * 0: split form everywhere, bit for bit the loop on L A L.  1: one polynomial in every preconditioned one-GPU solve.  2 (default): one polynomial where the degree comes from the size
+ * rule (dkmc_set_x_poly_auto(1)), split form where dkmc_set_x_poly(d) pinned a degree.  The slab-distributed and sharded loops keep the split form.
+ * dkmc_get_x_poly_form_used(): 1 if the last one-GPU block solve ran the one-polynomial form; dkmc_get_x_poly_products(): its N products per sweep
+ * (2 d, n(d), or 0 for the plain loop).  dkmc_stats.xb_poly_used keeps reporting the level d. */
+void dkmc_set_x_poly_form(int form);
+int dkmc_get_x_poly_form(void);
+int dkmc_get_x_poly_form_used(void);
+int dkmc_get_x_poly_products(void);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
  * the column's scaling folded into the weights (csrc/xtb_precond.h: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
  * Both give the same bits; 0 is kept for comparisons. */

@@ -76,6 +76,19 @@ int dkmc_xtb_test_gram(int m, const double *P, const double *T, const double *R,
 int dkmc_xtb_test_small(int it, int s, int nrg, const double *gblocks, double tol2, const dkmc_xtb_ctrl *ctrl_in, double *mats, dkmc_xtb_ctrl *ctrl_out);
 int dkmc_xtb_test_step(int m, int it, const double *mats, int done_word, double *y0, double *R, double *P, const double *T, const double *sc,
                        const int *nsrank, int ns, const int *rowlist, int nlist, double *Ypanel, double *qs);
+/* The one-polynomial form of the preconditioned loop (dkmc_set_x_poly_form).
+ * dkmc_xtb_poly1_coeffs: coefficients pc[0 ... n] of q (monomial basis), n in 1 ... 20, and (qmin may be null) the smallest q over the 4001 equidistant
+ *   points of [-1, 1]; host code only, no GPU needed.
+ * dkmc_debug_set_x_poly1_degree: measurement aid -- n > 0 overrides the degree map n(d) of that form (at most 20); 0 restores the map.
+ * dkmc_xtb_test_gram1: k_xtb_gram1 over ng workgroups (1 ... 4096), then k_xtb_gred, on six host panels of [m][16] in the order Pt, Pi, Q, U, Rt, Z.
+ *   gfin as in dkmc_xtb_test_gram: Pt'Q, Pt'Rt, Q'Z, Q'U, Rt'Z, Pt'Pi; the last three symmetrised.
+ * dkmc_xtb_test_step1: ONE launch of k_xtb_step1 for iteration `it` with the stop word preset to done_word.  panels as above: Pt, Pi, Rt, Z and y0 [m] are read
+ *   and written, Q and U read; sc, nsrank, ns, mats and qs as in dkmc_xtb_test_step. */
+int dkmc_xtb_poly1_coeffs(int n, double *pc, double *qmin);
+void dkmc_debug_set_x_poly1_degree(int n);
+int dkmc_xtb_test_gram1(int m, const double *const *panels, int ng, int done_word, double *gfin);
+int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
+                        double *qs);
 /* Measurement aid: average duration [us] of the tile x panel kernel of the block-CG over the X left resident by the last single-GPU solve
  * (`reps` launches).  variant 0: as a solve runs it; on the round-4 form of the loop: 1: without its matrix instructions (tile stream + LDS
  * traffic); 2: without re-reading the tile stream (matrix instructions + LDS traffic); 3: operand stages of one k-pair; 4: without LDS

@@ -3,7 +3,9 @@
 run with the degree forced, one JSON record appended to a file.
 
 usage: python tools/x_poly_by_size.py DEGREE RECORD_FILE [bench.py arguments ...]
-       DEGREE = an integer (dkmc_set_x_poly(DEGREE): pins it) or `default` (the library's defaults untouched: the rule where the library has one)
+       DEGREE = an integer (dkmc_set_x_poly(DEGREE): pins it) or `default` (the library's defaults untouched: the rule where the library has one);
+                with `+split` behind it the split form is forced (dkmc_set_x_poly_form(0)), with `+one` the one-polynomial form (1) at the level's own
+                degree n(d), with `+one:N` at degree N (dkmc_debug_set_x_poly1_degree), e.g. `default+one:16`
        python tools/x_poly_by_size.py compare REF_DUMP_DIR DUMP_DIR RECORD_FILE     (two --dump-outputs directories of the same steps)
        python tools/x_poly_by_size.py best RECORD_FILE                              (appends the best degree of every measured size)
 
@@ -92,8 +94,12 @@ def main():
     sys.argv = [os.path.join(bench.ROOT, "bench.py")] + sys.argv[3:]
     from devicekmc_amd import host, lib
     L = lib.load()
+    degree, _, form = degree.partition("+")
     if degree != "default":
         L.dkmc_set_x_poly(int(degree))
+    if form:
+        L.dkmc_set_x_poly_form(1 if form.startswith("one") else 0)
+        L.dkmc_debug_set_x_poly1_degree(int(form.partition(":")[2] or 0))
     solves = []
     step0 = bench.Sim.step
 
@@ -101,7 +107,8 @@ def main():
         t = step0(self, timed)
         if timed:
             st = host.get_stats()
-            solves.append((math.sqrt(max(st["cg_rr_X"], 0.0)), int(st["x_tile_f64_rounds"]), int(st["xb_fallback"]), int(st.get("xb_poly_used", -1))))
+            solves.append((math.sqrt(max(st["cg_rr_X"], 0.0)), int(st["x_tile_f64_rounds"]), int(st["xb_fallback"]), int(st.get("xb_poly_used", -1)),
+                           L.dkmc_get_x_poly_form_used(), L.dkmc_get_x_poly_products()))
         return t
     bench.Sim.step = step
     buf = Tee()
@@ -112,6 +119,7 @@ def main():
     roof = line.get("roofline") or {}
     rec = {"workload": line["config"]["workload"], "sites": line["config"]["sites"], "rows": line["config"]["atoms"] + 1, "tunnelling_set": line["per_step"]["tunnelling_set"],
            "degree": degree if degree == "default" else int(degree), "degree_used": sorted(set(s[3] for s in solves)),
+           "one_polynomial": sorted(set(s[4] for s in solves)), "n_products_per_sweep": sorted(set(s[5] for s in solves)),
            "steps": line["steps"], "warmup": line["warmup"], "steps_per_s": line["value"], "ms_per_step": line["ms_per_step"],
            "sweeps_per_step": line["per_step"]["cg_iters_X"], "sweeps_each": (detail.get("steady") or {}).get("cg_sweeps_X_each"),
            "k_xtb_apply_us": roof.get("avg_launch_us"), "row_kernel_us": roof.get("row_kernel_us"),
