@@ -276,6 +276,8 @@ enum {
     // gap analysis (gaps.hip: dkmc_find_gaps): per-site words (component flags, cell, node), control block + box partials, the cell list, the members
     // in cell order, the per-node picks and pointers, the forest's edges
     S_GAP_SITE, S_GAP_CTRL, S_GAP_CELLS, S_GAP_SORTED, S_GAP_NODES, S_GAP_EDGES,
+    // conduction-path analysis (paths.hip: dkmc_find_paths): the hop pairs, the predecessors, the profile rows + path, change words + stat block
+    S_PT_HOP, S_PT_PRED, S_PT_ROWS, S_PT_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

@@ -195,6 +195,35 @@ def find_gaps(label, x, y, z, lattice, pbc, n_left, n_right, r_max):
     return edges, chain, info
 
 
+PATH_INFO = ("status", "hops", "rounds", "reached_left", "reached_right", "corridor_sites", "constriction_level", "constriction_width")
+PATH_PROFILE = ("count", "xmin", "xmax")
+
+
+def find_paths(index, nn, label, x, n_left, n_right, slack=0):
+    """dkmc_find_paths on device tensors (index: N * nn int32; label: N int32, e.g. the first return value of find_clusters; x: N float64 or
+    None).  Returns (hops_left, hops_right: int32 device tensors of N; path: host int32 array of the hops + 1 sites of the canonical shortest
+    path, empty at status 0; profile: dict of host arrays PATH_PROFILE with hops + slack + 1 rows, empty at status 0; info: dict of PATH_INFO).
+    Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(label.numel())
+    _use_stream(label.device)
+    hl = torch.empty(N, dtype=torch.int32, device=label.device)
+    hr = torch.empty(N, dtype=torch.int32, device=label.device)
+    check(L.dkmc_find_paths(N, int(nn), _ptr(index), _ptr(label), _ptr(x) if x is not None else None, int(n_left), int(n_right), int(slack),
+                            _ptr(hl), _ptr(hr)))
+    i8 = (C.c_longlong * 8)()
+    check(L.dkmc_get_path_info(i8))
+    info = dict(zip(PATH_INFO, (int(v) for v in i8)))
+    rows = C.c_int(0)
+    n_path, n_prof = (info["hops"] + 1, info["hops"] + int(slack) + 1) if info["status"] else (0, 0)
+    path = np.empty(n_path, dtype=np.int32)
+    check(L.dkmc_copy_path_sites(n_path, _np_ptr(path), C.byref(rows)))
+    path = path[:rows.value]
+    cols = [np.empty(n_prof, dtype=np.int32), np.empty(n_prof), np.empty(n_prof)]
+    check(L.dkmc_copy_path_profile(n_prof, *[_np_ptr(c) for c in cols], C.byref(rows)))
+    return hl, hr, path, {k: c[:rows.value] for k, c in zip(PATH_PROFILE, cols)}, info
+
+
 # rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
 EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
 
@@ -358,6 +387,24 @@ class Device:
         self.gap_edges, self.gap_chain, self.gap_info = find_gaps(label, gpubuf.site_x, gpubuf.site_y, gpubuf.site_z, self.lattice, self.pbc,
                                                                   n_left, n_right, r_max)
         return self.gap_edges, self.gap_chain, self.gap_info
+
+    def find_paths(self, gpubuf: GPUBuffers, slack=0, label=None, link_index=None, n_left=None, n_right=None):
+        """Conduction-path analysis on the device (dkmc_find_paths; definitions: include/devicekmc_hip.h) over the labels of the last
+        find_clusters -- one with the default members is run if there is none -- or over label (int32 device tensor of N): the hop distance of
+        every member from either contact over gpubuf.neigh_idx, or over link_index = (int32 device tensor of N * nn, nn), the canonical shortest
+        path, the level profile of the corridor of the walks at most slack links longer and its constriction, with the contact seeds of
+        find_clusters.  Changes nothing in gpubuf.  Returns (hops_left, hops_right: host int32 arrays, path, profile, info) and keeps them as
+        site_hops_left, site_hops_right, path_sites, path_profile, path_info."""
+        if label is None:
+            if getattr(self, "_cluster_label", None) is None:
+                self.find_clusters(gpubuf, n_left=n_left, n_right=n_right)
+            label = self._cluster_label
+        n_left, n_right = self.contact_seeds(n_left, n_right)
+        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        hl, hr, path, profile, info = find_paths(index, nn, label, gpubuf.site_x, n_left, n_right, slack)
+        self.site_hops_left, self.site_hops_right = hl.cpu().numpy(), hr.cpu().numpy()
+        self.path_sites, self.path_profile, self.path_info = path, profile, info
+        return self.site_hops_left, self.site_hops_right, path, profile, info
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

@@ -180,6 +180,12 @@ SYMBOLS = {
     "dkmc_copy_gap_edges": (_I, [_I, vp, vp, vp, vp, vp, c_int_p]),
     "dkmc_copy_gap_chain": (_I, [_I, vp, vp, vp, c_int_p]),
     "dkmc_debug_set_gap_cell_skip": (None, [_I]),
+    "dkmc_find_paths": (_I, [_I, _I, vp, vp, vp, _I, _I, _I, vp, vp]),
+    "dkmc_get_path_info": (_I, [C.POINTER(C.c_longlong)]),
+    "dkmc_copy_path_sites": (_I, [_I, vp, c_int_p]),
+    "dkmc_copy_path_profile": (_I, [_I, vp, vp, vp, c_int_p]),
+    "dkmc_debug_set_path_round_cap": (None, [_I]),
+    "dkmc_debug_get_path_times": (_I, [c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

@@ -568,6 +568,41 @@ int dkmc_get_gap_info(long long *info8, double *d2x2);
 int dkmc_copy_gap_edges(int capacity, int *h_site_a, int *h_site_b, int *h_root_a, int *h_root_b, double *h_d2, int *rows_out);
 int dkmc_copy_gap_chain(int capacity, int *h_from, int *h_to, double *h_d2, int *rows_out);
 
+/* ---- conduction-path analysis: hops, shortest path, constriction (csrc/paths.hip; no counterpart in the reference) ----
+ * Where the filament is bridged: how long the shortest conducting path between the contacts is, which sites lie on a left-to-right walk at most
+ * slack links longer, how wide that corridor is level by level, and where it is narrowest.  A pure function of its arguments: no field of
+ * GPUBuffers, no engine state a later phase reads and no other kernel changes.
+ *   members     site i is a member when 0 <= d_label[i] < N (the rule of dkmc_find_gaps); nothing else of the labels is used.
+ *   link        members u and v are linked when v occurs in row u of d_index[N][nn] OR u occurs in row v (the rule of dkmc_find_clusters, symmetric
+ *               even where the index is not).  Entries < 0 or >= N are padding, anywhere in a row.
+ *   seeds       left: the members with index < n_left_sites; right: the members with index >= N - n_right_sites (both clamped to 0 ... N).
+ *   hops        d_hops_left[i] is the smallest number of links from any left seed to i: 0 on a left seed, -1 on a non-member and on a member no left
+ *               seed reaches.  d_hops_right is the same from the right seeds.  Device arrays of N int32, always written completely.
+ *   status, H   status 1 when some right seed has hops_left >= 0; H is then the smallest such value (= the smallest hops_right over the left seeds).
+ *               Otherwise -- an empty seed set, contacts not connected through members -- status 0 and H = -1.
+ *   path        at status 1, H + 1 rows: site[H] is the smallest-index right seed with hops_left == H, site[k - 1] the smallest-index member linked
+ *               to site[k] with hops_left == k - 1.  Row k has hops_left == k, row 0 is a left seed: canonical, whatever computes it.
+ *   corridor    the members with hops_left >= 0, hops_right >= 0 and hops_left + hops_right <= H + slack: exactly the sites on some left-to-right
+ *               walk of at most H + slack links.
+ *   profile     at status 1, H + slack + 1 rows: row k holds the count of the corridor sites with hops_left == k and xmin, xmax of d_site_x over
+ *               them -- the input doubles themselves.  A row with count == 0 holds +inf / -inf; so does every row when d_site_x is NULL.
+ *   constriction  the row k in 0 ... H with the smallest count, the smallest k on ties (each of those rows has count >= 1).
+ *   info8       (long long) [0] status, [1] H, [2] rounds (below), [3] members reached from the left (hops_left >= 0), [4] from the right,
+ *               [5] corridor sites, [6] constriction level, [7] constriction width.  At status 0, [5], [6], [7] are 0, -1, 0.
+ * dkmc_find_paths runs a level-synchronous breadth-first search from both contacts at once: round k sets hop k + 1 in both fields in one pass over
+ * the member rows; the first round that sets nothing in either field ends the loop, and rounds counts the rounds run, that one included:
+ * max(largest hops_left, largest hops_right, 0) + 1, a function of the input alone (0 when N == 0).  A search that needs more than 4096 rounds
+ * fails (dkmc_last_error): both hop arrays are then -1 everywhere and the getters fail until a call succeeds.  It keeps the results of the LAST
+ * call in the library and returns after they are complete; the three getters fail before any successful call.  Any getter pointer may be NULL;
+ * capacity truncates and *rows_out reports the rows copied (the true counts are H + 1 and H + slack + 1).  N == 0, no member or no seed at all
+ * succeed with empty tables and status 0.  N < 0, nn < 1, slack < 0 or > 65536, or d_index, d_label, d_hops_left or d_hops_right null with N > 0
+ * fail with code 3 before any launch.  Integer atomics only, no order-dependent sums: the same inputs give the same bytes on every call. */
+int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const double *d_site_x,
+                    int n_left_sites, int n_right_sites, int slack, int *d_hops_left, int *d_hops_right);
+int dkmc_get_path_info(long long *info8);
+int dkmc_copy_path_sites(int capacity, int *h_site, int *rows_out);
+int dkmc_copy_path_profile(int capacity, int *h_count, double *h_xmin, double *h_xmax, int *rows_out);
+
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
 int dkmc_update_temperatureglobal_gpu(const double *d_site_power, double *d_T_bg, int N, double a_coeff,

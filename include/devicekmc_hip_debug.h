@@ -215,6 +215,12 @@ int dkmc_debug_get_cluster_times(double *ms2);
  * it saves are the reads of those members' node words -- a pair of one node is never distance-tested --, so the results, info8[5] included, are
  * the same bytes either way. */
 void dkmc_debug_set_gap_cell_skip(int on);
+/* Test aid of dkmc_find_paths (csrc/paths.hip): the cap on the search's rounds, 1 ... 4096; cap <= 0 restores the default 4096.  A search that
+ * needs more rounds than the cap fails with a message, sets both hop arrays to -1 and leaves the getters failing.
+ * Measurement aid: with dkmc_set_profiling(1), ms2 = HIP-event time of the last call's seeding + search rounds (the host's read-backs between
+ * them included) and of its summaries (outputs, profile, predecessors, walk); both 0 with profiling off. */
+void dkmc_debug_set_path_round_cap(int cap);
+int dkmc_debug_get_path_times(double *ms2);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);

@@ -1,0 +1,390 @@
+"""The conduction-path analysis on the device (dkmc_find_paths, csrc/paths.hip) against the host reference path_ref.py: both hop arrays, the
+canonical path, every column of the profile -- doubles included -- and info with np.array_equal; the number of rounds against the reference's
+synchronous model."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+import pytest
+
+import cluster_ref as cr
+import path_ref as pr
+from conftest import params_7p5
+from test_cluster_ref import _random_case
+from test_path_ref import PINNED_2P5_BRIDGED, PINNED_7P5_BRIDGED
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from devicekmc_amd import host, lib
+    assert torch.cuda.is_available()
+    return host, lib.load()
+
+
+@pytest.fixture(autouse=True)
+def _default_cap(hip):
+    yield
+    hip[1].dkmc_debug_set_path_round_cap(0)
+
+
+def _dev(a, dtype):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
+
+
+def run_raw(hip, index, label, x, n_left, n_right, slack):
+    """the raw entry point on host arrays -> (hops_left, hops_right: host arrays, path, profile, info)"""
+    host, _ = hip
+    index = np.asarray(index)
+    hl, hr, path, prof, info = host.find_paths(_dev(index, np.int32), index.shape[1], _dev(label, np.int32),
+                                               None if x is None else _dev(x, np.float64), n_left, n_right, slack)
+    return hl.cpu().numpy(), hr.cpu().numpy(), path, prof, info
+
+
+def check_raw(hip, index, label, x, n_left, n_right, slacks=(0,)):
+    """one reference search for all slacks; -> [(device result, reference)] per slack"""
+    searched = pr.search(index, label, n_left, n_right)
+    out = []
+    for slack in slacks:
+        ref = pr.analyse(index, label, x, n_left, n_right, slack, searched=searched)
+        got = run_raw(hip, index, label, x, n_left, n_right, slack)
+        pr.assert_equal(*got, ref)
+        out.append((got, ref))
+    return out
+
+
+def _bytes(res):
+    hl, hr, path, prof, info = res
+    return hl.tobytes() + hr.tobytes() + path.tobytes() + b"".join(prof[k].tobytes() for k in pr.PROFILE) + repr([info[k] for k in pr.INFO]).encode()
+
+
+# ---- random graphs: workgroup and wave edges, both row-lane templates, the whole-wave row ------------------------------------------------------
+@pytest.mark.parametrize("one_way", [False, True])
+@pytest.mark.parametrize("N,nn,p_member,p_pad", [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1),
+                                                 (255, 3, 0.7, 0.3), (256, 16, 0.5, 0.85), (257, 17, 0.6, 0.9), (1000, 1, 0.9, 0.1),
+                                                 (1000, 128, 0.5, 0.985), (1000, 130, 0.6, 0.99)])
+def test_random_graphs(hip, N, nn, p_member, p_pad, one_way):
+    rng = np.random.default_rng(1000 * N + nn + one_way)
+    connected = 0
+    for trial in range(2):
+        index, element, _, x = _random_case(rng, N, nn, p_member, p_pad, one_way)
+        index[rng.random(N) < 0.1] = -1                                             # padding-only rows
+        index[rng.random((N, nn)) < 0.02] = N + 3                                   # padding past the end
+        # labels outside 0 ... N - 1 are non-members, whatever their value
+        label = np.where(element != 3, rng.integers(0, N, N), rng.choice([-1, N, N + 7, 2 ** 31 - 1, -2 ** 31], N)).astype(np.int32)
+        for got, ref in check_raw(hip, index, label, x, N // 4, N // 4, slacks=(0, 1, 3)):
+            connected += ref[4]["status"]
+    assert connected > 0 or N < 40
+
+
+def test_empty_seed_sets_clamping_and_missing_x(hip):
+    rng = np.random.default_rng(5)
+    N = 500
+    index, element, _, x = _random_case(rng, N, 4, 0.7, 0.4, False)
+    label = np.where(element != 3, 0, -1).astype(np.int32)
+    for nl, nr in ((0, 100), (100, 0), (0, 0), (-4, 3 * N), (N, N)):
+        (got, ref), = check_raw(hip, index, label, x, nl, nr, slacks=(2,))
+        assert got[4]["status"] == (1 if nl == N else 0)
+    # without x the rows hold +inf / -inf, the counts are the same
+    (got, ref), = check_raw(hip, index, label, None, 100, 100, slacks=(1,))
+    assert got[4]["status"] == 1 and np.isposinf(got[3]["xmin"]).all() and np.isneginf(got[3]["xmax"]).all() and got[3]["count"].sum() > 0
+    # no member at all
+    (got, _), = check_raw(hip, index, np.full(N, -1, dtype=np.int32), x, 100, 100, slacks=(0,))
+    assert got[4] == dict(zip(pr.INFO, (0, -1, 1, 0, 0, 0, -1, 0))) and (got[0] == -1).all() and (got[1] == -1).all() and len(got[2]) == 0
+
+
+def test_n_zero(hip):
+    import torch
+    host, _ = hip
+    e = torch.empty(0, dtype=torch.int32, device="cuda:0")
+    hl, hr, path, prof, info = host.find_paths(e, 3, e, torch.empty(0, dtype=torch.float64, device="cuda:0"), 0, 0, 2)
+    assert info == dict(zip(pr.INFO, (0, -1, 0, 0, 0, 0, -1, 0))) and hl.numel() == hr.numel() == len(path) == len(prof["count"]) == 0
+
+
+# ---- chains and ladders -------------------------------------------------------------------------------------------------------------------------
+def _chain(order):
+    """the sites of order linked in a row, both directions entered"""
+    n = len(order)
+    index = np.full((n, 2), -1, dtype=np.int32)
+    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
+    return index
+
+
+def test_ordered_chain_spans_many_batches(hip):
+    n = 300
+    index = _chain(np.arange(n))
+    (got, _), = check_raw(hip, index, np.zeros(n, dtype=np.int32), np.arange(n) * 0.5, 1, 1, slacks=(0,))
+    hl, hr, path, prof, info = got
+    assert (info["hops"], info["rounds"], info["corridor_sites"], info["constriction_level"], info["constriction_width"]) == (299, 300, 300, 0, 1)
+    assert np.array_equal(path, np.arange(n)) and np.array_equal(hl, np.arange(n)) and np.array_equal(prof["xmin"], np.arange(n) * 0.5)
+
+
+def test_randomly_numbered_chain(hip):
+    n = 2000
+    order = np.r_[0, 1 + np.random.default_rng(11).permutation(n - 2), n - 1]
+    (got, _), _ = check_raw(hip, _chain(order), np.zeros(n, dtype=np.int32), np.linspace(0.0, 1.0, n), 1, 1, slacks=(0, 2))
+    assert got[4]["hops"] == n - 1 and got[4]["rounds"] == n and np.array_equal(got[2], order)      # rows above PT_LDS_ROWS: the global profile
+
+
+def test_round_cap_fails_cleanly(hip):
+    """an error return, not a device fault: the error is set, both hop arrays are -1, the getters fail; the next call with the cap restored succeeds"""
+    import torch
+    host, L = hip
+    n = 40
+    index, label = _dev(_chain(np.arange(n)), np.int32), _dev(np.zeros(n), np.int32)
+    hl = torch.full((n,), 7, dtype=torch.int32, device="cuda:0")
+    hr = torch.full((n,), 7, dtype=torch.int32, device="cuda:0")
+    L.dkmc_debug_set_path_round_cap(8)
+    rc = L.dkmc_find_paths(n, 2, host._ptr(index), host._ptr(label), None, 1, 1, 0, host._ptr(hl), host._ptr(hr))
+    assert rc != 0 and "dkmc_find_paths" in L.dkmc_last_error().decode() and "8 rounds" in L.dkmc_last_error().decode()
+    L.dkmc_clear_error()
+    torch.cuda.synchronize()
+    assert (hl.cpu().numpy() == -1).all() and (hr.cpu().numpy() == -1).all()
+    rows = C.c_int(0)
+    for call in (lambda: L.dkmc_get_path_info(None), lambda: L.dkmc_copy_path_sites(4, None, C.byref(rows)),
+                 lambda: L.dkmc_copy_path_profile(4, None, None, None, C.byref(rows)), lambda: L.dkmc_debug_get_path_times(None)):
+        assert call() == 3
+        L.dkmc_clear_error()
+    L.dkmc_debug_set_path_round_cap(0)
+    (got, _), = check_raw(hip, _chain(np.arange(n)), np.zeros(n, dtype=np.int32), None, 1, 1)
+    assert got[4]["hops"] == n - 1 and L.dkmc_get_path_info(None) == 0
+
+
+def _ladder(length, branch_at=None, branch_len=0):
+    """Two parallel chains a, b of `length` sites with a rung at every level; sites 2 i, 2 i + 1 are level i, except the last level, which comes
+    after the optional dead-end branch (branch_len sites in a row, hung on a at level branch_at).  Seeds: the first and the last two sites."""
+    n = 2 * length + branch_len
+    a = np.r_[2 * np.arange(length - 1), n - 2]
+    b = a + 1
+    links = [(a[i], a[i + 1]) for i in range(length - 1)] + [(b[i], b[i + 1]) for i in range(length - 1)] + [(a[i], b[i]) for i in range(length)]
+    c = 2 * (length - 1) + np.arange(branch_len)
+    if branch_len:
+        links += [(a[branch_at], c[0])] + [(c[j], c[j + 1]) for j in range(branch_len - 1)]
+    index = np.full((n, 4), -1, dtype=np.int32)
+    fill = np.zeros(n, dtype=np.int64)
+    for u, v in links:                                                               # each link entered once, in the row of its first end
+        index[u, fill[u]] = v; fill[u] += 1
+    x = np.zeros(n)
+    x[a] = np.arange(length); x[b] = np.arange(length) + 0.25
+    x[c] = x[a[branch_at]] + 0.5 if branch_len else 0.0
+    return index, np.zeros(n, dtype=np.int32), x, c
+
+
+def test_ladder_and_dead_end_branch(hip):
+    length = 70
+    index, label, x, _ = _ladder(length)
+    for (got, _), slack in zip(check_raw(hip, index, label, x, 2, 2, slacks=(0, 1, 3)), (0, 1, 3)):
+        prof, info = got[3], got[4]
+        assert info["hops"] == length - 1 and info["corridor_sites"] == 2 * length and (info["constriction_level"], info["constriction_width"]) == (0, 2)
+        assert prof["count"].tolist() == [2] * length + [0] * slack                 # the levels above H are empty: +inf / -inf
+        assert np.array_equal(prof["xmin"][:length], np.arange(length)) and np.array_equal(prof["xmax"][:length], np.arange(length) + 0.25)
+        assert np.isposinf(prof["xmin"][length:]).all() and np.isneginf(prof["xmax"][length:]).all()
+        assert np.array_equal(got[2], np.r_[2 * np.arange(length - 1), 2 * length - 2])      # the a side: the smaller index at every level
+    # a dead-end branch of 3 sites on level 20: site j of it is 2 j links off the shortest walks
+    index, label, x, c = _ladder(length, 20, 3)
+    plain = [2] * length
+    for (got, _), slack in zip(check_raw(hip, index, label, x, 2, 2, slacks=(0, 1, 2, 4, 6)), (0, 1, 2, 4, 6)):
+        hl, hr, _, prof, info = got
+        assert hl[c].tolist() == [21, 22, 23] and hr[c].tolist() == [50, 51, 52]
+        want = list(plain) + [0] * slack
+        for j in range(min(slack // 2, 3)):
+            want[21 + j] += 1
+        assert prof["count"].tolist() == want and info["corridor_sites"] == 2 * length + min(slack // 2, 3)
+        assert (info["constriction_level"], info["constriction_width"]) == (0, 2)
+        assert prof["xmin"][21] == (20.5 if slack >= 2 else 21.0) and prof["xmax"][21] == 21.25
+
+
+# ---- the golden devices -----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def dev_2p5(hip, cell_2p5):
+    from devicekmc_amd import params as pm
+    host, _ = hip
+    p = pm.KMCParameters()
+    dev = host.Device(cell_2p5, p)
+    return dev, dev.make_gpubuf("cuda:0"), p, dev.site_element.copy()
+
+
+class _Planted:
+    """a planted filament in the device's site_element, taken out again on exit"""
+    def __init__(self, dev, gb, el0, r, skip):
+        self.dev, self.gb, self.el0 = dev, gb, el0
+        self.el2, _ = cr.plant_filament(el0, dev.site_x, dev.site_y, dev.site_z, r, skip)
+
+    def _set(self, el):
+        import torch
+        self.dev.site_element = el.copy()
+        self.gb.t["site_element"].copy_(torch.as_tensor(el))
+
+    def __enter__(self):
+        self._set(self.el2)
+
+    def __exit__(self, *exc):
+        self._set(self.el0)
+
+
+def _contacts(dev, p):
+    return dev.get_num_in_contacts(p.num_atoms_first_layer, "left"), dev.get_num_in_contacts(p.num_atoms_first_layer, "right")
+
+
+def _check_path(index, hl, path, nl, nr):
+    N = len(hl)
+    index = np.asarray(index).reshape(N, -1)
+    assert np.array_equal(hl[path], np.arange(len(path))) and path[0] < nl and path[-1] >= N - nr
+    for a, b in zip(path[:-1], path[1:]):
+        assert b in index[a] or a in index[b]
+
+
+@pytest.mark.parametrize("r,skip", [(3.0, None), (3.0, (25.0, 40.0)), (2.0, None)])
+def test_planted_filaments_2p5(hip, dev_2p5, r, skip):
+    """Device.find_clusters -> Device.find_paths on the three plantings, slack 0, 2, 4, against the reference and the pinned figures"""
+    dev, gb, p, el0 = dev_2p5
+    with _Planted(dev, gb, el0, r, skip):
+        nl, nr = _contacts(dev, p)
+        label, _, cinfo = dev.find_clusters(gb)
+        searched = pr.search(dev.neigh_idx, label, nl, nr)
+        for slack in (0, 2, 4):
+            ref = pr.analyse(dev.neigh_idx, label, dev.site_x, nl, nr, slack, searched=searched)
+            res = dev.find_paths(gb, slack=slack)
+            hl, hr, path, prof, info = res
+            print(r, skip, slack, info)
+            pr.assert_equal(*res, ref)
+            assert dev.site_hops_left is hl and dev.site_hops_right is hr and dev.path_sites is path and dev.path_profile is prof and dev.path_info is info
+            assert info["status"] == cinfo["bridged"]
+            if (r, skip) == (3.0, None):
+                assert (info["hops"], info["rounds"], info["reached_left"], info["reached_right"]) == (47, 49, 3533, 3533)
+                assert (info["corridor_sites"], info["constriction_level"], info["constriction_width"]) == PINNED_2P5_BRIDGED[slack]
+                _check_path(dev.neigh_idx, hl, path, nl, nr)
+                k = info["constriction_level"]
+                assert prof["count"][k] == info["constriction_width"] and prof["xmin"][k] <= prof["xmax"][k]
+            elif skip:
+                assert (info["reached_left"], info["reached_right"], int(hl.max()), int(hr.max()), info["rounds"]) == (1500, 2004, 21, 21, 22)
+            else:
+                assert (info["reached_left"], info["reached_right"]) == (1454, 2022)
+
+
+def test_device_find_paths_runs_a_labelling_and_takes_labels(hip, dev_2p5, cell_2p5):
+    """with no find_clusters before it, it runs one with the default members; a given label tensor is the one used"""
+    host, _ = hip
+    _, gb, p, _ = dev_2p5
+    dev = host.Device(cell_2p5, p)
+    assert not hasattr(dev, "site_cluster")
+    res = dev.find_paths(gb, slack=1)
+    nl, nr = _contacts(dev, p)
+    assert dev.cluster_info["n_components"] == 79 and res[4]["status"] == 0
+    pr.assert_equal(*res, pr.analyse(dev.neigh_idx, dev.site_cluster, dev.site_x, nl, nr, 1))
+    only_vac = np.where(dev.site_element == 2, 0, -1).astype(np.int32)
+    res = dev.find_paths(gb, label=_dev(only_vac, np.int32), n_left=3000, n_right=3000)
+    pr.assert_equal(*res, pr.analyse(dev.neigh_idx, only_vac, dev.site_x, 3000, 3000, 0))
+
+
+def test_wider_link_index_2p5(hip, dev_2p5):
+    """rows above 128 entries: the whole-wave row"""
+    import torch
+    host, _ = hip
+    dev, gb, p, el0 = dev_2p5
+    wide, nn = host.build_neighbor_index_gpu(dev.site_x, dev.site_y, dev.site_z, p.lattice, p.pbc, 7.0)
+    assert nn > 128
+    with _Planted(dev, gb, el0, 3.0, (25.0, 40.0)):
+        nl, nr = _contacts(dev, p)
+        link = (torch.as_tensor(wide.reshape(-1)).to("cuda:0"), nn)
+        label, _, cinfo = dev.find_clusters(gb, members=host.VACANCY, link_index=link)
+        res = dev.find_paths(gb, slack=2, link_index=link)
+        pr.assert_equal(*res, pr.analyse(wide, label, dev.site_x, nl, nr, 2))
+
+
+def test_planted_filament_7p5(hip, dev_7p5):
+    host, _ = hip
+    p = params_7p5()
+    dev = host.Device(dev_7p5, p, gpu_neighbors="cuda:0")
+    gb = dev.make_gpubuf("cuda:0")
+    with _Planted(dev, gb, dev.site_element.copy(), 3.0, None):
+        nl, nr = _contacts(dev, p)
+        label, _, _ = dev.find_clusters(gb)
+        searched = pr.search(dev.neigh_idx, label, nl, nr)
+        for slack in (0, 2):
+            res = dev.find_paths(gb, slack=slack)
+            pr.assert_equal(*res, pr.analyse(dev.neigh_idx, label, dev.site_x, nl, nr, slack, searched=searched))
+            info = res[4]
+            assert (info["status"], info["hops"], info["rounds"], info["reached_left"], info["reached_right"]) == (1, 45, 59, 30963, 30963)
+            assert (info["corridor_sites"], info["constriction_level"], info["constriction_width"]) == PINNED_7P5_BRIDGED[slack]
+            _check_path(dev.neigh_idx, res[0], res[2], nl, nr)
+        assert res[3]["count"][46:].tolist() == [233, 125]
+
+
+# ---- arguments and getters ----------------------------------------------------------------------------------------------------------------------
+def test_bad_arguments(hip):
+    import torch
+    host, L = hip
+    n = 100
+    index, label = _dev(_chain(np.arange(n)), np.int32), _dev(np.zeros(n), np.int32)
+    hl, hr = (torch.full((n,), 7, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    pi, pl, ph, pq = (host._ptr(t) for t in (index, label, hl, hr))
+    assert L.dkmc_find_paths(n, 2, pi, pl, None, 1, 1, 0, ph, pq) == 0
+    for args in ((-1, 2, pi, pl, None, 1, 1, 0, ph, pq), (n, 0, pi, pl, None, 1, 1, 0, ph, pq), (n, 2, pi, pl, None, 1, 1, -1, ph, pq),
+                 (n, 2, pi, pl, None, 1, 1, 65537, ph, pq), (n, 2, None, pl, None, 1, 1, 0, ph, pq), (n, 2, pi, None, None, 1, 1, 0, ph, pq),
+                 (n, 2, pi, pl, None, 1, 1, 0, None, pq), (n, 2, pi, pl, None, 1, 1, 0, ph, None)):
+        hl.fill_(7); hr.fill_(7)
+        assert L.dkmc_find_paths(*args) == 3
+        assert "dkmc_find_paths" in L.dkmc_last_error().decode()
+        L.dkmc_clear_error()
+        assert L.dkmc_get_path_info(None) != 0                                      # no results of a failed call
+        L.dkmc_clear_error()
+        torch.cuda.synchronize()
+        assert (hl.cpu().numpy() == 7).all() and (hr.cpu().numpy() == 7).all()     # nothing was launched
+    assert L.dkmc_find_paths(n, 2, pi, pl, None, 1, 1, 65536, ph, pq) == 0 and L.dkmc_get_path_info(None) == 0
+
+
+def test_getters_null_columns_and_capacity(hip):
+    _, L = hip
+    index, label, x, _ = _ladder(30)
+    (got, _), = check_raw(hip, index, label, x, 2, 2, slacks=(3,))
+    _, _, path, prof, info = got
+    assert len(path) == 30 and len(prof["count"]) == 33
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    s, rows = np.full(8, -9, dtype=np.int32), C.c_int(-1)
+    assert L.dkmc_copy_path_sites(5, vp(s), C.byref(rows)) == 0 and rows.value == 5 and np.array_equal(s[:5], path[:5]) and (s[5:] == -9).all()
+    assert L.dkmc_copy_path_sites(0, None, C.byref(rows)) == 0 and rows.value == 0
+    assert L.dkmc_copy_path_sites(10 ** 6, None, C.byref(rows)) == 0 and rows.value == 30
+    assert L.dkmc_copy_path_sites(10 ** 6, None, None) == 0
+    c, lo, hi = np.full(40, -9, dtype=np.int32), np.full(40, -9.0), np.full(40, -9.0)
+    assert L.dkmc_copy_path_profile(4, None, vp(lo), None, C.byref(rows)) == 0 and rows.value == 4
+    assert np.array_equal(lo[:4], prof["xmin"][:4]) and (lo[4:] == -9.0).all()
+    assert L.dkmc_copy_path_profile(40, vp(c), None, vp(hi), C.byref(rows)) == 0 and rows.value == 33
+    assert np.array_equal(c[:33], prof["count"]) and np.array_equal(hi[:33], prof["xmax"]) and (c[33:] == -9).all()
+    assert L.dkmc_copy_path_profile(-3, vp(c), None, None, C.byref(rows)) == 0 and rows.value == 0
+    i8 = (C.c_longlong * 8)()
+    assert L.dkmc_get_path_info(i8) == 0 and list(i8) == [info[k] for k in pr.INFO]
+
+
+# ---- repeatability and purity ---------------------------------------------------------------------------------------------------------------
+def test_two_calls_same_bytes(hip):
+    rng = np.random.default_rng(21)
+    N = 3000
+    index, element, _, x = _random_case(rng, N, 6, 0.8, 0.6, False)
+    label = np.where(element != 3, 0, -1).astype(np.int32)
+    a = run_raw(hip, index, label, x, 300, 300, 2)
+    b = run_raw(hip, index, label, x, 300, 300, 2)
+    pr.assert_equal(*a, pr.analyse(index, label, x, 300, 300, 2))
+    assert a[4]["status"] == 1 and _bytes(a) == _bytes(b)
+
+
+def test_call_changes_nothing_else(hip, dev_2p5):
+    """site_element, site_charge, neigh_idx and the labels hash the same before and after"""
+    dev, gb, p, el0 = dev_2p5
+    with _Planted(dev, gb, el0, 3.0, None):
+        dev.updateCharge(gb)
+        dev.find_clusters(gb)
+
+        def state():
+            return [hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                    for t in (gb.t["site_element"], gb.t["site_charge"], gb.neigh_idx, dev._cluster_label, gb.t["site_x"])]
+
+        before = state()
+        for slack in (0, 3):
+            dev.find_paths(gb, slack=slack)
+        assert before == state()

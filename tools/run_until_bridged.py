@@ -6,7 +6,10 @@ Prints one JSON line: steps run current-off, the step at which the verdict turne
 one of the tips does not exist), members of the analysis, and I_macro of the closing step with the current solve.
 With --gaps R every check also runs Device.find_gaps at r_max = R and the line carries, per step, the bottleneck hop of the tunnelling chain and the
 direct tip-to-tip gap (null: none within R): distances that close smoothly where the verdict only flips.
-usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0]"""
+With --paths SLACK every check from the one whose verdict is bridged on -- that one, and the check after the closing superstep -- also runs
+Device.find_paths at that slack and the line carries, per such check, the hops H of the shortest conducting path, the level and the width of the
+corridor's constriction and the x range of the sites at that level.
+usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1]"""
 import argparse
 import json
 import math
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--members", type=int, default=3, help="bit mask: 1 metal, 2 vacancies, 4 neutral vacancies only")
     ap.add_argument("--wide-radius", type=float, default=0.0, help="> 0: link members within this distance (gap-tolerant filament) instead of nearest neighbours")
     ap.add_argument("--gaps", type=float, default=0.0, metavar="R", help="> 0: log the bottleneck and the direct gap of Device.find_gaps(r_max=R) at every check")
+    ap.add_argument("--paths", type=int, default=-1, metavar="SLACK", help=">= 0: once bridged, log H and the constriction of Device.find_paths(slack=SLACK) at every check")
     a = ap.parse_args()
     import torch
     from bench import Sim
@@ -36,6 +40,15 @@ def main():
         link = (torch.as_tensor(wide.reshape(-1)).to("cuda:0"), nn)
     gaps, bridged_at, info = [], None, None
     bottleneck, direct = [], []
+    paths = []
+
+    def path_check(step):
+        _, _, _, prof, pinfo = dev.find_paths(gb, slack=a.paths, link_index=link)
+        lev = pinfo["constriction_level"]
+        paths.append(dict(step=step, status=pinfo["status"], hops=pinfo["hops"], constriction_level=lev, constriction_width=pinfo["constriction_width"],
+                          constriction_x=[float(prof["xmin"][lev]), float(prof["xmax"][lev])] if pinfo["status"] else None,
+                          corridor_sites=pinfo["corridor_sites"]))
+
     for k in range(a.max_steps):
         sim.step(False)
         _, _, info = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
@@ -46,10 +59,18 @@ def main():
             direct.append(None if ginfo["direct"] is None else ginfo["direct"][2])
         if info["bridged"]:
             bridged_at = k + 1
+            if a.paths >= 0:
+                path_check(k + 1)
             break
     p.solve_current = True
     sim.step(False)
+    if a.paths >= 0 and bridged_at is not None:                # the check after the closing superstep
+        _, _, after = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
+        if after["bridged"]:
+            path_check(bridged_at + 1)
     more = dict(gaps_r_max=a.gaps, bottleneck=bottleneck, direct=direct) if a.gaps > 0 else {}
+    if a.paths >= 0:
+        more.update(paths_slack=a.paths, paths=paths)
     print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
                           bridged_at_step=bridged_at, bridge_root=None if info is None else info["bridge_root"], gap_x=gaps,
                           n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro, **more)), flush=True)
