@@ -278,6 +278,9 @@ enum {
     S_GAP_SITE, S_GAP_CTRL, S_GAP_CELLS, S_GAP_SORTED, S_GAP_NODES, S_GAP_EDGES,
     // conduction-path analysis (paths.hip: dkmc_find_paths): the hop pairs, the predecessors, the profile rows + path, change words + stat block
     S_PT_HOP, S_PT_PRED, S_PT_ROWS, S_PT_CTRL,
+    // cluster tracking (track.hip: dkmc_track_clusters): the pair table, the per-component words of both sides, per-site slot + flags + positions,
+    // the rows of the tables, the control block
+    S_TR_HASH, S_TR_COMP, S_TR_SITE, S_TR_ROWS, S_TR_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

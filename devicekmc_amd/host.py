@@ -224,6 +224,48 @@ def find_paths(index, nn, label, x, n_left, n_right, slack=0):
     return hl, hr, path, {k: c[:rows.value] for k, c in zip(PATH_PROFILE, cols)}, info
 
 
+TRACK_INFO = ("n_prev", "n_now", "n_pairs", "stayed", "joined", "left", "regrouped", "transition", "bridge_prev", "bridge_now",
+              "born", "died", "merged", "split", "n_critical")
+TRACK_PAIRS = ("prev", "now", "count", "first_site")
+TRACK_NOW = ("root", "size", "joined", "n_parents", "main_parent", "flags")
+TRACK_PREV = ("root", "size", "left", "n_children", "main_child", "flags")
+TRACK_CHANGE = ("none", "stayed", "joined", "left", "regrouped")             # the codes of site_change
+TRACK_TRANSITION = ("open", "closed", "ruptured", "bridged")
+# flags of the two tables: bits 0, 1 the contacts; bits 2 ... 4 BORN / MERGED / FRAGMENT in the now table, DIED / SPLIT / ABSORBED in the prev table
+TRACK_LEFT, TRACK_RIGHT, TRACK_BORN, TRACK_MERGED, TRACK_FRAGMENT = 1, 2, 4, 8, 16
+TRACK_DIED, TRACK_SPLIT, TRACK_ABSORBED = 4, 8, 16
+
+
+def track_clusters(label_prev, label_now, x, n_left, n_right):
+    """dkmc_track_clusters on device tensors (label_prev, label_now: N int32, e.g. the first return values of two find_clusters calls -- they may
+    be one tensor; x: N float64 or None).  Returns (site_change: int32 device tensor of N, codes TRACK_CHANGE; pairs, now, prev: dicts of host
+    int32 arrays TRACK_PAIRS / TRACK_NOW / TRACK_PREV; critical: host int32 array of the sites that closed or broke the filament; info: dict of
+    TRACK_INFO + critical_xmin, critical_xmax).  Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(label_now.numel())
+    if int(label_prev.numel()) != N:
+        raise ValueError("track_clusters: label_prev has %d sites, label_now %d" % (int(label_prev.numel()), N))
+    _use_stream(label_now.device)
+    change = torch.empty(N, dtype=torch.int32, device=label_now.device)
+    check(L.dkmc_track_clusters(N, _ptr(label_prev), _ptr(label_now), _ptr(x) if x is not None else None, int(n_left), int(n_right), _ptr(change)))
+    i16, x2 = (C.c_longlong * 16)(), (C.c_double * 2)()
+    check(L.dkmc_get_track_info(i16, x2))
+    info = dict(zip(TRACK_INFO, (int(v) for v in i16)))
+    info.update(critical_xmin=x2[0], critical_xmax=x2[1])
+    rows = C.c_int(0)
+
+    def table(call, names, n):
+        cols = [np.empty(n, dtype=np.int32) for _ in names]
+        check(call(n, *[_np_ptr(c) for c in cols], C.byref(rows)))
+        return {k: c[:rows.value] for k, c in zip(names, cols)}
+
+    pairs = table(L.dkmc_copy_track_pairs, TRACK_PAIRS, info["n_pairs"])
+    now = table(L.dkmc_copy_track_now, TRACK_NOW, info["n_now"])
+    prev = table(L.dkmc_copy_track_prev, TRACK_PREV, info["n_prev"])
+    critical = table(L.dkmc_copy_track_critical, ("site",), info["n_critical"])["site"]
+    return change, pairs, now, prev, critical, info
+
+
 # rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
 EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
 
@@ -370,9 +412,30 @@ class Device:
         index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
         label, table, info = find_clusters(index, nn, gpubuf.site_element, gpubuf.site_charge, gpubuf.site_x, gpubuf.metal_types, members,
                                            n_left, n_right, capacity)
+        self._cluster_label_prev = getattr(self, "_cluster_label", None)       # the tensor this call replaces (a reference), for track_clusters
         self._cluster_label = label                # the device tensor, for find_gaps
         self.site_cluster, self.cluster_table, self.cluster_info = label.cpu().numpy(), table, info
         return self.site_cluster, table, info
+
+    def track_clusters(self, gpubuf: GPUBuffers, label_prev=None, label_now=None, n_left=None, n_right=None):
+        """Cluster tracking on the device (dkmc_track_clusters; definitions: include/devicekmc_hip.h) between the labels of the last two
+        find_clusters calls -- the earlier one as prev -- or between label_prev / label_now (int32 device tensors of N; one given alone replaces
+        that side): per-site change codes, the distinct (prev, now) pairs, one lineage row per component of either side, the transition of the
+        bridging verdict and the sites that closed or broke the filament, with the contact seeds of find_clusters.  Changes nothing in gpubuf.
+        Returns (site_change: host int32 array, pairs, now, prev, critical, info) and keeps them as site_change, track_pairs, track_now,
+        track_prev, track_critical, track_info."""
+        if label_now is None:
+            label_now = getattr(self, "_cluster_label", None)
+        if label_prev is None:
+            label_prev = getattr(self, "_cluster_label_prev", None)
+        if label_prev is None or label_now is None:
+            raise ValueError("track_clusters compares two labellings: fewer than two find_clusters calls were made on this Device "
+                             "(or pass label_prev and label_now)")
+        n_left, n_right = self.contact_seeds(n_left, n_right)
+        change, pairs, now, prev, critical, info = track_clusters(label_prev, label_now, gpubuf.site_x, n_left, n_right)
+        self.site_change = change.cpu().numpy()
+        self.track_pairs, self.track_now, self.track_prev, self.track_critical, self.track_info = pairs, now, prev, critical, info
+        return self.site_change, pairs, now, prev, critical, info
 
     def find_gaps(self, gpubuf: GPUBuffers, r_max=10.0, label=None, n_left=None, n_right=None):
         """Gap analysis on the device (dkmc_find_gaps; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- one with

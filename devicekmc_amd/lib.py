@@ -186,6 +186,14 @@ SYMBOLS = {
     "dkmc_copy_path_profile": (_I, [_I, vp, vp, vp, c_int_p]),
     "dkmc_debug_set_path_round_cap": (None, [_I]),
     "dkmc_debug_get_path_times": (_I, [c_dbl_p]),
+    "dkmc_track_clusters": (_I, [_I, vp, vp, vp, _I, _I, vp]),
+    "dkmc_get_track_info": (_I, [C.POINTER(C.c_longlong), c_dbl_p]),
+    "dkmc_copy_track_pairs": (_I, [_I, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_track_now": (_I, [_I, vp, vp, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_track_prev": (_I, [_I, vp, vp, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_track_critical": (_I, [_I, vp, c_int_p]),
+    "dkmc_debug_set_track_hash": (None, [_I]),
+    "dkmc_debug_get_track_times": (_I, [c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

@@ -603,6 +603,51 @@ int dkmc_get_path_info(long long *info8);
 int dkmc_copy_path_sites(int capacity, int *h_site, int *rows_out);
 int dkmc_copy_path_profile(int capacity, int *h_count, double *h_xmin, double *h_xmax, int *rows_out);
 
+/* ---- cluster tracking: lineage, merges, splits, rupture sites (csrc/track.hip; no counterpart in the reference) ----
+ * Switching is a change between two states: two labellings of one device are compared -- which sites joined or left the clusters, which clusters
+ * fused or broke, whether the bridging verdict turned, and at which sites.  A pure function of its arguments: no field of GPUBuffers, no engine
+ * state a later phase reads and no other kernel changes.
+ *   sides       a(i) = d_label_prev[i] if 0 <= d_label_prev[i] < N, else -1; b(i) the same from d_label_now: the membership rule of dkmc_find_gaps /
+ *               dkmc_find_paths.  Any label value in range is a component id; canonical labels are not required.  d_label_prev == d_label_now (the
+ *               same pointer) is allowed.
+ *   site_change d_site_change[i] (device, N int32, always written completely): 0 a = b = -1; 2 joined (a < 0 <= b); 3 left (b < 0 <= a); 1 stayed on
+ *               the main line: a, b >= 0, main_child(a) == b and main_parent(b) == a; 4 regrouped: a, b >= 0 otherwise.
+ *   pairs       the distinct (a, b) != (-1, -1), each with count = the number of sites carrying the pair and first_site = the smallest site index
+ *               carrying it.  Rows in ascending first_site: canonical, whatever computes it.
+ *   now table   one row per distinct b >= 0, ascending: root = b; size = sites with that b; joined = count(-1, b); n_parents = the number of a >= 0
+ *               with count(a, b) > 0; main_parent = the a >= 0 with the largest count(a, b), the smallest a on ties, -1 if none; flags: bit 0 touches
+ *               the left contact (a member with index < n_left_sites), bit 1 the right one (index >= N - n_right_sites; both clamped to 0 ... N, the
+ *               seeds of dkmc_find_clusters), bit 2 BORN (n_parents == 0), bit 3 MERGED (n_parents >= 2), bit 4 FRAGMENT (its main parent has
+ *               n_children >= 2).
+ *   prev table  the same from the other side: root, size, left = count(a, -1), n_children, main_child (largest count, smallest b on ties, -1 if
+ *               none), flags: bits 0, 1 the contact bits on the prev labels, bit 2 DIED (n_children == 0), bit 3 SPLIT (n_children >= 2), bit 4
+ *               ABSORBED (its main child has n_parents >= 2).
+ *   verdicts    a side is bridged when one of its components has both contact bits; bridge_prev / bridge_now = the smallest such root, or -1.
+ *               transition: 0 open -> open, 1 closed (open -> bridged), 2 ruptured (bridged -> open), 3 bridged -> bridged.
+ *   critical    at transition 1 the sites with b = bridge_now and a = -1: those whose arrival closed the filament; at transition 2 the sites with
+ *               a = bridge_prev and b = -1: those whose loss broke it; otherwise none.  In ascending site index.
+ *   x2          [0], [1] = min / max of d_site_x over the critical sites -- the input doubles themselves, compared through the integer key of
+ *               dkmc_find_clusters; +inf / -inf with no critical site or d_site_x == NULL.
+ *   info16      (long long) [0] prev components, [1] now components, [2] pairs, [3] stayed sites (codes 1 + 4), [4] joined, [5] left, [6] regrouped
+ *               (code 4), [7] transition, [8] bridge_prev, [9] bridge_now, [10] BORN rows, [11] DIED rows, [12] MERGED rows, [13] SPLIT rows,
+ *               [14] critical sites, [15] 0.
+ * dkmc_track_clusters collects the pairs in an open-addressing table of 64-bit keys with at least 2 N slots (a wave whose lanes carry one pair
+ * sends one set of atomics), derives both tables from one pass over the pairs and keeps the results of the LAST call in the library; it returns
+ * after they are complete.  The four row getters and dkmc_get_track_info fail (dkmc_last_error) before the first successful call.  Any getter
+ * pointer may be NULL; capacity truncates and *rows_out reports the rows copied (the true counts are info16[2], [1], [0] and [14]).  N == 0, or no
+ * member on either side, succeeds with empty tables, transition 0 and bridge roots -1.  N < 0, N > 2^30, or d_label_prev, d_label_now or
+ * d_site_change NULL with N > 0 fail with code 3 before any launch.  Integer atomics only (counts, minima, maxima of packed words), no
+ * floating-point arithmetic: the same inputs give the same bytes on every call. */
+enum { DKMC_TRACK_LEFT = 1, DKMC_TRACK_RIGHT = 2, DKMC_TRACK_BORN = 4, DKMC_TRACK_MERGED = 8, DKMC_TRACK_FRAGMENT = 16,
+       DKMC_TRACK_DIED = 4, DKMC_TRACK_SPLIT = 8, DKMC_TRACK_ABSORBED = 16 };
+int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, const double *d_site_x, int n_left_sites, int n_right_sites,
+                        int *d_site_change);
+int dkmc_get_track_info(long long *info16, double *x2);
+int dkmc_copy_track_pairs(int capacity, int *h_prev, int *h_now, int *h_count, int *h_first_site, int *rows_out);
+int dkmc_copy_track_now(int capacity, int *h_root, int *h_size, int *h_joined, int *h_n_parents, int *h_main_parent, int *h_flags, int *rows_out);
+int dkmc_copy_track_prev(int capacity, int *h_root, int *h_size, int *h_left, int *h_n_children, int *h_main_child, int *h_flags, int *rows_out);
+int dkmc_copy_track_critical(int capacity, int *h_site, int *rows_out);
+
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
 int dkmc_update_temperatureglobal_gpu(const double *d_site_power, double *d_T_bg, int N, double a_coeff,

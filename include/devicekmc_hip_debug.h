@@ -221,6 +221,13 @@ void dkmc_debug_set_gap_cell_skip(int on);
  * them included) and of its summaries (outputs, profile, predecessors, walk); both 0 with profiling off. */
 void dkmc_debug_set_path_round_cap(int cap);
 int dkmc_debug_get_path_times(double *ms2);
+/* Test aid of dkmc_track_clusters (csrc/track.hip): mode 0 (default) = the rule, a key starts probing at its hash; mode 1 = every key starts
+ * probing at the last slot of the pair table, so that the longest chains and the wrap-around are exercised.  The capacity is unchanged, so every
+ * insert still ends; the results are the same bytes either way.
+ * Measurement aid: with dkmc_set_profiling(1), ms2 = HIP-event time of the last call's pair pass (with the clearing of its table) and of
+ * everything after it (lineage, codes, scans, tables); both 0 with profiling off. */
+void dkmc_debug_set_track_hash(int mode);
+int dkmc_debug_get_track_times(double *ms2);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);

@@ -9,7 +9,10 @@ direct tip-to-tip gap (null: none within R): distances that close smoothly where
 With --paths SLACK every check from the one whose verdict is bridged on -- that one, and the check after the closing superstep -- also runs
 Device.find_paths at that slack and the line carries, per such check, the hops H of the shortest conducting path, the level and the width of the
 corridor's constriction and the x range of the sites at that level.
-usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1]"""
+With --track every check from the second on also runs Device.track_clusters between its labelling and the one before and the line carries, per
+such check, the transition, the sites that joined, left and regrouped and the MERGED rows; the closing check also carries the number of the sites
+whose arrival closed the filament and their x range.
+usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1] [--track]"""
 import argparse
 import json
 import math
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--wide-radius", type=float, default=0.0, help="> 0: link members within this distance (gap-tolerant filament) instead of nearest neighbours")
     ap.add_argument("--gaps", type=float, default=0.0, metavar="R", help="> 0: log the bottleneck and the direct gap of Device.find_gaps(r_max=R) at every check")
     ap.add_argument("--paths", type=int, default=-1, metavar="SLACK", help=">= 0: once bridged, log H and the constriction of Device.find_paths(slack=SLACK) at every check")
+    ap.add_argument("--track", action="store_true", help="from the second check on, log the transition and the joined / left / regrouped sites of Device.track_clusters")
     a = ap.parse_args()
     import torch
     from bench import Sim
@@ -49,9 +53,20 @@ def main():
                           constriction_x=[float(prof["xmin"][lev]), float(prof["xmax"][lev])] if pinfo["status"] else None,
                           corridor_sites=pinfo["corridor_sites"]))
 
+    track = []
+
+    def track_check(step):
+        _, _, _, _, _, t = dev.track_clusters(gb)
+        rec = dict(step=step, transition=host.TRACK_TRANSITION[t["transition"]], joined=t["joined"], left=t["left"], regrouped=t["regrouped"], merged=t["merged"])
+        if t["transition"] == 1:
+            rec.update(closing_sites=t["n_critical"], closing_x=[t["critical_xmin"], t["critical_xmax"]])
+        track.append(rec)
+
     for k in range(a.max_steps):
         sim.step(False)
         _, _, info = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
+        if a.track and k > 0:
+            track_check(k + 1)
         gaps.append(info["gap_x"] if math.isfinite(info["gap_x"]) else None)
         if a.gaps > 0:
             _, _, ginfo = dev.find_gaps(gb, r_max=a.gaps)
@@ -71,6 +86,8 @@ def main():
     more = dict(gaps_r_max=a.gaps, bottleneck=bottleneck, direct=direct) if a.gaps > 0 else {}
     if a.paths >= 0:
         more.update(paths_slack=a.paths, paths=paths)
+    if a.track:
+        more.update(track=track)
     print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
                           bridged_at_step=bridged_at, bridge_root=None if info is None else info["bridge_root"], gap_x=gaps,
                           n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro, **more)), flush=True)
