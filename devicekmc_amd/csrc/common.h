@@ -198,6 +198,10 @@ struct Engine {
     long long x_tile_drop_gate = 0;     // test aid (dkmc_set_x_tile_drop_auto_subblocks): stored sub-blocks at and above which that rule switches the live view on; 0 = the measured gate
     double x_tile_drop_used = 0.0;      // the threshold the sweeps of the last current solve ran on, 0 = the full view (dkmc_get_x_tile_drop_used)
     int xtl_census_form = 1;       // census of the live view: 1 (default; 0.87 of form 0's time per solve at 9.4e5 sites, profiles/x_tile_census_forms_tile10.jsonl) = from the fp32 image with a guard band and an fp64 re-read of the undecided sub-blocks, 0 = from the fp64 store; same result (dkmc_debug_xtl_census_form; xt_live.h)
+    int x_static_tiles = 2;        // S with the inner-contact metals FIRST, and the all-metal strips of the tile store kept from solve to solve (dkmc_set_x_static_tiles; current.hip step 2, xt_static.h): 0 = atom order and a full fill, 1 = on, 2 (default) = on where it applies (one GPU, tiled X)
+    int x_static_gate = 0;         // test aid (dkmc_debug_set_x_static_gate): members of S at and above which mode 2 takes the metals-first order; 0 = the measured gate (x_static_rule)
+    int x_static_nM = -1;          // this solve's S is in metals-first order with that many metals in front; -1 = atom order (set by current.hip step 2, read by xt.hip)
+    int x_static_verify = 0;       // test aid (dkmc_debug_x_static_verify): every assembly in metals-first order is followed by a full census and a full fill into separate buffers, compared word by word
     int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
@@ -224,6 +228,10 @@ struct Engine {
     size_t bufsz[NBUF] = {0};
 };
 
+// Size rule of dkmc_set_x_static_tiles(2): 1 = a tunnelling set of ns members takes the metals-first order.  Measured on whole supersteps against atom
+// order (profiles/ab_bench_x_static_tiles.txt): 7.5nm (8 353 members) and tile:5 (23 224) lose or tie, tile:6 (33 445) and everything above gain.
+constexpr int X_STATIC_GATE = 32768;
+static inline int x_static_rule(int ns, int gate_override) { return ns >= (gate_override > 0 ? gate_override : X_STATIC_GATE) ? 1 : 0; }
 Engine &eng();
 int dkmc_fail(int code, const char *what, const char *file, int line);
 // persistent scratch: returns a device buffer of at least `bytes`, identified by slot

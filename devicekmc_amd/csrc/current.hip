@@ -105,6 +105,24 @@ __global__ void k_tc_check_cols(int ns, const SEntry *__restrict__ S, const int 
     const int mr = mrank_atom[S[k].idx];
     if (mr >= nL && (mr < col_lo || mr >= col_lo + ncols)) flags[0] = 1;
 }
+// S with the metals first (dkmc_set_x_static_tiles): a member of S is a vacancy or an inner-contact metal.  moff = exclusive scan of the metal
+// flags, moff[Na] = their count nM; metal a goes to rank moff[a], vacancy a behind all metals, to nM + (vacancies of S in front of it)
+__global__ void k_S_metal_flags(int Na, const int *__restrict__ inS, const int *__restrict__ aflag, int *__restrict__ isM)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a < Na) isM[a] = (inS[a] && !(aflag[a] & AF_V)) ? 1 : 0;
+}
+__global__ void k_S_scatter_metals_first(int Na, const int *__restrict__ inS, const int *__restrict__ off, const int *__restrict__ moff,
+                                         const int *__restrict__ aflag, const double *__restrict__ acb, SEntry *S, int *srank)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= Na) return;
+    if (inS[a]) {
+        const int f = aflag[a];
+        const int r = (f & AF_V) ? moff[Na] + (off[a] - moff[a]) : moff[a];
+        SEntry e; e.cb = acb[a]; e.idx = a; e.flag = f; S[r] = e; srank[a] = r;
+    } else srank[a] = -1;
+}
 __global__ void k_fill_i32(int *p, int n, int v) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
 
 struct TCacheState {
@@ -139,9 +157,11 @@ void tcache_invalidate(const void *key) { if (XBufState *st = xstate_find(key)) 
 static void tc_release();
 // new structure behind the same buffer (initialize_sparsity) or buffer freed: drop everything kept for it
 void pairsum_invalidate();      // potential.hip: the cached site grouping of the pair sum is keyed on the same arrays
+void xt_static_invalidate();    // xt_static.h: the kept all-metal strips of the tile store describe the structure behind one buffer
 void xstate_reset(const void *key)
 {
     pairsum_invalidate();
+    xt_static_invalidate();
     XBufState *st = xstate_find(key);
     if (!st) return;
     XBufState *save = g_cur; g_cur = st;
@@ -525,8 +545,27 @@ static int update_power_body(dkmc_gpubuf *buf, int n_src, int n_gnd, int nlc, do
     rc = dkmc_exclusive_scan_i32(inS, soff, Na, soff + Na); if (rc) return rc;
     int ns = 0;
     HIPCHK(hipMemcpyAsync(&ns, soff + Na, sizeof(int), hipMemcpyDeviceToHost, st));
-    hipLaunchKernelGGL(k_S_scatter, dim3(nba), dim3(256), 0, st, Na, inS, soff, aflag, buf->atom_CB_edge, S, srank);
-    HIPCHK(hipStreamSynchronize(st));
+    // S order.  Atom order (the reference's; k_xpat_S of the CSR path and the windows of a sharded or slab-distributed solve rely on it), or -- one
+    // GPU, tiled X, dkmc_set_x_static_tiles -- [inner-contact metals in atom order | vacancies in atom order]: the S ranks of the metals then do not
+    // depend on the vacancies, and the all-metal strips of the tile store stay what they were from solve to solve (xt_static.h)
+    // Mode 2 takes the new order from the measured size on (x_static_rule: below it the tile launches of the sweeps lose more than the fill saves)
+    e.x_static_nM = -1;
+    bool metals_first = e.x_static_tiles != 0 && e.x_format != 0 && !comm_attached();
+    if (metals_first && e.x_static_tiles == 2) { HIPCHK(hipStreamSynchronize(st)); metals_first = x_static_rule(ns, e.x_static_gate) != 0; }
+    if (metals_first) {
+        int *isM = (int *)scratch(S_MISC0, (size_t)Na * 4), *moff = (int *)scratch(S_MISC1, (size_t)(Na + 4) * 4);
+        if (!isM || !moff) return e.err_code;
+        int nM = 0;
+        hipLaunchKernelGGL(k_S_metal_flags, dim3(nba), dim3(256), 0, st, Na, (const int *)inS, (const int *)aflag, isM);
+        rc = dkmc_exclusive_scan_i32(isM, moff, Na, moff + Na); if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(&nM, moff + Na, sizeof(int), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_S_scatter_metals_first, dim3(nba), dim3(256), 0, st, Na, (const int *)inS, (const int *)soff, (const int *)moff, aflag, buf->atom_CB_edge, S, srank);
+        HIPCHK(hipStreamSynchronize(st));
+        e.x_static_nM = nM;
+    } else {
+        hipLaunchKernelGGL(k_S_scatter, dim3(nba), dim3(256), 0, st, Na, inS, soff, aflag, buf->atom_CB_edge, S, srank);
+        HIPCHK(hipStreamSynchronize(st));
+    }
 
     const int nbr = (Nsub + 255) / 256;
     double *rhs = (double *)scratch(S_X_RHS, (size_t)(Na + 2) * 8);

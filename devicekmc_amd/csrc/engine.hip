@@ -93,6 +93,12 @@ int dkmc_get_x_tile_drop_auto(void) { return eng().x_tile_drop_auto; }
 void dkmc_set_x_tile_drop_auto_subblocks(long long gate) { eng().x_tile_drop_gate = gate > 0 ? gate : 0; }
 double dkmc_get_x_tile_drop_used(void) { return eng().x_tile_drop_used; }
 void dkmc_debug_fail_true_residual_once(void) { eng().x_tile_f32_fail_once = 1; }
+void dkmc_set_x_static_tiles(int mode) { eng().x_static_tiles = (mode == 0 || mode == 1) ? mode : 2; }
+int dkmc_get_x_static_tiles(void) { return eng().x_static_tiles; }
+int dkmc_debug_x_static_verify(int on) { const int was = eng().x_static_verify; eng().x_static_verify = on ? 1 : 0; return was; }
+void dkmc_debug_set_x_static_gate(int members) { eng().x_static_gate = members > 0 ? members : 0; }
+int dkmc_x_static_rule(int members) { return x_static_rule(members, eng().x_static_gate); }
+int dkmc_x_static_strips(int n_metals) { return n_metals > 0 ? n_metals / 256 : 0; }      // xt_static.h: w_static (256 = XT_C, the columns of a strip)
 void dkmc_set_x_nmul_form(int form) { eng().x_nmul_form = form == 0 ? 0 : 1; }
 int dkmc_get_x_nmul_form(void) { return eng().x_nmul_form; }
 void dkmc_set_x_nmul_lane_bytes(int bytes) { eng().x_nmul_lane_bytes = bytes == 8 ? 8 : 16; }

@@ -29,11 +29,14 @@ int tc_prepare_tiled(const XParams &P, dkmc_gpubuf *buf, int ns, const SEntry *S
 #include <vector>
 #include <algorithm>
 #include <stdlib.h>
+#include <string.h>
 
 // value of the tunnelling entry between two members of S (0 = no entry); symmetric in its two atoms bit for bit
+// have_pre: the coefficient-cache look-up of a (metal 1, vacancy 2) pair was made beforehand -- pre = the cached value, NaN = a miss (k_xt_fill<1>)
 __device__ __forceinline__ double xt_tvalue(const XParams &P, double prefac, const TCacheView &TC,
                                             double x1, double y1, double z1, double cb1, int f1, int slot1, int slotA1, int mr1,
-                                            double x2, double y2, double z2, double cb2, int f2, int slot2, int slotA2, int mr2)
+                                            double x2, double y2, double z2, double cb2, int f2, int slot2, int slotA2, int mr2,
+                                            bool have_pre = false, double pre = 0.0)
 {
     const double d = site_dist(x1, y1, z1, x2, y2, z2, P.laty, P.latz, P.pbc);
     if (d < P.nn_dist) return 0.0;                                   // neighbour pair: direct term, part of Xs
@@ -42,7 +45,8 @@ __device__ __forceinline__ double xt_tvalue(const XParams &P, double prefac, con
     if (kind == 1 && TC.enabled) {
         const bool v1 = f1 & AF_V;
         double cv;
-        if (tc_lookup(TC, v1 ? slot1 : slot2, v1 ? slotA1 : slotA2, v1 ? mr2 : mr1, cv)) return -cv;
+        if (have_pre && !v1) { if (pre == pre) return -pre; }
+        else if (tc_lookup(TC, v1 ? slot1 : slot2, v1 ? slotA1 : slotA2, v1 ? mr2 : mr1, cv)) return -cv;
     }
     return -wkb_T(kind, 1e-10 * d, fabs(cb1 - cb2), prefac, P.V0);
 }
@@ -76,11 +80,14 @@ __global__ void k_xt_snode_slots(int ns, int ns_pad, const SEntry *__restrict__ 
 // ---- census: which 32 x 32 sub-blocks of the upper triangle hold an entry -----------------------------------------------------
 // One wave per cell, cells in strip-major order (ci = w * nK + k).  Predicate only (no WKB value): class flags, |dE| > tol,
 // not a neighbour pair, column rank above row rank.  A full cell is recognised after its first row.
-__global__ __launch_bounds__(XT_NT) void k_xt_census(XParams P, int ns, int nK, int nW, SNodes S, unsigned *__restrict__ cmask)
+// keep_flags != null: the first n_keep_cells cells (the all-metal strips, xt_static.h) already hold their masks unless keep_flags[0] is set.
+__global__ __launch_bounds__(XT_NT) void k_xt_census(XParams P, int ns, int nK, int nW, SNodes S, unsigned *__restrict__ cmask,
+                                                     const int *__restrict__ keep_flags, long long n_keep_cells)
 {
     const int lane = threadIdx.x & 63;
     const long long ci = (long long)blockIdx.x * (XT_NT / 64) + (threadIdx.x >> 6);
     if (ci >= (long long)nK * nW) return;
+    if (keep_flags && ci < n_keep_cells && keep_flags[0] == 0) return;
     const int w = (int)(ci / nK), k = (int)(ci % nK);
     unsigned m = 0;
     if (XT_C * w + XT_C - 1 > XT_R * k) {                            // the cell reaches above the diagonal
@@ -213,11 +220,18 @@ __global__ void k_xt_rank_items(const int *__restrict__ nitems_dev, int ntiles, 
 // Element (row r, column 32 q + c) of sub-block slot sl sits at ((sl * 32 + r) * 32 + c): a sub-block is 8 consecutive
 // 1-KiB wave loads of the apply kernel.  tval32 != null: every value also goes, rounded to float, into the fp32 image of the store (xt_tval32_pos: the
 // same sub-block order at half width; a value that rounds to zero or to a subnormal stays within the image's error bound 2^-24 |v|).
+// The non-zeros of the first t_split tiles of the launch are counted in nnz_upper[1], the others' in nnz_upper[0] (xt_static.h: the kept prefix).
+// TR = 1 (S with the metals first: the vacancies are COLUMNS of the contact x vacancy tiles): the coefficient-cache values of the (metal row, vacancy
+// column) pairs are fetched with the lanes along the rows -- consecutive metals are consecutive cache columns, one 128-byte segment per vacancy -- and
+// turned through LDS, 16 rows at a time; a thread that walked its own vacancy's cache row instead would touch 32 cache lines per wave instruction
+// (measured at 9.4e5 sites: the 0.87 M sub-blocks behind the kept strips then take as long as all 2.0 M).  Same look-ups, same values, same bits.
+template <int TR>
 __global__ __launch_bounds__(XT_NT) void k_xt_fill(XParams P, int ns, const XTile *__restrict__ tiles, int sub_base, SNodes S, TCacheView TC,
-                                                   double *__restrict__ tval, unsigned long long *__restrict__ nnz_upper, float *__restrict__ tval32)
+                                                   double *__restrict__ tval, unsigned long long *__restrict__ nnz_upper, float *__restrict__ tval32, int t_split)
 {
     __shared__ double rx[XT_R], ry[XT_R], rz[XT_R], rcb[XT_R];
     __shared__ int rf[XT_R], rslot[XT_R], rslotA[XT_R], rmr[XT_R];
+    __shared__ double lt[TR ? XT_C / XT_SBW : 1][TR ? XT_R / 2 : 1][TR ? XT_SBW + 1 : 1];
     const XTile td = tiles[blockIdx.x];
     const int tid = threadIdx.x;
     if (tid < XT_R) {
@@ -235,18 +249,38 @@ __global__ __launch_bounds__(XT_NT) void k_xt_fill(XParams P, int ns, const XTil
         const double cx = S.x[sc], cy = S.y[sc], cz = S.z[sc], ccb = S.cb[sc];
         const int cf = S.flag[sc], cslot = S.slot[sc], cslotA = S.slotA[sc], cmr = S.mr[sc];
         const double prefac = -(sqrt(2 * P.m_e) / DKMC_HBAR) * (2.0 / 3.0);
-        for (int r = 0; r < XT_R; ++r) {
-            const int s = XT_R * td.k + r;
-            double v = 0.0;
-            if (sc > s && cf && rf[r])
-                v = xt_tvalue(P, prefac, TC, rx[r], ry[r], rz[r], rcb[r], rf[r], rslot[r], rslotA[r], rmr[r], cx, cy, cz, ccb, cf, cslot, cslotA, cmr);
-            dst[r * XT_SBW] = v;
-            if (dst32) dst32[xt_tval32_pos(r, c)] = (float)v;
-            cnt += v != 0.0;
+        const bool pre = TR && TC.enabled;
+#pragma unroll 1
+        for (int half = 0; half < (TR ? 2 : 1); ++half) {
+            if (pre) {
+                // lane (rr = c % 16, par = c / 16) of this sub-block's 32 lanes: row 16 half + rr, every second column from par
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int rr = c & 15, par = c >> 4;
+                const int my_mr = (rf[(XT_R / 2) * half + rr] & AF_V) ? -1 : rmr[(XT_R / 2) * half + rr];
+                for (int jj = 0; jj < XT_SBW / 2; ++jj) {
+                    const int j = 2 * jj + par;
+                    const int fj = __shfl(cf, j, 32), sj = __shfl(cslot, j, 32), sAj = __shfl(cslotA, j, 32);
+                    double cv, o = __longlong_as_double(0x7ff8000000000000ll);
+                    if ((fj & AF_V) && tc_lookup(TC, sj, sAj, my_mr, cv)) o = cv;
+                    lt[TR ? q : 0][TR ? rr : 0][TR ? j : 0] = o;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            const int r0 = TR ? (XT_R / 2) * half : 0, r1 = TR ? r0 + XT_R / 2 : XT_R;
+            for (int r = r0; r < r1; ++r) {
+                const int s = XT_R * td.k + r;
+                double v = 0.0;
+                if (sc > s && cf && rf[r])
+                    v = xt_tvalue(P, prefac, TC, rx[r], ry[r], rz[r], rcb[r], rf[r], rslot[r], rslotA[r], rmr[r], cx, cy, cz, ccb, cf, cslot, cslotA, cmr,
+                                  pre, pre ? lt[TR ? q : 0][TR ? r - r0 : 0][TR ? c : 0] : 0.0);
+                dst[r * XT_SBW] = v;
+                if (dst32) dst32[xt_tval32_pos(r, c)] = (float)v;
+                cnt += v != 0.0;
+            }
         }
     }
     cnt = wave_sum_all_i(cnt);
-    if ((tid & 63) == 0 && cnt) atomicAdd(nnz_upper, (unsigned long long)cnt);
+    if ((tid & 63) == 0 && cnt) atomicAdd(nnz_upper + ((int)blockIdx.x < t_split ? 1 : 0), (unsigned long long)cnt);
 }
 
 // ---- apply: one pass over the tiles (+ the sparse rows in the same launch) -----------------------------------------------
@@ -1028,6 +1062,7 @@ static int xt_build_items(int nK, int nW, int kc, int ntiles, long long nsub_tot
 }
 
 #include "xt_live.h"
+#include "xt_static.h"
 
 // Second stream of the sharded solve: the neighbour part of the product (replicated on every rank, ~0.3 GB at 9.4e5 sites) runs
 // here, beside the tile pass, the partial row sums and the all-reduce on the engine's stream; the two meet again before the rows
@@ -1067,6 +1102,17 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     float *tval32 = nullptr;
     SNodes SN{};
     double *xbuf = nullptr;
+    // the all-metal strips kept from the last solve (xt_static.h): dropped here, set again after this solve's last synchronisation
+    XStatic &K = g_xs;
+    const bool k_had = K.valid;
+    K.valid = false; K.pending = false; K.reused = false; K.verify_nnz = -1;
+    const int nM_first = (!sharded && e.x_format != 0) ? e.x_static_nM : -1;       // >= 0: S is in metals-first order (current.hip step 2)
+    const int w_static = nM_first >= 0 ? xs_w_static(nM_first) : 0;
+    for (int c = 0; c < 8; ++c) K.info[c] = 0;
+    for (int c = 0; c < 4; ++c) K.verify[c] = 0;
+    K.info[0] = nM_first >= 0 ? 1 : 0; K.info[1] = w_static; K.info[6] = XS_NA; K.info[7] = -1;
+    int t_static = 0, xs_reason = XS_NA; long long sub_static = 0;
+    bool k_cand = false;                 // the kept prefix is still in the running
     auto assemble = [&]() -> int {
         if (g_fault_phase == 1) { g_fault_phase = 0; return dkmc_fail(90, "injected fault (assembly of X)", __FILE__, __LINE__); }
         if (sharded) { xbuf = (double *)scratch(S_CG_XCHG, ((size_t)ns * (e.x_block > 1 ? 16 : 1) + 2) * (e.x_block > 1 ? comm_nranks() : 1) * 8); if (!xbuf) return e.err_code; if (ns > 0) { rc = side_stream_init(g_side); if (rc) return rc; } }
@@ -1104,6 +1150,17 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         hipLaunchKernelGGL(k_xt_snodes, dim3((ns_pad + 255) / 256), dim3(256), 0, st, ns, ns_pad, S, (const double *)buf->atom_x, (const double *)buf->atom_y,
                            (const double *)buf->atom_z, sd, sd + ns_pad, sd + 2 * (size_t)ns_pad, sd + 3 * (size_t)ns_pad, si, srow);
         g_xb.S = SN; g_xb.srow = srow;
+        if (w_static > 0) {
+            const double par[6] = {P.tol, P.nn_dist, P.m_e, P.V0, P.laty, P.latz};
+            if (!k_had || K.key != (const void *)buf->site_x) xs_reason = XS_FIRST;
+            else if (K.nM != nM_first || K.w_static != w_static) xs_reason = XS_METALS;
+            else if (memcmp(par, K.par, sizeof(par)) != 0 || K.pbc != P.pbc) xs_reason = XS_PARAMS;
+            else {
+                k_cand = true; xs_reason = XS_KEPT;
+                HIPCHK(hipMemsetAsync(K.flags, 0, 4 * sizeof(int), st));
+                hipLaunchKernelGGL(k_xs_cmp_metals, dim3((nM_first + 255) / 256), dim3(256), 0, st, nM_first, SN, (const double *)K.snap_d, (const int *)K.snap_f, K.flags);
+            }
+        }
 
         // ---- census -> tile list -> work items ----
         X.ntiles = 0; X.nitems = 0; X.nsub_total = 0; X.t_upper = 0; X.kc = 1;
@@ -1115,15 +1172,29 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
             toff = (int *)scratch(S_XT_TOFF, (size_t)(ncell + 4) * 4);
             soff = (int *)scratch(S_XT_SOFF, (size_t)(ncell + 4) * 4);
             if (!cmask || !is_tile || !nsubc || !toff || !soff) return e.err_code;
-            hipLaunchKernelGGL(k_xt_census, dim3((unsigned)((ncell + 3) / 4)), dim3(XT_NT), 0, st, P, ns, nK, nW, SN, cmask);
+            // (kept strips: their cells' masks come from the kept tile prefix; the census takes them only if the metals turn out to differ)
+            const long long n_keep = k_cand ? (long long)w_static * nK : 0;
+            if (k_cand) {
+                HIPCHK(hipMemsetAsync(cmask, 0, (size_t)n_keep * 4, st));
+                if (K.t_static > 0) hipLaunchKernelGGL(k_xs_scatter_masks, dim3((K.t_static + 255) / 256), dim3(256), 0, st, K.t_static, (const XTile *)K.tiles, nK, (const int *)K.flags, cmask);
+            }
+            hipLaunchKernelGGL(k_xt_census, dim3((unsigned)((ncell + 3) / 4)), dim3(XT_NT), 0, st, P, ns, nK, nW, SN, cmask, k_cand ? (const int *)K.flags : (const int *)nullptr, n_keep);
             hipLaunchKernelGGL(k_xt_cell_counts, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, ncell, (const unsigned *)cmask, is_tile, nsubc);
             rc = dkmc_exclusive_scan_i32(is_tile, toff, (int)ncell, toff + ncell); if (rc) return rc;
             rc = dkmc_exclusive_scan_i32(nsubc, soff, (int)ncell, soff + ncell); if (rc) return rc;
-            int h2[2] = {0, 0};
+            int h2[2] = {0, 0}, hs[2] = {0, 0}, hf = 0;
             HIPCHK(hipMemcpyAsync(&h2[0], toff + ncell, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(&h2[1], soff + ncell, sizeof(int), hipMemcpyDeviceToHost, st));
+            if (w_static > 0) {         // tiles and sub-blocks in front of strip w_static; the verdict on the metals
+                HIPCHK(hipMemcpyAsync(&hs[0], toff + (long long)w_static * nK, sizeof(int), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(&hs[1], soff + (long long)w_static * nK, sizeof(int), hipMemcpyDeviceToHost, st));
+                if (k_cand) HIPCHK(hipMemcpyAsync(&hf, K.flags, sizeof(int), hipMemcpyDeviceToHost, st));
+            }
             HIPCHK(hipStreamSynchronize(st));
             X.ntiles = h2[0]; X.nsub_total = h2[1];
+            t_static = hs[0]; sub_static = hs[1];
+            if (k_cand && hf) { k_cand = false; xs_reason = XS_METALS; }
+            if (k_cand && (t_static != K.t_static || sub_static != K.sub_static)) { k_cand = false; xs_reason = XS_PREFIX; }
             if (h2[1] < 0) return dkmc_fail(47, "update_power: more than 2^31 sub-blocks", __FILE__, __LINE__);
         }
         ntiles = X.ntiles;
@@ -1140,6 +1211,11 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
             hipLaunchKernelGGL(k_xt_tile_list, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, nK, ncell, (const unsigned *)cmask, (const int *)toff, (const int *)soff, tiles);
             hipLaunchKernelGGL(k_xt_wrange, dim3((nK + 255) / 256), dim3(256), 0, st, nK, nW, (const unsigned *)cmask, wrange);
         }
+        int h_prefix_differs = 0;            // (read back with the run list's counts, below)
+        if (k_cand && t_static > 0) {
+            hipLaunchKernelGGL(k_xs_cmp_tiles, dim3((t_static + 255) / 256), dim3(256), 0, st, t_static, (const XTile *)tiles, (const XTile *)K.tiles, K.flags);
+            HIPCHK(hipMemcpyAsync(&h_prefix_differs, K.flags + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+        }
         XShare sh{};
         if (e.x_items_kc > 0) X.kc = e.x_items_kc;
         rc = xt_build_items(nK, nW, X.kc, ntiles, X.nsub_total, toff, tiles, nr, me, S_XT_NITEMW, S_XT_ITEMS, S_XT_SPLIT, &sh, 2); if (rc) return rc;
@@ -1147,6 +1223,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         X.nitems = sh.nitems; X.maxchunk = sh.maxchunk; X.rec_shift = sh.rec_shift;
         items = sh.items; nitem_w = sh.nitem_w;
         KCHK();
+        if (k_cand && t_static > 0) { HIPCHK(hipStreamSynchronize(st)); if (h_prefix_differs) { k_cand = false; xs_reason = XS_PREFIX; } }
         g_xb.tiles = tiles; g_xb.items = items; g_xb.wrange = wrange; g_xb.nitem_w = nitem_w; g_xb.cmask = cmask; g_xb.toff = toff;
 
         // ---- this rank's share of the work items (contiguous in the strip-major tile list, balanced by stored bytes) ----
@@ -1162,6 +1239,13 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         hipLaunchKernelGGL(k_xt_snode_slots, dim3((ns_pad + 255) / 256), dim3(256), 0, st, ns, ns_pad, S, atom_site, TC, si + ns_pad, si + 4 * (size_t)ns_pad, si + 2 * (size_t)ns_pad);
 
         // ---- storage + fill ----
+        // (a kept prefix survives the growth of the store: xs_scratch_keep; an allocation that is not the one the prefix was written to ends it)
+        if (k_cand && (e.buf[S_XT_TVAL] != K.tval || e.bufsz[S_XT_TVAL] != K.tval_cap)) { k_cand = false; xs_reason = XS_STORE; }
+        if (k_cand) {
+            bool kept = true;
+            tval = (double *)xs_scratch_keep(S_XT_TVAL, (size_t)(X.sub_n + 4) * XT_SUB * 8, (size_t)sub_static * XT_SUB * 8, false, &kept);
+            if (!kept) { k_cand = false; xs_reason = XS_STORE; }
+        } else
         tval = (double *)scratch(S_XT_TVAL, (size_t)(X.sub_n + 4) * XT_SUB * 8);       // (slack: the block-CG product requests two sub-blocks beyond a full tile)
         rowpart = (double *)scratch(S_XT_ROWPART, (size_t)(ncell + 1) * XT_R * 8);
         colpart = (double *)scratch(S_XT_COLPART, (size_t)(X.nitems + 1) * XT_C * 8);       // one 256-entry record per run (32 MB at 9.4e5 sites; [run position][S rank] took 1.8 GB)
@@ -1172,15 +1256,53 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         tval32 = nullptr; e.stats.x_tile_stream = 0; e.stats.x_tile_f64_rounds = 0; e.stats.x_tile_f32_bytes = 0;
         if (e.x_tile_f32 != 0 && !sharded && e.x_block > 1 && e.x_poly > 0 && e.cg_tol >= 1e-8 && X.tile_n > 0) {
             const size_t b32 = (size_t)(X.sub_n + 4) * XT_SUB * 4;
-            tval32 = (float *)scratch_try(S_XT_TVAL32, b32);
+            if (k_cand && K.img && e.buf[S_XT_TVAL32] == K.tval32 && e.bufsz[S_XT_TVAL32] == K.tval32_cap) {
+                bool kept = true;
+                tval32 = (float *)xs_scratch_keep(S_XT_TVAL32, b32, (size_t)sub_static * XT_SUB * 4, true, &kept);
+                if (!kept) { k_cand = false; xs_reason = XS_IMAGE; }
+            } else {
+                if (k_cand) { k_cand = false; xs_reason = K.img ? XS_STORE : XS_IMAGE; }
+                tval32 = (float *)scratch_try(S_XT_TVAL32, b32);
+            }
             if (tval32) e.stats.x_tile_f32_bytes = (long long)b32; else e.stats.x_tile_stream = -1;
         }
         HIPCHK(hipMemsetAsync(rowpart, 0, (size_t)(ncell + 1) * XT_R * 8, st));
         HIPCHK(hipMemsetAsync(colpart, 0, (size_t)(X.nitems + 1) * XT_C * 8, st));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 16, st));
-        if (X.tile_n > 0)
-            hipLaunchKernelGGL(k_xt_fill, dim3(X.tile_n), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles + X.tile_lo, (int)X.sub_base, SN, TC, tval, d_cnt, tval32);
+        if (k_cand && (tval32 != nullptr) != K.img) { k_cand = false; xs_reason = XS_IMAGE; }       // (no image this time, or none last time: nothing of it is reused)
+        if (w_static > 0 && !k_cand) { rc = xs_reserve(nM_first, t_static); if (rc) return rc; }
+        // the kept prefix stands: the fill starts at the first tile of strip w_static
+        // (metals-first order: the all-metal strips hold no cache look-up and take the plain form, counted apart; the tiles behind them the form
+        // whose look-ups run along the metal rows)
+        const int t_fill0 = k_cand ? t_static : 0;
+        if (nM_first < 0) {
+            if (X.tile_n > 0)
+                hipLaunchKernelGGL((k_xt_fill<0>), dim3(X.tile_n), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles + X.tile_lo, (int)X.sub_base, SN, TC, tval, d_cnt, tval32, 0);
+        } else {
+            if (t_fill0 == 0 && t_static > 0)
+                hipLaunchKernelGGL((k_xt_fill<0>), dim3(t_static), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles, (int)X.sub_base, SN, TC, tval, d_cnt, tval32, t_static);
+            if (X.tile_n - t_static > 0)
+                hipLaunchKernelGGL((k_xt_fill<1>), dim3(X.tile_n - t_static), dim3(XT_NT), 0, st, P, ns, (const XTile *)tiles + t_static, (int)X.sub_base, SN, TC, tval, d_cnt, tval32, 0);
+        }
         KCHK();
+        K.info[2] = k_cand ? t_static : 0; K.info[3] = X.tile_n - t_fill0; K.info[4] = k_cand ? sub_static : 0; K.info[5] = X.sub_n - (k_cand ? sub_static : 0); K.info[6] = xs_reason;
+        if (w_static > 0) {
+            // what becomes the kept state once this solve has passed its last synchronisation (xt_assemble_and_solve, below)
+            if (!k_cand) {
+                if (t_static > 0) HIPCHK(hipMemcpyAsync(K.tiles, tiles, (size_t)t_static * sizeof(XTile), hipMemcpyDeviceToDevice, st));
+                hipLaunchKernelGGL(k_xs_snapshot, dim3((nM_first + 255) / 256), dim3(256), 0, st, nM_first, SN, K.snap_d, K.snap_f);
+                KCHK();
+                const double par[6] = {P.tol, P.nn_dist, P.m_e, P.V0, P.laty, P.latz};
+                memcpy(K.par, par, sizeof(par)); K.pbc = P.pbc;
+                K.key = (const void *)buf->site_x; K.nM = nM_first; K.w_static = w_static; K.t_static = t_static; K.sub_static = sub_static;
+            }
+            K.tval = e.buf[S_XT_TVAL]; K.tval_cap = e.bufsz[S_XT_TVAL]; K.img = tval32 != nullptr;
+            K.tval32 = K.img ? e.buf[S_XT_TVAL32] : nullptr; K.tval32_cap = K.img ? e.bufsz[S_XT_TVAL32] : 0;
+            K.pending = true; K.reused = k_cand;
+        }
+        if (e.x_static_verify && nM_first >= 0 && ncell > 0) {
+            rc = xs_verify(P, ns, nK, nW, ncell, SN, TC, cmask, tiles, ntiles, X.nsub_total, tval, tval32); if (rc) return rc;
+        }
         g_xb.tval32 = tval32;
         g_xb.tval = tval; g_xb.rowpart = rowpart; g_xb.colpart = colpart;
         X.valid = true;
@@ -1337,8 +1459,20 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     KCHK();
     // the solution every later phase starts from: rank 0's bits (the block-CG adds the ranks' slots in rank order on every rank: same bits already)
     if (sharded && !solved) { rc = comm_bcast0_f64(y, (size_t)m); if (rc) return rc; }
-    HIPCHK(hipMemcpyAsync(&X.t_upper, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    unsigned long long h_cnt[2] = {0, 0};               // non-zeros the fill counted: [0] behind the all-metal strips, [1] in them (0 where they were kept)
+    HIPCHK(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    X.t_upper = h_cnt[0] + (K.pending && K.reused ? K.nnz_static : h_cnt[1]);
+    if (K.pending && !e.err_code) {                     // the fill has completed and the solve went through: the prefix may be kept
+        if (!K.reused) K.nnz_static = h_cnt[1];
+        K.valid = true;
+    }
+    K.pending = false;
+    if (K.verify_nnz >= 0) {
+        const long long d = (long long)X.t_upper - K.verify_nnz;
+        K.verify[3] = d < 0 ? -d : d;
+        K.info[7] = K.verify[0] + K.verify[1] + K.verify[2] + K.verify[3];
+    }
     e.x_iter_hint = h.iters;
     if (iters_out) *iters_out = h.iters;
     if (rr_out) *rr_out = h.rr[h.iters & 1];

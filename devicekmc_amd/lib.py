@@ -93,6 +93,16 @@ SYMBOLS = {
     "dkmc_xt_get_live": (_I, [_D, vp, vp]),
     "dkmc_xt_get_live_masks": (_I, [_D, vp]),
     "dkmc_debug_fail_true_residual_once": (None, []),
+    "dkmc_set_x_static_tiles": (None, [_I]),
+    "dkmc_get_x_static_tiles": (_I, []),
+    "dkmc_get_x_static_info": (_I, [C.POINTER(C.c_longlong)]),
+    "dkmc_debug_x_static_verify": (_I, [_I]),
+    "dkmc_debug_get_x_static_verify": (_I, [C.POINTER(C.c_longlong)]),
+    "dkmc_x_static_strips": (_I, [_I]),
+    "dkmc_x_static_rule": (_I, [_I]),
+    "dkmc_debug_set_x_static_gate": (None, [_I]),
+    "dkmc_xt_get_srow": (_I, [c_int_p, vp]),
+    "dkmc_xt_get_diag": (_I, [vp]),
     "dkmc_set_x_nmul_form": (None, [_I]),
     "dkmc_get_x_nmul_form": (_I, []),
     "dkmc_set_x_nmul_lane_bytes": (None, [_I]),

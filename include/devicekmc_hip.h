@@ -235,6 +235,26 @@ int dkmc_get_x_tile_drop_unit(void);
 void dkmc_set_x_tile_drop_auto(int on);
 int dkmc_get_x_tile_drop_auto(void);
 double dkmc_get_x_tile_drop_used(void);
+/* Order of the tunnelling set S and the tunnelling tiles kept across current solves (csrc/xt_static.h).  0: S in atom order (the reference's: left
+ * contact, vacancies, right contact) and every stored sub-block generated at every solve, bit for bit as without the switch.  1: on wherever it
+ * can be -- one GPU, not sharded, not slab-distributed, the tiled X (dkmc_set_x_format(1)); everywhere else S keeps atom order and the fill is
+ * full, as with 0.  2 (default): as 1, from the measured size on -- a tunnelling set of at least 32 768 members (between the benchmark's tile:5
+ * and tile:6; below it the new order ties or loses: DESIGN.md section 6); smaller systems as with 0.
+ * On: S = [inner-contact metals in atom order | vacancies in atom order].  With nM metals the column strips w < nM / 256 of the tile store hold
+ * contact x contact entries only, which depend on the metals' positions and CB edges and on nothing an event changes; they are a prefix of the
+ * tile list, of the fp64 store and of its fp32 image.  After a solve the library keeps that prefix and, at the next solve, generates only the
+ * tiles behind it -- provided the metals (count, positions, CB edges, flags: compared bitwise on the device), the parameters the entries
+ * depend on, the two allocations and the tile-list prefix itself are what they were.  Anything else is a full fill; a failed solve keeps
+ * nothing.  The stored X is the same set of entries with the same values as in atom order; sums over a row of T run in the new order, so results
+ * agree to rounding, not bit for bit (dkmc_get_last_X exports rows by system row in either order).  Any other value selects 2.  Read at every
+ * current solve.  dkmc_get_x_static_info, for the last current solve: info8[0] 1 = S was in metals-first order; [1] strips that can be kept
+ * (nM / 256); [2] tiles kept; [3] tiles filled; [4] sub-blocks kept; [5] sub-blocks filled; [6] why nothing was kept: 0 = the prefix was kept,
+ * 1 first solve on this GPUBuffers (or the one before it failed), 2 metals changed, 3 parameters changed, 4 store moved, 5 image changed
+ * (made now and not before, or the reverse), 6 tile-list prefix differs, 7 not applicable (atom order, or fewer than 256 metals); [7] the
+ * self-check of devicekmc_hip_debug.h: -1 not run, else the number of differences it found. */
+void dkmc_set_x_static_tiles(int mode);
+int dkmc_get_x_static_tiles(void);
+int dkmc_get_x_static_info(long long *info8);
 /* How the packed N products (dkmc_set_x_nmul_form(1)) gather the panel rows: 16 (default) takes two slots of a matrix row per instruction, 16 bytes
  * per lane on eight lanes each (k_xtb_nmulp16); 8 one slot, 8 bytes per lane on sixteen lanes (k_xtb_nmulp).  Same packed N; every element is formed
  * by the same sequence of fp64 operations: the same bits.  8 is kept for comparisons; any other value selects 16. */

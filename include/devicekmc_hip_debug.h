@@ -144,6 +144,24 @@ int dkmc_xt_get_live(double theta, int *live_per_tile, double *sS_out);
 /* Test aid: from the same census, the mask of the sub-blocks LIVE ON THEIR OWN of every stored tile at threshold theta (a subset of the tile's stored
  * mask; 0 = dead tile), in dkmc_xt_get_tiles order: what dkmc_set_x_tile_drop_unit(1) streams of the tile. */
 int dkmc_xt_get_live_masks(double theta, int *mask_per_tile);
+/* Self-check of dkmc_set_x_static_tiles (csrc/xt_static.h); returns the setting before.  On: every assembly in metals-first order is followed by
+ * the FULL census and a FULL fill of the resident tile list into buffers of their own (a second store: tests and small sizes only; the resident
+ * store is only read), compared with what the assembly left.  dkmc_debug_get_x_static_verify, for the last solve: v4[0] differing words of the
+ * cell masks, [1] differing 64-bit words of the fp64 store, [2] differing 32-bit words of the fp32 image, [3] |X_nnz as reported - recounted|;
+ * their sum is info8[7] of dkmc_get_x_static_info.  dkmc_x_static_strips: the strips nM metals allow to keep, nM / 256 (0: a full fill); host
+ * code only.  dkmc_xt_get_srow: the system row of every S rank of the last one-GPU assembly (srow_out[ns]; null: the count only).
+ * dkmc_xt_get_diag: the row sums of the tunnelling block T of that assembly by SYSTEM row (d_out[rows of X], 0 outside S) -- the diagonal pass,
+ * summed in the S order of that assembly. */
+int dkmc_debug_x_static_verify(int on);
+int dkmc_debug_get_x_static_verify(long long *v4);
+int dkmc_x_static_strips(int n_metals);
+/* The size rule of dkmc_set_x_static_tiles(2) (csrc/common.h: x_static_rule): 1 when a tunnelling set of that many members takes the metals-first order
+ * -- at and above the measured gate of 32 768 members (profiles/ab_bench_x_static_tiles.txt); host code only.  dkmc_debug_set_x_static_gate: test aid --
+ * moves the gate so that a small workload takes the new order under mode 2; 0 (or less) selects the measured gate. */
+int dkmc_x_static_rule(int members);
+void dkmc_debug_set_x_static_gate(int members);
+int dkmc_xt_get_srow(int *ns_out, int *srow_out);
+int dkmc_xt_get_diag(double *d_out);
 void dkmc_set_x_apply_form(int form);
 int dkmc_get_x_apply_form(void);
 /* Test aid for the error path of a sharded current solve (no counterpart in the reference): the calling rank fails ONCE, in the
