@@ -223,7 +223,7 @@ struct Engine {
     double E_gen[DKMC_MAX_LAYERS] = {0}, E_rec[DKMC_MAX_LAYERS] = {0}, E_Vdiff[DKMC_MAX_LAYERS] = {0}, E_Odiff[DKMC_MAX_LAYERS] = {0};
     int num_layers = 0;
     // named persistent device buffers (grown on demand, never shrunk)
-    static const int NBUF = 176;
+    static const int NBUF = 184;
     void *buf[NBUF] = {nullptr};
     size_t bufsz[NBUF] = {0};
 };
@@ -289,6 +289,9 @@ enum {
     // cluster tracking (track.hip: dkmc_track_clusters): the pair table, the per-component words of both sides, per-site slot + flags + positions,
     // the rows of the tables, the control block
     S_TR_HASH, S_TR_COMP, S_TR_SITE, S_TR_ROWS, S_TR_CTRL,
+    // cut-site analysis (cuts.hip: dkmc_find_cuts): per-site words (position, forest, lo / hi, size, root flag + position), the bypass table, the
+    // per-position rows (difference arrays, path table, necks), change words + stat block
+    S_CUT_SITE, S_CUT_TABLE, S_CUT_ROWS, S_CUT_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

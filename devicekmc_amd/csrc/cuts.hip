@@ -1,0 +1,554 @@
+// cuts.hip -- cut-site analysis of the bridged filament: the members every conducting path between the contacts crosses, from ONE left-to-right
+// path, the connected components of the members off that path and the chords of the path (dkmc_find_cuts; definitions: include/devicekmc_hip.h,
+// the rule and its proof sketch: DESIGN.md section 4).  No counterpart in the reference.  A pure function of its arguments: nothing of GPUBuffers,
+// no engine state a later phase reads and no other kernel is touched.
+//
+// Positions: pos[site] = k for row k of the path, -1 elsewhere, by atomicMin of k into a word that starts at -1 read as unsigned: of two rows
+//   that name one site the smaller k stays, so the later row is the one reported as the duplicate.  The validation pass (one group of LPR lanes per
+//   path row) looks for row k - 1's site in the index row of row k's site and the other way round, and takes the smallest {row, reason} word.
+// Labelling of the off-path members ("label in range and pos < 0"): the min-hooking + compression rounds of clusters.hip, a copy of its own in this
+//   file: d_site_bypass holds the roots between the rounds and ends on the smallest site index of each off-path component; "rounds" is the number
+//   of rounds run, the one that changed nothing included, the number the synchronous host model (tests/cut_ref.py) gives.
+// Attachment: one pass over the member rows, LPR lanes per row.  A link is seen from whichever row holds it: an off-path row collects the positions
+//   of its path entries (and -1 / L as a seed) in registers, a wave whose rows share one root -- the rule inside a contact slab -- combines them
+//   and sends one atomicMin / atomicMax pair; a path row sends the pair for each off-path entry and marks the chords among its path entries.
+// Tables: the roots with hi - lo >= 2 add +1 at lo + 1 and -1 at hi to a difference array over the positions; the chords do the same in a second
+//   one; prefix sums (scan.hip) give n_bypass and the chord flag.  The bypass table is compacted by root flag + scan, the necks by the flags of
+//   the run starts + scan.  Integer atomics only (minima, maxima, counts): the same bytes on every call.
+#include "common.h"
+#include <vector>
+
+#define CU_NT 256
+#define CU_BATCH 8                   // rounds enqueued per read-back; a round after the one that changed nothing returns at once
+#define CU_CAP_DEFAULT 64
+#define CU_CAP_MAX 4096
+#define CU_NONE 0x7fffffff
+
+namespace {
+
+struct CuStat {
+    unsigned long long err;          // the smallest {path row << 3 | reason} of an invalid path, ~0 if none
+    int off_members, off_comps, n_byp, n_cut, max_nb, n_chord, n_necks, pad;
+};
+struct CutState {
+    int valid = 0;
+    long long info[16] = {0};
+    std::vector<int> site, n_bypass, chord, cut, b_root, b_size, b_lo, b_hi, n_first, n_last;
+    std::vector<double> n_xmin, n_xmax;
+    double ms_label = 0.0, ms_rest = 0.0;
+    hipEvent_t ev[4]; bool ev_ready = false;
+} g_cu;
+int g_cu_round_cap = CU_CAP_DEFAULT;
+
+const char *const kReason[6] = {"", "is not a member", "repeats the site of an earlier row", "is not a left seed (row 0)", "is not a right seed (the last row)",
+                                "is not linked to the row before"};
+
+// 1a. identities of the per-site words
+__global__ __launch_bounds__(CU_NT) void k_cu_init(int N, int *pos, int *lo, int *hi, int *csize)
+{
+    const int i = blockIdx.x * CU_NT + threadIdx.x;
+    if (i >= N) return;
+    pos[i] = -1; lo[i] = CU_NONE; hi[i] = -CU_NONE; csize[i] = 0;
+}
+
+// 1b. positions: rows that name no member are reported and scatter nothing
+__global__ __launch_bounds__(CU_NT) void k_cu_scatter(int N, int L, const int *__restrict__ path, const int *__restrict__ label, int *pos, CuStat *stat)
+{
+    const int k = blockIdx.x * CU_NT + threadIdx.x;
+    if (k >= L) return;
+    const int s = path[k];
+    bool ok = s >= 0 && s < N;
+    if (ok) { const int r = label[s]; ok = r >= 0 && r < N; }
+    if (!ok) atomicMin(&stat->err, ((unsigned long long)k << 3) | 1ull);
+    else atomicMin((unsigned int *)&pos[s], (unsigned int)k);
+}
+
+// 1c. validation, LPR lanes per path row: distinct sites, the seeds at the two ends, consecutive rows linked (v in row u OR u in row v)
+template <int LPR>
+__global__ __launch_bounds__(CU_NT) void k_cu_validate(int N, int nn, int L, const int *__restrict__ idx, const int *__restrict__ path,
+                                                       const int *__restrict__ pos, int n_left, int n_right, CuStat *stat)
+{
+    const int lane = threadIdx.x % LPR, gw = (threadIdx.x & (WAVE - 1)) / LPR;            // the group's place in its wave
+    const long long groups = (long long)gridDim.x * (CU_NT / LPR);
+    const long long wave0 = (long long)blockIdx.x * (CU_NT / LPR) + (threadIdx.x / WAVE) * (WAVE / LPR);
+    for (long long k0 = wave0; k0 < L; k0 += groups) {                                    // the same trip count in every lane of a wave
+        const long long k = k0 + gw;
+        const int s = k < L ? path[k] : -1;
+        const bool ok = s >= 0 && s < N && pos[s] >= 0;                                   // a member (else row k is reported already)
+        const int t = (ok && k > 0) ? path[k - 1] : -1;
+        const bool look = t >= 0 && t < N;                                                // else row k - 1 is reported already
+        bool found = false;
+        if (look) {
+            const int *rs = idx + (size_t)s * nn, *rt = idx + (size_t)t * nn;
+            for (int e = lane; e < nn; e += LPR) found = found || rs[e] == t || rt[e] == s;
+        }
+        const unsigned long long fm = __ballot(found);
+        const unsigned long long gm = LPR == WAVE ? ~0ull : (((1ull << (LPR & 63)) - 1ull) << (gw * LPR));
+        if (lane == 0 && ok) {
+            int why = 0;
+            if (pos[s] != (int)k) why = 2;
+            else if (k == 0 && !(s < n_left)) why = 3;
+            else if (k == L - 1 && !(s >= N - n_right)) why = 4;
+            else if (look && !(fm & gm)) why = 5;
+            if (why) atomicMin(&stat->err, ((unsigned long long)k << 3) | (unsigned long long)why);
+        }
+    }
+}
+
+// 2. off-path membership as the initial root / parent (the site itself, -1 for a non-member and for a path site)
+__global__ __launch_bounds__(CU_NT) void k_cu_members(int N, const int *__restrict__ label, const int *__restrict__ pos, int *root, int *parent)
+{
+    const int i = blockIdx.x * CU_NT + threadIdx.x;
+    if (i >= N) return;
+    const int r = label[i];
+    root[i] = parent[i] = (r >= 0 && r < N && pos[i] < 0) ? i : -1;
+}
+
+// 3a. hook: LPR lanes per off-path row (k_cl_hook's model: root[] is read-only inside the launch, only root entries of parent[] are targets)
+template <int LPR>
+__global__ __launch_bounds__(CU_NT) void k_cu_hook(int N, int nn, const int *__restrict__ idx, const int *__restrict__ root, int *parent, int *ctrl, int round)
+{
+    if (round > 0 && ctrl[round - 1] == 0) return;            // the round before changed nothing: the labelling is finished
+    const int lane = threadIdx.x % LPR;
+    const long long groups = (long long)gridDim.x * (CU_NT / LPR);
+    int changed = 0;
+    for (long long u = (long long)blockIdx.x * (CU_NT / LPR) + threadIdx.x / LPR; u < N; u += groups) {
+        const int ru = root[u];
+        if (ru < 0) continue;
+        const int *row = idx + (size_t)u * nn;
+        for (int k = lane; k < nn; k += LPR) {
+            const int v = row[k];
+            if (v < 0 || v >= N) continue;                    // padding, anywhere in the row
+            const int rv = root[v];
+            if (rv < 0 || rv == ru) continue;
+            const int hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
+            if (atomicMin(&parent[hi], lo) > lo) changed = 1;
+        }
+    }
+    if (changed) atomicOr(&ctrl[round], 1);
+}
+
+// 3b. compress: every off-path member to its root, with path halving on the way (k_cl_compress's argument: parents strictly decrease)
+__global__ __launch_bounds__(CU_NT) void k_cu_compress(int N, int *root, int *parent, const int *ctrl, int round)
+{
+    if (ctrl[round] == 0) return;                             // nothing was hooked: root[] and parent[] hold the roots already
+    const int i = blockIdx.x * CU_NT + threadIdx.x;
+    if (i >= N || root[i] < 0) return;
+    int c = i;
+    for (;;) {
+        const int p = ld_agent(&parent[c]);
+        if (p >= c || p < 0) break;
+        const int gp = ld_agent(&parent[p]);
+        if (gp >= p || gp < 0) { c = p; break; }
+        st_agent(&parent[c], gp);
+        c = gp;
+    }
+    root[i] = c;
+    st_agent(&parent[i], c);
+}
+
+__device__ __forceinline__ int cu_wave_min(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, WAVE));
+    return v;
+}
+__device__ __forceinline__ int cu_wave_max(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, WAVE));
+    return v;
+}
+__device__ __forceinline__ unsigned long long cu_wave_min64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
+    return v;
+}
+__device__ __forceinline__ unsigned long long cu_wave_max64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
+    return v;
+}
+
+// 4. attachment: lo / hi of the off-path roots and the chord marks, one pass over the member rows (root[u] >= 0: off-path, pos[u] >= 0: on the
+// path, both -1: no member).  cdiff has L + 1 words.
+template <int LPR>
+__global__ __launch_bounds__(CU_NT) void k_cu_attach(int N, int nn, int L, const int *__restrict__ idx, const int *__restrict__ root,
+                                                     const int *__restrict__ pos, int n_left, int n_right, int *lo, int *hi, int *cdiff)
+{
+    const int lane = threadIdx.x % LPR, gw = (threadIdx.x & (WAVE - 1)) / LPR;
+    const long long groups = (long long)gridDim.x * (CU_NT / LPR);
+    const long long wave0 = (long long)blockIdx.x * (CU_NT / LPR) + (threadIdx.x / WAVE) * (WAVE / LPR);
+    for (long long u0 = wave0; u0 < N; u0 += groups) {                                    // the same trip count in every lane of a wave
+        const long long u = u0 + gw;
+        const int ru = u < N ? root[u] : -1, pu = u < N ? pos[u] : -1;
+        int mylo = CU_NONE, myhi = -CU_NONE;
+        if (ru >= 0 || pu >= 0) {
+            const int *row = idx + (size_t)u * nn;
+            for (int e = lane; e < nn; e += LPR) {
+                const int v = row[e];
+                if (v < 0 || v >= N) continue;                // padding, anywhere in the row
+                const int pv = pos[v];
+                if (ru >= 0) {
+                    if (pv >= 0) { mylo = min(mylo, pv); myhi = max(myhi, pv); }
+                } else {
+                    const int rv = root[v];
+                    if (rv >= 0) { atomicMin(&lo[rv], pu); atomicMax(&hi[rv], pu); }
+                    else if (pv >= pu + 2) { atomicAdd(&cdiff[pu + 1], 1); atomicAdd(&cdiff[pv], -1); }
+                    else if (pv >= 0 && pv <= pu - 2) { atomicAdd(&cdiff[pv + 1], 1); atomicAdd(&cdiff[pu], -1); }
+                }
+            }
+            if (lane == 0) {
+                const int f = seed_bits((int)u, N, n_left, n_right);
+                if (ru >= 0) {
+                    if (f & 1) { mylo = min(mylo, -1); myhi = max(myhi, -1); }
+                    if (f & 2) { mylo = min(mylo, L); myhi = max(myhi, L); }
+                } else {                                      // a path site that is a seed away from its end: the chord from S / to T
+                    if ((f & 1) && pu >= 1) { atomicAdd(&cdiff[0], 1); atomicAdd(&cdiff[pu], -1); }
+                    if ((f & 2) && pu <= L - 2) { atomicAdd(&cdiff[pu + 1], 1); atomicAdd(&cdiff[L], -1); }
+                }
+            }
+        }
+        const bool has = mylo != CU_NONE;
+        const unsigned long long bm = __ballot(has);
+        if (bm == 0ull) continue;
+        const int first = __ffsll((long long)bm) - 1;
+        const int r0 = __shfl(ru, first, WAVE);
+        if (__all(!has || ru == r0)) {
+            const int l = cu_wave_min(mylo), h = cu_wave_max(myhi);
+            if ((int)(threadIdx.x & (WAVE - 1)) == first) { atomicMin(&lo[r0], l); atomicMax(&hi[r0], h); }
+        } else if (has) {
+            atomicMin(&lo[ru], mylo); atomicMax(&hi[ru], myhi);
+        }
+    }
+}
+
+// 5a. per site: the role of the off-path members (path sites: provisionally "other", k_cu_path decides), the sizes of the off-path components,
+// the root flags of the bypass table and the +1 / -1 of the bypass roots in bdiff (L + 1 words; no root is wide when L == 0)
+__global__ __launch_bounds__(CU_NT) void k_cu_sites(int N, const int *__restrict__ root, const int *__restrict__ pos, const int *__restrict__ lo,
+                                                    const int *__restrict__ hi, int *csize, int *role, int *isbyp, int *bdiff, CuStat *stat)
+{
+    const int i = blockIdx.x * CU_NT + threadIdx.x;
+    const int r = i < N ? root[i] : -1;
+    const bool off = r >= 0;
+    bool wide = false;
+    if (off) {
+        const int l = lo[r], h = hi[r];
+        wide = l != CU_NONE && h - l >= 2;
+        role[i] = l == CU_NONE ? DKMC_CUT_ROLE_APART : (wide ? DKMC_CUT_ROLE_BYPASS : DKMC_CUT_ROLE_SIDE);
+        if (wide && r == i) { atomicAdd(&bdiff[l + 1], 1); atomicAdd(&bdiff[h], -1); }
+    } else if (i < N) role[i] = pos[i] >= 0 ? DKMC_CUT_ROLE_PATH : DKMC_CUT_ROLE_NONE;
+    if (i < N) isbyp[i] = (wide && r == i) ? 1 : 0;
+    const unsigned long long bm = __ballot(off);
+    if (bm == 0ull) return;
+    const int nroot = __popcll(__ballot(off && r == i));
+    const int first = __ffsll((long long)bm) - 1;
+    const int r0 = __shfl(r, first, WAVE);
+    if (__all(!off || r == r0)) {
+        if ((int)(threadIdx.x & (WAVE - 1)) == first) atomicAdd(&csize[r0], __popcll(bm));
+    } else if (off) atomicAdd(&csize[r], 1);
+    if ((int)(threadIdx.x & (WAVE - 1)) == first) {
+        atomicAdd(&stat->off_members, __popcll(bm));
+        if (nroot) atomicAdd(&stat->off_comps, nroot);
+    }
+}
+
+// 5b. the bypass table: one row per wide root, ascending (bpos = exclusive scan of the flags)
+__global__ __launch_bounds__(CU_NT) void k_cu_table(int N, const int *__restrict__ isbyp, const int *__restrict__ bpos, const int *__restrict__ csize,
+                                                    const int *__restrict__ lo, const int *__restrict__ hi, int *t_root, int *t_size, int *t_lo, int *t_hi)
+{
+    const int i = blockIdx.x * CU_NT + threadIdx.x;
+    if (i >= N || !isbyp[i]) return;
+    const int p = bpos[i];
+    t_root[p] = i; t_size[p] = csize[i]; t_lo[p] = lo[i]; t_hi[p] = hi[i];
+}
+
+// 6a. the path table from the two scanned difference arrays (exclusive sums: the value at position k is word k + 1), the roles of the path
+// sites, the flags of the neck starts and the identities of the necks' keys
+__global__ __launch_bounds__(CU_NT) void k_cu_path(int L, const int *__restrict__ path, const int *__restrict__ bsum, const int *__restrict__ csum,
+                                                   int *t_nb, int *t_ch, int *t_cut, int *start, int *role, unsigned long long *kmin,
+                                                   unsigned long long *kmax, CuStat *stat)
+{
+    const int k = blockIdx.x * CU_NT + threadIdx.x;
+    int nb = 0, ch = 0, cut = 0;
+    if (k < L) {
+        nb = bsum[k + 1]; ch = csum[k + 1] > 0 ? 1 : 0; cut = (nb == 0 && ch == 0) ? 1 : 0;
+        const bool before = k > 0 && bsum[k] == 0 && csum[k] <= 0;
+        t_nb[k] = nb; t_ch[k] = ch; t_cut[k] = cut; start[k] = (cut && !before) ? 1 : 0;
+        role[path[k]] = cut ? DKMC_CUT_ROLE_CUT : DKMC_CUT_ROLE_PATH;
+        kmin[k] = ~0ull; kmax[k] = 0ull;
+    }
+    const int ncut = __popcll(__ballot(cut)), nch = __popcll(__ballot(ch)), mx = cu_wave_max(nb);
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        if (ncut) atomicAdd(&stat->n_cut, ncut);
+        if (nch) atomicAdd(&stat->n_chord, nch);
+        if (mx > 0) atomicMax(&stat->max_nb, mx);
+    }
+}
+
+// 6b. the necks: neck j = the j-th run of cut positions (nid = exclusive scan of the start flags); a wave inside one neck sends one pair of keys
+__global__ __launch_bounds__(CU_NT) void k_cu_necks(int L, const int *__restrict__ path, const double *__restrict__ x, const int *__restrict__ t_cut,
+                                                    const int *__restrict__ start, const int *__restrict__ nid, int *first, int *last,
+                                                    unsigned long long *kmin, unsigned long long *kmax)
+{
+    const int k = blockIdx.x * CU_NT + threadIdx.x;
+    const bool cut = k < L && t_cut[k];
+    int j = -1;
+    if (cut) {
+        j = nid[k] + start[k] - 1;
+        if (start[k]) first[j] = k;
+        if (k == L - 1 || !t_cut[k + 1]) last[j] = k;
+    }
+    if (!x) return;                                           // the same in every thread
+    const unsigned long long key = cut ? dbl_key(x[path[k]]) : 0ull;
+    const unsigned long long bm = __ballot(cut);
+    if (bm == 0ull) return;
+    const int f = __ffsll((long long)bm) - 1;
+    const int j0 = __shfl(j, f, WAVE);
+    if (__all(!cut || j == j0)) {
+        const unsigned long long l = cu_wave_min64(cut ? key : ~0ull), h = cu_wave_max64(cut ? key : 0ull);
+        if ((int)(threadIdx.x & (WAVE - 1)) == f) { atomicMin(&kmin[j0], l); atomicMax(&kmax[j0], h); }
+    } else if (cut) {
+        atomicMin(&kmin[j], key); atomicMax(&kmax[j], key);
+    }
+}
+
+void cut_reset()
+{
+    memset(g_cu.info, 0, sizeof(g_cu.info));
+    g_cu.info[5] = -1;
+    for (auto *v : {&g_cu.site, &g_cu.n_bypass, &g_cu.chord, &g_cu.cut, &g_cu.b_root, &g_cu.b_size, &g_cu.b_lo, &g_cu.b_hi, &g_cu.n_first, &g_cu.n_last}) v->clear();
+    g_cu.n_xmin.clear(); g_cu.n_xmax.clear();
+    g_cu.ms_label = g_cu.ms_rest = 0.0;
+}
+
+int copy_rows(int capacity, size_t have, int *rows_out)
+{
+    long long rows = (long long)have;
+    if (rows > capacity) rows = capacity;
+    if (rows < 0) rows = 0;
+    if (rows_out) *rows_out = (int)rows;
+    return (int)rows;
+}
+
+}   // namespace
+
+extern "C" {
+
+void dkmc_debug_set_cut_round_cap(int cap) { g_cu_round_cap = cap <= 0 ? CU_CAP_DEFAULT : (cap > CU_CAP_MAX ? CU_CAP_MAX : cap); }
+
+int dkmc_debug_get_cut_times(double *ms2)
+{
+    if (!g_cu.valid) return dkmc_fail(3, "dkmc_debug_get_cut_times: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    if (ms2) { ms2[0] = g_cu.ms_label; ms2[1] = g_cu.ms_rest; }
+    return 0;
+}
+
+int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const double *d_site_x, int n_left_sites, int n_right_sites,
+                   const int *d_path, int path_len, int *d_site_role, int *d_site_bypass)
+{
+    g_cu.valid = 0;
+    if (N < 0 || nn < 1 || path_len < 0 || path_len > N || (N > 0 && (!d_index || !d_label || !d_site_role || !d_site_bypass)) || (path_len > 0 && !d_path))
+        return dkmc_fail(3, "dkmc_find_cuts: bad arguments (N >= 0, nn >= 1, 0 <= path_len <= N, device arrays of N sites, a path of path_len sites)",
+                         __FILE__, __LINE__);
+    clamp_seeds(N, n_left_sites, n_right_sites);
+    cut_reset();
+    if (N == 0) { g_cu.valid = 1; return 0; }
+    hipStream_t st = eng().stream;
+    const int cap = g_cu_round_cap, L = path_len;
+    const size_t n = (size_t)N, lp = (size_t)L + 1;
+    int *site = (int *)scratch(S_CUT_SITE, 7 * n * sizeof(int));
+    int *tab = (int *)scratch(S_CUT_TABLE, 4 * n * sizeof(int));
+    char *rows = (char *)scratch(S_CUT_ROWS, lp * (2 * sizeof(unsigned long long) + 9 * sizeof(int)));
+    int *ctrl = (int *)scratch(S_CUT_CTRL, (size_t)CU_CAP_MAX * sizeof(int) + sizeof(CuStat));
+    if (!site || !tab || !rows || !ctrl) return eng().err_code;
+    int *pos = site, *parent = pos + n, *lo = parent + n, *hi = lo + n, *csize = hi + n, *isbyp = csize + n, *bpos = isbyp + n;
+    int *t_root = tab, *t_size = t_root + n, *t_lo = t_size + n, *t_hi = t_lo + n;
+    unsigned long long *kmin = (unsigned long long *)rows, *kmax = kmin + lp;
+    int *bdiff = (int *)(kmax + lp), *cdiff = bdiff + lp, *start = cdiff + lp, *nid = start + lp, *t_nb = nid + lp, *t_ch = t_nb + lp, *t_cut = t_ch + lp,
+        *first = t_cut + lp, *last = first + lp;
+    CuStat *d_stat = (CuStat *)(ctrl + CU_CAP_MAX);
+    int *root = d_site_bypass;
+    const bool timed = eng().profiling != 0;
+    if (timed && !g_cu.ev_ready) { for (auto &e : g_cu.ev) HIPCHK(hipEventCreate(&e)); g_cu.ev_ready = true; }
+
+    const int site_blocks = (N + CU_NT - 1) / CU_NT, path_blocks = (L + CU_NT - 1) / CU_NT;
+    const int lpr = nn <= 128 ? 16 : 64;
+    const int row_blocks = grid_blocks((long long)N * lpr, CU_NT, 8192);
+    CuStat h_stat;
+    if (timed) HIPCHK(hipEventRecord(g_cu.ev[0], st));
+    HIPCHK(hipMemsetAsync(ctrl, 0, (size_t)CU_CAP_MAX * sizeof(int) + sizeof(CuStat), st));
+    HIPCHK(hipMemsetAsync(&d_stat->err, 0xff, sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(bdiff, 0, 2 * lp * sizeof(int), st));
+    hipLaunchKernelGGL(k_cu_init, dim3(site_blocks), dim3(CU_NT), 0, st, N, pos, lo, hi, csize);
+    if (L > 0) {
+        // positions and validation: nothing below reads the path before it is known to be one
+        hipLaunchKernelGGL(k_cu_scatter, dim3(path_blocks), dim3(CU_NT), 0, st, N, L, d_path, d_label, pos, d_stat);
+        const int vblocks = grid_blocks((long long)L * lpr, CU_NT, 8192);
+        if (lpr == 16) hipLaunchKernelGGL(k_cu_validate<16>, dim3(vblocks), dim3(CU_NT), 0, st, N, nn, L, d_index, d_path, (const int *)pos, n_left_sites,
+                                          n_right_sites, d_stat);
+        else hipLaunchKernelGGL(k_cu_validate<64>, dim3(vblocks), dim3(CU_NT), 0, st, N, nn, L, d_index, d_path, (const int *)pos, n_left_sites,
+                                n_right_sites, d_stat);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(CuStat), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (h_stat.err != ~0ull) {
+            HIPCHK(hipMemsetAsync(d_site_role, 0xff, n * sizeof(int), st));
+            HIPCHK(hipMemsetAsync(d_site_bypass, 0xff, n * sizeof(int), st));
+            HIPCHK(hipStreamSynchronize(st));
+            const int why = (int)(h_stat.err & 7ull);
+            char msg[240];
+            snprintf(msg, sizeof(msg), "dkmc_find_cuts: not a left-to-right path over the member links: row %lld %s; site_role and site_bypass set to -1",
+                     (long long)(h_stat.err >> 3), kReason[why >= 1 && why <= 5 ? why : 0]);
+            return dkmc_fail(4, msg, __FILE__, __LINE__);
+        }
+    }
+    hipLaunchKernelGGL(k_cu_members, dim3(site_blocks), dim3(CU_NT), 0, st, N, d_label, (const int *)pos, root, parent);
+    KCHK();
+    if (timed) HIPCHK(hipEventRecord(g_cu.ev[1], st));
+    // rounds: CU_BATCH of them per read-back of their change words
+    int rounds = 0, launched = 0;
+    static int h_changed[CU_CAP_MAX];
+    while (!rounds && launched < cap) {
+        const int b = cap - launched < CU_BATCH ? cap - launched : CU_BATCH;
+        for (int r = launched; r < launched + b; ++r) {
+            if (lpr == 16) hipLaunchKernelGGL(k_cu_hook<16>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, d_index, (const int *)root, parent, ctrl, r);
+            else hipLaunchKernelGGL(k_cu_hook<64>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, d_index, (const int *)root, parent, ctrl, r);
+            hipLaunchKernelGGL(k_cu_compress, dim3(site_blocks), dim3(CU_NT), 0, st, N, root, parent, (const int *)ctrl, r);
+        }
+        KCHK();
+        HIPCHK(hipMemcpyAsync(h_changed + launched, ctrl + launched, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int r = launched; r < launched + b && !rounds; ++r) if (!h_changed[r]) rounds = r + 1;
+        launched += b;
+    }
+    if (!rounds) {
+        // not finished: no partial labels go out as valid
+        HIPCHK(hipMemsetAsync(d_site_role, 0xff, n * sizeof(int), st));
+        HIPCHK(hipMemsetAsync(d_site_bypass, 0xff, n * sizeof(int), st));
+        HIPCHK(hipStreamSynchronize(st));
+        char msg[240];
+        snprintf(msg, sizeof(msg), "dkmc_find_cuts: off-path labelling not finished after %d rounds (the cap: dkmc_debug_set_cut_round_cap); "
+                 "site_role and site_bypass set to -1", cap);
+        return dkmc_fail(4, msg, __FILE__, __LINE__);
+    }
+    if (timed) HIPCHK(hipEventRecord(g_cu.ev[2], st));
+    // attachment, roles, tables
+    if (L > 0) {
+        if (lpr == 16) hipLaunchKernelGGL(k_cu_attach<16>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, L, d_index, (const int *)root, (const int *)pos,
+                                          n_left_sites, n_right_sites, lo, hi, cdiff);
+        else hipLaunchKernelGGL(k_cu_attach<64>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, L, d_index, (const int *)root, (const int *)pos,
+                                n_left_sites, n_right_sites, lo, hi, cdiff);
+    }
+    hipLaunchKernelGGL(k_cu_sites, dim3(site_blocks), dim3(CU_NT), 0, st, N, (const int *)root, (const int *)pos, (const int *)lo, (const int *)hi, csize,
+                       d_site_role, isbyp, bdiff, d_stat);
+    KCHK();
+    if (int rc = dkmc_exclusive_scan_i32(isbyp, bpos, N, &d_stat->n_byp)) return rc;
+    hipLaunchKernelGGL(k_cu_table, dim3(site_blocks), dim3(CU_NT), 0, st, N, (const int *)isbyp, (const int *)bpos, (const int *)csize, (const int *)lo,
+                       (const int *)hi, t_root, t_size, t_lo, t_hi);
+    KCHK();
+    if (L > 0) {
+        if (int rc = dkmc_exclusive_scan_i32(bdiff, bdiff, L + 1, nullptr)) return rc;
+        if (int rc = dkmc_exclusive_scan_i32(cdiff, cdiff, L + 1, nullptr)) return rc;
+        hipLaunchKernelGGL(k_cu_path, dim3(path_blocks), dim3(CU_NT), 0, st, L, d_path, (const int *)bdiff, (const int *)cdiff, t_nb, t_ch, t_cut, start,
+                           d_site_role, kmin, kmax, d_stat);
+        KCHK();
+        if (int rc = dkmc_exclusive_scan_i32(start, nid, L, &d_stat->n_necks)) return rc;
+        hipLaunchKernelGGL(k_cu_necks, dim3(path_blocks), dim3(CU_NT), 0, st, L, d_path, d_site_x, (const int *)t_cut, (const int *)start, (const int *)nid,
+                           first, last, kmin, kmax);
+        KCHK();
+    }
+    if (timed) HIPCHK(hipEventRecord(g_cu.ev[3], st));
+    HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(CuStat), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // the host-side tables
+    const size_t nb = (size_t)h_stat.n_byp, nk = (size_t)h_stat.n_necks;
+    if (h_stat.n_byp < 0 || nb > n || h_stat.n_necks < 0 || nk > (size_t)L) return dkmc_fail(4, "dkmc_find_cuts: table counts outside their range", __FILE__, __LINE__);
+    std::vector<unsigned long long> h_min(nk), h_max(nk);
+    g_cu.b_root.resize(nb); g_cu.b_size.resize(nb); g_cu.b_lo.resize(nb); g_cu.b_hi.resize(nb);
+    g_cu.site.resize(L); g_cu.n_bypass.resize(L); g_cu.chord.resize(L); g_cu.cut.resize(L);
+    g_cu.n_first.resize(nk); g_cu.n_last.resize(nk); g_cu.n_xmin.resize(nk); g_cu.n_xmax.resize(nk);
+    if (nb) {
+        HIPCHK(hipMemcpyAsync(g_cu.b_root.data(), t_root, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.b_size.data(), t_size, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.b_lo.data(), t_lo, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.b_hi.data(), t_hi, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    if (L > 0) {
+        HIPCHK(hipMemcpyAsync(g_cu.site.data(), d_path, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.n_bypass.data(), t_nb, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.chord.data(), t_ch, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.cut.data(), t_cut, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    if (nk) {
+        HIPCHK(hipMemcpyAsync(g_cu.n_first.data(), first, nk * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(g_cu.n_last.data(), last, nk * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_min.data(), kmin, nk * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_max.data(), kmax, nk * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    long long longest = 0, longest_first = -1;
+    for (size_t j = 0; j < nk; ++j) {
+        g_cu.n_xmin[j] = d_site_x ? key_dbl(h_min[j]) : INFINITY; g_cu.n_xmax[j] = d_site_x ? key_dbl(h_max[j]) : -INFINITY;
+        const long long len = (long long)g_cu.n_last[j] - g_cu.n_first[j] + 1;
+        if (len > longest) { longest = len; longest_first = g_cu.n_first[j]; }       // ascending rows: the smallest position on ties
+    }
+    const long long info[12] = {L > 0 ? 1 : 0, L, h_stat.n_cut, (long long)nk, longest, longest_first, (long long)nb, h_stat.off_comps, h_stat.off_members,
+                                h_stat.max_nb, h_stat.n_chord, rounds};
+    memcpy(g_cu.info, info, sizeof(info));
+    if (timed) {
+        float a = 0.f, b = 0.f, c = 0.f;
+        HIPCHK(hipEventElapsedTime(&a, g_cu.ev[0], g_cu.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_cu.ev[1], g_cu.ev[2]));
+        HIPCHK(hipEventElapsedTime(&c, g_cu.ev[2], g_cu.ev[3]));
+        g_cu.ms_label = b; g_cu.ms_rest = a + c;
+    }
+    g_cu.valid = 1;
+    return 0;
+}
+
+int dkmc_get_cut_info(long long *info16)
+{
+    if (!g_cu.valid) return dkmc_fail(3, "dkmc_get_cut_info: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    if (info16) memcpy(info16, g_cu.info, sizeof(g_cu.info));
+    return 0;
+}
+
+int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord, int *h_cut, int *rows_out)
+{
+    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_path: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    const size_t r = (size_t)copy_rows(capacity, g_cu.site.size(), rows_out);
+    if (r == 0) return 0;
+    if (h_site) memcpy(h_site, g_cu.site.data(), r * sizeof(int));
+    if (h_n_bypass) memcpy(h_n_bypass, g_cu.n_bypass.data(), r * sizeof(int));
+    if (h_chord) memcpy(h_chord, g_cu.chord.data(), r * sizeof(int));
+    if (h_cut) memcpy(h_cut, g_cu.cut.data(), r * sizeof(int));
+    return 0;
+}
+
+int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, int *h_hi, int *rows_out)
+{
+    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_bypasses: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    const size_t r = (size_t)copy_rows(capacity, g_cu.b_root.size(), rows_out);
+    if (r == 0) return 0;
+    if (h_root) memcpy(h_root, g_cu.b_root.data(), r * sizeof(int));
+    if (h_size) memcpy(h_size, g_cu.b_size.data(), r * sizeof(int));
+    if (h_lo) memcpy(h_lo, g_cu.b_lo.data(), r * sizeof(int));
+    if (h_hi) memcpy(h_hi, g_cu.b_hi.data(), r * sizeof(int));
+    return 0;
+}
+
+int dkmc_copy_cut_necks(int capacity, int *h_first, int *h_last, double *h_xmin, double *h_xmax, int *rows_out)
+{
+    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_necks: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    const size_t r = (size_t)copy_rows(capacity, g_cu.n_first.size(), rows_out);
+    if (r == 0) return 0;
+    if (h_first) memcpy(h_first, g_cu.n_first.data(), r * sizeof(int));
+    if (h_last) memcpy(h_last, g_cu.n_last.data(), r * sizeof(int));
+    if (h_xmin) memcpy(h_xmin, g_cu.n_xmin.data(), r * sizeof(double));
+    if (h_xmax) memcpy(h_xmax, g_cu.n_xmax.data(), r * sizeof(double));
+    return 0;
+}
+
+}   // extern "C"

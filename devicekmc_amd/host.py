@@ -266,6 +266,49 @@ def track_clusters(label_prev, label_now, x, n_left, n_right):
     return change, pairs, now, prev, critical, info
 
 
+CUT_INFO = ("status", "path_len", "cut_sites", "necks", "longest_neck", "longest_neck_first", "bypasses", "offpath_components", "offpath_members",
+            "max_bypass", "chord_positions", "rounds")
+CUT_PATH = ("site", "n_bypass", "chord", "cut")
+CUT_BYPASSES = ("root", "size", "lo", "hi")
+CUT_NECKS = ("first", "last", "xmin", "xmax")
+CUT_ROLE = ("none", "cut", "path", "bypass", "side", "apart")                # the codes of site_role
+
+
+def find_cuts(index, nn, label, x, n_left, n_right, path):
+    """dkmc_find_cuts on device tensors (index: N * nn int32; label: N int32, e.g. the first return value of find_clusters; x: N float64 or
+    None; path: the sites of a left-to-right path, normally the third return value of find_paths -- a host array or an int32 device tensor;
+    empty or None: the status 0 answer).  Returns (site_role: int32 device tensor of N, codes CUT_ROLE; site_bypass: int32 device tensor of N;
+    path_table, bypasses, necks: dicts of host arrays CUT_PATH / CUT_BYPASSES / CUT_NECKS; info: dict of CUT_INFO).
+    Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(label.numel())
+    _use_stream(label.device)
+    if path is None:
+        path = np.zeros(0, dtype=np.int32)
+    if not torch.is_tensor(path):
+        path = torch.as_tensor(np.ascontiguousarray(path, dtype=np.int32).reshape(-1))
+    path = path.to(device=label.device, dtype=torch.int32).contiguous()
+    n_path = int(path.numel())
+    role = torch.empty(N, dtype=torch.int32, device=label.device)
+    bypass = torch.empty(N, dtype=torch.int32, device=label.device)
+    check(L.dkmc_find_cuts(N, int(nn), _ptr(index), _ptr(label), _ptr(x) if x is not None else None, int(n_left), int(n_right),
+                           _ptr(path) if n_path else None, n_path, _ptr(role), _ptr(bypass)))
+    i16 = (C.c_longlong * 16)()
+    check(L.dkmc_get_cut_info(i16))
+    info = dict(zip(CUT_INFO, (int(v) for v in i16)))
+    rows = C.c_int(0)
+
+    def table(call, names, n, doubles=0):
+        cols = [np.empty(n, dtype=np.int32) for _ in names[:len(names) - doubles]] + [np.empty(n) for _ in range(doubles)]
+        check(call(n, *[_np_ptr(c) for c in cols], C.byref(rows)))
+        return {k: c[:rows.value] for k, c in zip(names, cols)}
+
+    path_table = table(L.dkmc_copy_cut_path, CUT_PATH, info["path_len"])
+    bypasses = table(L.dkmc_copy_cut_bypasses, CUT_BYPASSES, info["bypasses"])
+    necks = table(L.dkmc_copy_cut_necks, CUT_NECKS, info["necks"], doubles=2)
+    return role, bypass, path_table, bypasses, necks, info
+
+
 # rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
 EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
 
@@ -468,6 +511,28 @@ class Device:
         self.site_hops_left, self.site_hops_right = hl.cpu().numpy(), hr.cpu().numpy()
         self.path_sites, self.path_profile, self.path_info = path, profile, info
         return self.site_hops_left, self.site_hops_right, path, profile, info
+
+    def find_cuts(self, gpubuf: GPUBuffers, path=None, label=None, link_index=None, n_left=None, n_right=None):
+        """Cut-site analysis on the device (dkmc_find_cuts; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- or
+        over label (int32 device tensor of N) -- and, by default, the path of the last find_paths (path_sites; an empty one gives status 0): the
+        sites every conducting path between the contacts crosses, the off-path components that bypass the others, and the necks, over
+        gpubuf.neigh_idx or link_index = (int32 device tensor of N * nn, nn) -- the index the path was found on -- with the contact seeds of
+        find_clusters.  Changes nothing in gpubuf.  Returns (site_role, site_bypass: host int32 arrays, path_table, bypasses, necks, info) and
+        keeps them as site_role, site_bypass, cut_path, cut_bypasses, cut_necks, cut_info."""
+        if label is None:
+            label = getattr(self, "_cluster_label", None)
+            if label is None:
+                raise ValueError("find_cuts runs on the labels of a find_clusters call: none was made on this Device (or pass label)")
+        if path is None:
+            path = getattr(self, "path_sites", None)
+            if path is None:
+                raise ValueError("find_cuts takes a left-to-right path: no find_paths call was made on this Device (or pass path)")
+        n_left, n_right = self.contact_seeds(n_left, n_right)
+        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        role, bypass, table, bypasses, necks, info = find_cuts(index, nn, label, gpubuf.site_x, n_left, n_right, path)
+        self.site_role, self.site_bypass = role.cpu().numpy(), bypass.cpu().numpy()
+        self.cut_path, self.cut_bypasses, self.cut_necks, self.cut_info = table, bypasses, necks, info
+        return self.site_role, self.site_bypass, table, bypasses, necks, info
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

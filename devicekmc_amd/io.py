@@ -24,16 +24,19 @@ def _g6(v: float) -> str:
     return "%g" % v
 
 
-def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None, cluster=None, hops=None, change=None):
+def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None, cluster=None, hops=None, change=None, role=None):
     """current: optional per-site array (e.g. Device.site_current) appended as one more column; read_xyz ignores it.  None: the reference's file.
     cluster: optional per-site integer array (Device.site_cluster: the label of the site's conducting cluster, -1 for none) appended as the last
     column, after current when both are given; read_xyz ignores it too.  None: the file as without it, byte for byte.
     hops: optional pair of per-site integer arrays (Device.site_hops_left, Device.site_hops_right: the hop distances from the two contacts, -1
     for none) appended as the last two columns, after current and cluster; read_xyz ignores them.  None: the file as without them, byte for byte.
     change: optional per-site integer array (Device.site_change: the code of the site between two labellings, host.TRACK_CHANGE) appended as the
-    last column, after current, cluster and hops; read_xyz ignores it.  None: the file as without it, byte for byte."""
+    last column, after current, cluster and hops; read_xyz ignores it.  None: the file as without it, byte for byte.
+    role: optional per-site integer array (Device.site_role: the role of the site in the cut-site analysis, host.CUT_ROLE) appended as the last
+    column, after current, cluster, hops and change; read_xyz ignores it.  None: the file as without it, byte for byte."""
     hop_cols = (lambda i: "") if hops is None else (lambda i: "   %d   %d" % (int(hops[0][i]), int(hops[1][i])))
-    tail = hop_cols if change is None else (lambda i: hop_cols(i) + "   %d" % int(change[i]))
+    chg_cols = hop_cols if change is None else (lambda i: hop_cols(i) + "   %d" % int(change[i]))
+    tail = chg_cols if role is None else (lambda i: chg_cols(i) + "   %d" % int(role[i]))
     fmt = (lambda v: repr(float(v))) if full_precision else _g6
     with open(path, "w") as f:
         f.write("%d\n\n" % len(element))

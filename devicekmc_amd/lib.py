@@ -204,6 +204,13 @@ SYMBOLS = {
     "dkmc_copy_track_critical": (_I, [_I, vp, c_int_p]),
     "dkmc_debug_set_track_hash": (None, [_I]),
     "dkmc_debug_get_track_times": (_I, [c_dbl_p]),
+    "dkmc_find_cuts": (_I, [_I, _I, vp, vp, vp, _I, _I, vp, _I, vp, vp]),
+    "dkmc_get_cut_info": (_I, [C.POINTER(C.c_longlong)]),
+    "dkmc_copy_cut_path": (_I, [_I, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_cut_bypasses": (_I, [_I, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_cut_necks": (_I, [_I, vp, vp, vp, vp, c_int_p]),
+    "dkmc_debug_set_cut_round_cap": (None, [_I]),
+    "dkmc_debug_get_cut_times": (_I, [c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

@@ -668,6 +668,58 @@ int dkmc_copy_track_now(int capacity, int *h_root, int *h_size, int *h_joined, i
 int dkmc_copy_track_prev(int capacity, int *h_root, int *h_size, int *h_left, int *h_n_children, int *h_main_child, int *h_flags, int *rows_out);
 int dkmc_copy_track_critical(int capacity, int *h_site, int *rows_out);
 
+/* ---- cut-site analysis: the sites every conducting path crosses (csrc/cuts.hip; no counterpart in the reference) ----
+ * Where the filament is bridged: which atoms hold it together -- the members whose loss alone opens the device --, from one left-to-right path,
+ * per-site work and one more component labelling.  A pure function of its arguments: no field of GPUBuffers, no engine state a later phase reads
+ * and no other kernel changes.
+ *   members     site i is a member when 0 <= d_label[i] < N (the rule of dkmc_find_gaps); nothing else of the labels is used.
+ *   link        members u and v are linked when v occurs in row u of d_index[N][nn] OR u occurs in row v (the rule of dkmc_find_clusters, symmetric
+ *               even where the index is not).  Entries < 0 or >= N are padding, anywhere in a row.
+ *   seeds       left: the members with index < n_left_sites; right: the members with index >= N - n_right_sites (both clamped to 0 ... N).
+ *   cut site    a member v such that, with v deleted, no left seed other than v is connected to a right seed other than v (connected: a walk of
+ *               zero or more links over members other than v).
+ *   path        d_path (device, path_len int32): the sites p_0 ... p_{L-1} of ANY simple left-to-right path, normally the rows of
+ *               dkmc_copy_path_sites: distinct members, row 0 a left seed, the last row a right seed, consecutive rows linked.  It is validated on
+ *               the device.  Every cut site lies on it, and the cut set does not depend on which path is given.  Row k sits at position k; the
+ *               left seeds hang on a virtual node at position -1, the right seeds on one at position L = path_len.
+ *   off-path    the members that are not on the path, and their connected components over the links between them.  d_site_bypass[i] (device, N
+ *               int32, always written completely) = the smallest site index of the off-path component of i: canonical; -1 for a non-member and
+ *               for a path site.
+ *   attachment  the positions an off-path component touches: k for every path site p_k linked to one of its sites, -1 if it holds a left seed,
+ *               L if it holds a right seed.  lo and hi are the smallest and the largest of them.
+ *   chord       a link between two path sites at positions a < b with b - a >= 2; a path site at k >= 1 that is a left seed gives the chord
+ *               (-1, k), one at k <= L - 2 that is a right seed the chord (k, L).
+ *   the rule    p_k is a cut site if and only if no off-path component has lo < k < hi and no chord has a < k < b.
+ *   site_role   d_site_role[i] (device, N int32, always written completely), the DKMC_CUT_ROLE_ values: 0 non-member; 1 path site that is a cut
+ *               site; 2 other path site; 3 bypass: off-path, its component has hi - lo >= 2; 4 side: off-path, its component has an attachment
+ *               but spans no position; 5 apart: off-path, no attachment.  At status 0 every member is 5.
+ *   path table  path_len rows: site, n_bypass = the number of off-path components with lo < k < hi, chord = 1 if some chord has a < k < b, else 0
+ *               (a flag, not a count: a link entered in both rows of the index and one entered in one row give the same bytes), cut = 1 iff
+ *               n_bypass == 0 and chord == 0.
+ *   bypass table  one row per off-path component with hi - lo >= 2, in ascending root: root (= its d_site_bypass value), size, lo, hi.
+ *   neck table  the maximal runs of consecutive cut positions, ascending: first, last, xmin, xmax = min / max of d_site_x over the run's sites --
+ *               the input doubles themselves, compared through the integer key of dkmc_find_clusters; +inf / -inf when d_site_x is NULL.
+ *   info16      (long long) [0] status: 1 = a path was given and is valid, 0 = empty path (the "not bridged" answer), [1] path_len, [2] cut sites,
+ *               [3] necks, [4] length of the longest neck (0: none), [5] its first position, the smallest on ties (-1: none), [6] bypass
+ *               components, [7] off-path components in all, [8] off-path members, [9] the largest n_bypass, [10] path positions under a chord,
+ *               [11] rounds (below), [12] ... [15] 0.
+ * dkmc_find_cuts labels the off-path members by min-hooking + pointer jumping in rounds from the host, as dkmc_find_clusters does, with the same
+ * cap; rounds counts the hook + compress rounds run, the one that changed nothing included: what the synchronous model needs, the same on every
+ * call (0 when N == 0).  With path_len == 0 it succeeds with status 0: the off-path components (all members) are still labelled, the three tables
+ * are empty.  A path that is none fails (dkmc_last_error names the first offending row and what is wrong with it), and so does a labelling that
+ * reaches the cap: d_site_role and d_site_bypass are then -1 everywhere and the getters fail until a call succeeds.  It keeps the results of the
+ * LAST call in the library and returns after they are complete; the four getters fail before any successful call.  Any getter pointer may be NULL;
+ * capacity truncates and *rows_out reports the rows copied (the true counts are info16[1], [6] and [3]).  N < 0, nn < 1, path_len < 0 or > N,
+ * d_index, d_label, d_site_role or d_site_bypass null with N > 0, or d_path null with path_len > 0 fail with code 3 before any launch; d_site_x is
+ * the only optional array.  Integer atomics only (minima, maxima, counts): the same inputs give the same bytes on every call. */
+enum { DKMC_CUT_ROLE_NONE = 0, DKMC_CUT_ROLE_CUT = 1, DKMC_CUT_ROLE_PATH = 2, DKMC_CUT_ROLE_BYPASS = 3, DKMC_CUT_ROLE_SIDE = 4, DKMC_CUT_ROLE_APART = 5 };
+int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const double *d_site_x, int n_left_sites, int n_right_sites,
+                   const int *d_path, int path_len, int *d_site_role, int *d_site_bypass);
+int dkmc_get_cut_info(long long *info16);
+int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord, int *h_cut, int *rows_out);
+int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, int *h_hi, int *rows_out);
+int dkmc_copy_cut_necks(int capacity, int *h_first, int *h_last, double *h_xmin, double *h_xmax, int *rows_out);
+
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
 int dkmc_update_temperatureglobal_gpu(const double *d_site_power, double *d_T_bg, int N, double a_coeff,

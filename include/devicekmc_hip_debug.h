@@ -246,6 +246,13 @@ int dkmc_debug_get_path_times(double *ms2);
  * everything after it (lineage, codes, scans, tables); both 0 with profiling off. */
 void dkmc_debug_set_track_hash(int mode);
 int dkmc_debug_get_track_times(double *ms2);
+/* Test aid of the cut-site analysis (csrc/cuts.hip): the cap on the rounds of its off-path labelling, by default 64 as for the filament analysis
+ * (<= 0 restores the default; at most 4096).  A labelling that needs more rounds than the cap fails with a message, sets both site arrays to -1
+ * and leaves the getters failing.
+ * Measurement aid: with dkmc_set_profiling(1), ms2 = HIP-event time of the last call's off-path labelling rounds (the host's read-backs between
+ * them included) and of everything else (positions, validation, attachment, roles, scans, tables); both 0 with profiling off. */
+void dkmc_debug_set_cut_round_cap(int cap);
+int dkmc_debug_get_cut_times(double *ms2);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);

@@ -12,7 +12,11 @@ corridor's constriction and the x range of the sites at that level.
 With --track every check from the second on also runs Device.track_clusters between its labelling and the one before and the line carries, per
 such check, the transition, the sites that joined, left and regrouped and the MERGED rows; the closing check also carries the number of the sites
 whose arrival closed the filament and their x range.
-usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1] [--track]"""
+With --cuts (needs --paths) every check that runs Device.find_paths with status 1 also runs Device.find_cuts on its path and the line carries, per
+such check, the number of cut sites -- the sites whose loss alone opens the filament --, the necks as [first, last] positions and the longest
+neck with its x range.
+usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1] [--track]
+       [--cuts]"""
 import argparse
 import json
 import math
@@ -32,7 +36,10 @@ def main():
     ap.add_argument("--gaps", type=float, default=0.0, metavar="R", help="> 0: log the bottleneck and the direct gap of Device.find_gaps(r_max=R) at every check")
     ap.add_argument("--paths", type=int, default=-1, metavar="SLACK", help=">= 0: once bridged, log H and the constriction of Device.find_paths(slack=SLACK) at every check")
     ap.add_argument("--track", action="store_true", help="from the second check on, log the transition and the joined / left / regrouped sites of Device.track_clusters")
+    ap.add_argument("--cuts", action="store_true", help="with --paths: log the cut sites, the necks and the longest neck of Device.find_cuts at every check with a path")
     a = ap.parse_args()
+    if a.cuts and a.paths < 0:
+        ap.error("--cuts needs --paths")
     import torch
     from bench import Sim
     from devicekmc_amd import host
@@ -44,7 +51,15 @@ def main():
         link = (torch.as_tensor(wide.reshape(-1)).to("cuda:0"), nn)
     gaps, bridged_at, info = [], None, None
     bottleneck, direct = [], []
-    paths = []
+    paths, cuts = [], []
+
+    def cut_check(step):
+        _, _, _, _, necks, c = dev.find_cuts(gb, link_index=link)
+        j = int((necks["first"] == c["longest_neck_first"]).argmax()) if c["necks"] else -1
+        cuts.append(dict(step=step, cut_sites=c["cut_sites"], necks=[[int(f), int(l)] for f, l in zip(necks["first"], necks["last"])],
+                         longest_neck=c["longest_neck"], longest_neck_first=c["longest_neck_first"],
+                         longest_neck_x=[float(necks["xmin"][j]), float(necks["xmax"][j])] if j >= 0 else None,
+                         bypasses=c["bypasses"], max_bypass=c["max_bypass"]))
 
     def path_check(step):
         _, _, _, prof, pinfo = dev.find_paths(gb, slack=a.paths, link_index=link)
@@ -52,6 +67,8 @@ def main():
         paths.append(dict(step=step, status=pinfo["status"], hops=pinfo["hops"], constriction_level=lev, constriction_width=pinfo["constriction_width"],
                           constriction_x=[float(prof["xmin"][lev]), float(prof["xmax"][lev])] if pinfo["status"] else None,
                           corridor_sites=pinfo["corridor_sites"]))
+        if a.cuts and pinfo["status"]:
+            cut_check(step)
 
     track = []
 
@@ -86,6 +103,8 @@ def main():
     more = dict(gaps_r_max=a.gaps, bottleneck=bottleneck, direct=direct) if a.gaps > 0 else {}
     if a.paths >= 0:
         more.update(paths_slack=a.paths, paths=paths)
+    if a.cuts:
+        more.update(cuts=cuts)
     if a.track:
         more.update(track=track)
     print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
