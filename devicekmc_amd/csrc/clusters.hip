@@ -2,23 +2,13 @@
 // and the bridging verdict (dkmc_find_clusters; definitions: include/devicekmc_hip.h).  No counterpart in the reference.  A pure function of its
 // arguments: nothing of GPUBuffers, no engine state a later phase reads and no other kernel is touched.
 //
-// Labelling: min-hooking + compression in rounds, the kernel boundary is the only synchronisation point.
-//   label[] (the caller's array) holds, between rounds, the ROOT of every member's tree (-1: not a member); it is read-only inside a hook launch.
-//   parent[] holds the forest.  A hook launch does atomicMin(parent[max(ru, rv)], min(ru, rv)) for every index entry between two members whose
-//   roots differ; only root entries are targets, and the result of a set of atomicMin on one word does not depend on their order, so the forest
-//   after the launch is a function of label[] alone.  The compress launch walks parent[] from every member to its root (parents strictly
-//   decrease: the walk is bounded; a walker that sees an older value of a word sees an older ANCESTOR, never a wrong one, so the path halving
-//   it does on the way may race freely) and writes the root -- the same value whatever the walkers did to each other -- into label[] and
-//   parent[].  A round whose atomicMins lowered nothing ends the loop: "rounds" is the number of rounds run, that last one included, and is the
-//   number the synchronous host model (tests/cluster_ref.py) needs: the same on every call.
-// Work shape: the hook kernel skips non-members in place (no member list: one 4-byte read per site decides, and the summaries need the per-site
-//   pass anyway); a member row is read by LPR lanes, 16 up to 128 entries per row and the whole wave above.
-#include "common.h"
+// Labelling: the min-hooking + compression rounds of rounds.h (label_rounds; the argument for their soundness is there) on label[], the caller's
+//   array, which ends on the smallest site index of each component; "rounds" is the number the synchronous host model (tests/cluster_ref.py) gives.
+#include "rounds.h"
 
 #define CL_NT 256
-#define CL_BATCH 8                   // rounds enqueued per read-back; a round after the one that changed nothing returns at once
 #define CL_CAP_DEFAULT 64
-#define CL_CAP_MAX 4096
+#define CL_CAP_MAX ROUND_CAP_MAX
 
 namespace {
 
@@ -30,7 +20,7 @@ struct ClusterState {
     int valid = 0, N = 0, rounds = 0;
     ClInfoDev info{};
     double ms_label = 0.0, ms_sum = 0.0;
-    hipEvent_t ev[3]; bool ev_ready = false;
+    PhaseTimer<2> timer;
 } g_cl;
 int g_round_cap = CL_CAP_DEFAULT;
 
@@ -47,63 +37,6 @@ __global__ __launch_bounds__(CL_NT) void k_cl_members(int N, const int *el, cons
     label[i] = parent[i] = m ? i : -1;
     csize[i] = 0; cvac[i] = 0; cflags[i] = 0;
     kmin[i] = ~0ull; kmax[i] = 0ull;
-}
-
-// 2a. hook: LPR lanes per member row
-template <int LPR>
-__global__ __launch_bounds__(CL_NT) void k_cl_hook(int N, int nn, const int *__restrict__ idx, const int *__restrict__ label, int *parent,
-                                                   int *ctrl, int round)
-{
-    if (round > 0 && ctrl[round - 1] == 0) return;            // the round before changed nothing: the labelling is finished
-    const int lane = threadIdx.x % LPR;
-    const long long groups = (long long)gridDim.x * (CL_NT / LPR);
-    int changed = 0;
-    for (long long u = (long long)blockIdx.x * (CL_NT / LPR) + threadIdx.x / LPR; u < N; u += groups) {
-        const int ru = label[u];
-        if (ru < 0) continue;
-        const int *row = idx + (size_t)u * nn;
-        for (int k = lane; k < nn; k += LPR) {
-            const int v = row[k];
-            if (v < 0 || v >= N) continue;                    // padding, anywhere in the row
-            const int rv = label[v];
-            if (rv < 0 || rv == ru) continue;
-            const int hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
-            if (atomicMin(&parent[hi], lo) > lo) changed = 1;
-        }
-    }
-    if (changed) atomicOr(&ctrl[round], 1);
-}
-
-// 2b. compress: every member to its root, with path halving on the way
-__global__ __launch_bounds__(CL_NT) void k_cl_compress(int N, int *label, int *parent, const int *ctrl, int round)
-{
-    if (ctrl[round] == 0) return;                             // nothing was hooked: label[] and parent[] hold the roots already
-    const int i = blockIdx.x * CL_NT + threadIdx.x;
-    if (i >= N || label[i] < 0) return;
-    int c = i;
-    for (;;) {
-        const int p = ld_agent(&parent[c]);
-        if (p >= c || p < 0) break;                           // c is a root (a parent is smaller than its child: the walk ends)
-        const int gp = ld_agent(&parent[p]);
-        if (gp >= p || gp < 0) { c = p; break; }
-        st_agent(&parent[c], gp);
-        c = gp;
-    }
-    label[i] = c;
-    st_agent(&parent[i], c);
-}
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
-    return v;
 }
 
 // 3a. summaries per root: integer atomics only (counts, OR, min / max of the keys), so the order of arrival does not matter.  A wave whose
@@ -126,7 +59,7 @@ __global__ __launch_bounds__(CL_NT) void k_cl_summaries(int N, const int *label,
     if (__all(!mem || r == r0)) {
         const int cnt = __popcll(bm), nv = __popcll(__ballot(vac));
         const int ff = (__ballot(f & 1) ? 1 : 0) | (__ballot(f & 2) ? 2 : 0);
-        const unsigned long long lo = wave_min_u64(mem ? key : ~0ull), hi = wave_max_u64(mem ? key : 0ull);
+        const unsigned long long lo = wave_min(mem ? key : ~0ull), hi = wave_max(mem ? key : 0ull);
         if ((int)(threadIdx.x & 63) == first) {
             atomicAdd(&csize[r0], cnt);
             if (nv) atomicAdd(&cvac[r0], nv);
@@ -239,33 +172,15 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
     int *d_ncomp = ctrl + CL_CAP_MAX;
     ClInfoDev *d_info = (ClInfoDev *)(ctrl + CL_CAP_MAX + 2);
     const ClTable T = table_of(tab, n);
-    const bool timed = eng().profiling != 0;
-    if (timed && !g_cl.ev_ready) { for (auto &e : g_cl.ev) HIPCHK(hipEventCreate(&e)); g_cl.ev_ready = true; }
 
     const int site_blocks = (N + CL_NT - 1) / CL_NT;
-    if (timed) HIPCHK(hipEventRecord(g_cl.ev[0], st));
+    HIPCHK(g_cl.timer.start(eng().profiling != 0, st));
     HIPCHK(hipMemsetAsync(ctrl, 0, (size_t)(CL_CAP_MAX + 2) * sizeof(int), st));
     hipLaunchKernelGGL(k_cl_members, dim3(site_blocks), dim3(CL_NT), 0, st, N, d_site_element, d_site_charge, load_metals(d_metals, (members & 1) ? num_metals : 0),
                        members, d_label, parent, csize, cvac, cflags, kmin, kmax);
     KCHK();
-    // rounds: CL_BATCH of them per read-back of their change words
-    const int lpr = nn <= 128 ? 16 : 64;
-    const int hook_blocks = grid_blocks((long long)N * lpr, CL_NT, 8192);
-    int rounds = 0, launched = 0;
-    static int h_changed[CL_CAP_MAX];
-    while (!rounds && launched < cap) {
-        const int b = cap - launched < CL_BATCH ? cap - launched : CL_BATCH;
-        for (int r = launched; r < launched + b; ++r) {
-            if (lpr == 16) hipLaunchKernelGGL(k_cl_hook<16>, dim3(hook_blocks), dim3(CL_NT), 0, st, N, nn, d_index, (const int *)d_label, parent, ctrl, r);
-            else hipLaunchKernelGGL(k_cl_hook<64>, dim3(hook_blocks), dim3(CL_NT), 0, st, N, nn, d_index, (const int *)d_label, parent, ctrl, r);
-            hipLaunchKernelGGL(k_cl_compress, dim3(site_blocks), dim3(CL_NT), 0, st, N, d_label, parent, (const int *)ctrl, r);
-        }
-        KCHK();
-        HIPCHK(hipMemcpyAsync(h_changed + launched, ctrl + launched, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int r = launched; r < launched + b && !rounds; ++r) if (!h_changed[r]) rounds = r + 1;
-        launched += b;
-    }
+    int rounds = 0;
+    if (int rc = label_rounds(st, N, nn, d_index, d_label, parent, ctrl, cap, &rounds)) return rc;
     if (!rounds) {
         // not finished: no partial labels go out as valid
         HIPCHK(hipMemsetAsync(d_label, 0xff, n * sizeof(int), st));
@@ -274,7 +189,7 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
         snprintf(msg, sizeof(msg), "dkmc_find_clusters: labelling not finished after %d rounds (the cap: dkmc_debug_set_cluster_round_cap); labels set to -1", cap);
         return dkmc_fail(4, msg, __FILE__, __LINE__);
     }
-    if (timed) HIPCHK(hipEventRecord(g_cl.ev[1], st));
+    HIPCHK(g_cl.timer.mark(1, st));
     // summaries, table, info
     hipLaunchKernelGGL(k_cl_summaries, dim3(site_blocks), dim3(CL_NT), 0, st, N, (const int *)d_label, d_site_element, d_site_x, n_left_sites, n_right_sites,
                        csize, cvac, cflags, kmin, kmax, isroot);
@@ -285,14 +200,12 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
     hipLaunchKernelGGL(k_cl_info, dim3(1), dim3(CL_NT), 0, st, (const int *)d_ncomp, (const int *)T.root, (const int *)T.size, (const int *)T.flags,
                        (const double *)T.xmin, (const double *)T.xmax, d_info);
     KCHK();
-    if (timed) HIPCHK(hipEventRecord(g_cl.ev[2], st));
+    HIPCHK(g_cl.timer.mark(2, st));
     HIPCHK(hipMemcpyAsync(&g_cl.info, d_info, sizeof(ClInfoDev), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (timed) {
-        float a = 0.f, b = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, g_cl.ev[0], g_cl.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_cl.ev[1], g_cl.ev[2]));
-        g_cl.ms_label = a; g_cl.ms_sum = b;
-    }
+    float ms[2] = {0.f, 0.f};
+    HIPCHK(g_cl.timer.read(ms));
+    g_cl.ms_label = ms[0]; g_cl.ms_sum = ms[1];
     g_cl.rounds = rounds;
     g_cl.valid = 1;
     return 0;
@@ -301,14 +214,10 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
 int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vacancy, int *h_flags, double *h_xmin, double *h_xmax, int *rows_out)
 {
     if (!g_cl.valid) return dkmc_fail(3, "dkmc_copy_cluster_table: no finished dkmc_find_clusters call", __FILE__, __LINE__);
-    int rows = g_cl.info.n_components;
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
-    if (rows == 0) return 0;
+    const size_t r = clamp_rows(capacity, g_cl.info.n_components, rows_out);
+    if (r == 0) return 0;
     hipStream_t st = eng().stream;
     const ClTable T = table_of(eng().buf[S_CL_TABLE], (size_t)g_cl.N);
-    const size_t r = (size_t)rows;
     if (h_root) HIPCHK(hipMemcpyAsync(h_root, T.root, r * sizeof(int), hipMemcpyDeviceToHost, st));
     if (h_size) HIPCHK(hipMemcpyAsync(h_size, T.size, r * sizeof(int), hipMemcpyDeviceToHost, st));
     if (h_n_vacancy) HIPCHK(hipMemcpyAsync(h_n_vacancy, T.vac, r * sizeof(int), hipMemcpyDeviceToHost, st));

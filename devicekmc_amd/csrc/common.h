@@ -97,6 +97,19 @@ template <int W> __device__ __forceinline__ int group_sum_i(int v)
 __device__ __forceinline__ double wave_sum(double v) { return group_sum<WAVE>(v); }       // valid in lane 0 (and everywhere)
 __device__ __forceinline__ double wave_sum_all(double v) { return group_sum<WAVE>(v); }   // same value in every lane
 __device__ __forceinline__ int wave_sum_all_i(int v) { return group_sum_i<WAVE>(v); }
+// minimum / maximum of an integer (int, unsigned long long) across the wave, the same value in every lane; no order dependence
+template <class T> __device__ __forceinline__ T wave_min(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const T t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
+    return v;
+}
+template <class T> __device__ __forceinline__ T wave_max(T v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const T t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
+    return v;
+}
 // inclusive scan across the wave
 __device__ __forceinline__ double wave_scan_incl(double v, int lane)
 {

@@ -6,22 +6,21 @@
 // Positions: pos[site] = k for row k of the path, -1 elsewhere, by atomicMin of k into a word that starts at -1 read as unsigned: of two rows
 //   that name one site the smaller k stays, so the later row is the one reported as the duplicate.  The validation pass (one group of LPR lanes per
 //   path row) looks for row k - 1's site in the index row of row k's site and the other way round, and takes the smallest {row, reason} word.
-// Labelling of the off-path members ("label in range and pos < 0"): the min-hooking + compression rounds of clusters.hip, a copy of its own in this
-//   file: d_site_bypass holds the roots between the rounds and ends on the smallest site index of each off-path component; "rounds" is the number
-//   of rounds run, the one that changed nothing included, the number the synchronous host model (tests/cut_ref.py) gives.
+// Labelling of the off-path members ("label in range and pos < 0"): the min-hooking + compression rounds of rounds.h (label_rounds, the ones
+//   dkmc_find_clusters runs): d_site_bypass holds the roots between the rounds and ends on the smallest site index of each off-path component;
+//   "rounds" is the number of rounds run, the one that changed nothing included, the number the synchronous host model (tests/cut_ref.py) gives.
 // Attachment: one pass over the member rows, LPR lanes per row.  A link is seen from whichever row holds it: an off-path row collects the positions
 //   of its path entries (and -1 / L as a seed) in registers, a wave whose rows share one root -- the rule inside a contact slab -- combines them
 //   and sends one atomicMin / atomicMax pair; a path row sends the pair for each off-path entry and marks the chords among its path entries.
 // Tables: the roots with hi - lo >= 2 add +1 at lo + 1 and -1 at hi to a difference array over the positions; the chords do the same in a second
 //   one; prefix sums (scan.hip) give n_bypass and the chord flag.  The bypass table is compacted by root flag + scan, the necks by the flags of
 //   the run starts + scan.  Integer atomics only (minima, maxima, counts): the same bytes on every call.
-#include "common.h"
+#include "rounds.h"
 #include <vector>
 
 #define CU_NT 256
-#define CU_BATCH 8                   // rounds enqueued per read-back; a round after the one that changed nothing returns at once
 #define CU_CAP_DEFAULT 64
-#define CU_CAP_MAX 4096
+#define CU_CAP_MAX ROUND_CAP_MAX
 #define CU_NONE 0x7fffffff
 
 namespace {
@@ -36,7 +35,7 @@ struct CutState {
     std::vector<int> site, n_bypass, chord, cut, b_root, b_size, b_lo, b_hi, n_first, n_last;
     std::vector<double> n_xmin, n_xmax;
     double ms_label = 0.0, ms_rest = 0.0;
-    hipEvent_t ev[4]; bool ev_ready = false;
+    PhaseTimer<3> timer;
 } g_cu;
 int g_cu_round_cap = CU_CAP_DEFAULT;
 
@@ -104,73 +103,7 @@ __global__ __launch_bounds__(CU_NT) void k_cu_members(int N, const int *__restri
     root[i] = parent[i] = (r >= 0 && r < N && pos[i] < 0) ? i : -1;
 }
 
-// 3a. hook: LPR lanes per off-path row (k_cl_hook's model: root[] is read-only inside the launch, only root entries of parent[] are targets)
-template <int LPR>
-__global__ __launch_bounds__(CU_NT) void k_cu_hook(int N, int nn, const int *__restrict__ idx, const int *__restrict__ root, int *parent, int *ctrl, int round)
-{
-    if (round > 0 && ctrl[round - 1] == 0) return;            // the round before changed nothing: the labelling is finished
-    const int lane = threadIdx.x % LPR;
-    const long long groups = (long long)gridDim.x * (CU_NT / LPR);
-    int changed = 0;
-    for (long long u = (long long)blockIdx.x * (CU_NT / LPR) + threadIdx.x / LPR; u < N; u += groups) {
-        const int ru = root[u];
-        if (ru < 0) continue;
-        const int *row = idx + (size_t)u * nn;
-        for (int k = lane; k < nn; k += LPR) {
-            const int v = row[k];
-            if (v < 0 || v >= N) continue;                    // padding, anywhere in the row
-            const int rv = root[v];
-            if (rv < 0 || rv == ru) continue;
-            const int hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
-            if (atomicMin(&parent[hi], lo) > lo) changed = 1;
-        }
-    }
-    if (changed) atomicOr(&ctrl[round], 1);
-}
-
-// 3b. compress: every off-path member to its root, with path halving on the way (k_cl_compress's argument: parents strictly decrease)
-__global__ __launch_bounds__(CU_NT) void k_cu_compress(int N, int *root, int *parent, const int *ctrl, int round)
-{
-    if (ctrl[round] == 0) return;                             // nothing was hooked: root[] and parent[] hold the roots already
-    const int i = blockIdx.x * CU_NT + threadIdx.x;
-    if (i >= N || root[i] < 0) return;
-    int c = i;
-    for (;;) {
-        const int p = ld_agent(&parent[c]);
-        if (p >= c || p < 0) break;
-        const int gp = ld_agent(&parent[p]);
-        if (gp >= p || gp < 0) { c = p; break; }
-        st_agent(&parent[c], gp);
-        c = gp;
-    }
-    root[i] = c;
-    st_agent(&parent[i], c);
-}
-
-__device__ __forceinline__ int cu_wave_min(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
-__device__ __forceinline__ int cu_wave_max(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, WAVE));
-    return v;
-}
-__device__ __forceinline__ unsigned long long cu_wave_min64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long cu_wave_max64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
-    return v;
-}
+// 3. the rounds: label_rounds (rounds.h) on root[] / parent[]
 
 // 4. attachment: lo / hi of the off-path roots and the chord marks, one pass over the member rows (root[u] >= 0: off-path, pos[u] >= 0: on the
 // path, both -1: no member).  cdiff has L + 1 words.
@@ -217,7 +150,7 @@ __global__ __launch_bounds__(CU_NT) void k_cu_attach(int N, int nn, int L, const
         const int first = __ffsll((long long)bm) - 1;
         const int r0 = __shfl(ru, first, WAVE);
         if (__all(!has || ru == r0)) {
-            const int l = cu_wave_min(mylo), h = cu_wave_max(myhi);
+            const int l = wave_min(mylo), h = wave_max(myhi);
             if ((int)(threadIdx.x & (WAVE - 1)) == first) { atomicMin(&lo[r0], l); atomicMax(&hi[r0], h); }
         } else if (has) {
             atomicMin(&lo[ru], mylo); atomicMax(&hi[ru], myhi);
@@ -280,7 +213,7 @@ __global__ __launch_bounds__(CU_NT) void k_cu_path(int L, const int *__restrict_
         role[path[k]] = cut ? DKMC_CUT_ROLE_CUT : DKMC_CUT_ROLE_PATH;
         kmin[k] = ~0ull; kmax[k] = 0ull;
     }
-    const int ncut = __popcll(__ballot(cut)), nch = __popcll(__ballot(ch)), mx = cu_wave_max(nb);
+    const int ncut = __popcll(__ballot(cut)), nch = __popcll(__ballot(ch)), mx = wave_max(nb);
     if ((threadIdx.x & (WAVE - 1)) == 0) {
         if (ncut) atomicAdd(&stat->n_cut, ncut);
         if (nch) atomicAdd(&stat->n_chord, nch);
@@ -308,7 +241,7 @@ __global__ __launch_bounds__(CU_NT) void k_cu_necks(int L, const int *__restrict
     const int f = __ffsll((long long)bm) - 1;
     const int j0 = __shfl(j, f, WAVE);
     if (__all(!cut || j == j0)) {
-        const unsigned long long l = cu_wave_min64(cut ? key : ~0ull), h = cu_wave_max64(cut ? key : 0ull);
+        const unsigned long long l = wave_min(cut ? key : ~0ull), h = wave_max(cut ? key : 0ull);
         if ((int)(threadIdx.x & (WAVE - 1)) == f) { atomicMin(&kmin[j0], l); atomicMax(&kmax[j0], h); }
     } else if (cut) {
         atomicMin(&kmin[j], key); atomicMax(&kmax[j], key);
@@ -322,15 +255,6 @@ void cut_reset()
     for (auto *v : {&g_cu.site, &g_cu.n_bypass, &g_cu.chord, &g_cu.cut, &g_cu.b_root, &g_cu.b_size, &g_cu.b_lo, &g_cu.b_hi, &g_cu.n_first, &g_cu.n_last}) v->clear();
     g_cu.n_xmin.clear(); g_cu.n_xmax.clear();
     g_cu.ms_label = g_cu.ms_rest = 0.0;
-}
-
-int copy_rows(int capacity, size_t have, int *rows_out)
-{
-    long long rows = (long long)have;
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = (int)rows;
-    return (int)rows;
 }
 
 }   // namespace
@@ -371,14 +295,12 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
         *first = t_cut + lp, *last = first + lp;
     CuStat *d_stat = (CuStat *)(ctrl + CU_CAP_MAX);
     int *root = d_site_bypass;
-    const bool timed = eng().profiling != 0;
-    if (timed && !g_cu.ev_ready) { for (auto &e : g_cu.ev) HIPCHK(hipEventCreate(&e)); g_cu.ev_ready = true; }
 
     const int site_blocks = (N + CU_NT - 1) / CU_NT, path_blocks = (L + CU_NT - 1) / CU_NT;
-    const int lpr = nn <= 128 ? 16 : 64;
+    const int lpr = lpr_of(nn);
     const int row_blocks = grid_blocks((long long)N * lpr, CU_NT, 8192);
     CuStat h_stat;
-    if (timed) HIPCHK(hipEventRecord(g_cu.ev[0], st));
+    HIPCHK(g_cu.timer.start(eng().profiling != 0, st));
     HIPCHK(hipMemsetAsync(ctrl, 0, (size_t)CU_CAP_MAX * sizeof(int) + sizeof(CuStat), st));
     HIPCHK(hipMemsetAsync(&d_stat->err, 0xff, sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(bdiff, 0, 2 * lp * sizeof(int), st));
@@ -387,10 +309,7 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
         // positions and validation: nothing below reads the path before it is known to be one
         hipLaunchKernelGGL(k_cu_scatter, dim3(path_blocks), dim3(CU_NT), 0, st, N, L, d_path, d_label, pos, d_stat);
         const int vblocks = grid_blocks((long long)L * lpr, CU_NT, 8192);
-        if (lpr == 16) hipLaunchKernelGGL(k_cu_validate<16>, dim3(vblocks), dim3(CU_NT), 0, st, N, nn, L, d_index, d_path, (const int *)pos, n_left_sites,
-                                          n_right_sites, d_stat);
-        else hipLaunchKernelGGL(k_cu_validate<64>, dim3(vblocks), dim3(CU_NT), 0, st, N, nn, L, d_index, d_path, (const int *)pos, n_left_sites,
-                                n_right_sites, d_stat);
+        LAUNCH_LPR(lpr, k_cu_validate, dim3(vblocks), dim3(CU_NT), st, N, nn, L, d_index, d_path, (const int *)pos, n_left_sites, n_right_sites, d_stat);
         KCHK();
         HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(CuStat), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -407,23 +326,9 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
     }
     hipLaunchKernelGGL(k_cu_members, dim3(site_blocks), dim3(CU_NT), 0, st, N, d_label, (const int *)pos, root, parent);
     KCHK();
-    if (timed) HIPCHK(hipEventRecord(g_cu.ev[1], st));
-    // rounds: CU_BATCH of them per read-back of their change words
-    int rounds = 0, launched = 0;
-    static int h_changed[CU_CAP_MAX];
-    while (!rounds && launched < cap) {
-        const int b = cap - launched < CU_BATCH ? cap - launched : CU_BATCH;
-        for (int r = launched; r < launched + b; ++r) {
-            if (lpr == 16) hipLaunchKernelGGL(k_cu_hook<16>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, d_index, (const int *)root, parent, ctrl, r);
-            else hipLaunchKernelGGL(k_cu_hook<64>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, d_index, (const int *)root, parent, ctrl, r);
-            hipLaunchKernelGGL(k_cu_compress, dim3(site_blocks), dim3(CU_NT), 0, st, N, root, parent, (const int *)ctrl, r);
-        }
-        KCHK();
-        HIPCHK(hipMemcpyAsync(h_changed + launched, ctrl + launched, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int r = launched; r < launched + b && !rounds; ++r) if (!h_changed[r]) rounds = r + 1;
-        launched += b;
-    }
+    HIPCHK(g_cu.timer.mark(1, st));
+    int rounds = 0;
+    if (int rc = label_rounds(st, N, nn, d_index, root, parent, ctrl, cap, &rounds)) return rc;
     if (!rounds) {
         // not finished: no partial labels go out as valid
         HIPCHK(hipMemsetAsync(d_site_role, 0xff, n * sizeof(int), st));
@@ -434,14 +339,11 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
                  "site_role and site_bypass set to -1", cap);
         return dkmc_fail(4, msg, __FILE__, __LINE__);
     }
-    if (timed) HIPCHK(hipEventRecord(g_cu.ev[2], st));
+    HIPCHK(g_cu.timer.mark(2, st));
     // attachment, roles, tables
-    if (L > 0) {
-        if (lpr == 16) hipLaunchKernelGGL(k_cu_attach<16>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, L, d_index, (const int *)root, (const int *)pos,
-                                          n_left_sites, n_right_sites, lo, hi, cdiff);
-        else hipLaunchKernelGGL(k_cu_attach<64>, dim3(row_blocks), dim3(CU_NT), 0, st, N, nn, L, d_index, (const int *)root, (const int *)pos,
-                                n_left_sites, n_right_sites, lo, hi, cdiff);
-    }
+    if (L > 0)
+        LAUNCH_LPR(lpr, k_cu_attach, dim3(row_blocks), dim3(CU_NT), st, N, nn, L, d_index, (const int *)root, (const int *)pos, n_left_sites, n_right_sites,
+                   lo, hi, cdiff);
     hipLaunchKernelGGL(k_cu_sites, dim3(site_blocks), dim3(CU_NT), 0, st, N, (const int *)root, (const int *)pos, (const int *)lo, (const int *)hi, csize,
                        d_site_role, isbyp, bdiff, d_stat);
     KCHK();
@@ -460,7 +362,7 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
                            first, last, kmin, kmax);
         KCHK();
     }
-    if (timed) HIPCHK(hipEventRecord(g_cu.ev[3], st));
+    HIPCHK(g_cu.timer.mark(3, st));
     HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(CuStat), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     // the host-side tables
@@ -498,12 +400,9 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
     const long long info[12] = {L > 0 ? 1 : 0, L, h_stat.n_cut, (long long)nk, longest, longest_first, (long long)nb, h_stat.off_comps, h_stat.off_members,
                                 h_stat.max_nb, h_stat.n_chord, rounds};
     memcpy(g_cu.info, info, sizeof(info));
-    if (timed) {
-        float a = 0.f, b = 0.f, c = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, g_cu.ev[0], g_cu.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_cu.ev[1], g_cu.ev[2]));
-        HIPCHK(hipEventElapsedTime(&c, g_cu.ev[2], g_cu.ev[3]));
-        g_cu.ms_label = b; g_cu.ms_rest = a + c;
-    }
+    float ms[3] = {0.f, 0.f, 0.f};
+    HIPCHK(g_cu.timer.read(ms));
+    g_cu.ms_label = ms[1]; g_cu.ms_rest = ms[0] + ms[2];
     g_cu.valid = 1;
     return 0;
 }
@@ -518,7 +417,7 @@ int dkmc_get_cut_info(long long *info16)
 int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord, int *h_cut, int *rows_out)
 {
     if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_path: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = (size_t)copy_rows(capacity, g_cu.site.size(), rows_out);
+    const size_t r = clamp_rows(capacity, (long long)g_cu.site.size(), rows_out);
     if (r == 0) return 0;
     if (h_site) memcpy(h_site, g_cu.site.data(), r * sizeof(int));
     if (h_n_bypass) memcpy(h_n_bypass, g_cu.n_bypass.data(), r * sizeof(int));
@@ -530,7 +429,7 @@ int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord,
 int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, int *h_hi, int *rows_out)
 {
     if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_bypasses: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = (size_t)copy_rows(capacity, g_cu.b_root.size(), rows_out);
+    const size_t r = clamp_rows(capacity, (long long)g_cu.b_root.size(), rows_out);
     if (r == 0) return 0;
     if (h_root) memcpy(h_root, g_cu.b_root.data(), r * sizeof(int));
     if (h_size) memcpy(h_size, g_cu.b_size.data(), r * sizeof(int));
@@ -542,7 +441,7 @@ int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, in
 int dkmc_copy_cut_necks(int capacity, int *h_first, int *h_last, double *h_xmin, double *h_xmax, int *rows_out)
 {
     if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_necks: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = (size_t)copy_rows(capacity, g_cu.n_first.size(), rows_out);
+    const size_t r = clamp_rows(capacity, (long long)g_cu.n_first.size(), rows_out);
     if (r == 0) return 0;
     if (h_first) memcpy(h_first, g_cu.n_first.data(), r * sizeof(int));
     if (h_last) memcpy(h_last, g_cu.n_last.data(), r * sizeof(int));

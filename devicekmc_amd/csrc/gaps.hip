@@ -22,6 +22,7 @@
 // The picked edges of all rounds are the forest; their rows (labels and contact flags of both ends) are gathered on the device, the at most
 // n_components - 1 rows are sorted by key and the L -> R tree path is walked on the host.
 #include "cellgrid.h"
+#include "rounds.h"
 #include <algorithm>
 #include <vector>
 
@@ -456,7 +457,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
         hipLaunchKernelGGL(k_gp_save_direct, dim3(1), dim3(1), 0, st, N, best_d2[1], best_pair[1], ctrl);
         KCHK();
     }
-    // rounds: GP_BATCH of them per read-back of the control block
+    // rounds: GP_BATCH of them per read-back of the control block (not run_rounds, rounds.h: the host needs GpCtrl's other fields too -- one copy here)
     int rounds = 0, launched = 0;
     while (!rounds && launched < GP_ROUND_CAP) {
         const int b = GP_ROUND_CAP - launched < GP_BATCH ? GP_ROUND_CAP - launched : GP_BATCH;
@@ -536,12 +537,8 @@ int dkmc_get_gap_info(long long *info8, double *d2x2)
 int dkmc_copy_gap_edges(int capacity, int *h_site_a, int *h_site_b, int *h_root_a, int *h_root_b, double *h_d2, int *rows_out)
 {
     if (!g_gap.valid) return dkmc_fail(3, "dkmc_copy_gap_edges: no finished dkmc_find_gaps call", __FILE__, __LINE__);
-    int rows = (int)g_gap.e_a.size();
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
-    const size_t r = (size_t)rows;
-    if (rows == 0) return 0;
+    const size_t r = clamp_rows(capacity, (long long)g_gap.e_a.size(), rows_out);
+    if (r == 0) return 0;
     if (h_site_a) memcpy(h_site_a, g_gap.e_a.data(), r * sizeof(int));
     if (h_site_b) memcpy(h_site_b, g_gap.e_b.data(), r * sizeof(int));
     if (h_root_a) memcpy(h_root_a, g_gap.e_ra.data(), r * sizeof(int));
@@ -553,12 +550,8 @@ int dkmc_copy_gap_edges(int capacity, int *h_site_a, int *h_site_b, int *h_root_
 int dkmc_copy_gap_chain(int capacity, int *h_from, int *h_to, double *h_d2, int *rows_out)
 {
     if (!g_gap.valid) return dkmc_fail(3, "dkmc_copy_gap_chain: no finished dkmc_find_gaps call", __FILE__, __LINE__);
-    int rows = (int)g_gap.c_from.size();
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
-    const size_t r = (size_t)rows;
-    if (rows == 0) return 0;
+    const size_t r = clamp_rows(capacity, (long long)g_gap.c_from.size(), rows_out);
+    if (r == 0) return 0;
     if (h_from) memcpy(h_from, g_gap.c_from.data(), r * sizeof(int));
     if (h_to) memcpy(h_to, g_gap.c_to.data(), r * sizeof(int));
     if (h_d2) memcpy(h_d2, g_gap.c_d2.data(), r * sizeof(double));

@@ -14,16 +14,16 @@
 //   max(largest hops_left, largest hops_right, 0) + 1, the number the synchronous host model (tests/path_ref.py) gives.
 // Work shape: one pass over a row serves both fields (one 8-byte read per entry).  Non-members are skipped in place, and so is a member whose
 //   two words are both settled below k (its links were all used in an earlier round).  A member row is read by LPR lanes, 16 up to 128 entries per
-//   row and the whole wave above (the shape of k_cl_hook, clusters.hip).  PT_BATCH rounds are enqueued per read-back of their change words.
+//   row and the whole wave above (the shape of k_lab_hook, rounds.h).  The host loop is run_rounds (rounds.h): ROUND_BATCH rounds are enqueued
+//   per read-back of their change words.
 // After the rounds: H = the smallest hops_left on a right seed; the corridor's rows (count, min and max of the x keys per hops_left) by integer
 //   atomics, combined inside a wave whose corridor sites share a level and privatised in LDS when the rows fit; the predecessors of the sites on
 //   shortest paths by one atomicMin pass, walked from the end site by one thread.  Integer atomics only: the same bytes on every call.
-#include "common.h"
+#include "rounds.h"
 #include <vector>
 
 #define PT_NT 256
-#define PT_BATCH 8                   // rounds enqueued per read-back; a round after the one that changed nothing returns at once
-#define PT_CAP_MAX 4096
+#define PT_CAP_MAX ROUND_CAP_MAX
 #define PT_SLACK_MAX 65536
 #define PT_LDS_ROWS 1024             // profile rows privatised per workgroup: 20 bytes each
 #define PT_NONE 0x7fffffff
@@ -37,7 +37,7 @@ struct PathState {
     std::vector<int> site, count;
     std::vector<double> xmin, xmax;
     double ms_label = 0.0, ms_sum = 0.0;
-    hipEvent_t ev[3]; bool ev_ready = false;
+    PhaseTimer<2> timer;
 } g_pt;
 int g_pt_round_cap = PT_CAP_MAX;
 
@@ -98,27 +98,12 @@ __global__ __launch_bounds__(PT_NT) void k_pt_finish(int N, const int2 *__restri
         hl[i] = l; hr[i] = r;
     }
     const int nl = __popcll(__ballot(l >= 0)), nr = __popcll(__ballot(r >= 0));
-    int h = (i < N && i >= N - n_right && l >= 0) ? l : PT_NONE;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) h = min(h, __shfl_xor(h, off, WAVE));
+    const int h = wave_min((i < N && i >= N - n_right && l >= 0) ? l : PT_NONE);
     if ((threadIdx.x & (WAVE - 1)) == 0) {
         if (nl) atomicAdd(&stat->reached_left, nl);
         if (nr) atomicAdd(&stat->reached_right, nr);
         if (h != PT_NONE) atomicMin(&stat->H, h);
     }
-}
-
-__device__ __forceinline__ unsigned long long pt_wave_min(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long pt_wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
-    return v;
 }
 
 // 3b. the corridor's rows, R of them (R > H + slack), and the end site of the path.  LDS = 1: the rows are privatised per workgroup (R <=
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(PT_NT) void k_pt_profile(int N, const int *__restri
         const int first = __ffsll((long long)bm) - 1;
         const int l0 = __shfl(l, first, WAVE);
         if (__all(!in || l == l0)) {
-            const unsigned long long lo = pt_wave_min(in ? key : ~0ull), hi = pt_wave_max(in ? key : 0ull);
+            const unsigned long long lo = wave_min(in ? key : ~0ull), hi = wave_max(in ? key : 0ull);
             if ((int)(threadIdx.x & (WAVE - 1)) == first) {
                 atomicAdd(&c_[l0], __popcll(bm));
                 if (x) { atomicMin(&lo_[l0], lo); atomicMax(&hi_[l0], hi); }
@@ -255,31 +240,17 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
     int *ctrl = (int *)scratch(S_PT_CTRL, (size_t)PT_CAP_MAX * sizeof(int) + sizeof(PtStat));
     if (!hop || !pred || !ctrl) return eng().err_code;
     PtStat *d_stat = (PtStat *)(ctrl + PT_CAP_MAX);
-    const bool timed = eng().profiling != 0;
-    if (timed && !g_pt.ev_ready) { for (auto &e : g_pt.ev) HIPCHK(hipEventCreate(&e)); g_pt.ev_ready = true; }
 
     const int site_blocks = (N + PT_NT - 1) / PT_NT;
-    if (timed) HIPCHK(hipEventRecord(g_pt.ev[0], st));
+    HIPCHK(g_pt.timer.start(eng().profiling != 0, st));
     HIPCHK(hipMemsetAsync(ctrl, 0, (size_t)PT_CAP_MAX * sizeof(int) + sizeof(PtStat), st));
     hipLaunchKernelGGL(k_pt_init, dim3(site_blocks), dim3(PT_NT), 0, st, N, d_label, n_left_sites, n_right_sites, hop, pred);
     KCHK();
-    // rounds: PT_BATCH of them per read-back of their change words
-    const int lpr = nn <= 128 ? 16 : 64;
+    const int lpr = lpr_of(nn);
     const int row_blocks = grid_blocks((long long)N * lpr, PT_NT, 8192);
-    int rounds = 0, launched = 0;
-    static int h_changed[PT_CAP_MAX];
-    while (!rounds && launched < cap) {
-        const int b = cap - launched < PT_BATCH ? cap - launched : PT_BATCH;
-        for (int r = launched; r < launched + b; ++r) {
-            if (lpr == 16) hipLaunchKernelGGL(k_pt_round<16>, dim3(row_blocks), dim3(PT_NT), 0, st, N, nn, d_index, hop, ctrl, r);
-            else hipLaunchKernelGGL(k_pt_round<64>, dim3(row_blocks), dim3(PT_NT), 0, st, N, nn, d_index, hop, ctrl, r);
-        }
-        KCHK();
-        HIPCHK(hipMemcpyAsync(h_changed + launched, ctrl + launched, (size_t)b * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int r = launched; r < launched + b && !rounds; ++r) if (!h_changed[r]) rounds = r + 1;
-        launched += b;
-    }
+    int rounds = 0;
+    if (int rc = run_rounds(st, ctrl, cap, ROUND_BATCH, &rounds,
+                            [&](int r) { LAUNCH_LPR(lpr, k_pt_round, dim3(row_blocks), dim3(PT_NT), st, N, nn, d_index, hop, ctrl, r); })) return rc;
     if (!rounds) {
         // not finished: no partial hop counts go out as valid
         HIPCHK(hipMemsetAsync(d_hops_left, 0xff, n * sizeof(int), st));
@@ -289,7 +260,7 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
         snprintf(msg, sizeof(msg), "dkmc_find_paths: labelling not finished after %d rounds (the cap: dkmc_debug_set_path_round_cap); hops set to -1", cap);
         return dkmc_fail(4, msg, __FILE__, __LINE__);
     }
-    if (timed) HIPCHK(hipEventRecord(g_pt.ev[1], st));
+    HIPCHK(g_pt.timer.mark(1, st));
     // summaries.  H <= rounds - 1, so R = rounds + slack rows hold every level of the profile
     const int R = rounds + slack;
     const size_t nr = (size_t)R;
@@ -306,13 +277,11 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
     else
         hipLaunchKernelGGL(k_pt_profile<0>, dim3(grid_blocks(N, PT_NT, 8192)), dim3(PT_NT), 0, st, N, (const int *)d_hops_left, (const int *)d_hops_right,
                            d_site_x, slack, n_right_sites, R, d_stat, cnt, kmin, kmax);
-    if (lpr == 16) hipLaunchKernelGGL(k_pt_pred<16>, dim3(row_blocks), dim3(PT_NT), 0, st, N, nn, d_index, (const int *)d_hops_left, (const int *)d_hops_right,
-                                      (const PtStat *)d_stat, pred);
-    else hipLaunchKernelGGL(k_pt_pred<64>, dim3(row_blocks), dim3(PT_NT), 0, st, N, nn, d_index, (const int *)d_hops_left, (const int *)d_hops_right,
-                            (const PtStat *)d_stat, pred);
+    LAUNCH_LPR(lpr, k_pt_pred, dim3(row_blocks), dim3(PT_NT), st, N, nn, d_index, (const int *)d_hops_left, (const int *)d_hops_right, (const PtStat *)d_stat,
+               pred);
     hipLaunchKernelGGL(k_pt_walk, dim3(1), dim3(1), 0, st, N, R, (const PtStat *)d_stat, (const int *)pred, path);
     KCHK();
-    if (timed) HIPCHK(hipEventRecord(g_pt.ev[2], st));
+    HIPCHK(g_pt.timer.mark(2, st));
     HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(PtStat), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     g_pt.info[2] = rounds; g_pt.info[3] = h_stat.reached_left; g_pt.info[4] = h_stat.reached_right;
@@ -340,11 +309,9 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
             if (s < 0 || s >= N) { path_reset(); return dkmc_fail(4, "dkmc_find_paths: the path walk left the members", __FILE__, __LINE__); }
         g_pt.info[0] = 1; g_pt.info[1] = H; g_pt.info[5] = corridor; g_pt.info[6] = level; g_pt.info[7] = g_pt.count[level];
     }
-    if (timed) {
-        float a = 0.f, b = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, g_pt.ev[0], g_pt.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_pt.ev[1], g_pt.ev[2]));
-        g_pt.ms_label = a; g_pt.ms_sum = b;
-    }
+    float ms[2] = {0.f, 0.f};
+    HIPCHK(g_pt.timer.read(ms));
+    g_pt.ms_label = ms[0]; g_pt.ms_sum = ms[1];
     g_pt.valid = 1;
     return 0;
 }
@@ -359,23 +326,16 @@ int dkmc_get_path_info(long long *info8)
 int dkmc_copy_path_sites(int capacity, int *h_site, int *rows_out)
 {
     if (!g_pt.valid) return dkmc_fail(3, "dkmc_copy_path_sites: no finished dkmc_find_paths call", __FILE__, __LINE__);
-    int rows = (int)g_pt.site.size();
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
-    if (rows && h_site) memcpy(h_site, g_pt.site.data(), (size_t)rows * sizeof(int));
+    const size_t r = clamp_rows(capacity, (long long)g_pt.site.size(), rows_out);
+    if (r && h_site) memcpy(h_site, g_pt.site.data(), r * sizeof(int));
     return 0;
 }
 
 int dkmc_copy_path_profile(int capacity, int *h_count, double *h_xmin, double *h_xmax, int *rows_out)
 {
     if (!g_pt.valid) return dkmc_fail(3, "dkmc_copy_path_profile: no finished dkmc_find_paths call", __FILE__, __LINE__);
-    int rows = (int)g_pt.count.size();
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
-    const size_t r = (size_t)rows;
-    if (rows == 0) return 0;
+    const size_t r = clamp_rows(capacity, (long long)g_pt.count.size(), rows_out);
+    if (r == 0) return 0;
     if (h_count) memcpy(h_count, g_pt.count.data(), r * sizeof(int));
     if (h_xmin) memcpy(h_xmin, g_pt.xmin.data(), r * sizeof(double));
     if (h_xmax) memcpy(h_xmax, g_pt.xmax.data(), r * sizeof(double));

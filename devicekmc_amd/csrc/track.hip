@@ -15,7 +15,7 @@
 //   atomicMax on the packed word (count << 32 | ~id) of main_child / main_parent: the larger count wins, the smaller id on ties -- the tie-break
 //   is part of the word, so the order of arrival cannot matter.  Integer atomics only, no floating-point arithmetic: the same inputs give the same
 //   bytes on every call.
-#include "common.h"
+#include "rounds.h"
 #include <vector>
 
 #define TR_NT 256
@@ -44,7 +44,7 @@ struct TrackState {
     double x2[2] = {INFINITY, -INFINITY};
     std::vector<int> pairs[4], now[6], prev[6], critical;
     double ms_pairs = 0.0, ms_rest = 0.0;
-    hipEvent_t ev[3]; bool ev_ready = false;
+    PhaseTimer<2> timer;
 } g_tr;
 int g_tr_hash = 0;
 
@@ -56,18 +56,6 @@ __device__ __forceinline__ unsigned long long tr_mix(unsigned long long x)
 {
     x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31;
     return x;
-}
-__device__ __forceinline__ unsigned long long tr_wave_min(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long tr_wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long t = __shfl_xor(v, off, WAVE); v = t > v ? t : v; }
-    return v;
 }
 
 // the slot of key, claimed if the key is new; -1 (and the error word) after mask + 1 probes without one
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(TR_NT) void k_tr_sites(int N, const int *lp, const 
     unsigned long long lo = TR_EMPTY, hi = 0ull;
     if (cm && x) {
         const unsigned long long k = cr ? dbl_key(x[i]) : 0ull;
-        lo = tr_wave_min(cr ? k : TR_EMPTY); hi = tr_wave_max(k);
+        lo = wave_min(cr ? k : TR_EMPTY); hi = wave_max(k);
     }
     if ((threadIdx.x & 63) == 0) {
         if (n1) atomicAdd(&ctrl->mainline, n1);
@@ -258,12 +246,9 @@ int copy_rows(const char *who, const std::vector<int> *cols, int ncols, int capa
         snprintf(msg, sizeof(msg), "%s: no finished dkmc_track_clusters call", who);
         return dkmc_fail(3, msg, __FILE__, __LINE__);
     }
-    int rows = (int)cols[0].size();
-    if (rows > capacity) rows = capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = rows;
+    const size_t rows = clamp_rows(capacity, (long long)cols[0].size(), rows_out);
     for (int c = 0; c < ncols && rows; ++c)
-        if (out[c]) memcpy(out[c], cols[c].data(), (size_t)rows * sizeof(int));
+        if (out[c]) memcpy(out[c], cols[c].data(), rows * sizeof(int));
     return 0;
 }
 
@@ -304,10 +289,9 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
     const TrSide P = side_of(comp, n), Q = side_of(comp + n * (sizeof(unsigned long long) + 4 * sizeof(int)), n);
     int *slot = site, *flags4 = site + n, *pos4 = site + 5 * n;           // flags / positions: pair firsts, prev ids, now ids, critical sites
     const bool timed = eng().profiling != 0;
-    if (timed && !g_tr.ev_ready) { for (auto &e : g_tr.ev) HIPCHK(hipEventCreate(&e)); g_tr.ev_ready = true; }
 
     const int blocks = (N + TR_NT - 1) / TR_NT;
-    if (timed) HIPCHK(hipEventRecord(g_tr.ev[0], st));
+    HIPCHK(g_tr.timer.start(timed, st));
     HIPCHK(hipMemsetAsync(keys, 0xff, cap * (sizeof(unsigned long long) + sizeof(unsigned)), st));      // free slots, first_site = the identity of the minimum
     HIPCHK(hipMemsetAsync(cnt, 0, cap * sizeof(int), st));
     HIPCHK(hipMemsetAsync(comp, 0, 2 * n * (sizeof(unsigned long long) + 4 * sizeof(int)), st));
@@ -316,7 +300,7 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
     hipLaunchKernelGGL(k_tr_pairs, dim3(blocks), dim3(TR_NT), 0, st, N, d_label_prev, d_label_now, n_left_sites, n_right_sites, (unsigned)(cap - 1), g_tr_hash,
                        keys, first, cnt, P.flags, Q.flags, slot, ctrl);
     KCHK();
-    if (timed) HIPCHK(hipEventRecord(g_tr.ev[1], st));
+    HIPCHK(g_tr.timer.mark(1, st));
     hipLaunchKernelGGL(k_tr_links, dim3(blocks), dim3(TR_NT), 0, st, N, d_label_prev, d_label_now, (const int *)slot, (const unsigned *)first, (const int *)cnt,
                        flags4, P, Q);
     hipLaunchKernelGGL(k_tr_comps, dim3(blocks), dim3(TR_NT), 0, st, N, P, Q, flags4 + n, flags4 + 2 * n, ctrl);
@@ -339,11 +323,11 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
         hipLaunchKernelGGL(k_tr_scatter, dim3(blocks), dim3(TR_NT), 0, st, N, d_label_prev, d_label_now, (const int *)slot, (const int *)cnt, (const int *)flags4,
                            (const int *)pos4, P, Q, rows_of(d_rows, np, nn, nv, nc));
         KCHK();
-        if (timed) HIPCHK(hipEventRecord(g_tr.ev[2], st));
+        HIPCHK(g_tr.timer.mark(2, st));
         HIPCHK(hipMemcpyAsync(rows.data(), d_rows, total * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
-    else if (timed) { HIPCHK(hipEventRecord(g_tr.ev[2], st)); HIPCHK(hipStreamSynchronize(st)); }
+    else if (timed) { HIPCHK(g_tr.timer.mark(2, st)); HIPCHK(hipStreamSynchronize(st)); }
     const TrRows R = rows_of(rows.data(), np, nn, nv, nc);
     for (int c = 0; c < 4; ++c) g_tr.pairs[c].assign(R.pairs + c * np, R.pairs + (c + 1) * np);
     for (int c = 0; c < 6; ++c) { g_tr.now[c].assign(R.now + c * nn, R.now + (c + 1) * nn); g_tr.prev[c].assign(R.prev + c * nv, R.prev + (c + 1) * nv); }
@@ -353,11 +337,9 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
                                 (bp >= 0 ? 2 : 0) | (bn >= 0 ? 1 : 0), bp, bn, h.born, h.died, h.merged, h.split, h.n_crit, 0};
     memcpy(g_tr.info, info, sizeof(info));
     if (d_site_x && h.n_crit > 0) { g_tr.x2[0] = key_dbl(h.kmin); g_tr.x2[1] = key_dbl(h.kmax); }
-    if (timed) {
-        float a = 0.f, b = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, g_tr.ev[0], g_tr.ev[1])); HIPCHK(hipEventElapsedTime(&b, g_tr.ev[1], g_tr.ev[2]));
-        g_tr.ms_pairs = a; g_tr.ms_rest = b;
-    }
+    float ms[2] = {0.f, 0.f};
+    HIPCHK(g_tr.timer.read(ms));
+    g_tr.ms_pairs = ms[0]; g_tr.ms_rest = ms[1];
     g_tr.valid = 1;
     return 0;
 }

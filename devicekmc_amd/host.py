@@ -137,6 +137,15 @@ def _use_stream(dev):
     check(_lib.load().dkmc_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
 
+def _copy_table(call, int_names, double_names, n):
+    """One dkmc_copy_* entry point (capacity, the int32 columns, the float64 columns, rows_out) into fresh host columns of n rows: a dict of
+    the columns by name, sliced to the rows the call reports."""
+    cols = [np.empty(max(n, 0), dtype=np.int32) for _ in int_names] + [np.empty(max(n, 0)) for _ in double_names]
+    rows = C.c_int(0)
+    check(call(n, *[_np_ptr(c) for c in cols], C.byref(rows)))
+    return {k: c[:rows.value] for k, c in zip(tuple(int_names) + tuple(double_names), cols)}
+
+
 # member sets of the filament analysis (include/devicekmc_hip.h: dkmc_find_clusters); NEUTRAL_ONLY restricts the vacancies to site_charge == 0
 METAL, VACANCY, NEUTRAL_ONLY = 1, 2, 4
 CLUSTER_INFO = ("n_members", "n_components", "bridged", "bridge_root", "largest_free_size", "rounds")
@@ -158,10 +167,7 @@ def find_clusters(index, nn, element, charge, x, metal_types, members, n_left, n
     info = dict(zip(CLUSTER_INFO, (int(v) for v in i8)))
     info.update(tip_left_x=x3[0], tip_right_x=x3[1], gap_x=x3[2])
     cap = info["n_components"] if capacity is None else int(capacity)
-    cols = [np.empty(max(cap, 0), dtype=np.int32) for _ in range(4)] + [np.empty(max(cap, 0)) for _ in range(2)]
-    rows = C.c_int(0)
-    check(L.dkmc_copy_cluster_table(cap, *[_np_ptr(c) for c in cols], C.byref(rows)))
-    return label, {k: c[:rows.value] for k, c in zip(CLUSTER_TABLE, cols)}, info
+    return label, _copy_table(L.dkmc_copy_cluster_table, CLUSTER_TABLE[:4], CLUSTER_TABLE[4:], cap), info
 
 
 GAP_EDGES = ("site_a", "site_b", "root_a", "root_b")
@@ -181,13 +187,8 @@ def find_gaps(label, x, y, z, lattice, pbc, n_left, n_right, r_max):
     check(L.dkmc_find_gaps(N, _ptr(x), _ptr(y), _ptr(z), _np_ptr(lat), int(bool(pbc)), _ptr(label), int(n_left), int(n_right), float(r_max)))
     i8, d2 = (C.c_longlong * 8)(), (C.c_double * 2)()
     check(L.dkmc_get_gap_info(i8, d2))
-    rows = C.c_int(0)
-    cols = [np.empty(i8[1], dtype=np.int32) for _ in GAP_EDGES] + [np.empty(i8[1])]
-    check(L.dkmc_copy_gap_edges(int(i8[1]), *[_np_ptr(c) for c in cols], C.byref(rows)))
-    edges = {k: c[:rows.value] for k, c in zip(GAP_EDGES + ("d2",), cols)}
-    cols = [np.empty(i8[3], dtype=np.int32) for _ in GAP_CHAIN] + [np.empty(i8[3])]
-    check(L.dkmc_copy_gap_chain(int(i8[3]), *[_np_ptr(c) for c in cols], C.byref(rows)))
-    chain = {k: c[:rows.value] for k, c in zip(GAP_CHAIN + ("d2",), cols)}
+    edges = _copy_table(L.dkmc_copy_gap_edges, GAP_EDGES, ("d2",), int(i8[1]))
+    chain = _copy_table(L.dkmc_copy_gap_chain, GAP_CHAIN, ("d2",), int(i8[3]))
     edges["dist"], chain["dist"] = np.sqrt(edges["d2"]), np.sqrt(chain["d2"])
     info = dict(n_components=int(i8[0]), n_edges=int(i8[1]), status=int(i8[2]), n_hops=int(i8[3]), rounds=int(i8[4]), pairs_tested=int(i8[5]),
                 direct=(int(i8[6]), int(i8[7]), float(np.sqrt(d2[1]))) if i8[6] >= 0 else None,
@@ -214,14 +215,9 @@ def find_paths(index, nn, label, x, n_left, n_right, slack=0):
     i8 = (C.c_longlong * 8)()
     check(L.dkmc_get_path_info(i8))
     info = dict(zip(PATH_INFO, (int(v) for v in i8)))
-    rows = C.c_int(0)
     n_path, n_prof = (info["hops"] + 1, info["hops"] + int(slack) + 1) if info["status"] else (0, 0)
-    path = np.empty(n_path, dtype=np.int32)
-    check(L.dkmc_copy_path_sites(n_path, _np_ptr(path), C.byref(rows)))
-    path = path[:rows.value]
-    cols = [np.empty(n_prof, dtype=np.int32), np.empty(n_prof), np.empty(n_prof)]
-    check(L.dkmc_copy_path_profile(n_prof, *[_np_ptr(c) for c in cols], C.byref(rows)))
-    return hl, hr, path, {k: c[:rows.value] for k, c in zip(PATH_PROFILE, cols)}, info
+    path = _copy_table(L.dkmc_copy_path_sites, ("site",), (), n_path)["site"]
+    return hl, hr, path, _copy_table(L.dkmc_copy_path_profile, PATH_PROFILE[:1], PATH_PROFILE[1:], n_prof), info
 
 
 TRACK_INFO = ("n_prev", "n_now", "n_pairs", "stayed", "joined", "left", "regrouped", "transition", "bridge_prev", "bridge_now",
@@ -252,17 +248,10 @@ def track_clusters(label_prev, label_now, x, n_left, n_right):
     check(L.dkmc_get_track_info(i16, x2))
     info = dict(zip(TRACK_INFO, (int(v) for v in i16)))
     info.update(critical_xmin=x2[0], critical_xmax=x2[1])
-    rows = C.c_int(0)
-
-    def table(call, names, n):
-        cols = [np.empty(n, dtype=np.int32) for _ in names]
-        check(call(n, *[_np_ptr(c) for c in cols], C.byref(rows)))
-        return {k: c[:rows.value] for k, c in zip(names, cols)}
-
-    pairs = table(L.dkmc_copy_track_pairs, TRACK_PAIRS, info["n_pairs"])
-    now = table(L.dkmc_copy_track_now, TRACK_NOW, info["n_now"])
-    prev = table(L.dkmc_copy_track_prev, TRACK_PREV, info["n_prev"])
-    critical = table(L.dkmc_copy_track_critical, ("site",), info["n_critical"])["site"]
+    pairs = _copy_table(L.dkmc_copy_track_pairs, TRACK_PAIRS, (), info["n_pairs"])
+    now = _copy_table(L.dkmc_copy_track_now, TRACK_NOW, (), info["n_now"])
+    prev = _copy_table(L.dkmc_copy_track_prev, TRACK_PREV, (), info["n_prev"])
+    critical = _copy_table(L.dkmc_copy_track_critical, ("site",), (), info["n_critical"])["site"]
     return change, pairs, now, prev, critical, info
 
 
@@ -296,16 +285,9 @@ def find_cuts(index, nn, label, x, n_left, n_right, path):
     i16 = (C.c_longlong * 16)()
     check(L.dkmc_get_cut_info(i16))
     info = dict(zip(CUT_INFO, (int(v) for v in i16)))
-    rows = C.c_int(0)
-
-    def table(call, names, n, doubles=0):
-        cols = [np.empty(n, dtype=np.int32) for _ in names[:len(names) - doubles]] + [np.empty(n) for _ in range(doubles)]
-        check(call(n, *[_np_ptr(c) for c in cols], C.byref(rows)))
-        return {k: c[:rows.value] for k, c in zip(names, cols)}
-
-    path_table = table(L.dkmc_copy_cut_path, CUT_PATH, info["path_len"])
-    bypasses = table(L.dkmc_copy_cut_bypasses, CUT_BYPASSES, info["bypasses"])
-    necks = table(L.dkmc_copy_cut_necks, CUT_NECKS, info["necks"], doubles=2)
+    path_table = _copy_table(L.dkmc_copy_cut_path, CUT_PATH, (), info["path_len"])
+    bypasses = _copy_table(L.dkmc_copy_cut_bypasses, CUT_BYPASSES, (), info["bypasses"])
+    necks = _copy_table(L.dkmc_copy_cut_necks, CUT_NECKS[:2], CUT_NECKS[2:], info["necks"])
     return role, bypass, path_table, bypasses, necks, info
 
 
@@ -480,15 +462,23 @@ class Device:
         self.track_pairs, self.track_now, self.track_prev, self.track_critical, self.track_info = pairs, now, prev, critical, info
         return self.site_change, pairs, now, prev, critical, info
 
+    def _labels_or(self, label, otherwise):
+        """The labels an analysis runs on: label if given, else the device tensor of the last find_clusters.  Where there is neither, otherwise
+        decides: an exception is raised, a callable is called and has to make that find_clusters call."""
+        if label is not None:
+            return label
+        if getattr(self, "_cluster_label", None) is None:
+            if isinstance(otherwise, Exception):
+                raise otherwise
+            otherwise()
+        return self._cluster_label
+
     def find_gaps(self, gpubuf: GPUBuffers, r_max=10.0, label=None, n_left=None, n_right=None):
         """Gap analysis on the device (dkmc_find_gaps; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- one with
         the default members is run if there is none -- or over label (int32 device tensor of N): the island graph within r_max, the tunnelling
         chain between the contact clusters with its bottleneck hop, and the direct tip-to-tip gap, with this device's pbc and lattice and the
         contact seeds of find_clusters.  Changes nothing in gpubuf.  Returns (edges, chain, info) and keeps them as gap_edges, gap_chain, gap_info."""
-        if label is None:
-            if getattr(self, "_cluster_label", None) is None:
-                self.find_clusters(gpubuf, n_left=n_left, n_right=n_right)
-            label = self._cluster_label
+        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
         n_left, n_right = self.contact_seeds(n_left, n_right)
         self.gap_edges, self.gap_chain, self.gap_info = find_gaps(label, gpubuf.site_x, gpubuf.site_y, gpubuf.site_z, self.lattice, self.pbc,
                                                                   n_left, n_right, r_max)
@@ -501,10 +491,7 @@ class Device:
         path, the level profile of the corridor of the walks at most slack links longer and its constriction, with the contact seeds of
         find_clusters.  Changes nothing in gpubuf.  Returns (hops_left, hops_right: host int32 arrays, path, profile, info) and keeps them as
         site_hops_left, site_hops_right, path_sites, path_profile, path_info."""
-        if label is None:
-            if getattr(self, "_cluster_label", None) is None:
-                self.find_clusters(gpubuf, n_left=n_left, n_right=n_right)
-            label = self._cluster_label
+        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
         n_left, n_right = self.contact_seeds(n_left, n_right)
         index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
         hl, hr, path, profile, info = find_paths(index, nn, label, gpubuf.site_x, n_left, n_right, slack)
@@ -519,10 +506,7 @@ class Device:
         gpubuf.neigh_idx or link_index = (int32 device tensor of N * nn, nn) -- the index the path was found on -- with the contact seeds of
         find_clusters.  Changes nothing in gpubuf.  Returns (site_role, site_bypass: host int32 arrays, path_table, bypasses, necks, info) and
         keeps them as site_role, site_bypass, cut_path, cut_bypasses, cut_necks, cut_info."""
-        if label is None:
-            label = getattr(self, "_cluster_label", None)
-            if label is None:
-                raise ValueError("find_cuts runs on the labels of a find_clusters call: none was made on this Device (or pass label)")
+        label = self._labels_or(label, ValueError("find_cuts runs on the labels of a find_clusters call: none was made on this Device (or pass label)"))
         if path is None:
             path = getattr(self, "path_sites", None)
             if path is None:

@@ -49,11 +49,11 @@ def labels_of(index, mask):
     return label
 
 
-def model_rounds(index, mask):
-    """Rounds of the synchronous model the device runs: every round hooks, for every index entry between two members whose roots differ, the
-    larger root under the smaller (minimum per root), then compresses every member to its root; the round in which nothing is hooked counts."""
+def hook_compress_rounds(u, v, mask):
+    """The synchronous model of the device's labelling on the links (u[k], v[k]) between members of mask: every round hooks, for every link whose
+    ends have different roots, the larger root under the smaller (minimum per root), then compresses every member to its root; the round in which
+    nothing is hooked counts.  -> (rounds, root int64 [N]: the smallest site index of the component, -1 outside mask)."""
     N = len(mask)
-    u, v = member_edges(index, mask)
     root = np.where(mask, np.arange(N), -1).astype(np.int64)
     rounds = 0
     while True:
@@ -70,6 +70,11 @@ def model_rounds(index, mask):
                 break
             parent = pp
         root = np.where(mask, parent[np.where(mask, root, 0)], -1)
+
+
+def model_rounds(index, mask):
+    """Rounds (and final roots) of hook_compress_rounds over every index entry between two members."""
+    return hook_compress_rounds(*member_edges(index, mask), mask)
 
 
 def analyse(index, element, charge, x, metals, members, n_left, n_right, with_rounds=True):

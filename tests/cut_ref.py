@@ -1,9 +1,10 @@
 """Host reference of the cut-site analysis (dkmc_find_cuts; definitions: include/devicekmc_hip.h): the members every conducting path between the
 contacts crosses, by the rule of the off-path components and the chords of one left-to-right path, plus a brute force that deletes a member and
-searches, a randomised simple path and the synchronous model of the off-path labelling's rounds.  numpy only (the link rows are path_ref's).
+searches, a randomised simple path and the synchronous model of the off-path labelling's rounds (cluster_ref's; the link rows are path_ref's).
 Everything it returns is an integer or one of the input doubles, so the device result is compared with np.array_equal."""
 import numpy as np
 
+import cluster_ref as cr
 import path_ref as pr
 
 INFO = ("status", "path_len", "cut_sites", "necks", "longest_neck", "longest_neck_first", "bypasses", "offpath_components", "offpath_members",
@@ -27,31 +28,14 @@ def graph(index, label, n_left, n_right):
 
 
 def model_rounds(ptr, nb, mask):
-    """Rounds of the synchronous model the device runs on the members of mask (the links between them only): every round hooks, for every link
-    whose ends have different roots, the larger root under the smaller (minimum per root), then compresses every member to its root; the round in
-    which nothing is hooked counts.  -> (rounds, root int64 [N]: the smallest site index of the component, -1 outside mask).  0 rounds at N == 0."""
+    """Rounds of the synchronous model the device runs (cluster_ref.hook_compress_rounds) on the members of mask, over the links between them
+    only.  -> (rounds, root int64 [N]: the smallest site index of the component, -1 outside mask).  0 rounds at N == 0."""
     N = len(mask)
     if N == 0:
         return 0, np.zeros(0, dtype=np.int64)
     u = np.repeat(np.arange(N), np.diff(ptr))
     ok = mask[u] & mask[nb]
-    u, v = u[ok], nb[ok]
-    root = np.where(mask, np.arange(N), -1).astype(np.int64)
-    rounds = 0
-    while True:
-        rounds += 1
-        ru, rv = root[u], root[v]
-        d = ru != rv
-        if not d.any():
-            return rounds, root
-        parent = np.arange(N)
-        np.minimum.at(parent, np.maximum(ru[d], rv[d]), np.minimum(ru[d], rv[d]))
-        while True:                                                         # pointer doubling to the roots
-            pp = parent[parent]
-            if np.array_equal(pp, parent):
-                break
-            parent = pp
-        root = np.where(mask, parent[np.where(mask, root, 0)], -1)
+    return cr.hook_compress_rounds(u[ok], nb[ok], mask)
 
 
 def check_path(path, N, mask, ptr, nb, seeds_left, seeds_right):
