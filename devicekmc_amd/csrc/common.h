@@ -305,6 +305,9 @@ enum {
     // cut-site analysis (cuts.hip: dkmc_find_cuts): per-site words (position, forest, lo / hi, size, root flag + position), the bypass table, the
     // per-position rows (difference arrays, path table, necks), change words + stat block
     S_CUT_SITE, S_CUT_TABLE, S_CUT_ROWS, S_CUT_CTRL,
+    // min-cut analysis (flow.hip: dkmc_find_flow): per-site words (strand neighbours, the level pairs of both closing searches, the nearest seeds,
+    // predecessors, first-site flag + rank, the strand sites), the strand table, change words + stat block
+    S_FL_SITE, S_FL_ROWS, S_FL_CTRL,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

@@ -41,12 +41,6 @@ struct PathState {
 } g_pt;
 int g_pt_round_cap = PT_CAP_MAX;
 
-__device__ __forceinline__ int2 ld_hop(const int2 *p)
-{
-    const unsigned long long w = __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_int2((int)(w & 0xffffffffull), (int)(w >> 32));
-}
-
 // 1. seeds: {0 on a seed, -1 on any other member, -2 on a non-member} in both fields; the predecessor words at their identity
 __global__ __launch_bounds__(PT_NT) void k_pt_init(int N, const int *__restrict__ label, int n_left, int n_right, int2 *hop, int *pred)
 {
@@ -68,7 +62,7 @@ __global__ __launch_bounds__(PT_NT) void k_pt_round(int N, int nn, const int *__
     const long long groups = (long long)gridDim.x * (PT_NT / LPR);
     int changed = 0;
     for (long long u = (long long)blockIdx.x * (PT_NT / LPR) + threadIdx.x / LPR; u < N; u += groups) {
-        const int2 hu = ld_hop(&hop[u]);
+        const int2 hu = ld_pair(&hop[u]);
         if (hu.x == -2) continue;                             // not a member
         const bool al = hu.x == k || hu.x == -1, ar = hu.y == k || hu.y == -1;
         if (!al && !ar) continue;                             // both settled below k (or just set to k + 1): nothing to give, nothing to take
@@ -76,7 +70,7 @@ __global__ __launch_bounds__(PT_NT) void k_pt_round(int N, int nn, const int *__
         for (int e = lane; e < nn; e += LPR) {
             const int v = row[e];
             if (v < 0 || v >= N) continue;                    // padding, anywhere in the row
-            const int2 hv = ld_hop(&hop[v]);
+            const int2 hv = ld_pair(&hop[v]);
             if (hv.x == -2) continue;
             if (hu.x == k && hv.x == -1) { st_agent(&hop[v].x, k + 1); changed = 1; }
             else if (hu.x == -1 && hv.x == k) { st_agent(&hop[u].x, k + 1); changed = 1; }

@@ -1,4 +1,4 @@
-// rounds.h -- what the filament analyses share (clusters.hip, gaps.hip, paths.hip, track.hip, cuts.hip): the min-hooking + compression labelling,
+// rounds.h -- what the filament analyses share (clusters.hip, gaps.hip, paths.hip, track.hip, cuts.hip, flow.hip): the min-hooking + compression labelling,
 // the host loop that runs rounds until one changes nothing, the lanes-per-row rule of the row kernels, the phase timer of the debug splits and the
 // row clamp of the copy-out entry points.  Kernels with internal linkage and inline host helpers, as in cellgrid.h: no symbol of its own.
 //
@@ -28,6 +28,13 @@ inline int lpr_of(int nn) { return nn <= 128 ? 16 : 64; }
         if ((lpr) == 16) hipLaunchKernelGGL(kernel<16>, grid, block, 0, st, __VA_ARGS__); \
         else hipLaunchKernelGGL(kernel<64>, grid, block, 0, st, __VA_ARGS__); \
     } while (0)
+
+// ---- a pair of level words (paths.hip, flow.hip) in one relaxed agent-scope read -----------------
+__device__ __forceinline__ int2 ld_pair(const int2 *p)
+{
+    const unsigned long long w = __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return make_int2((int)(w & 0xffffffffull), (int)(w >> 32));
+}
 
 // ---- the round driver ---------------------------------------------------------------------------
 inline int *round_words() { static int h_changed[ROUND_CAP_MAX]; return h_changed; }

@@ -291,6 +291,35 @@ def find_cuts(index, nn, label, x, n_left, n_right, path):
     return role, bypass, path_table, bypasses, necks, info
 
 
+FLOW_INFO = ("status", "width", "left_shore", "right_shore", "shared_cut", "interior", "near_left", "near_right", "searches", "rounds",
+             "longest_strand", "shortest_strand")
+FLOW_STRANDS = ("first_site", "last_site", "length", "offset", "left_seed", "right_seed", "cut_left_site", "cut_left_pos", "cut_right_site",
+                "cut_right_pos")
+FLOW_ZONE = ("member", "left_shore", "left_cut", "right_cut", "right_shore")   # bit k of site_zone
+
+
+def find_flow(index, nn, label, x, n_left, n_right, max_strands=64):
+    """dkmc_find_flow on device tensors (index: N * nn int32; label: N int32, e.g. the first return value of find_clusters; x: N float64 or
+    None; max_strands: 1 ... 4096, the search stops with status 3 once that many disjoint strands exist).  Returns (site_zone: int32 device
+    tensor of N, bit k = FLOW_ZONE[k]; site_strand: int32 device tensor of N; strands: dict of host int32 arrays FLOW_STRANDS, one row per strand;
+    strand_sites: host int32 array, the strands' sites in table order; info: dict of FLOW_INFO + cut_left_xmin, cut_left_xmax, cut_right_xmin,
+    cut_right_xmax).  Definitions: include/devicekmc_hip.h."""
+    L = _lib.load()
+    N = int(label.numel())
+    _use_stream(label.device)
+    zone = torch.empty(N, dtype=torch.int32, device=label.device)
+    strand = torch.empty(N, dtype=torch.int32, device=label.device)
+    check(L.dkmc_find_flow(N, int(nn), _ptr(index), _ptr(label), _ptr(x) if x is not None else None, int(n_left), int(n_right), int(max_strands),
+                           _ptr(zone), _ptr(strand)))
+    i16, x4 = (C.c_longlong * 16)(), (C.c_double * 4)()
+    check(L.dkmc_get_flow_info(i16, x4))
+    info = dict(zip(FLOW_INFO, (int(v) for v in i16)))
+    info.update(cut_left_xmin=x4[0], cut_left_xmax=x4[1], cut_right_xmin=x4[2], cut_right_xmax=x4[3])
+    strands = _copy_table(L.dkmc_copy_flow_strands, FLOW_STRANDS, (), max(info["width"], 0))
+    sites = _copy_table(L.dkmc_copy_flow_strand_sites, ("site",), (), int(strands["length"].sum()))["site"]
+    return zone, strand, strands, sites, info
+
+
 # rate census of an event table (include/devicekmc_hip.h: dkmc_event_rate_census); classes in the order of the EVENTTYPE enum
 EVENT_CLASSES = ("gen", "rec", "vdiff", "idiff")
 
@@ -517,6 +546,21 @@ class Device:
         self.site_role, self.site_bypass = role.cpu().numpy(), bypass.cpu().numpy()
         self.cut_path, self.cut_bypasses, self.cut_necks, self.cut_info = table, bypasses, necks, info
         return self.site_role, self.site_bypass, table, bypasses, necks, info
+
+    def find_flow(self, gpubuf: GPUBuffers, max_strands=64, label=None, link_index=None, n_left=None, n_right=None):
+        """Min-cut analysis on the device (dkmc_find_flow; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- one
+        with the default members is run if there is none -- or over label (int32 device tensor of N): W, the largest number of conducting paths
+        between the contacts that share no atom, the minimum separators nearest either contact with their shores, and one canonical family of W
+        strands, over gpubuf.neigh_idx or link_index = (int32 device tensor of N * nn, nn), with the contact seeds of find_clusters.  Changes
+        nothing in gpubuf.  Returns (site_zone, site_strand: host int32 arrays, strands, strand_sites, info) and keeps them as site_zone,
+        site_strand, flow_strands, flow_strand_sites, flow_info."""
+        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
+        n_left, n_right = self.contact_seeds(n_left, n_right)
+        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        zone, strand, strands, sites, info = find_flow(index, nn, label, gpubuf.site_x, n_left, n_right, max_strands)
+        self.site_zone, self.site_strand = zone.cpu().numpy(), strand.cpu().numpy()
+        self.flow_strands, self.flow_strand_sites, self.flow_info = strands, sites, info
+        return self.site_zone, self.site_strand, strands, sites, info
 
     # heat_solver.cpp:250-312 (global branch; computed on the device instead of copy_power_fromGPU + host sum)
     def updateTemperature(self, gpubuf: GPUBuffers, p: KMCParameters, step_time: float):

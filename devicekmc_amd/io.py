@@ -24,7 +24,8 @@ def _g6(v: float) -> str:
     return "%g" % v
 
 
-def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None, cluster=None, hops=None, change=None, role=None):
+def write_snapshot(path, element, x, y, z, potential, power, full_precision=False, current=None, cluster=None, hops=None, change=None, role=None,
+                   zone=None):
     """current: optional per-site array (e.g. Device.site_current) appended as one more column; read_xyz ignores it.  None: the reference's file.
     cluster: optional per-site integer array (Device.site_cluster: the label of the site's conducting cluster, -1 for none) appended as the last
     column, after current when both are given; read_xyz ignores it too.  None: the file as without it, byte for byte.
@@ -33,10 +34,13 @@ def write_snapshot(path, element, x, y, z, potential, power, full_precision=Fals
     change: optional per-site integer array (Device.site_change: the code of the site between two labellings, host.TRACK_CHANGE) appended as the
     last column, after current, cluster and hops; read_xyz ignores it.  None: the file as without it, byte for byte.
     role: optional per-site integer array (Device.site_role: the role of the site in the cut-site analysis, host.CUT_ROLE) appended as the last
-    column, after current, cluster, hops and change; read_xyz ignores it.  None: the file as without it, byte for byte."""
+    column, after current, cluster, hops and change; read_xyz ignores it.  None: the file as without it, byte for byte.
+    zone: optional per-site integer array (Device.site_zone: the bit mask of the site in the min-cut analysis, host.FLOW_ZONE) appended as the
+    last column, after role when both are given; read_xyz ignores it.  None: the file as without it, byte for byte."""
     hop_cols = (lambda i: "") if hops is None else (lambda i: "   %d   %d" % (int(hops[0][i]), int(hops[1][i])))
     chg_cols = hop_cols if change is None else (lambda i: hop_cols(i) + "   %d" % int(change[i]))
-    tail = chg_cols if role is None else (lambda i: chg_cols(i) + "   %d" % int(role[i]))
+    role_cols = chg_cols if role is None else (lambda i: chg_cols(i) + "   %d" % int(role[i]))
+    tail = role_cols if zone is None else (lambda i: role_cols(i) + "   %d" % int(zone[i]))
     fmt = (lambda v: repr(float(v))) if full_precision else _g6
     with open(path, "w") as f:
         f.write("%d\n\n" % len(element))

@@ -211,6 +211,12 @@ SYMBOLS = {
     "dkmc_copy_cut_necks": (_I, [_I, vp, vp, vp, vp, c_int_p]),
     "dkmc_debug_set_cut_round_cap": (None, [_I]),
     "dkmc_debug_get_cut_times": (_I, [c_dbl_p]),
+    "dkmc_find_flow": (_I, [_I, _I, vp, vp, vp, _I, _I, _I, vp, vp]),
+    "dkmc_get_flow_info": (_I, [C.POINTER(C.c_longlong), c_dbl_p]),
+    "dkmc_copy_flow_strands": (_I, [_I, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int_p]),
+    "dkmc_copy_flow_strand_sites": (_I, [_I, vp, c_int_p]),
+    "dkmc_debug_set_flow_round_cap": (None, [_I]),
+    "dkmc_debug_get_flow_times": (_I, [c_dbl_p]),
     "dkmc_update_temperatureglobal_gpu": (_I, [vp, vp, _I, _D, _D, _D, _D, _D]),
     "dkmc_update_temperature_global_analytic": (_I, [vp, vp, _I, _D, _D, _D, _D, _D, c_dbl_p]),
     "dkmc_set_heat_cg_tolerance": (None, [_D]),

@@ -720,6 +720,73 @@ int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord,
 int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, int *h_hi, int *rows_out);
 int dkmc_copy_cut_necks(int capacity, int *h_first, int *h_last, double *h_xmin, double *h_xmax, int *rows_out);
 
+/* ---- min-cut analysis: disjoint conducting paths and the narrowest cross-section (csrc/flow.hip; no counterpart in the reference) ----
+ * Where the filament is bridged: how thick it is at its thinnest, in atoms, and where -- the largest number of conducting paths that share no
+ * atom, and the two smallest sets of atoms nearest either contact whose loss opens the device.  A maximum flow with unit vertex capacities.  A
+ * pure function of its arguments: no field of GPUBuffers, no engine state a later phase reads and no other kernel changes.
+ *   members     site i is a member when 0 <= d_label[i] < N (the rule of dkmc_find_paths); nothing else of the labels is used.
+ *   link        members u and v are linked when v occurs in row u of d_index[N][nn] OR u occurs in row v.  Entries < 0 or >= N are padding,
+ *               anywhere in a row.
+ *   seeds       left: the members with index < n_left_sites; right: the members with index >= N - n_right_sites (both clamped to 0 ... N).
+ *   interior    the members that are no seed.  Only they carry capacity, one path each; the seeds of a side act as one terminal.
+ *   near-left   an interior site linked to a left seed; near-right likewise.
+ *   strand      interior sites v_1 ... v_m (m >= 1), consecutive ones linked, v_1 near-left and v_m near-right.  A family of strands is disjoint
+ *               when no site lies on two of them.
+ *   W           the largest size of a disjoint family = the smallest number of interior sites whose deletion leaves no left seed connected to a
+ *               right seed (Menger).
+ *   contacts touch  some member is both a left and a right seed, or a left seed is linked to a right seed: W is unbounded, status 2, W = -1.
+ *   left-most minimum cut C_L  the minimum separator whose left shore -- the members still connected to a left seed once the separator is
+ *               deleted, the left seeds included -- lies inside the left shore of every other minimum separator.  Unique: the interior sites
+ *               whose in-node is reachable from the source in the residual graph of ANY maximum flow while their out-node is not.  C_R, the
+ *               right-most minimum cut, and the right shore are the mirror image.  Every strand of a maximum family crosses C_L in exactly one
+ *               site and C_R in exactly one.
+ *   site_zone   d_site_zone[i] (device, N int32, always written completely), a mask of the DKMC_FLOW_ bits: 1 member, 2 on the left shore, 4 in
+ *               C_L, 8 in C_R, 16 on the right shore.  A non-member is 0; a site may carry both cut bits.  At status 0 the shores are the members
+ *               connected to each contact (its seeds included) and no cut bit is set; at status 2 and 3 only the member bit is set.
+ *   info16      (long long) [0] status: 0 not connected (W = 0), 1 W found, 2 contacts touch, 3 stopped at max_strands (W >= max_strands; cuts
+ *               and shores not computed), [1] W (-1 at status 2), [2] left-shore members, [3] right-shore members, [4] sites in both C_L and C_R,
+ *               [5] interior members, [6] near-left sites, [7] near-right sites, [8] searches run, [9] rounds (below), [10] longest strand,
+ *               [11] shortest strand (both 0 without a strand), [12] ... [15] 0.  [2], [3], [4] are 0 at status 2 and 3.
+ *   x4          min, max of d_site_x over C_L, then over C_R -- the input doubles themselves, compared through the integer key of
+ *               dkmc_find_clusters; +inf / -inf with no cut or when d_site_x is NULL.
+ * All of the above is a property of the input.  The following describe ONE maximum family, made canonical by the search rule below:
+ *   site_strand d_site_strand[i] (device, N int32, always written completely): the row of the strand through i, -1 otherwise.
+ *   strand table  one row per strand, in ascending first site: first_site, last_site, length, offset into the strand sites, left_seed = the
+ *               smallest left seed linked to first_site, right_seed = the smallest right seed linked to last_site, cut_left_site, cut_left_pos,
+ *               cut_right_site, cut_right_pos = the strand's site in C_L / C_R and its position along the strand (0 = first_site); -1 at status 3.
+ *   strand sites  the strands' sites concatenated in table order, each from its left end to its right end.
+ * The search rule (a synchronous model; tests/flow_ref.py implements it literally).  Nodes: the source S and, for every interior site v, the
+ * in-node 2 v and the out-node 2 v + 1, ordered by these numbers with S before all.  Per interior site the flow state is pred and succ, its
+ * neighbours on its strand, with the contact itself at a strand's first and last site; v is on a strand when it has them.  Residual arcs:
+ * S -> v_in for every near-left v, always (the terminal arc has no capacity limit); v_in -> v_out if v is on no strand, v_out -> v_in if it is
+ * on one; v_out -> w_in for linked interior v, w unless succ[v] = w; w_in -> v_out if succ[v] = w.  v_out is an exit if v is near-right and not
+ * a last site.  A search labels levels breadth-first: S has level 0, round k = 0, 1, ... gives level k + 1 to every unlabelled node with an arc
+ * from a node of level k.  It stops after the first round that labels an exit -- the end node is the smallest exit of that level -- or that
+ * labels nothing.  The augmenting path is walked back from the end node, at every node to the smallest predecessor one level lower; forward
+ * link arcs on it become flow, backward ones cancel it, the end site becomes a last site and the path's first site a first site.  Searches repeat
+ * until one finds no exit (W is reached) or max_strands strands exist (status 3).  The levels of that last search give C_L (in-node labelled,
+ * out-node not) and the left shore (out-node labelled, and the left seeds); one more search on the mirrored problem -- left and right seeds,
+ * pred and succ, in-node and out-node change places -- gives C_R and the right shore.
+ * Counting: a search's rounds are the rounds that labelled something plus ONE closing round -- the round that labelled nothing, or, after an
+ * exit, the round that sees the exit and does nothing: the largest level labelled + 1.  info16[9] is the total over all searches and info16[8]
+ * their number, the mirrored one included: W + 2 at status 0 and 1, max_strands at status 3, 0 at status 2 and when N == 0.  Both are
+ * functions of the input alone.
+ * dkmc_find_flow runs every round as one pass over the member rows; after a successful search one atomicMin pass fixes the smallest
+ * predecessors and one thread walks the path back.  A search that needs more than 4096 rounds fails (dkmc_last_error): both site arrays are then
+ * -1 everywhere and the getters fail until a call succeeds.  It keeps the results of the LAST call in the library and returns after they are
+ * complete; the three getters fail before any successful call.  Any getter pointer may be NULL; capacity truncates and *rows_out reports the
+ * rows copied (the true counts are W and the sum of the lengths).  N == 0, no member or an empty seed set succeed with status 0 and empty
+ * tables.  max_strands outside 1 ... 4096, N < 0, nn < 1, or d_index, d_label, d_site_zone or d_site_strand NULL with N > 0 fail with code 3
+ * before any launch; d_site_x is the only optional array.  Integer atomics only (minima, maxima, counts): the same inputs give the same bytes
+ * on every call. */
+enum { DKMC_FLOW_MEMBER = 1, DKMC_FLOW_LEFT_SHORE = 2, DKMC_FLOW_LEFT_CUT = 4, DKMC_FLOW_RIGHT_CUT = 8, DKMC_FLOW_RIGHT_SHORE = 16 };
+int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const double *d_site_x, int n_left_sites, int n_right_sites,
+                   int max_strands, int *d_site_zone, int *d_site_strand);
+int dkmc_get_flow_info(long long *info16, double *x4);
+int dkmc_copy_flow_strands(int capacity, int *h_first_site, int *h_last_site, int *h_length, int *h_offset, int *h_left_seed, int *h_right_seed,
+                           int *h_cut_left_site, int *h_cut_left_pos, int *h_cut_right_site, int *h_cut_right_pos, int *rows_out);
+int dkmc_copy_flow_strand_sites(int capacity, int *h_site, int *rows_out);
+
 /* ---- heat ------------------------------------------------------------------------------------ */
 /* update_temperatureglobal_gpu (heat_solver_gpu.cu:52-69), the reference's (uncalled) device form */
 int dkmc_update_temperatureglobal_gpu(const double *d_site_power, double *d_T_bg, int N, double a_coeff,

@@ -253,6 +253,13 @@ int dkmc_debug_get_track_times(double *ms2);
  * them included) and of everything else (positions, validation, attachment, roles, scans, tables); both 0 with profiling off. */
 void dkmc_debug_set_cut_round_cap(int cap);
 int dkmc_debug_get_cut_times(double *ms2);
+/* Test aid of the min-cut analysis (csrc/flow.hip): the cap on the rounds of ONE of its searches, 1 ... 4096; cap <= 0 restores the default 4096.
+ * A search that needs more rounds than the cap fails with a message, sets both site arrays to -1 and leaves the getters failing.
+ * Measurement aid: with dkmc_set_profiling(1), ms3 = HIP-event time of the last call's strand searches (seeding, rounds with the host's read-backs,
+ * predecessor passes and the one-thread walks), of its two closing searches (the one that finds no exit and the mirrored one; 0 at status 2 and
+ * 3) and of the tables with their copy-out; all 0 with profiling off. */
+void dkmc_debug_set_flow_round_cap(int cap);
+int dkmc_debug_get_flow_times(double *ms3);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);

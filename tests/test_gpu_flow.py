@@ -1,0 +1,370 @@
+"""The min-cut analysis on the device (dkmc_find_flow, csrc/flow.hip) against the host reference flow_ref.py: both site arrays, every column of
+the strand table, the strand sites, info and the four doubles with np.array_equal; searches and rounds against the reference's synchronous
+model."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import cluster_ref as cr
+import flow_ref as fl
+from conftest import params_7p5
+from test_cluster_ref import _random_case
+from test_cut_ref import index_of, ladder
+from test_flow_ref import PINNED_2P5, PINNED_2P5_ROUNDS, rails
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import torch
+    import __graft_entry__ as g
+    g.build()
+    from devicekmc_amd import host, lib
+    assert torch.cuda.is_available()
+    return host, lib.load()
+
+
+@pytest.fixture(autouse=True)
+def _default_cap(hip):
+    yield
+    hip[1].dkmc_debug_set_flow_round_cap(0)
+
+
+def _dev(a, dtype):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
+
+
+def run_raw(hip, index, label, x, n_left, n_right, max_strands=64):
+    """the raw entry point on host arrays -> (site_zone, site_strand: host arrays, strand table, strand sites, info)"""
+    host, _ = hip
+    index = np.asarray(index)
+    zone, strand, table, sites, info = host.find_flow(_dev(index, np.int32), index.shape[1], _dev(label, np.int32),
+                                                      None if x is None else _dev(x, np.float64), n_left, n_right, max_strands)
+    return zone.cpu().numpy(), strand.cpu().numpy(), table, sites, info
+
+
+def check_raw(hip, index, label, x, n_left, n_right, max_strands=64, trace=None):
+    ref = fl.analyse(index, label, x, n_left, n_right, max_strands, trace=trace)
+    got = run_raw(hip, index, label, x, n_left, n_right, max_strands)
+    fl.assert_equal(*got, ref)
+    return got
+
+
+def _bytes(res):
+    zone, strand, table, sites, info = res
+    return zone.tobytes() + strand.tobytes() + b"".join(table[k].tobytes() for k in fl.STRANDS) + sites.tobytes() + \
+        repr([info[k] for k in fl.INFO]).encode() + np.array([info[k] for k in fl.X4]).tobytes()
+
+
+# ---- random graphs: workgroup and wave edges, every row-lane template, the whole-wave row ---------------------------------------------------
+RANDOM = [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1), (255, 3, 0.7, 0.3), (256, 16, 0.5, 0.85),
+          (257, 17, 0.6, 0.9), (1000, 1, 0.9, 0.1), (1000, 128, 0.5, 0.985), (1000, 130, 0.6, 0.99)]
+
+
+def random_inputs(N, nn, p_member, p_pad, one_way):
+    """the inputs of one parameter set: two graphs, each with wide seed sets (two fifths of the sites: the contacts mostly touch) and narrow
+    ones (a twelfth: most are connected through the interior), the second graph without x"""
+    rng = np.random.default_rng(1000 * N + nn + one_way)
+    out = []
+    for trial in range(2):
+        index, element, _, x = _random_case(rng, N, nn, p_member, p_pad, one_way)
+        index[rng.random(N) < 0.1] = -1                                             # padding-only rows
+        index[rng.random((N, nn)) < 0.02] = N + 3                                   # padding past the end
+        # labels outside 0 ... N - 1 are non-members, whatever their value
+        label = np.where(element != 3, rng.integers(0, N, N), rng.choice([-1, N, N + 7, 2 ** 31 - 1, -2 ** 31], N)).astype(np.int32)
+        for seeds in (max(1, (2 * N) // 5), max(1, N // 12)):
+            out.append((index, label, x if trial == 0 else None, seeds, seeds))
+    return out
+
+
+@pytest.mark.parametrize("one_way", [False, True])
+@pytest.mark.parametrize("N,nn,p_member,p_pad", RANDOM)
+def test_random_graphs(hip, N, nn, p_member, p_pad, one_way):
+    for index, label, x, nl, nr in random_inputs(N, nn, p_member, p_pad, one_way):
+        got = check_raw(hip, index, label, x, nl, nr)
+        W = got[4]["width"]
+        if W > 0:                                                                   # the stop, at 1 and at W
+            for cap in {1, W}:
+                assert check_raw(hip, index, label, x, nl, nr, max_strands=cap)[4]["status"] == 3
+
+
+def test_random_graphs_cover_the_statuses():
+    """(no GPU work) the list above reaches status 0, 1 and 2 and W >= 3 (searches that cancel flow: test_shuffled_rails_cancel_flow)"""
+    seen, widest = set(), 0
+    for case in RANDOM:
+        for one_way in (False, True):
+            for index, label, x, nl, nr in random_inputs(*case, one_way):
+                info = fl.analyse(index, label, x, nl, nr)[4]
+                seen.add(info["status"])
+                widest = max(widest, info["width"])
+    print(seen, widest)
+    assert seen == {0, 1, 2} and widest >= 3
+
+
+# ---- chains, ladders, rails -----------------------------------------------------------------------------------------------------------------
+def _chain(order):
+    """the sites of order linked in a row, both directions entered"""
+    n = len(order)
+    index = np.full((n, 2), -1, dtype=np.int32)
+    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
+    return index
+
+
+def test_ordered_chain(hip):
+    n = 300
+    x = np.arange(n) * 0.5
+    zone, strand, table, sites, info = check_raw(hip, _chain(np.arange(n)), np.zeros(n, dtype=np.int32), x, 1, 1)
+    assert [info[k] for k in fl.INFO] == [1, 1, 1, 1, 0, n - 2, 1, 1, 3, 2 * (n - 2) + 5, n - 2, n - 2]
+    assert np.array_equal(sites, np.arange(1, n - 1)) and zone[1] == fl.MEMBER | fl.LEFT_CUT and zone[n - 2] == fl.MEMBER | fl.RIGHT_CUT
+    assert [info[k] for k in fl.X4] == [0.5, 0.5, x[n - 2], x[n - 2]]
+
+
+def test_randomly_numbered_chain(hip):
+    """a search deeper than any LDS-resident table, over sites in random order: two levels per site"""
+    n = 2000
+    order = np.r_[0, 1 + np.random.default_rng(11).permutation(n - 2), n - 1]
+    got = check_raw(hip, _chain(order), np.zeros(n, dtype=np.int32), np.linspace(0.0, 1.0, n), 1, 1)
+    assert got[4]["width"] == 1 and got[4]["rounds"] == 2 * (n - 2) + 5 and np.array_equal(got[3], order[1:-1])
+
+
+def test_ladder(hip):
+    length = 500
+    n = 2 * length
+    got = check_raw(hip, index_of(ladder(length), n), np.zeros(n, dtype=np.int32), np.arange(n) * 0.25, 2, 2)
+    assert got[4]["width"] == 2 and got[4]["status"] == 1 and got[4]["shared_cut"] == 0
+    assert np.flatnonzero(got[0] & fl.LEFT_CUT).tolist() == [2, 3] and np.flatnonzero(got[0] & fl.RIGHT_CUT).tolist() == [n - 4, n - 3]
+
+
+def test_shuffled_rails_cancel_flow(hip):
+    """six rails whose sites swap numbers at random from level to level, with a diagonal between levels: augmenting paths have to cancel flow"""
+    rng = np.random.default_rng(5)
+    k, length = 6, 200
+    n = k * length
+    links = rails(k, length, rng) + [(int(rng.integers(k * i, k * i + k)), int(rng.integers(k * i + k, k * i + 2 * k))) for i in range(length - 1)]
+    trace = {}
+    got = check_raw(hip, index_of(links, n, nn=6), np.zeros(n, dtype=np.int32), None, k, k, trace=trace)
+    assert got[4]["width"] == k and trace["backward"] >= 1                          # not vacuous: some search used a backward arc
+
+
+def test_grid(hip):
+    w, h = 7, 40
+    n = w * h
+    got = check_raw(hip, index_of(rails(w, h), n, nn=3), np.zeros(n, dtype=np.int32), np.arange(n) * 1.0, w, w)
+    assert got[4]["width"] == w and got[4]["longest_strand"] == got[4]["shortest_strand"] == h - 2
+    assert np.flatnonzero(got[0] & fl.LEFT_CUT).tolist() == list(range(w, 2 * w))
+
+
+def test_contacts_that_touch(hip):
+    n = 40
+    idx, label = _chain(np.arange(n)), np.zeros(n, dtype=np.int32)
+    # a member that is a seed of both sides
+    got = check_raw(hip, idx, label, np.arange(n) * 1.0, 21, 20)
+    assert [got[4][k] for k in fl.INFO][:5] == [2, -1, 0, 0, 0] and (got[0] == fl.MEMBER).all() and (got[1] == -1).all() and len(got[3]) == 0
+    # a left seed linked to a right seed
+    got = check_raw(hip, idx, label, None, 20, 20)
+    assert got[4]["status"] == 2 and got[4]["searches"] == 0
+    # the link taken out (the member between them, once it is no seed): W = 1 through one site
+    got = check_raw(hip, idx, label, None, 20, 19)
+    assert got[4]["status"] == 1 and got[4]["width"] == 1 and got[3].tolist() == [20]
+
+
+def test_status_zero_and_empty_inputs(hip):
+    import torch
+    host, _ = hip
+    rng = np.random.default_rng(5)
+    N = 500
+    index, element, _, x = _random_case(rng, N, 4, 0.7, 0.4, False)
+    label = np.where(element != 3, 0, -1).astype(np.int32)
+    label[200:300] = -1                                                             # a slab without members between the contacts
+    index[:200][index[:200] >= 300] = -1
+    index[300:][(index[300:] >= 0) & (index[300:] < 200)] = -1
+    got = check_raw(hip, index, label, x, 50, 50)
+    assert got[4]["status"] == 0 and got[4]["left_shore"] >= 50 * 0.5 and (got[0] & (fl.LEFT_CUT | fl.RIGHT_CUT) == 0).all()
+    # an empty seed set on one side, on both; no member at all
+    assert check_raw(hip, index, label, x, 0, 50)[4]["left_shore"] == 0
+    assert check_raw(hip, index, label, None, 0, 0)[4]["rounds"] == 2
+    got = check_raw(hip, index, np.full(N, -1, dtype=np.int32), x, 50, 50)
+    assert [got[4][k] for k in fl.INFO] == [0, 0, 0, 0, 0, 0, 0, 0, 2, 2, 0, 0] and (got[0] == 0).all() and (got[1] == -1).all()
+    # N == 0
+    e = torch.empty(0, dtype=torch.int32, device="cuda:0")
+    zone, strand, table, sites, info = host.find_flow(e, 3, e, torch.empty(0, dtype=torch.float64, device="cuda:0"), 0, 0)
+    assert [info[k] for k in fl.INFO] == [0] * 12 and zone.numel() == strand.numel() == len(table["first_site"]) == len(sites) == 0
+    assert [info[k] for k in fl.X4] == [np.inf, -np.inf, np.inf, -np.inf]
+
+
+# ---- the round cap, arguments, getters ------------------------------------------------------------------------------------------------------
+def _getters_fail(L):
+    rows = C.c_int(0)
+    for call in (lambda: L.dkmc_get_flow_info(None, None), lambda: L.dkmc_copy_flow_strands(4, *([None] * 10), C.byref(rows)),
+                 lambda: L.dkmc_copy_flow_strand_sites(4, None, C.byref(rows)), lambda: L.dkmc_debug_get_flow_times(None)):
+        assert call() == 3
+        L.dkmc_clear_error()
+
+
+def test_round_cap_fails_cleanly(hip):
+    """an error return, not a device fault: the error is set, both site arrays are -1, the getters fail; the next call with the cap restored succeeds"""
+    import torch
+    host, L = hip
+    n = 300
+    idx, lab = _chain(np.arange(n)), np.zeros(n, dtype=np.int32)
+    with pytest.raises(OverflowError):
+        fl.analyse(idx, lab, None, 1, 1, cap=40)
+    index, label = _dev(idx, np.int32), _dev(lab, np.int32)
+    zone, strand = (torch.full((n,), 7, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    L.dkmc_debug_set_flow_round_cap(40)
+    rc = L.dkmc_find_flow(n, 2, host._ptr(index), host._ptr(label), None, 1, 1, 64, host._ptr(zone), host._ptr(strand))
+    assert rc != 0 and "dkmc_find_flow" in L.dkmc_last_error().decode() and "40 rounds" in L.dkmc_last_error().decode()
+    L.dkmc_clear_error()
+    torch.cuda.synchronize()
+    assert (zone.cpu().numpy() == -1).all() and (strand.cpu().numpy() == -1).all()
+    _getters_fail(L)
+    # a cap the search just fits: 2 (n - 2) + 1 rounds
+    L.dkmc_debug_set_flow_round_cap(2 * (n - 2) + 1)
+    assert fl.analyse(idx, lab, None, 1, 1, cap=2 * (n - 2) + 1)[4]["width"] == 1
+    assert check_raw(hip, idx, lab, None, 1, 1)[4]["width"] == 1
+    L.dkmc_debug_set_flow_round_cap(0)
+    got = check_raw(hip, idx, lab, None, 1, 1)
+    assert got[4]["status"] == 1 and L.dkmc_get_flow_info(None, None) == 0
+
+
+def test_bad_arguments(hip):
+    import torch
+    host, L = hip
+    n = 100
+    index, label = _dev(_chain(np.arange(n)), np.int32), _dev(np.zeros(n), np.int32)
+    zone, strand = (torch.full((n,), 7, dtype=torch.int32, device="cuda:0") for _ in range(2))
+    pi, pl, pz, ps = (host._ptr(t) for t in (index, label, zone, strand))
+    assert L.dkmc_find_flow(n, 2, pi, pl, None, 1, 1, 64, pz, ps) == 0
+    for args in ((-1, 2, pi, pl, None, 1, 1, 64, pz, ps), (n, 0, pi, pl, None, 1, 1, 64, pz, ps), (n, 2, pi, pl, None, 1, 1, 0, pz, ps),
+                 (n, 2, pi, pl, None, 1, 1, 4097, pz, ps), (n, 2, None, pl, None, 1, 1, 64, pz, ps), (n, 2, pi, None, None, 1, 1, 64, pz, ps),
+                 (n, 2, pi, pl, None, 1, 1, 64, None, ps), (n, 2, pi, pl, None, 1, 1, 64, pz, None)):
+        zone.fill_(7); strand.fill_(7)
+        assert L.dkmc_find_flow(*args) == 3
+        assert "dkmc_find_flow" in L.dkmc_last_error().decode()
+        L.dkmc_clear_error()
+        _getters_fail(L)                                                            # no results of a failed call
+        torch.cuda.synchronize()
+        assert (zone.cpu().numpy() == 7).all() and (strand.cpu().numpy() == 7).all()        # nothing was launched
+    assert L.dkmc_find_flow(n, 2, pi, pl, None, -5, 10 ** 6, 4096, pz, ps) == 0 and L.dkmc_get_flow_info(None, None) == 0      # seeds are clamped
+
+
+def test_getters_null_columns_and_capacity(hip):
+    _, L = hip
+    w, h = 3, 6
+    n = w * h
+    zone, strand, table, sites, info = check_raw(hip, index_of(rails(w, h), n, nn=3), np.zeros(n, dtype=np.int32), np.arange(n) * 1.0, w, w)
+    assert len(table["first_site"]) == w and len(sites) == w * (h - 2)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    a, b, rows = np.full(8, -9, dtype=np.int32), np.full(8, -9, dtype=np.int32), C.c_int(-1)
+    assert L.dkmc_copy_flow_strands(2, vp(a), *([None] * 8), vp(b), C.byref(rows)) == 0 and rows.value == 2
+    assert np.array_equal(a[:2], table["first_site"][:2]) and np.array_equal(b[:2], table["cut_right_pos"][:2]) and (a[2:] == -9).all() and (b[2:] == -9).all()
+    assert L.dkmc_copy_flow_strands(10 ** 6, *([None] * 10), C.byref(rows)) == 0 and rows.value == w
+    assert L.dkmc_copy_flow_strands(-3, vp(a), *([None] * 9), C.byref(rows)) == 0 and rows.value == 0
+    assert L.dkmc_copy_flow_strands(10 ** 6, *([None] * 10), None) == 0
+    s = np.full(w * h, -9, dtype=np.int32)
+    assert L.dkmc_copy_flow_strand_sites(5, vp(s), C.byref(rows)) == 0 and rows.value == 5 and np.array_equal(s[:5], sites[:5]) and (s[5:] == -9).all()
+    assert L.dkmc_copy_flow_strand_sites(10 ** 6, None, C.byref(rows)) == 0 and rows.value == len(sites)
+    i16, x4 = (C.c_longlong * 16)(), (C.c_double * 4)()
+    assert L.dkmc_get_flow_info(i16, x4) == 0 and list(i16) == [info[k] for k in fl.INFO] + [0, 0, 0, 0] and list(x4) == [info[k] for k in fl.X4]
+    assert L.dkmc_get_flow_info(None, x4) == 0 and L.dkmc_get_flow_info(i16, None) == 0
+
+
+def local_graph(rng, N, nn, reach, p_member):
+    """every site linked to nn sites at most `reach` numbers away: a slab the contacts cannot touch across"""
+    index = np.clip(np.arange(N)[:, None] + rng.integers(-reach, reach + 1, (N, nn)), 0, N - 1).astype(np.int32)
+    return index, np.where(rng.random(N) < p_member, 0, -1).astype(np.int32), rng.normal(size=N)
+
+
+def test_two_calls_same_bytes(hip):
+    index, label, x = local_graph(np.random.default_rng(21), 3000, 3, 30, 0.8)
+    a = check_raw(hip, index, label, x, 60, 60)
+    b = run_raw(hip, index, label, x, 60, 60)
+    assert a[4]["status"] == 1 and a[4]["width"] >= 4 and _bytes(a) == _bytes(b)
+
+
+# ---- the golden devices ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def dev_2p5(hip, cell_2p5):
+    from devicekmc_amd import params as pm
+    host, _ = hip
+    p = pm.KMCParameters()
+    dev = host.Device(cell_2p5, p)
+    return dev, dev.make_gpubuf("cuda:0"), p, dev.site_element.copy()
+
+
+class _Planted:
+    """a planted filament in the device's site_element, taken out again on exit"""
+    def __init__(self, dev, gb, el0, r):
+        self.dev, self.gb, self.el0 = dev, gb, el0
+        self.el2, _ = cr.plant_filament(el0, dev.site_x, dev.site_y, dev.site_z, r)
+
+    def _set(self, el):
+        import torch
+        self.dev.site_element = el.copy()
+        self.gb.t["site_element"].copy_(torch.as_tensor(el))
+
+    def __enter__(self):
+        self._set(self.el2)
+
+    def __exit__(self, *exc):
+        self._set(self.el0)
+
+
+def _contacts(dev, p):
+    return dev.get_num_in_contacts(p.num_atoms_first_layer, "left"), dev.get_num_in_contacts(p.num_atoms_first_layer, "right")
+
+
+def test_pristine_2p5(hip, dev_2p5):
+    dev, gb, p, el0 = dev_2p5
+    nl, nr = _contacts(dev, p)
+    label, _, _ = dev.find_clusters(gb)
+    res = dev.find_flow(gb)
+    fl.assert_equal(*res, fl.analyse(dev.neigh_idx, label, dev.site_x, nl, nr))
+    assert res[4]["status"] == 0 and res[4]["width"] == 0
+
+
+@pytest.mark.parametrize("r", sorted(PINNED_2P5))
+def test_planted_filaments_2p5(hip, dev_2p5, r):
+    """Device.find_clusters -> find_paths -> find_cuts -> find_flow against the reference, the pinned figures and, at W = 1, find_cuts"""
+    dev, gb, p, el0 = dev_2p5
+    with _Planted(dev, gb, el0, r):
+        nl, nr = _contacts(dev, p)
+        label, _, _ = dev.find_clusters(gb)
+        _, _, path, _, pinfo = dev.find_paths(gb)
+        table = dev.find_cuts(gb)[2]
+        res = dev.find_flow(gb)
+        zone, strand, strands, sites, info = res
+        print(r, info)
+        fl.assert_equal(*res, fl.analyse(dev.neigh_idx, label, dev.site_x, nl, nr))
+        assert dev.site_zone is zone and dev.site_strand is strand and dev.flow_strands is strands and dev.flow_strand_sites is sites
+        assert dev.flow_info is info and pinfo["status"] == 1
+        cl, cr_ = np.flatnonzero(zone & fl.LEFT_CUT).tolist(), np.flatnonzero(zone & fl.RIGHT_CUT).tolist()
+        assert (info["width"], cl, cr_) == PINNED_2P5[r] and (info["searches"], info["rounds"]) == PINNED_2P5_ROUNDS[r]
+        if info["width"] == 1:
+            cuts = [v for v in table["site"][table["cut"] == 1] if nl <= v < dev.N - nr]
+            assert cl == [cuts[0]] and cr_ == [cuts[-1]]
+        assert dev.find_flow(gb, max_strands=1)[4]["status"] == 3
+
+
+def test_device_find_flow_runs_find_clusters_itself(hip, dev_2p5, cell_2p5):
+    host, _ = hip
+    _, gb, p, _ = dev_2p5
+    dev = host.Device(cell_2p5, p)
+    assert dev.find_flow(gb)[4]["status"] == 0 and dev.cluster_info["bridged"] == 0
+
+
+def test_planted_filament_7p5(hip, dev_7p5):
+    host, _ = hip
+    p = params_7p5()
+    dev = host.Device(dev_7p5, p, gpu_neighbors="cuda:0")
+    gb = dev.make_gpubuf("cuda:0")
+    with _Planted(dev, gb, dev.site_element.copy(), 3.0):
+        nl, nr = _contacts(dev, p)
+        label, _, _ = dev.find_clusters(gb)
+        res = dev.find_flow(gb)
+        print(res[4])
+        assert res[4]["status"] == 1
+        fl.assert_equal(*res, fl.analyse(dev.neigh_idx, label, dev.site_x, nl, nr))

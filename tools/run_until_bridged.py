@@ -15,8 +15,11 @@ whose arrival closed the filament and their x range.
 With --cuts (needs --paths) every check that runs Device.find_paths with status 1 also runs Device.find_cuts on its path and the line carries, per
 such check, the number of cut sites -- the sites whose loss alone opens the filament --, the necks as [first, last] positions and the longest
 neck with its x range.
+With --flow MAX every check from the one whose verdict is bridged on -- that one, and the check after the closing superstep -- also runs
+Device.find_flow with max_strands = MAX and the line carries, per such check, the status, W -- the number of atoms the filament is thick at its
+thinnest --, the x range of the minimum cut nearest either contact and the searches and rounds it took.
 usage: python tools/run_until_bridged.py [2.5nm] [--max-steps 50] [--vd 5.0] [--members 3] [--wide-radius 0] [--gaps 0] [--paths -1] [--track]
-       [--cuts]"""
+       [--cuts] [--flow 0]"""
 import argparse
 import json
 import math
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--paths", type=int, default=-1, metavar="SLACK", help=">= 0: once bridged, log H and the constriction of Device.find_paths(slack=SLACK) at every check")
     ap.add_argument("--track", action="store_true", help="from the second check on, log the transition and the joined / left / regrouped sites of Device.track_clusters")
     ap.add_argument("--cuts", action="store_true", help="with --paths: log the cut sites, the necks and the longest neck of Device.find_cuts at every check with a path")
+    ap.add_argument("--flow", type=int, default=0, metavar="MAX", help="> 0: once bridged, log W and the x range of both minimum cuts of Device.find_flow(max_strands=MAX)")
     a = ap.parse_args()
     if a.cuts and a.paths < 0:
         ap.error("--cuts needs --paths")
@@ -70,6 +74,14 @@ def main():
         if a.cuts and pinfo["status"]:
             cut_check(step)
 
+    flow = []
+
+    def flow_check(step):
+        _, _, _, _, f = dev.find_flow(gb, max_strands=a.flow, link_index=link)
+        flow.append(dict(step=step, status=f["status"], width=f["width"], searches=f["searches"], rounds=f["rounds"],
+                         cut_left_x=[f["cut_left_xmin"], f["cut_left_xmax"]] if f["status"] == 1 else None,
+                         cut_right_x=[f["cut_right_xmin"], f["cut_right_xmax"]] if f["status"] == 1 else None))
+
     track = []
 
     def track_check(step):
@@ -93,13 +105,17 @@ def main():
             bridged_at = k + 1
             if a.paths >= 0:
                 path_check(k + 1)
+            if a.flow > 0:
+                flow_check(k + 1)
             break
     p.solve_current = True
     sim.step(False)
-    if a.paths >= 0 and bridged_at is not None:                # the check after the closing superstep
+    if (a.paths >= 0 or a.flow > 0) and bridged_at is not None:            # the check after the closing superstep
         _, _, after = dev.find_clusters(gb, members=a.members, link_index=link, capacity=0)
-        if after["bridged"]:
+        if after["bridged"] and a.paths >= 0:
             path_check(bridged_at + 1)
+        if after["bridged"] and a.flow > 0:
+            flow_check(bridged_at + 1)
     more = dict(gaps_r_max=a.gaps, bottleneck=bottleneck, direct=direct) if a.gaps > 0 else {}
     if a.paths >= 0:
         more.update(paths_slack=a.paths, paths=paths)
@@ -107,6 +123,8 @@ def main():
         more.update(cuts=cuts)
     if a.track:
         more.update(track=track)
+    if a.flow > 0:
+        more.update(flow_max_strands=a.flow, flow=flow)
     print(json.dumps(dict(workload=a.workload, sites=int(dev.N), Vd=a.vd, members=a.members, wide_radius=a.wide_radius, steps_current_off=len(gaps),
                           bridged_at_step=bridged_at, bridge_root=None if info is None else info["bridge_root"], gap_x=gaps,
                           n_components_last=None if info is None else info["n_components"], I_macro=dev.imacro, **more)), flush=True)
