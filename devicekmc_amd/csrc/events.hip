@@ -370,62 +370,53 @@ extern "C" int dkmc_debug_get_event_times(double *ms2)
     return 0;
 }
 
-extern "C" int dkmc_execute_kmc_step_gpu(int N, int nn, const int *neigh, const int *layer, const double *lattice, int pbc,
-                                         const double *T_bg, const double *freq, const double *sigma, const double *k,
-                                         const double *x, const double *y, const double *z, const double *pb, const double *pc,
-                                         const double *temperature, int *element, int *charge,
-                                         const double *h_uniform, int n_uniform, int resume,
-                                         int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out)
+// ---- host side of the event loop, shared by the production step and the test aid (dkmc_debug_event_loop) ----
+struct EvBufs { double *ev_prob, *rowsum, *g2, *g3, *uni; int *evlog; EvOut *out; int ng2, ng3, max_log; };
+// the engine's table, tree, draw, log and mailbox scratch for an N x nn table; the draws are uploaded
+static int ev_bufs(int N, int nn, const double *h_uniform, int n_uniform, EvBufs *b)
 {
-    // mode 0: the temperature is unused, as by the reference kernel (Ekin = 0, kmc_events.cu:65), and may be null
+    Engine &e = eng();
+    b->ng2 = (N + 63) / 64; b->ng3 = (b->ng2 + 63) / 64; b->max_log = n_uniform / 2;
+    b->ev_prob = (double *)scratch(S_EV_PROB, (size_t)N * nn * 8);
+    b->rowsum = (double *)scratch(S_EV_ROWSUM, (size_t)N * 8);
+    b->g2 = (double *)scratch(S_EV_G2, (size_t)b->ng2 * 8); b->g3 = (double *)scratch(S_EV_G3, (size_t)b->ng3 * 8);
+    b->uni = (double *)scratch(S_EV_UNI, (size_t)(n_uniform > 0 ? n_uniform : 1) * 8);
+    b->evlog = (int *)scratch(S_EV_LOG, (size_t)(b->max_log > 0 ? b->max_log : 1) * 16);
+    b->out = (EvOut *)scratch(S_EV_CTRL, sizeof(EvOut));
+    if (!b->ev_prob || !b->rowsum || !b->g2 || !b->g3 || !b->uni || !b->evlog || !b->out) return e.err_code;
+    if (n_uniform > 0) HIPCHK(hipMemcpyAsync(b->uni, h_uniform, (size_t)n_uniform * 8, hipMemcpyHostToDevice, e.stream));
+    return 0;
+}
+// the two upper levels of the sum tree from the row sums
+static void ev_levels(int N, const EvBufs &b)
+{
+    hipStream_t st = eng().stream;
+    hipLaunchKernelGGL(k_ev_level, dim3((b.ng2 + 3) / 4), dim3(256), 0, st, N, b.rowsum, b.ng2, b.g2);
+    hipLaunchKernelGGL(k_ev_level, dim3((b.ng3 + 3) / 4), dim3(256), 0, st, b.ng2, b.g2, b.ng3, b.g3);
+}
+// k_ev_loop on the table and tree in b, then the mailbox, the log, the statistics and the return code.  census_info (may be null): device
+// buffer of a census enqueued before, delivered with the mailbox; timed: the HIP events of the build and the census were recorded.
+static int ev_loop_run(int N, int nn, const int *neigh, const EvBufs &b, int *element, int *charge, const double *freq, int n_uniform,
+                       const int *n_bad, const double *census_info, bool timed,
+                       int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out)
+{
     Engine &e = eng(); hipStream_t st = e.stream;
-    const int mode = e.event_temperature;
-    if (mode != 0 && !temperature)
-        return dkmc_fail(13, "execute_kmc_step: dkmc_set_event_temperature is 1 or 2 and site_temperature is null (bad arguments)", __FILE__, __LINE__);
-    const size_t total = (size_t)N * nn;
-    const int ng2 = (N + 63) / 64, ng3 = (ng2 + 63) / 64;
-    const int max_log = n_uniform / 2;
-    double *ev_prob = (double *)scratch(S_EV_PROB, total * 8);
-    double *rowsum = (double *)scratch(S_EV_ROWSUM, (size_t)N * 8);
-    double *g2 = (double *)scratch(S_EV_G2, (size_t)ng2 * 8), *g3 = (double *)scratch(S_EV_G3, (size_t)ng3 * 8);
-    double *uni = (double *)scratch(S_EV_UNI, (size_t)(n_uniform > 0 ? n_uniform : 1) * 8);
-    int *evlog = (int *)scratch(S_EV_LOG, (size_t)(max_log > 0 ? max_log : 1) * 16);
-    EvOut *out = (EvOut *)scratch(S_EV_CTRL, sizeof(EvOut));
-    if (!ev_prob || !rowsum || !g2 || !g3 || !uni || !evlog || !out) return e.err_code;
-    const bool build = !resume, census = build && e.event_census != 0, timed = build && e.profiling != 0;
-    int *n_bad = nullptr; double *census_info = nullptr;
-    if (build && mode != 0) { n_bad = (int *)scratch(S_EV_NBAD, sizeof(int)); if (!n_bad) return e.err_code; }
-    if (timed && !g_ev_t_ready) { for (auto &t : g_ev_t) HIPCHK(hipEventCreate(&t)); g_ev_t_ready = true; }
-    if (n_uniform > 0) HIPCHK(hipMemcpyAsync(uni, h_uniform, (size_t)n_uniform * 8, hipMemcpyHostToDevice, st));
-    if (build) {
-        if (n_bad) HIPCHK(hipMemsetAsync(n_bad, 0, sizeof(int), st));
-        if (timed) HIPCHK(hipEventRecord(g_ev_t[0], st));
-        ev_build_launch(mode, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge, (int *)nullptr, ev_prob, rowsum,
-                        temperature, n_bad);
-        if (timed) HIPCHK(hipEventRecord(g_ev_t[1], st));
-        hipLaunchKernelGGL(k_ev_level, dim3((ng2 + 3) / 4), dim3(256), 0, st, N, rowsum, ng2, g2);
-        hipLaunchKernelGGL(k_ev_level, dim3((ng3 + 3) / 4), dim3(256), 0, st, ng2, g2, ng3, g3);
-        if (census) {       // on the step's own table, before the loop zeroes any of it
-            if (timed) HIPCHK(hipEventRecord(g_ev_t[2], st));
-            if (ev_census_enqueue(N, nn, neigh, element, temperature, ev_prob, &census_info)) return e.err_code;
-            if (timed) HIPCHK(hipEventRecord(g_ev_t[3], st));
-        }
-    }
-    hipLaunchKernelGGL(k_ev_loop, dim3(1), dim3(EVL_NT), 0, st, N, nn, neigh, ev_prob, rowsum, g2, g3, ng2, ng3, element, charge,
-                       uni, n_uniform, freq, out, h_event_log ? evlog : (int *)nullptr, max_log, (const int *)e.buf[S_PW_CNT], (const int *)n_bad);
+    const bool census = census_info != nullptr;
+    hipLaunchKernelGGL(k_ev_loop, dim3(1), dim3(EVL_NT), 0, st, N, nn, neigh, b.ev_prob, b.rowsum, b.g2, b.g3, b.ng2, b.ng3, element, charge,
+                       b.uni, n_uniform, freq, b.out, h_event_log ? b.evlog : (int *)nullptr, b.max_log, (const int *)e.buf[S_PW_CNT], n_bad);
     KCHK();
     EvOut h;
-    HIPCHK(hipMemcpyAsync(&h, out, sizeof(EvOut), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&h, b.out, sizeof(EvOut), hipMemcpyDeviceToHost, st));
     if (census) HIPCHK(hipMemcpyAsync(e.event_census_info, census_info, sizeof(e.event_census_info), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (census) e.event_census_valid = 1;
     if (timed) {
-        float a = 0.0f, b = 0.0f;
+        float a = 0.0f, c = 0.0f;
         HIPCHK(hipEventElapsedTime(&a, g_ev_t[0], g_ev_t[1]));
-        if (census) HIPCHK(hipEventElapsedTime(&b, g_ev_t[2], g_ev_t[3]));
-        g_ev_ms[0] = a; g_ev_ms[1] = b;
+        if (census) HIPCHK(hipEventElapsedTime(&c, g_ev_t[2], g_ev_t[3]));
+        g_ev_ms[0] = a; g_ev_ms[1] = c;
     }
-    if (h_event_log && h.n_events > 0) HIPCHK(hipMemcpy(h_event_log, evlog, (size_t)h.n_events * 16, hipMemcpyDeviceToHost));
+    if (h_event_log && h.n_events > 0) HIPCHK(hipMemcpy(h_event_log, b.evlog, (size_t)h.n_events * 16, hipMemcpyDeviceToHost));
     e.stats.n_events = h.n_events; e.stats.psum_last = h.psum_last;
     if (h.n_charged >= 0) e.stats.n_charged = h.n_charged;
     if (n_events_out) *n_events_out = h.n_events;
@@ -438,4 +429,69 @@ extern "C" int dkmc_execute_kmc_step_gpu(int N, int nn, const int *neigh, const 
     }
     if (h.bad) return dkmc_fail(7, "execute_kmc_step: no event with a positive rate", __FILE__, __LINE__);
     return 0;
+}
+
+extern "C" int dkmc_execute_kmc_step_gpu(int N, int nn, const int *neigh, const int *layer, const double *lattice, int pbc,
+                                         const double *T_bg, const double *freq, const double *sigma, const double *k,
+                                         const double *x, const double *y, const double *z, const double *pb, const double *pc,
+                                         const double *temperature, int *element, int *charge,
+                                         const double *h_uniform, int n_uniform, int resume,
+                                         int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out)
+{
+    // mode 0: the temperature is unused, as by the reference kernel (Ekin = 0, kmc_events.cu:65), and may be null
+    Engine &e = eng(); hipStream_t st = e.stream;
+    const int mode = e.event_temperature;
+    if (mode != 0 && !temperature)
+        return dkmc_fail(13, "execute_kmc_step: dkmc_set_event_temperature is 1 or 2 and site_temperature is null (bad arguments)", __FILE__, __LINE__);
+    const bool build = !resume, census = build && e.event_census != 0, timed = build && e.profiling != 0;
+    int *n_bad = nullptr; double *census_info = nullptr;
+    if (build && mode != 0) { n_bad = (int *)scratch(S_EV_NBAD, sizeof(int)); if (!n_bad) return e.err_code; }
+    if (timed && !g_ev_t_ready) { for (auto &t : g_ev_t) HIPCHK(hipEventCreate(&t)); g_ev_t_ready = true; }
+    EvBufs b;
+    if (ev_bufs(N, nn, h_uniform, n_uniform, &b)) return e.err_code;
+    if (build) {
+        if (n_bad) HIPCHK(hipMemsetAsync(n_bad, 0, sizeof(int), st));
+        if (timed) HIPCHK(hipEventRecord(g_ev_t[0], st));
+        ev_build_launch(mode, N, nn, neigh, layer, lattice, pbc, T_bg, freq, sigma, k, x, y, z, pb, pc, element, charge, (int *)nullptr, b.ev_prob,
+                        b.rowsum, temperature, n_bad);
+        if (timed) HIPCHK(hipEventRecord(g_ev_t[1], st));
+        ev_levels(N, b);
+        if (census) {       // on the step's own table, before the loop zeroes any of it
+            if (timed) HIPCHK(hipEventRecord(g_ev_t[2], st));
+            if (ev_census_enqueue(N, nn, neigh, element, temperature, b.ev_prob, &census_info)) return e.err_code;
+            if (timed) HIPCHK(hipEventRecord(g_ev_t[3], st));
+        }
+    }
+    return ev_loop_run(N, nn, neigh, b, element, charge, freq, n_uniform, n_bad, census_info, timed,
+                       n_events_out, exhausted_out, h_event_log, event_time_out);
+}
+
+// one wave per site row of a table that is already in place: its row sum, by the row_sum() of the loop's repair
+__global__ __launch_bounds__(256) void k_ev_rowsum(int N, int nn, const double *__restrict__ ev_prob, double *__restrict__ rowsum)
+{
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const double s = row_sum(ev_prob + (size_t)i * nn, nn, lane);
+    if (lane == 0) rowsum[i] = s;
+}
+
+// test aid (include/devicekmc_hip_debug.h): the production loop on a caller's table
+extern "C" int dkmc_debug_event_loop(int N, int nn, const int *neigh, const double *ev_prob_in, int *element, int *charge, const double *freq,
+                                     const double *h_uniform, int n_uniform, int resume,
+                                     int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (N <= 0 || nn <= 0 || (long long)N * nn > 2147483647LL || !neigh || !element || !charge || !freq || n_uniform < 0 ||
+        (n_uniform > 0 && !h_uniform) || (!resume && !ev_prob_in))
+        return dkmc_fail(13, "debug_event_loop: bad arguments", __FILE__, __LINE__);
+    EvBufs b;
+    if (ev_bufs(N, nn, h_uniform, n_uniform, &b)) return e.err_code;
+    if (!resume) {
+        HIPCHK(hipMemcpyAsync(b.ev_prob, ev_prob_in, (size_t)N * nn * 8, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_ev_rowsum, dim3((N + 3) / 4), dim3(256), 0, st, N, nn, b.ev_prob, b.rowsum);
+        ev_levels(N, b);
+    }
+    return ev_loop_run(N, nn, neigh, b, element, charge, freq, n_uniform, (const int *)nullptr, (const double *)nullptr, false,
+                       n_events_out, exhausted_out, h_event_log, event_time_out);
 }

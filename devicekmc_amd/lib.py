@@ -173,6 +173,7 @@ SYMBOLS = {
     "dkmc_get_event_census_on": (_I, []),
     "dkmc_get_event_census": (_I, [c_dbl_p]),
     "dkmc_debug_get_event_times": (_I, [c_dbl_p]),
+    "dkmc_debug_event_loop": (_I, [_I, _I, vp, vp, vp, vp, vp, vp, _I, _I, c_int_p, c_int_p, vp, c_dbl_p]),
     "dkmc_update_power_gpu_sparse": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _I, _D, _D, _D, _D, _D, _D, _D, _D, _I,
                                           c_dbl_p, _I, _I, _D]),
     "dkmc_get_last_X": (_I, [c_int_p, C.POINTER(C.c_longlong), vp, vp, vp]),

@@ -263,6 +263,27 @@ int dkmc_debug_get_flow_times(double *ms3);
 /* Measurement aid of the event phase (csrc/events.hip): with dkmc_set_profiling(1), ms2 = HIP-event time of k_ev_build and of the rate census
  * (dkmc_set_event_census; 0 when none ran) of the last dkmc_execute_kmc_step_gpu that built a table; both 0 before the first such call. */
 int dkmc_debug_get_event_times(double *ms2);
+/* Test aid of the event loop (csrc/events.hip): the PRODUCTION loop k_ev_loop on a table the caller supplies, so that a test can feed rates whose
+ * sums are exact (through dkmc_execute_kmc_step_gpu every rate comes out of exp()).
+ * resume == 0: d_ev_prob_in [N * nn] (device) is copied into the engine's own table; the row sums are formed by the row_sum() the loop's repair uses,
+ *   the two upper levels of the sum tree by the kernel of the production build; then the loop runs.  The caller's table is only read.
+ * resume == 1: the loop alone, on the table and tree the last call (of this aid, with the same N and nn) left behind; d_ev_prob_in is not read.
+ * Everything after the table build is the code of dkmc_execute_kmc_step_gpu, and so are the meanings of d_site_element, d_site_charge (device, updated
+ * in place), d_freq (device), h_uniform / n_uniform (host; two draws per event, the loop stops with *exhausted_out = 1 before a selection for which
+ * 2 * events + 1 >= n_uniform), h_event_log (host, may be null: 4 ints per event -- slot, i, j, type -- room for n_uniform / 2 events),
+ * *event_time_out (the waiting time of the last event) and the return code: error 7 when no positive rate is left (the events before it are
+ * delivered, *event_time_out is infinite).
+ * CONTRACT -- the loop trusts its index, as it may in production, where the index comes from the neighbour search; nothing here validates it:
+ *   - every entry of d_neigh_idx [N * nn] lies in [-1, N): the loop dereferences every non-negative entry of the rows of i and j.  The table BUILD
+ *     tolerates entries >= N (their rate is 0); the LOOP does not -- it would read and write out of bounds;
+ *   - the index is symmetric: j is in row i if and only if i is in row j.  The loop zeroes the slots that target i or j only inside the rows of
+ *     the neighbours of i and j;
+ *   - the table holds finite values >= 0;
+ *   - N * nn < 2^31 (the log holds the slot as an int);
+ *   - a call to the aid overwrites the engine's table and tree: it discards a pending resume of dkmc_execute_kmc_step_gpu. */
+int dkmc_debug_event_loop(int N, int nn, const int *d_neigh_idx, const double *d_ev_prob_in, int *d_site_element, int *d_site_charge, const double *d_freq,
+                          const double *h_uniform, int n_uniform, int resume,
+                          int *n_events_out, int *exhausted_out, int *h_event_log, double *event_time_out);
 
 #ifdef __cplusplus
 }
