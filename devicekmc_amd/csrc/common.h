@@ -216,6 +216,8 @@ struct Engine {
     int x_static_nM = -1;          // this solve's S is in metals-first order with that many metals in front; -1 = atom order (set by current.hip step 2, read by xt.hip)
     int x_static_verify = 0;       // test aid (dkmc_debug_x_static_verify): every assembly in metals-first order is followed by a full census and a full fill into separate buffers, compared word by word
     int x_tile_f32_fail_once = 0;  // test aid (dkmc_debug_fail_true_residual_once): the next true-residual check of the preconditioned loop reports "above tolerance" once, on the host side
+    int x_fold_form = 1;           // fold of the tile launch's row partial sums in the one-GPU preconditioned loop: 1 (default) = only the cells of the launch view's tiles, by the window lists (xtb_wlist_sum2; no zeroed cells, the one-column products at one vector group), 0 = every cell of wrange[k] with the per-solve memset and k_xtl_zero_dead; same bits (dkmc_set_x_fold_form; xtb.hip)
+    int x_fold_poison = 0;         // test aid (dkmc_debug_poison_fold_cells, sticky): a solve in fold form 1 fills the row partial sums with NaN where form 0 zeroes them
     int x_nmul_form = 1;           // N products of the split polynomial preconditioner: 1 = on the per-solve packed copy of N (k_xtb_nmulp16 / k_xtb_nmulp, x_nmul_lane_bytes), 0 = on the CSR of Xs (k_xtb_nmul); same results (dkmc_set_x_nmul_form)
     int x_nmul_lane_bytes = 16;    // gathers of the packed N products: 16 = two slots of a row per instruction, 16 bytes per lane (k_xtb_nmulp16), 8 = one slot, 8 bytes per lane (k_xtb_nmulp); same results (dkmc_set_x_nmul_lane_bytes)
     int x_nmul_window = 2;         // panel operands of the packed 16-byte N products from LDS row windows (k_xtb_nmulw, nwin_plan.h): 0 = off, 1 = on, 2 = by size (xb_nwin_rows); same results (dkmc_set_x_nmul_window)
@@ -236,7 +238,7 @@ struct Engine {
     double E_gen[DKMC_MAX_LAYERS] = {0}, E_rec[DKMC_MAX_LAYERS] = {0}, E_Vdiff[DKMC_MAX_LAYERS] = {0}, E_Odiff[DKMC_MAX_LAYERS] = {0};
     int num_layers = 0;
     // named persistent device buffers (grown on demand, never shrunk)
-    static const int NBUF = 184;
+    static const int NBUF = 192;
     void *buf[NBUF] = {nullptr};
     size_t bufsz[NBUF] = {0};
 };
@@ -283,6 +285,7 @@ enum {
     S_XTB_EMU_Y, S_XTB_EMU_CTRL, S_XTB_YPANEL, S_XTB_PRE_V, S_XTB_PRE_W1, S_XTB_PRE_W2, S_XTB_PRE_Z, S_XTB_PRE_U,
     S_XTB_NPACK_CNT, S_XTB_NPACK_OFF, S_XTB_NPACK_COL, S_XTB_NPACK_W,
     S_XTL_CELLS, S_XTL_TFLAG, S_XTL_TVAL32, S_XTL_TILES, S_XTL_WRANGE, S_XTL_NITEMW, S_XTL_ITEMS, S_XTL_SPLIT,      // live view of the tile list (xt_live.h)
+    S_XT_WLIST, S_XTL_WLIST,       // windows holding a tile, by row block: the full view's and the live view's (k_xt_wrange; the list fold of xtb.hip)
     S_KS_TAB, S_KS_OWNER, S_KS_LISTS, S_KS_FLAG, S_KS_BOX, S_KS_RLISTS, S_KS_XA, S_KS_XB, S_KS_SEND, S_KS_RECV, S_KS_YBUF, S_KS_EMU,
     // test aids of the preconditioner (xtb_precond.h: dkmc_xtb_test_nstep, dkmc_xtb_check_poly): their own buffers, nothing a solve reads
     S_XTB_TEST_RP, S_XTB_TEST_CI, S_XTB_TEST_VAL, S_XTB_TEST_SC, S_XTB_TEST_NSR, S_XTB_TEST_LIST, S_XTB_TEST_IN, S_XTB_TEST_ADD, S_XTB_TEST_OUT,

@@ -93,6 +93,9 @@ int dkmc_get_x_tile_drop_auto(void) { return eng().x_tile_drop_auto; }
 void dkmc_set_x_tile_drop_auto_subblocks(long long gate) { eng().x_tile_drop_gate = gate > 0 ? gate : 0; }
 double dkmc_get_x_tile_drop_used(void) { return eng().x_tile_drop_used; }
 void dkmc_debug_fail_true_residual_once(void) { eng().x_tile_f32_fail_once = 1; }
+void dkmc_set_x_fold_form(int form) { eng().x_fold_form = form == 0 ? 0 : 1; }
+int dkmc_get_x_fold_form(void) { return eng().x_fold_form; }
+void dkmc_debug_poison_fold_cells(int on) { eng().x_fold_poison = on ? 1 : 0; }
 void dkmc_set_x_static_tiles(int mode) { eng().x_static_tiles = (mode == 0 || mode == 1) ? mode : 2; }
 int dkmc_get_x_static_tiles(void) { return eng().x_static_tiles; }
 int dkmc_debug_x_static_verify(int on) { const int was = eng().x_static_verify; eng().x_static_verify = on ? 1 : 0; return was; }

@@ -125,14 +125,17 @@ __global__ void k_xt_tile_list(int nK, long long ncell, const unsigned *__restri
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < ncell && cmask[i]) { XTile t; t.k = (int)(i % nK); t.w = (int)(i / nK); t.mask = cmask[i]; t.soff = soff[i]; tiles[toff[i]] = t; }
 }
-// per row block: first / one-past-last window holding a tile
-__global__ void k_xt_wrange(int nK, int nW, const unsigned *__restrict__ cmask, int2 *__restrict__ wrange)
+// per row block: first / one-past-last window holding a tile, and the ascending list of those windows (the list fold of the block loop, xtb.hip:
+// xtb_wlist_sum2): row k of wlist is nW + 1 ints, the count and then the windows.  One pass over the cell masks for both
+__global__ void k_xt_wrange(int nK, int nW, const unsigned *__restrict__ cmask, int2 *__restrict__ wrange, int *__restrict__ wlist)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nK) {
-        int b = nW, e = 0;
-        for (int w = 0; w < nW; ++w) if (cmask[(long long)w * nK + i]) { b = min(b, w); e = w + 1; }
+        int b = nW, e = 0, n = 0;
+        int *wl = wlist + (size_t)i * (nW + 1);
+        for (int w = 0; w < nW; ++w) if (cmask[(long long)w * nK + i]) { b = min(b, w); e = w + 1; wl[++n] = w; }
         wrange[i] = make_int2(b, e);
+        wl[0] = n;
     }
 }
 // Work items = runs of tiles of one strip.  The tile list (strip-major) is cut into the ranks' shares at tile boundaries, balanced by
@@ -1098,7 +1101,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
     xrp_t *rp = nullptr, *dpos = nullptr;
     double *val = nullptr, *sd = nullptr, *tval = nullptr, *rowpart = nullptr, *colpart = nullptr, *sc = nullptr, *r = nullptr, *p = nullptr, *t = nullptr,
            *q = nullptr, *vS = nullptr, *part = nullptr, *qS = nullptr, *sS = nullptr, *xS = nullptr, *part_pt = nullptr, *part_rr = nullptr;
-    XTile *tiles = nullptr; int2 *wrange = nullptr; XItem *items = nullptr; unsigned long long *d_cnt = nullptr; XCtrl *ctrl = nullptr;
+    XTile *tiles = nullptr; int2 *wrange = nullptr; int *wlist = nullptr; XItem *items = nullptr; unsigned long long *d_cnt = nullptr; XCtrl *ctrl = nullptr;
     float *tval32 = nullptr;
     SNodes SN{};
     double *xbuf = nullptr;
@@ -1206,10 +1209,11 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         if (e.x_block > 1 && ntiles <= 2048 * nr) X.kc = std::max(1, std::min(XT_MAXKC, (ntiles + 1024 * nr - 1) / (1024 * nr)));
         tiles = (XTile *)scratch(S_XT_TILES, (size_t)(ntiles + 1) * sizeof(XTile));
         wrange = (int2 *)scratch(S_XT_WRANGE, (size_t)(nK + 4) * sizeof(int2));
-        if (!tiles || !wrange) return e.err_code;
+        wlist = (int *)scratch(S_XT_WLIST, ((size_t)nK * (nW + 1) + 4) * sizeof(int));
+        if (!tiles || !wrange || !wlist) return e.err_code;
         if (ncell > 0) {
             hipLaunchKernelGGL(k_xt_tile_list, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, nK, ncell, (const unsigned *)cmask, (const int *)toff, (const int *)soff, tiles);
-            hipLaunchKernelGGL(k_xt_wrange, dim3((nK + 255) / 256), dim3(256), 0, st, nK, nW, (const unsigned *)cmask, wrange);
+            hipLaunchKernelGGL(k_xt_wrange, dim3((nK + 255) / 256), dim3(256), 0, st, nK, nW, (const unsigned *)cmask, wrange, wlist);
         }
         int h_prefix_differs = 0;            // (read back with the run list's counts, below)
         if (k_cand && t_static > 0) {
@@ -1224,7 +1228,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         items = sh.items; nitem_w = sh.nitem_w;
         KCHK();
         if (k_cand && t_static > 0) { HIPCHK(hipStreamSynchronize(st)); if (h_prefix_differs) { k_cand = false; xs_reason = XS_PREFIX; } }
-        g_xb.tiles = tiles; g_xb.items = items; g_xb.wrange = wrange; g_xb.nitem_w = nitem_w; g_xb.cmask = cmask; g_xb.toff = toff;
+        g_xb.tiles = tiles; g_xb.items = items; g_xb.wrange = wrange; g_xb.wlist = wlist; g_xb.nitem_w = nitem_w; g_xb.cmask = cmask; g_xb.toff = toff;
 
         // ---- this rank's share of the work items (contiguous in the strip-major tile list, balanced by stored bytes) ----
         X.item_lo = sh.item_lo; X.item_n = sh.item_n; X.tile_lo = sh.tile_lo; X.tile_n = sh.tile_n; X.sub_base = sh.sub_base; X.sub_n = sh.sub_n;
@@ -1412,7 +1416,7 @@ int xt_assemble_and_solve(dkmc_gpubuf *buf, const XParams &P, int ns, const SEnt
         XtbArgs B{};
         B.m = m; B.ns = ns; B.ns_pad = ns_pad; B.nK = nK; B.nW = nW; B.s = e.x_block;
         B.items = (const XItem *)items + X.item_lo; B.item_n = X.item_n; B.tiles = tiles; B.sub_base = (int)X.sub_base; B.tval = tval; B.tval32 = tval32;
-        B.wrange = wrange; B.nitem_w = nitem_w; B.nrecords = X.nitems >> X.rec_shift;
+        B.wrange = wrange; B.wlist = wlist; B.nitem_w = nitem_w; B.nrecords = X.nitems >> X.rec_shift;
         B.srow = srow; B.sS = sS; B.nsrank = nsrank; B.rp = rp; B.ci = col; B.val = val; B.sc = sc; B.ax = buf->atom_x; B.ay = buf->atom_y; B.az = buf->atom_z; B.b = rhs; B.y = y;
         B.yaux = yaux; B.yaux_valid = yaux_valid;
         B.ctrl = ctrl; B.tol2 = tol2; B.nt_loads = nt_loads; B.sharded = sharded; B.w_lo = X.w_lo; B.w_hi = X.w_hi;
@@ -1763,7 +1767,7 @@ extern "C" int dkmc_xtb_emulate_slabs(int nranks, int width, double tol, int tim
     XtbArgs B{};
     B.m = m; B.ns = ns; B.ns_pad = X.ns_pad; B.nK = X.nK; B.nW = X.nW; B.s = s;
     B.items = (const XItem *)g_xb.items + X.item_lo; B.item_n = X.item_n; B.tiles = g_xb.tiles; B.sub_base = (int)X.sub_base; B.tval = g_xb.tval;
-    B.wrange = g_xb.wrange; B.nitem_w = g_xb.nitem_w; B.nrecords = X.nitems >> X.rec_shift;
+    B.wrange = g_xb.wrange; B.wlist = g_xb.wlist; B.nitem_w = g_xb.nitem_w; B.nrecords = X.nitems >> X.rec_shift;
     B.srow = g_xb.srow; B.sS = sS; B.nsrank = g_xb.nsrank; B.rp = g_xb.rp; B.ci = g_xb.ci; B.val = g_xb.val; B.sc = sc;
     B.ax = g_xb.ax; B.ay = g_xb.ay; B.az = g_xb.az; B.b = rhs; B.ctrl = ctrl; B.tol2 = tol * tol;
     B.nt_loads = (size_t)X.sub_n * XT_SUB * 8 > ((size_t)200 << 20); B.sharded = false; B.w_lo = X.w_lo; B.w_hi = X.w_hi;

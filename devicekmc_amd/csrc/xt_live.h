@@ -12,7 +12,7 @@
 //   k_xtl_compact   the fp32 sub-blocks of the live tiles, in tile-list order, into a second grow-only buffer -- layout of a sub-block unchanged
 //                   (xt_tval32_pos); the tiles of a run stay contiguous, which the chain prefetch of k_xtb_apply relies on
 //   k_xt_tile_list, k_xt_wrange, xt_build_items   the builders of the assembly on the live cell mask: a complete second launch view (tiles with the
-//                   same k, w, mask and a new soff; items; nitem_w; wrange; records) -- the view of a one-rank share whose tile list is the live list
+//                   same k, w, mask and a new soff; items; nitem_w; wrange and the window lists; records) -- the view of a one-rank share whose tile list is the live list
 // k_xtb_apply is not touched: it gets another tile list, item list and image pointer.
 // SUB-BLOCK UNIT (dkmc_set_x_tile_drop_unit(1)): the same rule one level down -- a stored sub-block is live when one of its stored entries reaches theta,
 // a tile when one of its sub-blocks is, so the SET OF LIVE TILES is the same in both units (tflag, k_xtl_zero_dead and the argument below stand as
@@ -24,6 +24,8 @@
 // The partial-sum arrays of the block loop are grid- and record-indexed and a launch rewrites only the cells of its own tiles: after a full-view launch
 // the cells of the dead tiles hold that launch's sums, which the live view's fold would add -- xt_live_zero_dead clears exactly those cells (the dead
 // tiles' 32 x so doubles each; the whole array is GBs at 9.4e5 sites).  Going back to the full view needs nothing: it rewrites every stored cell.
+// That holds for the range fold (dkmc_set_x_fold_form(0)).  The list fold (the default) adds only the cells of the view's own tiles, which its launch has
+// just written: the dead tiles' cells are never read and nothing clears them.
 // AUTO MODE (dkmc_set_x_tile_drop_auto, on by default): with no explicit threshold set, a WARM-STARTED solve (it starts from the previous solution, so
 // the dropped part acts on the correction only; from a zero start it acts on the whole solution and costs an fp64 re-entry round) whose stored X has at
 // least XTL_DROP_GATE sub-blocks runs its sweeps on the live view at XTL_DROP_AUTO_THETA.  The gate is measured on whole supersteps, not chosen: the
@@ -239,11 +241,12 @@ int xt_live_build(double theta, int unit, const double *sS, XLive *lv)
     if (!c32) { lv->state = -1; return 0; }
     XTile *ltiles = (XTile *)scratch(S_XTL_TILES, (size_t)(nlive + 1) * sizeof(XTile));
     int2 *lwrange = (int2 *)scratch(S_XTL_WRANGE, (size_t)(nK + 4) * sizeof(int2));
-    if (!ltiles || !lwrange) return e.err_code;
+    int *lwlist = (int *)scratch(S_XTL_WLIST, ((size_t)nK * (nW + 1) + 4) * sizeof(int));
+    if (!ltiles || !lwrange || !lwlist) return e.err_code;
     hipLaunchKernelGGL(k_xtl_compact, dim3(X.ntiles), dim3(XT_NT), 0, st, nK, (const XTile *)g_xb.tiles, (int)X.sub_base, (const unsigned *)lcmask, (const int *)lsoff,
                        reinterpret_cast<const float4 *>(g_xb.tval32), reinterpret_cast<float4 *>(c32));
     hipLaunchKernelGGL(k_xt_tile_list, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, nK, ncell, (const unsigned *)lcmask, (const int *)ltoff, (const int *)lsoff, ltiles);
-    hipLaunchKernelGGL(k_xt_wrange, dim3((nK + 255) / 256), dim3(256), 0, st, nK, nW, (const unsigned *)lcmask, lwrange);
+    hipLaunchKernelGGL(k_xt_wrange, dim3((nK + 255) / 256), dim3(256), 0, st, nK, nW, (const unsigned *)lcmask, lwrange, lwlist);
     KCHK();
     XShare sh{};
     if (int rc = xt_build_items(nK, nW, X.kc, nlive, nsub_live, ltoff, ltiles, 1, 0, S_XTL_NITEMW, S_XTL_ITEMS, S_XTL_SPLIT, &sh, 2)) return rc;
@@ -255,7 +258,7 @@ int xt_live_build(double theta, int unit, const double *sS, XLive *lv)
         HIPCHK(hipEventElapsedTime(&ms, g_xl_ev[0], g_xl_ev[1])); lv->ms[0] = ms;
         HIPCHK(hipEventElapsedTime(&ms, g_xl_ev[1], g_xl_ev[2])); lv->ms[1] = ms;
     }
-    lv->tiles = ltiles; lv->items = sh.items ? sh.items + sh.item_lo : nullptr; lv->item_n = sh.item_n; lv->wrange = lwrange; lv->nitem_w = sh.nitem_w;
+    lv->tiles = ltiles; lv->items = sh.items ? sh.items + sh.item_lo : nullptr; lv->item_n = sh.item_n; lv->wrange = lwrange; lv->wlist = lwlist; lv->nitem_w = sh.nitem_w;
     lv->nrecords = sh.nitems >> sh.rec_shift; lv->nitems = sh.nitems; lv->tval32 = c32;
     lv->info[6] = (long long)bytes;
     lv->state = 1;
@@ -276,6 +279,18 @@ extern "C" int dkmc_get_x_tile_live_info(long long *info8, double *ms2)
 {
     if (info8) { for (int c = 0; c < 8; ++c) info8[c] = g_xlive.info[c]; info8[0] = g_xlive.state; }
     if (ms2 && eng().profiling) { ms2[0] = g_xlive.ms[0]; ms2[1] = g_xlive.ms[1]; }
+    return 0;
+}
+// the window lists (XTBuffers::wlist) of the last one-GPU assembly, or of the live view the last solve ran on
+extern "C" int dkmc_xt_get_fold_lists(int live, int *nK_out, int *nW_out, int *rows)
+{
+    Engine &e = eng(); const XTState &X = g_xt;
+    if (!X.valid || comm_attached() || X.tile_n != X.ntiles || !g_xb.wlist) return dkmc_fail(13, "xt_get_fold_lists: needs the X of a single-GPU solve", __FILE__, __LINE__);
+    if (live && (g_xlive.state != 1 || !g_xlive.wlist)) return dkmc_fail(13, "xt_get_fold_lists: the last solve had no live view", __FILE__, __LINE__);
+    HIPCHK(hipStreamSynchronize(e.stream));
+    if (nK_out) *nK_out = X.nK;
+    if (nW_out) *nW_out = X.nW;
+    if (rows && X.nK > 0) HIPCHK(hipMemcpy(rows, live ? g_xlive.wlist : (const int *)g_xb.wlist, (size_t)X.nK * (X.nW + 1) * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 // the scaling by S rank of the last one-GPU solve (device, padded), or null

@@ -38,6 +38,8 @@
 // scaled full-length copy of P exists; the compact scaled copy over S (QS) feeds the tiles.
 // The split polynomial preconditioner (dkmc_set_x_poly) and the row gather the neighbour part shares with it: xtb_precond.h.  Its one-polynomial form
 // (dkmc_set_x_poly_form: the same loop in transformed variables, one q(N) per sweep): k_xtb_gram1, k_xtb_step1 and the `one` branches of xtb_cg_body.
+// The fold of the grid-indexed row sums in that loop reads only the cells of the launch view's tiles (dkmc_set_x_fold_form: xtb_wlist_sum2, `listf` in
+// xtb_cg_body); every other loop folds the window range of a row block over zeroed cells (xtb_list_sum2).
 #include "xtiles.h"
 #include "slab.h"
 #include <hip/hip_ext.h>
@@ -625,6 +627,40 @@ __device__ __forceinline__ void xtb_list_sum2(const double *__restrict__ p, size
     const double got = xor_lane<1>(odd ? sx : sy);
     sa = odd ? got : sx; sb = odd ? sy : got;
 }
+// The LIST FORM of the same sum over the windows of a row block (dkmc_set_x_fold_form(1); k_xtb_fold_rows): wl[0 ... n) are the windows whose cell holds
+// a tile of the launch view, ascending (k_xt_wrange: the same for every thread of the workgroup, so they arrive by scalar loads); only those cells are
+// loaded, 16 in flight, with the pair loads and the exchange of xtb_list_sum2.  The range form walks every window of [wl[0], wl[n - 1] + 1) and gives
+// the term of window w to accumulator (w - wl[0]) % 4; a window without a tile of the view contributes +0.0 there (a zeroed cell), and x + (+0.0) = x
+// bit for bit for every x an accumulator can hold (it starts at +0.0 and a sum in round-to-nearest is -0.0 only when both terms are).  Here the term of
+// window w goes to the same accumulator, in the same increasing order of w, and the +0.0 terms are left out: the same bits, and no cell outside the
+// list is read, so nothing has to zero one.
+__device__ __forceinline__ void xtb_wlist_sum2(const double *__restrict__ p, size_t stride, size_t off, const int *__restrict__ wl, int n, int v, double &sa, double &sb)
+{
+    const bool odd = (v & 1) != 0;
+    const dbl2 *__restrict__ q = reinterpret_cast<const dbl2 *>(odd ? p - 1 + off : p);
+    const size_t st2 = stride >> 1;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    const int w0 = n > 0 ? wl[0] : 0;
+    for (int c = 0; c < n; c += 16) {
+        dbl2 x[16]; int sel[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int cu = c + u, w = cu < n ? wl[cu] : w0;
+            sel[u] = cu < n ? (w - w0) & 3 : 4;                                // (4: the predicated tail, added nowhere)
+            x[u] = cu < n ? __builtin_nontemporal_load(q + (size_t)w * st2) : (dbl2)(0.0);
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {                                         // (sel is uniform over the workgroup: scalar branches)
+            if (sel[u] == 0) { a0 += x[u].x; b0 += x[u].y; }
+            else if (sel[u] == 1) { a1 += x[u].x; b1 += x[u].y; }
+            else if (sel[u] == 2) { a2 += x[u].x; b2 += x[u].y; }
+            else if (sel[u] == 3) { a3 += x[u].x; b3 += x[u].y; }
+        }
+    }
+    const double sx = (a0 + a1) + (a2 + a3), sy = (b0 + b1) + (b2 + b3);
+    const double got = xor_lane<1>(odd ? sx : sy);
+    sa = odd ? got : sx; sb = odd ? sy : got;
+}
 // ---- sharded solve: this rank's tile sums of every S row -> the exchange buffer xbuf[ns][so]; behind them the control words: rank 0's stop
 // decision and any rank's abort word.  [w_lo, w_hi): windows that can hold this rank's partial sums (every other cell of its arrays is zero)
 __global__ __launch_bounds__(XT_NT) void k_xtb_fold_local(int ns, int nK, int nW, int so, const int2 *__restrict__ wrange, const int *__restrict__ nitem_w,
@@ -794,7 +830,8 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_rows(int ns, int nK, int nW, int 
     }
 }
 // the fold of k_xtb_rows alone: S rows of T <- scaling x (sparse sum + tile sums), driver rows from their partial sums
-__global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW, int so, const int2 *__restrict__ wrange, const int *__restrict__ nitem_w,
+// wlist != null (dkmc_set_x_fold_form(1)): the row partial sums by the launch view's window lists (xtb_wlist_sum2) instead of its window ranges
+__global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW, int so, const int2 *__restrict__ wrange, const int *__restrict__ wlist, const int *__restrict__ nitem_w,
                                                          const double *__restrict__ rowpartB, const double *__restrict__ colpartB, const int *__restrict__ srow,
                                                          const double *__restrict__ sS, const double *__restrict__ sc, const double *__restrict__ drvpart,
                                                          double *__restrict__ T, const XCtrl *ctrl)
@@ -810,7 +847,8 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW,
         T[(size_t)row * XB_SP + v] = sc[row] * sd;
     }
     for (int k = blockIdx.x; k < nK; k += gridDim.x) {
-        const int2 wr = wrange[k];
+        const int *wl = wlist ? wlist + (size_t)k * (nW + 1) : nullptr;
+        const int2 wr = wl ? make_int2(0, 0) : wrange[k];
         const int wk = k / (XT_C / XT_R);
         const int nc = nitem_w[wk] >> rec_shift, cbase = nitem_w[nW + 2 + wk] >> rec_shift;
         double tA = 0.0, tB = 0.0;
@@ -821,7 +859,8 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_fold_rows(int ns, int nK, int nW,
             const size_t rs = (size_t)XT_R * so, cs = (size_t)XT_C * so;
             double cA, cB, rA_, rB_;
             xtb_list_sum2(cpp, cs, (size_t)16 * so, 0, nc, v, cA, cB);
-            xtb_list_sum2(rpp, rs, (size_t)16 * so, wr.x, wr.y, v, rA_, rB_);
+            if (wl) xtb_wlist_sum2(rpp, rs, (size_t)16 * so, wl + 1, wl[0], v, rA_, rB_);
+            else xtb_list_sum2(rpp, rs, (size_t)16 * so, wr.x, wr.y, v, rA_, rB_);
             tA = cA + rA_; tB = cB + rB_;
         }
         if (sA < ns) { const size_t o = (size_t)srow[sA] * XB_SP + v; T[o] = sS[sA] * (T[o] + tA); }
@@ -1501,7 +1540,16 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     // split form: ||r|| <= 1.42 ||L r||, the loop stops a little early; one polynomial: the loop tests rt'q(N)rt >= min q ||rt||^2.  The true residual is checked at the end
     const double tol2_loop = one ? A.tol2 * qmin : (pd > 0 ? A.tol2 / 2.25 : A.tol2);
     HIPCHK(hipMemsetAsync(QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
-    HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
+    // fold of the tile launch's row partial sums (dkmc_set_x_fold_form): the one-GPU preconditioned loop adds only the cells of the launch view's tiles, by
+    // the window lists of the assembly and of the live view (xtb_wlist_sum2; same bits as the range form).  Every launch writes the whole cell of each of its
+    // tiles before the fold that follows it reads them, so nothing zeroes the array (GBs at 9.4e5 sites) or the dead tiles' cells, and a launch may pick
+    // its own width: the two products of ONE column that frame the solve -- A Y0 and the true-residual pass; the other columns of their panel are zero,
+    // keep_aux needs pd == 0 -- run at one vector group (so1 = 4), HBM-bound where the full width is matrix-pipe-bound on columns of zeros.  Column 0 comes
+    // from the same instructions on the same operands; the other columns of T are sS (0 + 0) either way.  The plain, sharded and slab loops keep the range form
+    const bool listf = e.x_fold_form == 1 && pd > 0 && !A.sharded && A.wlist != nullptr && (!lv || lv->wlist != nullptr);
+    const int so1 = listf ? 4 : so;
+    if (!listf) HIPCHK(hipMemsetAsync(rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
+    else if (e.x_fold_poison) HIPCHK(hipMemsetAsync(rowpartB, 0xff, (size_t)(ncell + 1) * XT_R * so * 8, st));       // test aid (dkmc_debug_poison_fold_cells): NaN in every cell
     HIPCHK(hipMemsetAsync(colpartB, 0, (size_t)(nrec + 1) * XT_C * so * 8, st));
     HIPCHK(hipMemsetAsync(A.ctrl, 0, sizeof(XCtrl), st));
     // sharded solve (comm.hip): this rank streams its share of the tiles; the tile sums of the S rows are completed by ONE all-gather of
@@ -1528,9 +1576,9 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     hipLaunchKernelGGL(k_xtb_init, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, A.sc, A.nsrank, y0, P, QS,
                        (const double *)((keep_aux && A.yaux_valid) ? A.yaux : nullptr), hs, s, Ypanel);
     // launch view of the tile kernel and of the folds of its partial sums: the full one, or -- inside product_pre, with a live view -- the live one
-    struct XbView { const XItem *items; int item_n; const XTile *tiles; const int2 *wrange; const int *nitem_w; };
-    const XbView full{A.items, A.item_n, A.tiles, A.wrange, A.nitem_w};
-    const XbView live = lv ? XbView{lv->items, lv->item_n, lv->tiles, lv->wrange, lv->nitem_w} : full;
+    struct XbView { const XItem *items; int item_n; const XTile *tiles; const int2 *wrange; const int *nitem_w; const int *wlist; };
+    const XbView full{A.items, A.item_n, A.tiles, A.wrange, A.nitem_w, listf ? A.wlist : nullptr};
+    const XbView live = lv ? XbView{lv->items, lv->item_n, lv->tiles, lv->wrange, lv->nitem_w, listf ? lv->wlist : nullptr} : full;
     const XbView *vw = &full;
     const int ntb = (A.item_n + 3) / 4;
     const int nnb = 2 * XB_DSPLIT + (std::max(m - 2, 1) + 15) / 16;
@@ -1543,7 +1591,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     // where both are latency-bound: 15.0 against 13.5 ms per superstep -- the two event hand-overs per sweep cost more than the overlap gains).
     const bool side = sharded && m > 20000 && ntb > 0 && side_stream_init(g_xb_side) == 0;
     const float *t32 = nullptr;                                               // the tile launch of product() streams the fp32 image (product_pre) or the fp64 store
-    auto product = [&](hipEvent_t e0, hipEvent_t e1) {
+    auto product = [&](hipEvent_t e0, hipEvent_t e1, int sw) {                 // sw: vectors per row of the partial sums this launch writes (so, or so1)
         int sl = 0;
         if (side) {
             SideStream &S = g_xb_side; sl = (int)(S.seq++ % SideStream::RING);
@@ -1552,7 +1600,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, S.st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
             (void)hipEventRecord(S.b[sl], S.st);
         }
-        if (vw->item_n > 0) xtb_apply({vw->item_n, vw->items, vw->tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl, t32}, A.nt_loads, so, 0, st, e0, e1);
+        if (vw->item_n > 0) xtb_apply({vw->item_n, vw->items, vw->tiles, A.sub_base, A.tval, QS, A.nW, rowpartB, colpartB, A.ctrl, t32}, A.nt_loads, sw, 0, st, e0, e1);
         if (side) (void)hipStreamWaitEvent(st, g_xb_side.b[sl], 0);           // the sparse sums are in T before the row kernel reads them
         else hipLaunchKernelGGL(k_xtb_neigh, dim3(nnb), dim3(XT_NT), 0, st, m, A.rp, A.ci, A.val, (const double *)P, A.sc, A.nsrank, (const XCtrl *)A.ctrl, T, drvpart);
     };
@@ -1561,8 +1609,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     auto applyL = [&](double *src, double *dst, bool qs) {
         xtb_applyL(st, A, pn, pc, src, dst, W1, W2, qs, [](int, double *) { return 0; }, [&](bool, auto f) { f(nk, [](double *p) { return p; }); return 0; });
     };
-    auto fold_rows = [&](double *Tt) {
-        hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, so, vw->wrange, vw->nitem_w, (const double *)rowpartB, (const double *)colpartB,
+    auto fold_rows = [&](double *Tt, int sw) {                                 // (the width of the launch it folds)
+        hipLaunchKernelGGL(k_xtb_fold_rows, dim3(std::max(ng, 1)), dim3(XT_NT), 0, st, A.ns, A.nK, A.nW, sw, vw->wrange, vw->wlist, vw->nitem_w, (const double *)rowpartB, (const double *)colpartB,
                            A.srow, A.sS, A.sc, (const double *)drvpart, Tt, (const XCtrl *)A.ctrl);
     };
     // T = L A L P
@@ -1571,10 +1619,10 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         double *Pk = P, *Tk = T; P = Vp; T = Zp;                              // (the product reads P and QS, writes T)
         t32 = f32 ? A.tval32 : nullptr;                                       // (the first product A y0 and the true-residual pass call product() themselves: fp64 store)
         if (lv) { vw = &live; t32 = lv->tval32; }                             // dkmc_set_x_tile_drop: the live view and its compact image instead
-        product(e0, e1);
+        product(e0, e1, so);
         t32 = nullptr;
         P = Pk; T = Tk;
-        fold_rows(Zp);
+        fold_rows(Zp, so);
         vw = &full;
         applyL(Zp, T, false);
     };
@@ -1582,9 +1630,9 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     auto product_one = [&](hipEvent_t e0, hipEvent_t e1) {
         t32 = f32 ? A.tval32 : nullptr;
         if (lv) { vw = &live; t32 = lv->tval32; }
-        product(e0, e1);
+        product(e0, e1, so);
         t32 = nullptr;
-        fold_rows(T);
+        fold_rows(T, so);
         vw = &full;
         applyL(T, Up, false);
     };
@@ -1622,18 +1670,18 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         return 0;
     };
     // ---- R = A Y0 - B ; first directions ----
-    product(nullptr, nullptr);
+    product(nullptr, nullptr, so1);
     if (one) {
         // Rt = A Y0 - B in every column (column 0 from the start vector, the auxiliary columns from zero: their right-hand sides are those of A), Z = q(N) Rt
-        fold_rows(T);
-        if (lv) xt_live_zero_dead(*lv, rowpartB, so);
+        fold_rows(T, so1);
+        if (lv && !listf) xt_live_zero_dead(*lv, rowpartB, so);
         if (int rcx = rows(true, -1, nullptr, nullptr)) return rcx;
         applyL(R, Zp, false);
         gram_one(nullptr, nullptr);
     } else if (pd > 0) {
         // the start vector goes into the right-hand side: column 0 solves L A L dh = L (b - A y0) from zero, the auxiliary columns keep their own
-        fold_rows(T);                                                         // T = A Y0
-        if (lv) xt_live_zero_dead(*lv, rowpartB, so);                         // the sweeps fold on the live view: the dead tiles' row sums of this launch must not be added
+        fold_rows(T, so1);                                                    // T = A Y0
+        if (lv && !listf) xt_live_zero_dead(*lv, rowpartB, so);                        // the sweeps fold on the live view: the dead tiles' row sums of this launch must not be added
         hipLaunchKernelGGL(k_xtb_pre_resid, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)T, A.b, Zp);
         applyL(Zp, T, false);                                                 // T(:, 0) = L (A y0 - b), the other columns 0
         bsel = bz;                                                            // R = T - [0 | auxiliary right-hand sides]
@@ -1652,7 +1700,7 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             if (one) { product_one(ev[0], ev[1]); gram_one(ev[2], ev[3]); }
             else {
                 if (pd > 0) product_pre(ev[0], ev[1]);
-                else product(ev[0], ev[1]);
+                else product(ev[0], ev[1], so);
                 if (int rcx = rows(false, it, ev[2], ev[3])) return rcx;
             }
             hipLaunchKernelGGL(k_xtb_gred, dim3(XB_NG * 16), dim3(XT_NT), 0, st, ng, (const double *)gpart, gfin, (const XCtrl *)A.ctrl);
@@ -1679,8 +1727,8 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
         if (!h.pad[0]) {
             hipLaunchKernelGGL(k_xtb_pre_col0, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)A.y, P);
             hipLaunchKernelGGL(k_xtb_qs_from, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const double *)P, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl);
-            product(nullptr, nullptr);
-            fold_rows(T);
+            product(nullptr, nullptr, so1);
+            fold_rows(T, so1);
             const int nrp = std::min(XB_RR_MAXPART, (m + 1023) / 1024);       // (the partial Gram matrices have served: gpart holds the partial sums)
             hipLaunchKernelGGL(k_xtb_pre_rr_part, dim3(nrp), dim3(256), 0, st, m, (const double *)T, A.b, gpart);
             hipLaunchKernelGGL(k_xtb_pre_rr, dim3(1), dim3(256), 0, st, nrp, (const double *)gpart, bz + m);

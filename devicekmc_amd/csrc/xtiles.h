@@ -43,6 +43,7 @@ struct XTState {
 
 struct XTBuffers {
     SNodes S; int *srow; XTile *tiles; XItem *items; int2 *wrange; int *nitem_w; double *tval, *rowpart, *colpart;
+    int *wlist;                      // per row block: nW + 1 ints, the count and the ascending windows that hold a tile (k_xt_wrange; the list fold of xtb.hip)
     float *tval32;                   // fp32 image of tval for the block-CG's sweeps (dkmc_set_x_tile_f32; xt_tval32_pos), null if none
     xrp_t *rp, *dpos; int *ci; double *val; int *nsrank;
     unsigned *cmask; int *toff;      // census of the last assembly (kept for dkmc_xt_time_share)
@@ -58,7 +59,8 @@ extern XTBuffers g_xb;
 struct XLive {
     int state = 0;                   // 0 off or not applicable, 1 usable, -1 no buffer for the compact image, -2 nothing to drop
     const XTile *tiles = nullptr; const XItem *items = nullptr; int item_n = 0; const int2 *wrange = nullptr; const int *nitem_w = nullptr; int nrecords = 0;
-    int nitems = 0;                  // runs of the live view (what dkmc_stats.xt_items reports after a solve whose sweeps ran on it)
+    const int *wlist = nullptr;      // the live tiles' windows by row block (the layout of XTBuffers::wlist)
+    int nitems = 0;                 // runs of the live view (what dkmc_stats.xt_items reports after a solve whose sweeps ran on it)
     const float *tval32 = nullptr;   // the compact image (sub-block slot = the live tile's soff; with dkmc_set_x_tile_drop_unit(1) only the live sub-blocks of a tile, its mask reduced to them)
     const int *tflag = nullptr;      // per STORED tile: 1 live, 0 dead
     long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0}; double ms[2] = {0.0, 0.0};
@@ -79,6 +81,7 @@ struct XtbArgs {
     const XTile *tiles; int sub_base; const double *tval;
     const float *tval32;                          // fp32 image of tval (null: none): the sweeps of the one-GPU preconditioned loop stream it (dkmc_set_x_tile_f32)
     const int2 *wrange; const int *nitem_w; int nrecords;
+    const int *wlist;                             // windows holding a tile, by row block (XTBuffers::wlist); null: the folds walk wrange
     const int *srow; const double *sS; const int *nsrank;
     const xrp_t *rp; const int *ci; const double *val;      // neighbour part Xs (CSR, unscaled, diagonal included)
     const double *sc;                             // Jacobi scaling 1 / sqrt(diag)

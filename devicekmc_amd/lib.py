@@ -93,6 +93,10 @@ SYMBOLS = {
     "dkmc_xt_get_live": (_I, [_D, vp, vp]),
     "dkmc_xt_get_live_masks": (_I, [_D, vp]),
     "dkmc_debug_fail_true_residual_once": (None, []),
+    "dkmc_set_x_fold_form": (None, [_I]),
+    "dkmc_get_x_fold_form": (_I, []),
+    "dkmc_debug_poison_fold_cells": (None, [_I]),
+    "dkmc_xt_get_fold_lists": (_I, [_I, c_int_p, c_int_p, vp]),
     "dkmc_set_x_static_tiles": (None, [_I]),
     "dkmc_get_x_static_tiles": (_I, []),
     "dkmc_get_x_static_info": (_I, [C.POINTER(C.c_longlong)]),

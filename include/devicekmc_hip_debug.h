@@ -144,6 +144,19 @@ int dkmc_xt_get_live(double theta, int *live_per_tile, double *sS_out);
 /* Test aid: from the same census, the mask of the sub-blocks LIVE ON THEIR OWN of every stored tile at threshold theta (a subset of the tile's stored
  * mask; 0 = dead tile), in dkmc_xt_get_tiles order: what dkmc_set_x_tile_drop_unit(1) streams of the tile. */
 int dkmc_xt_get_live_masks(double theta, int *mask_per_tile);
+/* The fold of the tile launch's row partial sums in the one-GPU preconditioned block-CG (csrc/xtb.hip: k_xtb_fold_rows).  Form 1 (default): it adds only
+ * the cells of the launch view's tiles, by the per-row-block window lists of the assembly and of the live view; nothing zeroes the partial-sum array, and
+ * the two one-column fp64 products that frame a solve run at one vector group.  Form 0: every cell of a row block's window range, over a per-solve
+ * memset and k_xtl_zero_dead.  Same bits; other values select 1.  Every other loop keeps the range form.
+ * dkmc_debug_poison_fold_cells: test aid, sticky until called with 0 -- a solve in form 1 fills the whole partial-sum array with NaN where form 0 zeroes
+ *   it; a correct list fold never reads one.
+ * dkmc_xt_get_fold_lists: test aid -- the window lists of the last one-GPU assembly (live 0) or of the live view of the last solve (live 1; error 13
+ *   where that solve had none): rows[k * (nW + 1)] = windows of row block k that hold a tile of the view, then the windows, ascending.  rows may be
+ *   null: the shape only. */
+void dkmc_set_x_fold_form(int form);
+int dkmc_get_x_fold_form(void);
+void dkmc_debug_poison_fold_cells(int on);
+int dkmc_xt_get_fold_lists(int live, int *nK, int *nW, int *rows);
 /* Self-check of dkmc_set_x_static_tiles (csrc/xt_static.h); returns the setting before.  On: every assembly in metals-first order is followed by
  * the FULL census and a FULL fill of the resident tile list into buffers of their own (a second store: tests and small sizes only; the resident
  * store is only read), compared with what the assembly left.  dkmc_debug_get_x_static_verify, for the last solve: v4[0] differing words of the
