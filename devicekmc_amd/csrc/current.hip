@@ -596,7 +596,9 @@ static int update_power_body(dkmc_gpubuf *buf, int n_src, int n_gnd, int nlc, do
         if (yaux) g_cur->warm_aux_valid = 0;                    // (a solve that fails leaves nothing to start from)
         rc = xt_assemble_and_solve(buf, P, ns, S, aneigh, ancnt, aflag, srank, atom_site, rhs, m, &e.stats.cg_iters_X, &e.stats.cg_rr_X, yaux, yaux_valid, warm);
         if (rc) return rc;
-        if (yaux && e.stats.xb_width > 1 && !e.stats.xb_fallback) g_cur->warm_aux_valid = 1;
+        // valid only after a solve that WROTE the panel: the block loops keep the auxiliary iterate at degree 0 alone (xtb.hip, xtb_slab.inc: keep_aux),
+        // and a preconditioned solve leaves the allocation as it found it
+        if (yaux && e.stats.xb_width > 1 && !e.stats.xb_fallback && e.stats.xb_poly_used == 0) g_cur->warm_aux_valid = 1;
         rp = xt_xs_rp(); col = xt_xs_col(); data = xt_xs_val();
     } else {
         // ---- 3. sparsity: counts -> row_ptr -> columns ----

@@ -1827,7 +1827,7 @@ extern "C" int dkmc_xtb_check_product(int width, double *max_abs_diff, double *m
     hipLaunchKernelGGL(k_xtb_test_panel, dim3((ns * XB_SP + 255) / 256), dim3(256), 0, st, ns, QS);
     const XbApplyArgs xa{X.item_n, (const XItem *)g_xb.items + X.item_lo, (const XTile *)g_xb.tiles, (int)X.sub_base, (const double *)g_xb.tval, QS, X.nW, rowpartB,
                          colpartB, ctrl};
-    xtb_apply(xa, true, so, 0, st);
+    if (xa.n > 0) xtb_apply(xa, true, so, 0, st);                          // (a tunnelling set without a pair stores no tile: nothing to launch, all sums 0)
     hipLaunchKernelGGL((k_xtb_rows<1, 0>), dim3(ng), dim3(XT_NT), 0, st, ns, X.nK, X.nW, m, s, so, (const int2 *)g_xb.wrange, (const int *)g_xb.nitem_w, (const double *)rowpartB,
                        (const double *)colpartB, (const int *)g_xb.srow, (const double *)sS, (const int *)g_xb.nsrank, (const double *)sc, (const double *)drvpart, T,
                        (const double *)P, R, (const double *)rhs, gpart, ctrl, (const double *)nullptr, -1, 1, (const XbAux *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr);

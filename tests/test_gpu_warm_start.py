@@ -126,8 +126,9 @@ def test_warm_vector_export_import(cell_2p5, hip):
 def test_auxiliary_columns_warm_start_option(cell_2p5, hip):
     """dkmc_set_x_aux_warm(1) (off by default: profiles/r05_ab_aux_warm.json): the hash auxiliary columns start from the solutions the previous
     solve left, the default set becomes half smooth + half hash.  Whatever the auxiliary columns start from, the physical column's solution meets
-    the reference's stop test in the true scaled residual of the CSR X; here over four coupled supersteps, and the auxiliary panel survives an
-    export / import (restart)."""
+    the reference's stop test in the true scaled residual of the CSR X; here over four coupled supersteps.  The block loops keep the auxiliary
+    iterate at degree 0 alone, so after these preconditioned solves there is no panel to export (n = 0, whatever ran before in the process); a fifth
+    superstep with the degree pinned to 0 writes it, and that panel survives an export / import (restart)."""
     import ctypes as C
     from devicekmc_amd import params as pm
     from devicekmc_amd.lib import check
@@ -144,6 +145,7 @@ def test_auxiliary_columns_warm_start_option(cell_2p5, hip):
             dev.updatePower(gb, p, Vd)
             st = host.get_stats()
             assert st["xb_width"] == 16 and st["xb_fallback"] == 0 and st["xb_aux"] == 2       # 2: mixed set
+            assert st["xb_poly_used"] > 0                      # preconditioned, as by default
             sweeps.append(st["cg_iters_X"])
             m = get(gb, "atom_virtual_potentials").copy()
             L.dkmc_set_x_format(0); L.dkmc_set_current_warm_start(0)
@@ -154,7 +156,18 @@ def test_auxiliary_columns_warm_start_option(cell_2p5, hip):
                 L.dkmc_set_x_format(1); L.dkmc_set_current_warm_start(1)
             assert _scaled_residual(rp, ci, data, m, p.G0, p.X_loop_G) <= 10 * p.cg_tol, (k, sweeps)
         print("sweeps with the warm auxiliary start (2.5 nm):", sweeps)
-        n = C.c_longlong(0)
+        n = C.c_longlong(-1)
+        # a preconditioned solve never writes the auxiliary panel (the block loops keep it at degree 0 alone): nothing to export after one,
+        # whatever the allocation held
+        check(L.dkmc_get_current_warm_aux(C.byref(gb.c), None, 0, C.byref(n)))
+        assert n.value == 0
+        # export / import on a solve that wrote the panel: the degree pinned to 0
+        L.dkmc_set_x_poly(0)
+        dev.updateCharge(gb); dev.updatePotential(gb, p, Vd, 4)
+        sim.executeKMCStep(gb, dev)
+        dev.updatePower(gb, p, Vd)
+        st = host.get_stats()
+        assert st["xb_width"] == 16 and st["xb_fallback"] == 0 and st["xb_aux"] == 2 and st["xb_poly_used"] == 0
         check(L.dkmc_get_current_warm_aux(C.byref(gb.c), None, 0, C.byref(n)))
         assert n.value == 16 * (dev.N_atom + 1)
         w = np.zeros(n.value)
