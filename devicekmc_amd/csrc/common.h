@@ -177,7 +177,12 @@ struct KBlocked {
     int word_bytes = 4; // form 2: bytes of a stored word of the assembled cf (dkmc_set_k_window_word_bytes when the pattern was built); pcol stays 32-bit
 };
 // ---- host side ---------------------------------------------------------------------------------
+constexpr double X_STOP_MARGIN_DEFAULT = 1.0;      // Engine::x_stop_margin
 constexpr int X_POLY_DEFAULT = 8;   // base degree of the split polynomial preconditioner (Engine::x_poly)
+// how the last round of a one-polynomial block solve stopped (dkmc_get_x_stop_info): fired 0 = no such round, 1 = the bound test of k_xtb_small (or a
+// breakdown), 2 = the norm test; with_norm: the norm test ran beside the bound; rows of the system; ||Rt(:, 0)|| at the stop (-1: not measured),
+// (Rt'Z)_00 at the stop, the true residual ||A y - b|| behind it
+struct XStopLast { int fired = 0, with_norm = 0, m = 0; double norm = -1.0, rz = 0.0, true_res = 0.0; };
 struct Engine {
     hipStream_t stream = nullptr;
     int device = 0;
@@ -200,7 +205,10 @@ struct Engine {
     int x_poly_form = 2;           // form of the one-GPU preconditioned loop (dkmc_set_x_poly_form; xtb.hip): 0 = split, CG on L A L (2 d N products per sweep); 1 = one polynomial q(N) ~ (I - N)^-1 as M^-1, in transformed variables (n(d) products); 2 = one polynomial where the degree comes from the rule (x_poly_auto), split where a degree is pinned
     int x_poly1_degree = 0;        // measurement aid (dkmc_debug_set_x_poly1_degree): > 0 overrides the degree n(d) of the one-polynomial form
     int x_poly_form_used = 0, x_poly_products = 0;      // the last one-GPU block solve: 1 = it ran the one-polynomial form; its N products per sweep (dkmc_get_x_poly_form_used / _products)
-    int x_slab_poly = 0;           // 1: the slab-distributed block-CG (> 1 rank, x_slab) runs on L A L too (dkmc_set_x_slab_poly; xtb_slab.inc); 0 (default): plain
+    int x_stop_form = 2;           // stop test of the one-polynomial loop (dkmc_set_x_stop_form; xtb.hip): 0 = the bound rt'q(N)rt <= tol^2 min q alone; 1 = beside it the norm it bounds, ||Rt(:, 0)|| <= x_stop_margin tol (k_xtb_stop_norm), whichever fires first; 2 (default) = 1 from the measured size gate on (xtb_stop_rule, xtb_precond.h), 0 below it
+    double x_stop_margin = X_STOP_MARGIN_DEFAULT;   // kappa of that test (dkmc_set_x_stop_margin): the largest of {1, 0.8, 1 / 1.5} without a re-entry round over 100 steps at 9.4e5 sites (profiles/x_stop_soak_tile10.jsonl)
+    XStopLast x_stop_last{};       // the stop of the last one-polynomial round (dkmc_get_x_stop_info)
+    int x_slab_poly = 0;          // 1: the slab-distributed block-CG (> 1 rank, x_slab) runs on L A L too (dkmc_set_x_slab_poly; xtb_slab.inc); 0 (default): plain
     int x_aux_warm = 0;            // 1: with the warm start of the current solve the hash auxiliary columns start from the previous solve's solutions too (dkmc_set_x_aux_warm; off: no gain beyond 1e4 rows, profiles/r05_ab_aux_warm.json)
     int x_items_kc = 0;            // > 0: overrides the nominal run length kc (tiles) of the tile runs (dkmc_set_x_items; measurement)
     int x_apply_form = 0;          // tile x panel kernel of the block-CG: 0 = the product form, 1 = the round-4 form of its loop (same results; same-box comparisons, dkmc_set_x_apply_form)
@@ -311,6 +319,8 @@ enum {
     // min-cut analysis (flow.hip: dkmc_find_flow): per-site words (strand neighbours, the level pairs of both closing searches, the nearest seeds,
     // predecessors, first-site flag + rank, the strand sites), the strand table, change words + stat block
     S_FL_SITE, S_FL_ROWS, S_FL_CTRL,
+    // norm stop test of the one-polynomial block loop (xtb.hip: k_xtb_step1's partial sums, k_xtb_stop_norm's record)
+    S_XTB_STOPN,
     S_NSLOTS
 };
 static_assert(S_NSLOTS <= Engine::NBUF, "scratch slots");

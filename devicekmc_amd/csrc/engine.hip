@@ -78,6 +78,19 @@ void dkmc_set_x_poly_form(int form) { eng().x_poly_form = form == 1 ? 1 : (form 
 int dkmc_get_x_poly_form(void) { return eng().x_poly_form; }
 int dkmc_get_x_poly_form_used(void) { return eng().x_poly_form_used; }
 int dkmc_get_x_poly_products(void) { return eng().x_poly_products; }
+void dkmc_set_x_stop_form(int form) { eng().x_stop_form = form == 1 ? 1 : (form == 2 ? 2 : 0); }
+int dkmc_get_x_stop_form(void) { return eng().x_stop_form; }
+void dkmc_set_x_stop_margin(double kappa) { eng().x_stop_margin = (kappa > 0.0 && kappa <= 1.0) ? kappa : X_STOP_MARGIN_DEFAULT; }      // (NaN compares false: the default)
+double dkmc_get_x_stop_margin(void) { return eng().x_stop_margin; }
+int dkmc_get_x_stop_info(int *fired, double *norm, double *rz, double *true_residual)
+{
+    const XStopLast &l = eng().x_stop_last;
+    if (fired) *fired = l.fired;
+    if (norm) *norm = l.norm;
+    if (rz) *rz = l.rz;
+    if (true_residual) *true_residual = l.true_res;
+    return l.fired ? 0 : 1;
+}
 void dkmc_debug_set_x_poly1_degree(int n) { eng().x_poly1_degree = n < 0 ? 0 : (n > 20 ? 20 : n); }
 void dkmc_set_x_poly_auto_rows(int n0, int n1) { Engine &e = eng(); e.x_poly_rows[0] = n0 > 0 ? n0 : 0; e.x_poly_rows[1] = n1 > e.x_poly_rows[0] ? n1 : e.x_poly_rows[0]; }
 void dkmc_set_x_apply_form(int form) { eng().x_apply_form = form == 1 ? 1 : 0; }

@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_gram1(int m, const double *__rest
 __global__ __launch_bounds__(XT_NT) void k_xtb_step1(int m, int it, const double *__restrict__ mats, double *__restrict__ y0, double *__restrict__ Rt,
                                                      double *__restrict__ Z, double *__restrict__ Pt, double *__restrict__ Pi, const double *__restrict__ Q,
                                                      const double *__restrict__ U, const double *__restrict__ sc, const int *__restrict__ nsrank,
-                                                     double *__restrict__ QS, const XCtrl *ctrl)
+                                                     double *__restrict__ QS, const XCtrl *ctrl, double *__restrict__ npart = nullptr)
 {
     __shared__ int sdone;
     if (threadIdx.x == 0) { const int d = ctrl->done; sdone = d != 0 && it + 1 >= d; }
@@ -1249,6 +1249,7 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_step1(int m, int it, const double
         cB[kk] = mats[o]; m1B[kk] = mats[256 + o]; m2B[kk] = mats[512 + o]; m3B[kk] = mats[768 + o];
         c0[kk] = mats[(4 * kk + b) * 16];
     }
+    double nacc = 0.0;                                                        // npart: sum of Rt+(i, 0)^2 over the rows this thread stores (the lanes of column 0)
     const int ngroups = (m + 15) / 16;
     for (int g = (int)blockIdx.x * 4 + wv; g < ngroups; g += (int)gridDim.x * 4) {
         const int row0 = 16 * g;
@@ -1288,8 +1289,35 @@ __global__ __launch_bounds__(XT_NT) void k_xtb_step1(int m, int it, const double
                 Rt[o] = rN[u]; Z[o] = zN[u]; Pt[o] = pN[u]; Pi[o] = iN[u];
                 const int sr = nsrank[row];
                 if (sr >= 0) QS[xtb_qs_pos(sr, a)] = sc[row] * pN[u];
+                if (a == 0) nacc += rN[u] * rN[u];
             }
         }
+    }
+    // ||Rt+(:, 0)||^2 of this workgroup's rows (dkmc_set_x_stop_form): per thread over its rows in the order it stored them, then the workgroup tree; no
+    // atomics -- the partial sums depend on m and the grid alone.  k_xtb_stop_norm adds them.  (npart is a kernel argument: uniform over the launch)
+    if (npart) {
+        const double t = xtb_tree256(nacc);
+        if (threadIdx.x == 0) npart[blockIdx.x] = t;
+    }
+}
+// The contract's stop test itself (dkmc_set_x_stop_form(1)): ||Rt+(:, 0)||_2 <= kappa tol on the Jacobi-scaled system, from the partial sums k_xtb_step1 of
+// sweep `it` wrote.  ONE workgroup adds them in index order (the pattern of k_xtb_pre_rr).  The bound test of k_xtb_small stays beside it: this kernel ends
+// the loop after sweep `it` exactly as that test's stop branch of the same sweep would have (done = it + 2: the step of the sweep has run, nothing after it
+// does; iters = it + 1; rr is what k_xtb_small of the sweep wrote), unless the stop word is set already.  rec: [0] the sum, [1] (Rt+'Z+)_00 of the
+// sweep, [2] 1.0 where this test ended the loop -- of the last sweep whose step ran.
+__global__ __launch_bounds__(256) void k_xtb_stop_norm(int np, int it, const double *__restrict__ part, double bound2, XCtrl *ctrl, double *__restrict__ rec)
+{
+    __shared__ int sdone;
+    if (threadIdx.x == 0) { const int d = ctrl->done; sdone = d != 0 && it + 1 >= d; }
+    __syncthreads();
+    if (sdone) return;                                                        // the step of this sweep did not run: its partial sums are not this sweep's
+    double a = 0.0;
+    for (int i = threadIdx.x; i < np; i += 256) a += part[i];
+    a = xtb_tree256(a);
+    if (threadIdx.x == 0) {
+        const bool fire = !(a > bound2) && ctrl->done == 0;
+        rec[0] = a; rec[1] = ctrl->rr[(it + 1) & 1]; rec[2] = fire ? 1.0 : 0.0;
+        if (fire) { ctrl->iters = it + 1; ctrl->done = it + 2; }
     }
 }
 // before the first product: P = Y0 stands in for Y0 (the product below is A Y0), QS = S Y0 over S; y0 = column 0.  Column 0 starts from y;
@@ -1435,7 +1463,7 @@ static int xtb_finish(const XCtrl &h, bool hint, bool again, bool prof, int *ite
     if (h.pad[0]) return DKMC_XTB_BREAKDOWN;
     return again ? DKMC_XTB_AGAIN : 0;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv);
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv, bool first_round);
 static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shares, int time_rank, int *iters_out, double *rr_out);
 // split polynomial preconditioner: the loop stops on the residual of L A L; when the TRUE residual of column 0 does not meet the stop test yet, the
 // solve is re-entered from the iterate it reached (the check and the code DKMC_XTB_AGAIN: end of xtb_cg_body / xtb_cg_slab).  A round that no longer
@@ -1490,13 +1518,13 @@ int xtb_cg(const XtbArgs &A, int *iters_out, double *rr_out)
         if (int rcl = xt_live_build(theta, e.x_tile_drop_unit, A.sS, &g_xlive)) return rcl;
         if (g_xlive.state == 1) { lv = &g_xlive; e.x_tile_drop_used = theta; }
     }
-    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32, lv);
-    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false, nullptr); });
+    int rc = xtb_cg_body(A, iters_out, &rr0, &peer_used, np, f32, lv, true);
+    rc = xtb_reenter(rc, rr0, iters_out, rr_out, [&](int *it, double *rr) { ++e.stats.x_tile_f64_rounds; return xtb_cg_body(A, it, rr, &peer_used, np, false, nullptr, false); });
     // a sharded solve that failed with the peer-write exchange in use: the ranks' sequence counters may have drifted (comm.hip)
     if (rc != 0 && rc != DKMC_XTB_BREAKDOWN && peer_used) comm_peer_drop();
     return rc;
 }
-static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv)
+static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *peer_used, const XbNPack *np, bool f32, XLive *lv, bool first_round)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     const int m = A.m, s = A.s, so = 4 * ((s + 3) / 4);                       // vector groups of four: the matrix instruction's width
@@ -1539,6 +1567,14 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
     if (one) xtb_poly1_coeffs(pn, pc, &qmin); else xtb_poly_coeffs(pd, pc);
     // split form: ||r|| <= 1.42 ||L r||, the loop stops a little early; one polynomial: the loop tests rt'q(N)rt >= min q ||rt||^2.  The true residual is checked at the end
     const double tol2_loop = one ? A.tol2 * qmin : (pd > 0 ? A.tol2 / 2.25 : A.tol2);
+    // one polynomial, dkmc_set_x_stop_form(1): beside that bound, the quantity it bounds -- ||Rt+(:, 0)||^2 from k_xtb_step1's partial sums against (kappa tol)^2
+    // (k_xtb_stop_norm); whichever fires first ends the loop.  First round only: a round that follows a failed true-residual check stops on the bound alone
+    const bool nstop = one && first_round && (e.x_stop_form == 1 || (e.x_stop_form == 2 && xtb_stop_rule(m) != 0));
+    double *npart = nstop ? (double *)scratch(S_XTB_STOPN, (size_t)(2048 + 4) * 8) : nullptr, *nstoprec = npart ? npart + 2048 : nullptr;
+    if (nstop && !npart) return e.err_code;
+    if (nstop) HIPCHK(hipMemsetAsync(nstoprec, 0, 4 * 8, st));
+    const double nbound2 = e.x_stop_margin * e.x_stop_margin * A.tol2;
+    e.x_stop_last = XStopLast{};
     HIPCHK(hipMemsetAsync(QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
     // fold of the tile launch's row partial sums (dkmc_set_x_fold_form): the one-GPU preconditioned loop adds only the cells of the launch view's tiles, by
     // the window lists of the assembly and of the live view (xtb_wlist_sum2; same bits as the range form).  Every launch writes the whole cell of each of its
@@ -1641,8 +1677,12 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
                               (const double *)R, (const double *)Zp, gpart, (const XCtrl *)A.ctrl);
     };
     auto step = [&](int it) {
-        if (one) hipLaunchKernelGGL(k_xtb_step1, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, Zp, P, Vp, (const double *)T, (const double *)Up, A.sc,
-                                    A.nsrank, QS, (const XCtrl *)A.ctrl);
+        if (one) {
+            const bool nt = nstop && it >= 0;                                  // (the set-up pass takes no step in Rt)
+            hipLaunchKernelGGL(k_xtb_step1, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, Zp, P, Vp, (const double *)T, (const double *)Up, A.sc,
+                               A.nsrank, QS, (const XCtrl *)A.ctrl, nt ? npart : (double *)nullptr);
+            if (nt) hipLaunchKernelGGL(k_xtb_stop_norm, dim3(1), dim3(256), 0, st, gs, it, (const double *)npart, nbound2, A.ctrl, nstoprec);
+        }
         else hipLaunchKernelGGL(k_xtb_step, dim3(gs), dim3(XT_NT), 0, st, m, it, (const double *)mats, y0, R, P, (const double *)T, A.sc, A.nsrank, QS, (const XCtrl *)A.ctrl,
                                 (const int *)nullptr, Ypanel);
     };
@@ -1732,9 +1772,12 @@ static int xtb_cg_body(const XtbArgs &A, int *iters_out, double *rr_out, bool *p
             const int nrp = std::min(XB_RR_MAXPART, (m + 1023) / 1024);       // (the partial Gram matrices have served: gpart holds the partial sums)
             hipLaunchKernelGGL(k_xtb_pre_rr_part, dim3(nrp), dim3(256), 0, st, m, (const double *)T, A.b, gpart);
             hipLaunchKernelGGL(k_xtb_pre_rr, dim3(1), dim3(256), 0, st, nrp, (const double *)gpart, bz + m);
-            double rr_true = 0.0;
+            double rr_true = 0.0, hrec[3] = {-1.0, h.rr[h.iters & 1], 0.0};
             HIPCHK(hipMemcpyAsync(&rr_true, bz + m, 8, hipMemcpyDeviceToHost, st));
+            if (nstop && h.iters > 0) HIPCHK(hipMemcpyAsync(hrec, nstoprec, 3 * 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
+            // the stop of this round (dkmc_get_x_stop_info): which test ended it, ||Rt(:, 0)|| there (form 1), (Rt'Z)_00 there, the true residual
+            if (one) e.x_stop_last = XStopLast{hrec[2] != 0.0 ? 2 : 1, nstop ? 1 : 0, m, hrec[0] >= 0.0 ? sqrt(hrec[0]) : -1.0, hrec[1], sqrt(rr_true)};
             h.rr[h.iters & 1] = rr_true;
             again = rr_true > A.tol2;
             if (e.x_tile_f32_fail_once) { e.x_tile_f32_fail_once = 0; again = true; }       // test aid (dkmc_debug_fail_true_residual_once)
@@ -2037,9 +2080,10 @@ extern "C" int dkmc_xtb_test_gram1(int m, const double *const *panels, int ng, i
     return e.err_code;
 }
 // Step stage: ONE launch of k_xtb_step1 with the grid of a solve.  Pt, Pi, Rt, Z and y0 [m] go up and come back, Q and U go up; qs [ns][16] as in
-// dkmc_xtb_test_step.
-extern "C" int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
-                                   double *qs)
+// dkmc_xtb_test_step.  rec3 (dkmc_xtb_test_step1_norm): the kernel also writes its partial sums of Rt+(:, 0)^2 and k_xtb_stop_norm follows it, as in a solve
+// under dkmc_set_x_stop_form(1), with the bound bound2 and the XCtrl the aid starts from (done_word; rr = rr_in); rec3 and ctrl_out receive its record and the XCtrl.
+static int xtb_test_step1_run(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
+                              double *qs, double bound2, double rr_in, double *rec3, dkmc_xtb_ctrl *ctrl_out)
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     if (m < 1 || m > XTB_ALG_MAXROWS || it < -1 || it > 0x3fffffff || !mats || !y0 || !panels || !sc || !nsrank || (ns > 0 && !qs))
@@ -2050,13 +2094,16 @@ extern "C" int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_w
     const size_t b_qs = xtb_alg_up((size_t)(ns + 2) * XB_SP * 8);
     char *dp = (char *)scratch(S_XTB_ALG_PANELS, 6 * pan_up + 2 * vec_up);
     int *dnsr = (int *)scratch(S_XTB_ALG_INTS, xtb_alg_up((size_t)m * 4));
-    double *dmats = (double *)scratch(S_XTB_ALG_GRAM, 4 * 256 * 8);
+    double *dmats = (double *)scratch(S_XTB_ALG_GRAM, (4 * 256 + 2048 + 4) * 8);
     char *qsb = (char *)scratch(S_XTB_ALG_QS, 2 * b_qs);
     XCtrl *ctrl = (XCtrl *)scratch(S_XTB_ALG_CTRL, sizeof(XCtrl));
     if (!dp || !dnsr || !dmats || !qsb || !ctrl) return e.err_code;
     double *dy0 = (double *)(dp + 6 * pan_up), *dsc = (double *)(dp + 6 * pan_up + vec_up);
     double *QS = (double *)qsb, *dq = (double *)(qsb + b_qs);
-    XCtrl h{}; h.done = done_word;
+    double *dnpart = rec3 ? dmats + 4 * 256 : nullptr, *dnrec = dmats + 4 * 256 + 2048;
+    const int gs1 = grid_blocks((m + 15) / 16, 4, 2048);
+    XCtrl h{}; h.done = done_word; h.rr[0] = h.rr[1] = rr_in;
+    if (rec3) { HIPCHK(hipMemsetAsync(dnpart, 0xff, 2048 * 8, st)); HIPCHK(hipMemcpyAsync(dnrec, rec3, 3 * 8, hipMemcpyHostToDevice, st)); }      // (NaN in every partial sum: the kernel must write all it launches)
     for (int k = 0; k < 6; ++k) HIPCHK(hipMemcpyAsync(dp + k * pan_up, panels[k], pan, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dy0, y0, (size_t)m * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(dsc, sc, (size_t)m * 8, hipMemcpyHostToDevice, st));
@@ -2070,14 +2117,41 @@ extern "C" int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_w
     HIPCHK(hipMemcpyAsync(ctrl, &h, sizeof(XCtrl), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
 #define XB_DP(k_) (double *)(dp + (k_) * pan_up)
-    hipLaunchKernelGGL(k_xtb_step1, dim3(grid_blocks((m + 15) / 16, 4, 2048)), dim3(XT_NT), 0, st, m, it, (const double *)dmats, dy0, XB_DP(4), XB_DP(5), XB_DP(0), XB_DP(1),
-                       (const double *)XB_DP(2), (const double *)XB_DP(3), (const double *)dsc, (const int *)dnsr, QS, (const XCtrl *)ctrl);
+    hipLaunchKernelGGL(k_xtb_step1, dim3(gs1), dim3(XT_NT), 0, st, m, it, (const double *)dmats, dy0, XB_DP(4), XB_DP(5), XB_DP(0), XB_DP(1),
+                       (const double *)XB_DP(2), (const double *)XB_DP(3), (const double *)dsc, (const int *)dnsr, QS, (const XCtrl *)ctrl, dnpart);
 #undef XB_DP
+    if (rec3) hipLaunchKernelGGL(k_xtb_stop_norm, dim3(1), dim3(256), 0, st, gs1, it, (const double *)dnpart, bound2, ctrl, dnrec);
     if (ns > 0) hipLaunchKernelGGL(k_xtb_test_qs_decode, dim3((unsigned)(((size_t)ns * XB_SP + 255) / 256)), dim3(256), 0, st, ns, (const double *)QS, dq);
     KCHK();
     for (int k = 0; k < 6; ++k) if (k != 2 && k != 3) HIPCHK(hipMemcpyAsync(panels[k], dp + k * pan_up, pan, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(y0, dy0, (size_t)m * 8, hipMemcpyDeviceToHost, st));
     if (ns > 0) HIPCHK(hipMemcpyAsync(qs, dq, (size_t)ns * XB_SP * 8, hipMemcpyDeviceToHost, st));
+    if (rec3) HIPCHK(hipMemcpyAsync(rec3, dnrec, 3 * 8, hipMemcpyDeviceToHost, st));
+    if (ctrl_out) HIPCHK(hipMemcpyAsync(ctrl_out, ctrl, sizeof(XCtrl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return e.err_code;
+}
+extern "C" int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
+                                   double *qs)
+{
+    return xtb_test_step1_run(m, it, mats, done_word, y0, panels, sc, nsrank, ns, qs, 0.0, 0.0, nullptr, nullptr);
+}
+// The step stage under dkmc_set_x_stop_form(1) (tests/test_gpu_x_stop_norm.py): k_xtb_step1 with its partial sums, then k_xtb_stop_norm against bound2.
+// rec3 is read (the pre-fill) and written: the sum of Rt+(i, 0)^2, rr_in as the kernel found it in the XCtrl, 1.0 where the test set the stop word.
+extern "C" int dkmc_xtb_test_step1_norm(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank,
+                                        int ns, double *qs, double bound2, double rr_in, double *rec3, dkmc_xtb_ctrl *ctrl_out)
+{
+    if (!rec3 || !ctrl_out || it < 0) return dkmc_fail(13, "xtb_test_step1_norm: bad arguments", __FILE__, __LINE__);
+    return xtb_test_step1_run(m, it, mats, done_word, y0, panels, sc, nsrank, ns, qs, bound2, rr_in, rec3, ctrl_out);
+}
+// Test aid: column 0 of Rt as the last round of the last one-polynomial solve left it (the panel a stop of that round measured), rt0 [m]; fails where the
+// last one-GPU block solve ran no such round or m is not its row count
+extern "C" int dkmc_debug_get_x_stop_rt0(int m, double *rt0)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    const double *R = (const double *)e.buf[S_XTB_PANELS];
+    if (!rt0 || !R || e.x_stop_last.fired == 0 || e.x_stop_last.m != m) return dkmc_fail(13, "get_x_stop_rt0: no one-polynomial round of that size", __FILE__, __LINE__);
+    HIPCHK(hipMemcpy2DAsync(rt0, 8, R, (size_t)XB_SP * 8, 8, (size_t)m, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return e.err_code;
 }

@@ -524,6 +524,13 @@ static int xtb_poly1_degree(const Engine &e, int d)
 }
 // which form a preconditioned one-GPU solve runs (dkmc_set_x_poly_form): a pinned degree is a statement about L and keeps the split form under 2
 static bool xtb_poly_one(const Engine &e) { return e.x_poly_form == 1 || (e.x_poly_form == 2 && e.x_poly_auto != 0); }
+// Where the norm stop test runs by size (dkmc_set_x_stop_form(2)): rows from which it paid.  Same-box A/B against the bound alone, three alternating runs each
+// (profiles/ab_bench_x_stop_form.txt), margin 1: 57 782 rows 226.1 -> 223.8 steps/s (-1.0 %, inside the spread of 2.6 %: the loop runs 8.6 sweeps there and
+// saves 0.2, the fold launch costs as much), 160 526 rows 52.54 -> 57.69 (+9.8 %, 3 x the spread is 5.2 %), 642 101 rows 6.419 -> 7.215 (+12.4 %, 3 x the
+// spread is 0.5 %).  Nothing was measured in between: the gate is the geometric midpoint of the first two sizes.
+static const int xb_stop_rows = 96000;
+static int xtb_stop_rule(int m) { return m >= xb_stop_rows ? 1 : 0; }
+extern "C" int dkmc_xtb_stop_rule(int m) { return xtb_stop_rule(m); }         // host code only (no HIP call)
 // ---- the degree a solve runs ---------------------------------------------------------------------------------------------------------------
 // A sweep costs (tile pass + row passes) + 2 d N products and the sweep count falls with d, so the best degree grows with the share of the tile pass,
 // that is with the rows m of the system.  Step function of m from profiles/x_poly_degree_by_size.jsonl (steady warm-started steps, degrees 6 ... 16,

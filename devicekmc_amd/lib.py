@@ -80,6 +80,13 @@ SYMBOLS = {
     "dkmc_get_x_poly_form_used": (_I, []),
     "dkmc_get_x_poly_products": (_I, []),
     "dkmc_debug_set_x_poly1_degree": (None, [_I]),
+    "dkmc_set_x_stop_form": (None, [_I]),
+    "dkmc_get_x_stop_form": (_I, []),
+    "dkmc_set_x_stop_margin": (None, [_D]),
+    "dkmc_get_x_stop_margin": (_D, []),
+    "dkmc_get_x_stop_info": (_I, [c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "dkmc_debug_get_x_stop_rt0": (_I, [_I, vp]),
+    "dkmc_xtb_stop_rule": (_I, [_I]),
     "dkmc_set_x_tile_f32": (None, [_I]),
     "dkmc_get_x_tile_f32": (_I, []),
     "dkmc_set_x_tile_drop": (None, [_D]),
@@ -254,6 +261,7 @@ SYMBOLS = {
     "dkmc_xtb_test_step": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, vp, vp, _I, vp, _I, vp, vp]),
     "dkmc_xtb_test_gram1": (_I, [_I, vp, _I, _I, vp]),
     "dkmc_xtb_test_step1": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, _I, vp]),
+    "dkmc_xtb_test_step1_norm": (_I, [_I, _I, vp, _I, vp, vp, vp, vp, _I, vp, _D, _D, vp, C.POINTER(dkmc_xtb_ctrl)]),
     "dkmc_kcg_emulate_slabs": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _D, _D, _D, _I, _I, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong)]),
     "dkmc_xtb_emulate_slabs": (_I, [_I, _I, _D, _I, _I, c_dbl_p, c_int_p, c_int_p, c_dbl_p, C.POINTER(C.c_longlong), c_int_p]),
     "dkmc_xtb_slab_last": (_I, [c_int_p, C.POINTER(C.c_longlong), c_dbl_p]),

@@ -184,6 +184,24 @@ void dkmc_set_x_poly_form(int form);
 int dkmc_get_x_poly_form(void);
 int dkmc_get_x_poly_form_used(void);
 int dkmc_get_x_poly_products(void);
+/* Stop test of the one-polynomial form.  Its loop works with Rt and Z = q(N) Rt and tests (Rt'Z)_00 <= tol^2 min q, which BOUNDS what the contract
+ * names -- ||Rt(:, 0)||_2 <= tol on the Jacobi-scaled system -- and so solves further than asked.
+ * dkmc_set_x_stop_form(0): that bound alone, bit for bit the loop without the feature.  1: beside it the norm itself, ||Rt+(:, 0)||_2 <= kappa tol, from partial sums the panel-step
+ * kernel writes for its rows and one workgroup adds in a fixed order (csrc/xtb.hip: k_xtb_step1, k_xtb_stop_norm; no atomics); whichever fires first
+ * ends the loop.  First round of a one-GPU one-polynomial solve only: the true-residual check behind the loop and the re-entry rounds (which stop on
+ * the bound alone) are as before; the split form, the plain, sharded and slab loops are untouched.  2 (default): 1 for systems of 96 000 rows and
+ * more, 0 below -- where it was measured to pay (profiles/ab_bench_x_stop_form.txt): at 9.4e5 sites 36.05 -> 30.9 sweeps per step.  Other
+ * values select 0.  Solutions under 1 differ from those under 0 within the stop test (I_macro by 1.4e-7 relative at 9.4e5 sites); events are the same.
+ * dkmc_set_x_stop_margin(kappa): kappa in (0, 1], default 1 (anything else restores it) -- the largest of {1, 0.8, 1 / 1.5} without a re-entry round over
+ * 100 steps at 9.4e5 sites; a smaller one leaves slack for the fp32 tile image's perturbation (the true residual exceeded the norm by 1 % at the most).
+ * dkmc_get_x_stop_info, for the last round of the last one-polynomial solve (returns 1 and fired = 0 where there was none): fired 1 = the bound (or a
+ * breakdown) ended it, 2 = the norm test; norm = ||Rt(:, 0)|| at the stop (-1 under form 0: not measured); rz = (Rt'Z)_00 there; true_residual =
+ * ||A y - b|| of column 0 from the pass behind the loop.  Any pointer may be null. */
+void dkmc_set_x_stop_form(int form);
+int dkmc_get_x_stop_form(void);
+void dkmc_set_x_stop_margin(double kappa);
+double dkmc_get_x_stop_margin(void);
+int dkmc_get_x_stop_info(int *fired, double *norm, double *rz, double *true_residual);
 /* How the preconditioner's N products read N: 1 (default) from a copy packed once per solve -- slices of four rows as wide as their longest row,
  * the column's scaling folded into the weights (csrc/xtb_precond.h: k_xtb_npack, k_xtb_nmulp16 / k_xtb_nmulp); 0 from the CSR of the neighbour part (k_xtb_nmul).
  * Both give the same bits; 0 is kept for comparisons. */

@@ -89,6 +89,17 @@ void dkmc_debug_set_x_poly1_degree(int n);
 int dkmc_xtb_test_gram1(int m, const double *const *panels, int ng, int done_word, double *gfin);
 int dkmc_xtb_test_step1(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
                         double *qs);
+/* The norm stop test of that form (dkmc_set_x_stop_form; csrc/xtb.hip: k_xtb_stop_norm).
+ * dkmc_xtb_test_step1_norm: dkmc_xtb_test_step1 for it >= 0 with the kernel's partial sums of Rt+(i, 0)^2 switched on (pre-filled with NaN), then ONE
+ *   launch of k_xtb_stop_norm against bound2, on an XCtrl with done = done_word and rr = {rr_in, rr_in}.  rec3 is read (the pre-fill) and written:
+ *   the sum, rr_in as the kernel read it, 1.0 where the test set the stop word (done = it + 2, iters = it + 1); ctrl_out receives the XCtrl.
+ * dkmc_debug_get_x_stop_rt0: column 0 of Rt as the last round of the last one-polynomial solve left it -- the panel whose norm dkmc_get_x_stop_info
+ *   reports under form 1; rt0 [m], m = rows of X.  Fails where there was no such round or m differs. */
+int dkmc_xtb_test_step1_norm(int m, int it, const double *mats, int done_word, double *y0, double *const *panels, const double *sc, const int *nsrank, int ns,
+                             double *qs, double bound2, double rr_in, double *rec3, dkmc_xtb_ctrl *ctrl_out);
+int dkmc_debug_get_x_stop_rt0(int m, double *rt0);
+/* The size rule of dkmc_set_x_stop_form(2) (csrc/xtb_precond.h: xtb_stop_rule): 1 when a system of m rows runs the norm test; host code only. */
+int dkmc_xtb_stop_rule(int m);
 /* Measurement aid: average duration [us] of the tile x panel kernel of the block-CG over the X left resident by the last single-GPU solve
  * (`reps` launches).  variant 0: as a solve runs it; on the round-4 form of the loop: 1: without its matrix instructions (tile stream + LDS
  * traffic); 2: without re-reading the tile stream (matrix instructions + LDS traffic); 3: operand stages of one k-pair; 4: without LDS
