@@ -816,11 +816,16 @@ int kcg_run_start(KcgRun &c, KCtrl *ctrl_out)
     KCHK();
     return 0;
 }
+// the product of an iteration: t = S K q and the block partials of p.t, r.t and t.t, on the form c holds
+static void kcg_run_product(KcgRun &c, hipStream_t st)
+{
+    KC_APPLY(0, c.cf, c.diag, (const double *)c.s, (const double *)c.q, c.w_high, c.w_low,
+             (const double *)c.p, c.t, c.part, (const KCtrl *)c.ctrl, (const double *)nullptr, c.r, (double *)nullptr);
+}
 int kcg_run_iterate(KcgRun &c, int it)
 {
     hipStream_t st = eng().stream;
-    KC_APPLY(0, c.cf, c.diag, (const double *)c.s, (const double *)c.q, c.w_high, c.w_low,
-             (const double *)c.p, c.t, c.part, (const KCtrl *)c.ctrl, (const double *)nullptr, c.r, (double *)nullptr);
+    kcg_run_product(c, st);
     if (c.kb && !c.kbw) hipLaunchKernelGGL(k_kc_step, dim3(c.gv), dim3(KC_NT), 0, st, c.m, it, c.part, c.p, (const double *)c.t, c.y, c.r, (const double *)c.s, c.q, c.ctrl, c.tol2, c.npa);
     else {
         hipLaunchKernelGGL(k_kc_update, dim3(c.gv), dim3(KC_NT), 0, st, c.m, it, (const double *)c.part, c.npa, (const double *)c.p, (const double *)c.t, c.y, c.r, c.part + 3 * KC_NPA, (const KCtrl *)c.ctrl);
@@ -868,6 +873,26 @@ int kcg_run(KcgRun &c, KCtrl &h, int first)
     return kcg_run_unscale(c);
 }
 
+// Diagonal, right-hand side and stored words of K for the current elements / charges, in the layout of the form kb holds (null: CSR positions).
+static void kcg_assemble(int cb, int m, int N_left, const int *element, const int *charge, MetalSet ms, double high_G, double low_G,
+                         const int *rp, const int *ci, const int *lrp, const int *lci, const int *rrp, const int *rci,
+                         double VL, double VR, const KBlocked *kb, int *cf, double *diag, double *rhs)
+{
+    hipStream_t st = eng().stream;
+    const bool kbw = kb && kb->form == 2, kbw2 = kbw && kb->word_bytes == 2;
+    const int ab = (m + 15) / 16;
+    kc_with_cb(cb, [&](auto cbv) {
+        constexpr int CB = decltype(cbv)::value;
+        if (kbw2) hipLaunchKernelGGL((k_kbw_assemble<CB, 2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
+                                     (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else if (kbw) hipLaunchKernelGGL((k_kbw_assemble<CB, 4>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
+                                         (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else if (kb) hipLaunchKernelGGL((k_kb_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol,
+                                        element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+        else hipLaunchKernelGGL((k_kc_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
+    });
+}
+
 // Assemble K for the current elements / charges and solve K y = rhs in place in y (warm start = y on entry).
 // kb: the blocked form of the pattern (or nullptr): the whole solve then runs in the blocked order, y is gathered on entry and scattered on exit.
 static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag, const double *s, const double *b, double high_G, double low_G, double *y, double *q0,
@@ -892,17 +917,7 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     double *diag = rhs + m;
     KcgRun c;
     if (int rc = kcg_run_setup(c, m, rp, nnz, kb, cf, diag, rhs, rhs + 2 * (size_t)m, high_G, low_G, e.cg_tol, y_site)) return rc;
-    const int ab = (m + 15) / 16;
-    kc_with_cb(cb, [&](auto cbv) {
-        constexpr int CB = decltype(cbv)::value;
-        if (kbw2) hipLaunchKernelGGL((k_kbw_assemble<CB, 2>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
-                                     (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else if (kbw) hipLaunchKernelGGL((k_kbw_assemble<CB, 4>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, kb->nb, (const int4 *)kb->blk, (const int4 *)kb->seg, (const int *)kb->perm,
-                                         (const int *)kb->pcol, element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else if (kb) hipLaunchKernelGGL((k_kb_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, kb->R, (const int4 *)kb->blk, (const int *)kb->perm, (const int *)kb->pcol,
-                                        element, charge, ms, high_G, low_G, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-        else hipLaunchKernelGGL((k_kc_assemble<CB>), dim3(ab), dim3(KC_NT), 0, st, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, cf, diag, rhs);
-    });
+    kcg_assemble(cb, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, kb, cf, diag, rhs);
     // more than one rank (or the emulation of it) on a system above the size of the blocked form: the loop distributed by row slabs
     const bool slab = !kb && row_y && row_z && (emu_nr > 0 || (e.k_slab && comm_attached() && comm_nranks() > 1 && comm_nranks() <= XS_MAXR));
     if (slab) {
@@ -926,6 +941,49 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
     e.stats.kcg_bytes = kcg_run_bytes(c);
     if (iters_out) *iters_out = h.iters;
     if (rr_out) *rr_out = kb && !kbw ? h.rr[0] : h.rr[h.iters & 1];
+    return e.err_code;
+}
+
+// Test aid (dkmc_debug_k_system): K assembled as above on the form kb holds (null: CSR positions; the windowed form is refused), its diagonal and
+// right-hand side in the pattern's row order, and t = K v from ONE launch of the form's product kernel with s = 1, q = v and a cleared stop
+// word.  v, t, diag_out, rhs_out: host arrays of m doubles in the pattern's row order (the blocked order is entered and left through perm, on the
+// host).  Writes only scratch that every solve rewrites before it reads it.
+int kcg_debug_system(int cb, int m, int N_left, const int *element, const int *charge, MetalSet ms, double high_G, double low_G,
+                     const int *rp, const int *ci, int nnz, const int *lrp, const int *lci, const int *rrp, const int *rci,
+                     double VL, double VR, const KBlocked *kb, const double *v, double *t, double *diag_out, double *rhs_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m <= 0 || !v || !t || !diag_out || !rhs_out) return dkmc_fail(13, "debug_k_system: bad arguments", __FILE__, __LINE__);
+    if (kb && kb->m != m) return dkmc_fail(6, "K-CG: the blocked form belongs to another pattern", __FILE__, __LINE__);
+    if (kb && kb->form == 2) return dkmc_fail(13, "debug_k_system: not for the windowed blocked form", __FILE__, __LINE__);
+    int *cf = (int *)scratch(S_K_DATA, kb ? (size_t)kb->total * 4 : (size_t)nnz * 4);
+    double *rhs = (double *)scratch(S_K_RHS, (size_t)m * 8 * 3);
+    if (!cf || !rhs) return e.err_code;
+    double *diag = rhs + m;
+    KcgRun c;
+    if (int rc = kcg_run_setup(c, m, rp, nnz, kb, cf, diag, rhs, rhs + 2 * (size_t)m, high_G, low_G, e.cg_tol, nullptr)) return rc;
+    kcg_assemble(cb, m, N_left, element, charge, ms, high_G, low_G, rp, ci, lrp, lci, rrp, rci, VL, VR, kb, cf, diag, rhs);
+    std::vector<int> perm((size_t)m);
+    if (kb) HIPCHK(hipMemcpyAsync(perm.data(), kb->perm, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    else for (int i = 0; i < m; ++i) perm[i] = i;
+    std::vector<double> h((size_t)m), ones((size_t)m, 1.0);
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < m; ++i) h[i] = v[perm[i]];
+    HIPCHK(hipMemcpyAsync(c.q, h.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c.s, ones.data(), (size_t)m * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(c.p, 0, (size_t)m * 8, st));
+    HIPCHK(hipMemsetAsync(c.r, 0, (size_t)m * 8, st));
+    HIPCHK(hipMemsetAsync(c.t, 0xff, (size_t)m * 8, st));            // a row no pass writes comes back as NaN
+    HIPCHK(hipMemsetAsync(c.ctrl, 0, sizeof(KCtrl), st));
+    HIPCHK(hipStreamSynchronize(st));                                // (h is refilled below)
+    kcg_run_product(c, st);
+    KCHK();
+    const double *src[3] = {c.t, diag, rhs}; double *dst[3] = {t, diag_out, rhs_out};
+    for (int k = 0; k < 3; ++k) {
+        HIPCHK(hipMemcpyAsync(h.data(), src[k], (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int i = 0; i < m; ++i) dst[k][perm[i]] = h[i];
+    }
     return e.err_code;
 }
 

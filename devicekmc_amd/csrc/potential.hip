@@ -10,6 +10,9 @@ int kcg_assemble_and_solve(int cb, int m, int N_left, const int *element, const 
                            const int *rp, const int *ci, int nnz, const int *lrp, const int *lci, const int *rrp, const int *rci,
                            double VL, double VR, double *y, int *iters_out, double *rr_out, const KBlocked *kb,
                            const double *row_y, const double *row_z, int emu_nr, int emu_time_rank);
+int kcg_debug_system(int cb, int m, int N_left, const int *element, const int *charge, MetalSet ms, double high_G, double low_G,
+                     const int *rp, const int *ci, int nnz, const int *lrp, const int *lci, const int *rrp, const int *rci,
+                     double VL, double VR, const KBlocked *kb, const double *v, double *t, double *diag_out, double *rhs_out);
 void kcg_slab_report(double *times_us, long long *halo_rows);
 void kcg_slab_iter_cap(int cap);
 KBlocked *kpattern_form_build(const int *rp_d, const int *ci_d, int m, int nnz, const double *x_d, const double *y_d, const double *z_d, hipStream_t st);
@@ -221,6 +224,24 @@ static int solve_K(dkmc_gpubuf *buf, int N, int N_left, int N_right, double VL, 
                                   buf->Device_nnz, buf->contact_left_row_ptr, buf->contact_left_col_indices, buf->contact_right_row_ptr,
                                   buf->contact_right_col_indices, VL, VR, field + N_left, iters, rr, kpat_blocked(buf->Device_row_ptr_d),
                                   buf->site_y + N_left, buf->site_z + N_left, 0, -1);
+}
+
+// ---- test aid: the K system solve_K would assemble for this state (dkmc_debug_k_system, devicekmc_hip_debug.h) ------------------------------------
+// rule: 0 potential, 1 CB edge, 2 CB edge on atoms only.  v_site in; t_site = K v, diag_site, rhs_site out: host arrays of m doubles, row r = site
+// N_left + r.  The buffer's fields are not touched.
+extern "C" int dkmc_debug_k_system(dkmc_gpubuf *buf, int rule, int N, int N_left, int N_right, double VL, double VR, double high_G, double low_G, int num_metals,
+                                   const double *v_site, double *t_site, double *diag_site, double *rhs_site)
+{
+    const int m = N - N_left - N_right;
+    if (!buf || rule < 0 || rule > 2) return dkmc_fail(13, "debug_k_system: bad arguments", __FILE__, __LINE__);
+    if (!buf->Device_row_ptr_d || !buf->Device_col_indices_d || !buf->contact_left_row_ptr || !buf->contact_right_row_ptr)
+        return dkmc_fail(6, "K sparsity not initialised (call initialize_sparsity)", __FILE__, __LINE__);
+    if (N_left != N_right || !kpat_matches(buf->Device_row_ptr_d, m, N_left))
+        return dkmc_fail(6, "K sparsity was built for other contact sizes than this solve asks for", __FILE__, __LINE__);
+    MetalSet ms = load_metals(buf->metal_types, num_metals);
+    return kcg_debug_system(rule, m, N_left, buf->site_element, buf->site_charge, ms, high_G, low_G, buf->Device_row_ptr_d, buf->Device_col_indices_d,
+                            buf->Device_nnz, buf->contact_left_row_ptr, buf->contact_left_col_indices, buf->contact_right_row_ptr,
+                            buf->contact_right_col_indices, VL, VR, kpat_blocked(buf->Device_row_ptr_d), v_site, t_site, diag_site, rhs_site);
 }
 
 // ---- test / measurement aid: the slab-distributed CG on K (kcg.hip) with nranks VIRTUAL ranks on ONE GPU ---------------------------------------

@@ -229,6 +229,13 @@ int dkmc_kcg_form_info(dkmc_gpubuf *buf, long long *info /* [9] */);
  * dkmc_set_k_window_word_bytes when the pattern was built; 0 when the pattern has no windowed form: the other two are 0 then too), stored words,
  * bytes of the assembled words one product reads (words x word bytes). */
 int dkmc_kcg_form_words(dkmc_gpubuf *buf, long long *info /* [3] */);
+/* Test aid: the K system a solve of this buffer's state would assemble (rule 0: background potential, 1: CB edge, 2: CB edge on atoms only, with
+ * the contacts at VL and VR), on the form the buffer's pattern holds (CSR positions or blocked; the windowed blocked form is refused).  All four
+ * arrays are host arrays of m = N - N_left - N_right doubles, row r = site N_left + r: diag_site and rhs_site are the assembled diagonal and
+ * right-hand side; t_site = K v_site, formed by ONE launch of the form's own product kernel with unit scaling and a cleared stop word (a row that
+ * launch does not write comes back as NaN).  Changes no field of the buffer and nothing a later solve reads. */
+int dkmc_debug_k_system(dkmc_gpubuf *buf, int rule, int N, int N_left, int N_right, double VL, double VR, double high_G, double low_G, int num_metals,
+                        const double *v_site, double *t_site, double *diag_site, double *rhs_site);
 /* Test aid: position, in 16-bit words from the start of its row, of stored entry `entry` of a row padded to `width` (32 or 64) entries in the 2-byte
  * layout of the windowed blocked form (csrc/kbw_plan.h: kbw_halfword_pos); -1 for any other width or an entry outside the row. */
 int dkmc_debug_kbw_halfword_pos(int width, int entry);
