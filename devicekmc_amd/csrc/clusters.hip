@@ -134,11 +134,11 @@ ClTable table_of(void *base, size_t N)
 
 extern "C" {
 
-void dkmc_debug_set_cluster_round_cap(int cap) { g_round_cap = cap <= 0 ? CL_CAP_DEFAULT : (cap > CL_CAP_MAX ? CL_CAP_MAX : cap); }
+void dkmc_debug_set_cluster_round_cap(int cap) { g_round_cap = clamp_round_cap(cap, CL_CAP_DEFAULT); }
 
 int dkmc_debug_get_cluster_times(double *ms2)
 {
-    if (!g_cl.valid) return dkmc_fail(3, "dkmc_debug_get_cluster_times: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    NEED_FINISHED(g_cl.valid, "dkmc_debug_get_cluster_times", "dkmc_find_clusters");
     if (ms2) { ms2[0] = g_cl.ms_label; ms2[1] = g_cl.ms_sum; }
     return 0;
 }
@@ -182,12 +182,9 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
     int rounds = 0;
     if (int rc = label_rounds(st, N, nn, d_index, d_label, parent, ctrl, cap, &rounds)) return rc;
     if (!rounds) {
-        // not finished: no partial labels go out as valid
-        HIPCHK(hipMemsetAsync(d_label, 0xff, n * sizeof(int), st));
-        HIPCHK(hipStreamSynchronize(st));
         char msg[200];
         snprintf(msg, sizeof(msg), "dkmc_find_clusters: labelling not finished after %d rounds (the cap: dkmc_debug_set_cluster_round_cap); labels set to -1", cap);
-        return dkmc_fail(4, msg, __FILE__, __LINE__);
+        return abandon(st, n, {d_label}, msg, __FILE__, __LINE__);
     }
     HIPCHK(g_cl.timer.mark(1, st));
     // summaries, table, info
@@ -213,7 +210,7 @@ int dkmc_find_clusters(int N, int nn, const int *d_index, const int *d_site_elem
 
 int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vacancy, int *h_flags, double *h_xmin, double *h_xmax, int *rows_out)
 {
-    if (!g_cl.valid) return dkmc_fail(3, "dkmc_copy_cluster_table: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    NEED_FINISHED(g_cl.valid, "dkmc_copy_cluster_table", "dkmc_find_clusters");
     const size_t r = clamp_rows(capacity, g_cl.info.n_components, rows_out);
     if (r == 0) return 0;
     hipStream_t st = eng().stream;
@@ -230,7 +227,7 @@ int dkmc_copy_cluster_table(int capacity, int *h_root, int *h_size, int *h_n_vac
 
 int dkmc_get_cluster_info(int *info8, double *x3)
 {
-    if (!g_cl.valid) return dkmc_fail(3, "dkmc_get_cluster_info: no finished dkmc_find_clusters call", __FILE__, __LINE__);
+    NEED_FINISHED(g_cl.valid, "dkmc_get_cluster_info", "dkmc_find_clusters");
     const ClInfoDev &I = g_cl.info;
     if (info8) {
         info8[0] = I.n_members; info8[1] = I.n_components; info8[2] = I.bridged; info8[3] = I.bridge_root; info8[4] = I.largest_free_size;

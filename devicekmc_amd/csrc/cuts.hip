@@ -31,11 +31,19 @@ struct CuStat {
 };
 struct CutState {
     int valid = 0;
-    long long info[16] = {0};
-    std::vector<int> site, n_bypass, chord, cut, b_root, b_size, b_lo, b_hi, n_first, n_last;
-    std::vector<double> n_xmin, n_xmax;
-    double ms_label = 0.0, ms_rest = 0.0;
+    long long info[16];
+    ResultTable<4> path;             // site, n_bypass, chord, cut
+    ResultTable<4> bypasses;         // root, size, lo, hi
+    ResultTable<2, 2> necks;         // first, last; xmin, xmax
+    double ms_label, ms_rest;
     PhaseTimer<3> timer;
+    void reset()
+    {
+        memset(info, 0, sizeof(info));
+        info[5] = -1;
+        path.clear(); bypasses.clear(); necks.clear();
+        ms_label = ms_rest = 0.0;
+    }
 } g_cu;
 int g_cu_round_cap = CU_CAP_DEFAULT;
 
@@ -248,24 +256,15 @@ __global__ __launch_bounds__(CU_NT) void k_cu_necks(int L, const int *__restrict
     }
 }
 
-void cut_reset()
-{
-    memset(g_cu.info, 0, sizeof(g_cu.info));
-    g_cu.info[5] = -1;
-    for (auto *v : {&g_cu.site, &g_cu.n_bypass, &g_cu.chord, &g_cu.cut, &g_cu.b_root, &g_cu.b_size, &g_cu.b_lo, &g_cu.b_hi, &g_cu.n_first, &g_cu.n_last}) v->clear();
-    g_cu.n_xmin.clear(); g_cu.n_xmax.clear();
-    g_cu.ms_label = g_cu.ms_rest = 0.0;
-}
-
 }   // namespace
 
 extern "C" {
 
-void dkmc_debug_set_cut_round_cap(int cap) { g_cu_round_cap = cap <= 0 ? CU_CAP_DEFAULT : (cap > CU_CAP_MAX ? CU_CAP_MAX : cap); }
+void dkmc_debug_set_cut_round_cap(int cap) { g_cu_round_cap = clamp_round_cap(cap, CU_CAP_DEFAULT); }
 
 int dkmc_debug_get_cut_times(double *ms2)
 {
-    if (!g_cu.valid) return dkmc_fail(3, "dkmc_debug_get_cut_times: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    NEED_FINISHED(g_cu.valid, "dkmc_debug_get_cut_times", "dkmc_find_cuts");
     if (ms2) { ms2[0] = g_cu.ms_label; ms2[1] = g_cu.ms_rest; }
     return 0;
 }
@@ -278,7 +277,7 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
         return dkmc_fail(3, "dkmc_find_cuts: bad arguments (N >= 0, nn >= 1, 0 <= path_len <= N, device arrays of N sites, a path of path_len sites)",
                          __FILE__, __LINE__);
     clamp_seeds(N, n_left_sites, n_right_sites);
-    cut_reset();
+    g_cu.reset();
     if (N == 0) { g_cu.valid = 1; return 0; }
     hipStream_t st = eng().stream;
     const int cap = g_cu_round_cap, L = path_len;
@@ -314,14 +313,11 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
         HIPCHK(hipMemcpyAsync(&h_stat, d_stat, sizeof(CuStat), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (h_stat.err != ~0ull) {
-            HIPCHK(hipMemsetAsync(d_site_role, 0xff, n * sizeof(int), st));
-            HIPCHK(hipMemsetAsync(d_site_bypass, 0xff, n * sizeof(int), st));
-            HIPCHK(hipStreamSynchronize(st));
             const int why = (int)(h_stat.err & 7ull);
             char msg[240];
             snprintf(msg, sizeof(msg), "dkmc_find_cuts: not a left-to-right path over the member links: row %lld %s; site_role and site_bypass set to -1",
                      (long long)(h_stat.err >> 3), kReason[why >= 1 && why <= 5 ? why : 0]);
-            return dkmc_fail(4, msg, __FILE__, __LINE__);
+            return abandon(st, n, {d_site_role, d_site_bypass}, msg, __FILE__, __LINE__);
         }
     }
     hipLaunchKernelGGL(k_cu_members, dim3(site_blocks), dim3(CU_NT), 0, st, N, d_label, (const int *)pos, root, parent);
@@ -330,14 +326,10 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
     int rounds = 0;
     if (int rc = label_rounds(st, N, nn, d_index, root, parent, ctrl, cap, &rounds)) return rc;
     if (!rounds) {
-        // not finished: no partial labels go out as valid
-        HIPCHK(hipMemsetAsync(d_site_role, 0xff, n * sizeof(int), st));
-        HIPCHK(hipMemsetAsync(d_site_bypass, 0xff, n * sizeof(int), st));
-        HIPCHK(hipStreamSynchronize(st));
         char msg[240];
         snprintf(msg, sizeof(msg), "dkmc_find_cuts: off-path labelling not finished after %d rounds (the cap: dkmc_debug_set_cut_round_cap); "
                  "site_role and site_bypass set to -1", cap);
-        return dkmc_fail(4, msg, __FILE__, __LINE__);
+        return abandon(st, n, {d_site_role, d_site_bypass}, msg, __FILE__, __LINE__);
     }
     HIPCHK(g_cu.timer.mark(2, st));
     // attachment, roles, tables
@@ -369,33 +361,20 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
     const size_t nb = (size_t)h_stat.n_byp, nk = (size_t)h_stat.n_necks;
     if (h_stat.n_byp < 0 || nb > n || h_stat.n_necks < 0 || nk > (size_t)L) return dkmc_fail(4, "dkmc_find_cuts: table counts outside their range", __FILE__, __LINE__);
     std::vector<unsigned long long> h_min(nk), h_max(nk);
-    g_cu.b_root.resize(nb); g_cu.b_size.resize(nb); g_cu.b_lo.resize(nb); g_cu.b_hi.resize(nb);
-    g_cu.site.resize(L); g_cu.n_bypass.resize(L); g_cu.chord.resize(L); g_cu.cut.resize(L);
-    g_cu.n_first.resize(nk); g_cu.n_last.resize(nk); g_cu.n_xmin.resize(nk); g_cu.n_xmax.resize(nk);
-    if (nb) {
-        HIPCHK(hipMemcpyAsync(g_cu.b_root.data(), t_root, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.b_size.data(), t_size, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.b_lo.data(), t_lo, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.b_hi.data(), t_hi, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    if (L > 0) {
-        HIPCHK(hipMemcpyAsync(g_cu.site.data(), d_path, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.n_bypass.data(), t_nb, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.chord.data(), t_ch, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.cut.data(), t_cut, (size_t)L * sizeof(int), hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = fetch_columns(st, g_cu.bypasses, nb, {t_root, t_size, t_lo, t_hi})) return rc;
+    if (int rc = fetch_columns(st, g_cu.path, (size_t)L, {d_path, t_nb, t_ch, t_cut})) return rc;
+    if (int rc = fetch_columns(st, g_cu.necks, nk, {first, last})) return rc;
     if (nk) {
-        HIPCHK(hipMemcpyAsync(g_cu.n_first.data(), first, nk * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_cu.n_last.data(), last, nk * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_min.data(), kmin, nk * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_max.data(), kmax, nk * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));
+    const std::vector<int> &n_first = g_cu.necks.i[0], &n_last = g_cu.necks.i[1];
     long long longest = 0, longest_first = -1;
     for (size_t j = 0; j < nk; ++j) {
-        g_cu.n_xmin[j] = d_site_x ? key_dbl(h_min[j]) : INFINITY; g_cu.n_xmax[j] = d_site_x ? key_dbl(h_max[j]) : -INFINITY;
-        const long long len = (long long)g_cu.n_last[j] - g_cu.n_first[j] + 1;
-        if (len > longest) { longest = len; longest_first = g_cu.n_first[j]; }       // ascending rows: the smallest position on ties
+        key_range(d_site_x != nullptr, h_min[j], h_max[j], &g_cu.necks.d[0][j], &g_cu.necks.d[1][j]);     // a neck has a site: no empty row
+        const long long len = (long long)n_last[j] - n_first[j] + 1;
+        if (len > longest) { longest = len; longest_first = n_first[j]; }            // ascending rows: the smallest position on ties
     }
     const long long info[12] = {L > 0 ? 1 : 0, L, h_stat.n_cut, (long long)nk, longest, longest_first, (long long)nb, h_stat.off_comps, h_stat.off_members,
                                 h_stat.max_nb, h_stat.n_chord, rounds};
@@ -409,44 +388,29 @@ int dkmc_find_cuts(int N, int nn, const int *d_index, const int *d_label, const 
 
 int dkmc_get_cut_info(long long *info16)
 {
-    if (!g_cu.valid) return dkmc_fail(3, "dkmc_get_cut_info: no finished dkmc_find_cuts call", __FILE__, __LINE__);
+    NEED_FINISHED(g_cu.valid, "dkmc_get_cut_info", "dkmc_find_cuts");
     if (info16) memcpy(info16, g_cu.info, sizeof(g_cu.info));
     return 0;
 }
 
 int dkmc_copy_cut_path(int capacity, int *h_site, int *h_n_bypass, int *h_chord, int *h_cut, int *rows_out)
 {
-    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_path: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_cu.site.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_site) memcpy(h_site, g_cu.site.data(), r * sizeof(int));
-    if (h_n_bypass) memcpy(h_n_bypass, g_cu.n_bypass.data(), r * sizeof(int));
-    if (h_chord) memcpy(h_chord, g_cu.chord.data(), r * sizeof(int));
-    if (h_cut) memcpy(h_cut, g_cu.cut.data(), r * sizeof(int));
+    NEED_FINISHED(g_cu.valid, "dkmc_copy_cut_path", "dkmc_find_cuts");
+    g_cu.path.copy_out(capacity, rows_out, {h_site, h_n_bypass, h_chord, h_cut});
     return 0;
 }
 
 int dkmc_copy_cut_bypasses(int capacity, int *h_root, int *h_size, int *h_lo, int *h_hi, int *rows_out)
 {
-    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_bypasses: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_cu.b_root.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_root) memcpy(h_root, g_cu.b_root.data(), r * sizeof(int));
-    if (h_size) memcpy(h_size, g_cu.b_size.data(), r * sizeof(int));
-    if (h_lo) memcpy(h_lo, g_cu.b_lo.data(), r * sizeof(int));
-    if (h_hi) memcpy(h_hi, g_cu.b_hi.data(), r * sizeof(int));
+    NEED_FINISHED(g_cu.valid, "dkmc_copy_cut_bypasses", "dkmc_find_cuts");
+    g_cu.bypasses.copy_out(capacity, rows_out, {h_root, h_size, h_lo, h_hi});
     return 0;
 }
 
 int dkmc_copy_cut_necks(int capacity, int *h_first, int *h_last, double *h_xmin, double *h_xmax, int *rows_out)
 {
-    if (!g_cu.valid) return dkmc_fail(3, "dkmc_copy_cut_necks: no finished dkmc_find_cuts call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_cu.n_first.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_first) memcpy(h_first, g_cu.n_first.data(), r * sizeof(int));
-    if (h_last) memcpy(h_last, g_cu.n_last.data(), r * sizeof(int));
-    if (h_xmin) memcpy(h_xmin, g_cu.n_xmin.data(), r * sizeof(double));
-    if (h_xmax) memcpy(h_xmax, g_cu.n_xmax.data(), r * sizeof(double));
+    NEED_FINISHED(g_cu.valid, "dkmc_copy_cut_necks", "dkmc_find_cuts");
+    g_cu.necks.copy_out(capacity, rows_out, {h_first, h_last}, {h_xmin, h_xmax});
     return 0;
 }
 

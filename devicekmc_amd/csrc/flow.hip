@@ -39,11 +39,19 @@ struct FlStat {
 };
 struct FlowState {
     int valid = 0;
-    long long info[16] = {0};
-    double x4[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
-    std::vector<int> col[FL_COLS], site;
-    double ms[3] = {0.0, 0.0, 0.0};
+    long long info[16];
+    double x4[4];
+    ResultTable<FL_COLS> strands;    // the columns of dkmc_copy_flow_strands, in its order
+    ResultTable<1> sites;
+    double ms[3];
     PhaseTimer<3> timer;
+    void reset()
+    {
+        memset(info, 0, sizeof(info));
+        x4[0] = x4[2] = INFINITY; x4[1] = x4[3] = -INFINITY;
+        strands.clear(); sites.clear();
+        ms[0] = ms[1] = ms[2] = 0.0;
+    }
 } g_fl;
 int g_fl_round_cap = FL_CAP_MAX;
 
@@ -302,34 +310,15 @@ __global__ __launch_bounds__(FL_NT) void k_fl_sites(int N, int rows, const int2 
     }
 }
 
-void flow_reset()
-{
-    memset(g_fl.info, 0, sizeof(g_fl.info));
-    g_fl.x4[0] = g_fl.x4[2] = INFINITY; g_fl.x4[1] = g_fl.x4[3] = -INFINITY;
-    for (auto &c : g_fl.col) c.clear();
-    g_fl.site.clear();
-    g_fl.ms[0] = g_fl.ms[1] = g_fl.ms[2] = 0.0;
-}
-
-// a call that cannot deliver: no partial result goes out as valid
-int flow_abandon(hipStream_t st, size_t n, int *zone, int *strand, const char *msg)
-{
-    HIPCHK(hipMemsetAsync(zone, 0xff, n * sizeof(int), st));
-    HIPCHK(hipMemsetAsync(strand, 0xff, n * sizeof(int), st));
-    HIPCHK(hipStreamSynchronize(st));
-    flow_reset();
-    return dkmc_fail(4, msg, __FILE__, __LINE__);
-}
-
 }   // namespace
 
 extern "C" {
 
-void dkmc_debug_set_flow_round_cap(int cap) { g_fl_round_cap = cap <= 0 ? FL_CAP_MAX : (cap > FL_CAP_MAX ? FL_CAP_MAX : cap); }
+void dkmc_debug_set_flow_round_cap(int cap) { g_fl_round_cap = clamp_round_cap(cap, FL_CAP_MAX); }
 
 int dkmc_debug_get_flow_times(double *ms3)
 {
-    if (!g_fl.valid) return dkmc_fail(3, "dkmc_debug_get_flow_times: no finished dkmc_find_flow call", __FILE__, __LINE__);
+    NEED_FINISHED(g_fl.valid, "dkmc_debug_get_flow_times", "dkmc_find_flow");
     if (ms3) memcpy(ms3, g_fl.ms, sizeof(g_fl.ms));
     return 0;
 }
@@ -341,7 +330,7 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
     if (N < 0 || nn < 1 || max_strands < 1 || max_strands > FL_STRANDS_MAX || (N > 0 && (!d_index || !d_label || !d_site_zone || !d_site_strand)))
         return dkmc_fail(3, "dkmc_find_flow: bad arguments (N >= 0, nn >= 1, 1 <= max_strands <= 4096, device arrays of N sites)", __FILE__, __LINE__);
     clamp_seeds(N, n_left_sites, n_right_sites);
-    flow_reset();
+    g_fl.reset();
     if (N == 0) { g_fl.valid = 1; return 0; }
     hipStream_t st = eng().stream;
     const int cap = g_fl_round_cap;
@@ -379,7 +368,7 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
             char msg[240];
             snprintf(msg, sizeof(msg), "dkmc_find_flow: search %d not finished after %d rounds (the cap: dkmc_debug_set_flow_round_cap); "
                      "site_zone and site_strand set to -1", searches + 1, cap);
-            return flow_abandon(st, n, d_site_zone, d_site_strand, msg);
+            return abandon(st, n, {d_site_zone, d_site_strand}, msg, __FILE__, __LINE__);
         }
         ++searches;
         rounds_all += rounds;
@@ -402,7 +391,7 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
     if (status == 0 || status == 1) {
         int found = 0, E = 0;
         if (int rc = search(mlvl, near_r, near_l, 1, &found, &E)) return rc;
-        if (found) return flow_abandon(st, n, d_site_zone, d_site_strand, "dkmc_find_flow: the mirrored closing search found an exit");
+        if (found) return abandon(st, n, {d_site_zone, d_site_strand}, "dkmc_find_flow: the mirrored closing search found an exit", __FILE__, __LINE__);
     }
     HIPCHK(g_fl.timer.mark(2, st));
     // zones, counts, tables
@@ -428,20 +417,19 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
         char msg[200];
         snprintf(msg, sizeof(msg), "dkmc_find_flow: the strands are not consistent (walk code %d, %d first sites for %d strands); "
                  "site_zone and site_strand set to -1", h_stat.err, h_stat.n_strands, W);
-        return flow_abandon(st, n, d_site_zone, d_site_strand, msg);
+        return abandon(st, n, {d_site_zone, d_site_strand}, msg, __FILE__, __LINE__);
     }
     long long longest = 0, shortest = 0;
     if (W > 0) {
-        for (int c = 0; c < FL_COLS; ++c) {
-            g_fl.col[c].resize(W);
-            HIPCHK(hipMemcpyAsync(g_fl.col[c].data(), tab + (size_t)c * W, (size_t)W * sizeof(int), hipMemcpyDeviceToHost, st));
-        }
-        g_fl.site.resize(h_stat.n_sites);
-        HIPCHK(hipMemcpyAsync(g_fl.site.data(), ssites, (size_t)h_stat.n_sites * sizeof(int), hipMemcpyDeviceToHost, st));
+        const int *cols[FL_COLS];
+        for (int c = 0; c < FL_COLS; ++c) cols[c] = tab + (size_t)c * W;
+        if (int rc = fetch_columns(st, g_fl.strands, (size_t)W, cols)) return rc;
+        if (int rc = fetch_columns(st, g_fl.sites, (size_t)h_stat.n_sites, {ssites})) return rc;
         HIPCHK(g_fl.timer.mark(3, st));
         HIPCHK(hipStreamSynchronize(st));
-        shortest = g_fl.col[2][0];
-        for (int len : g_fl.col[2]) { longest = len > longest ? len : longest; shortest = len < shortest ? len : shortest; }
+        const std::vector<int> &length = g_fl.strands.i[2];
+        shortest = length[0];
+        for (int len : length) { longest = len > longest ? len : longest; shortest = len < shortest ? len : shortest; }
     } else {
         HIPCHK(g_fl.timer.mark(3, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -449,10 +437,9 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
     const long long info[12] = {status, status == 2 ? -1 : W, h_stat.shore_l, h_stat.shore_r, h_stat.shared, h_stat.interior, h_stat.near_l, h_stat.near_r,
                                 searches, rounds_all, longest, shortest};
     memcpy(g_fl.info, info, sizeof(info));
-    if (d_site_x && full && W > 0) {
-        g_fl.x4[0] = key_dbl(h_stat.kmin_l); g_fl.x4[1] = key_dbl(h_stat.kmax_l);
-        g_fl.x4[2] = key_dbl(h_stat.kmin_r); g_fl.x4[3] = key_dbl(h_stat.kmax_r);
-    }
+    const bool has_x = d_site_x && full && W > 0;             // else the empty ranges of the reset
+    key_range(has_x, h_stat.kmin_l, h_stat.kmax_l, &g_fl.x4[0], &g_fl.x4[1]);
+    key_range(has_x, h_stat.kmin_r, h_stat.kmax_r, &g_fl.x4[2], &g_fl.x4[3]);
     float ms[3] = {0.f, 0.f, 0.f};
     HIPCHK(g_fl.timer.read(ms));
     for (int i = 0; i < 3; ++i) g_fl.ms[i] = ms[i];
@@ -462,7 +449,7 @@ int dkmc_find_flow(int N, int nn, const int *d_index, const int *d_label, const 
 
 int dkmc_get_flow_info(long long *info16, double *x4)
 {
-    if (!g_fl.valid) return dkmc_fail(3, "dkmc_get_flow_info: no finished dkmc_find_flow call", __FILE__, __LINE__);
+    NEED_FINISHED(g_fl.valid, "dkmc_get_flow_info", "dkmc_find_flow");
     if (info16) memcpy(info16, g_fl.info, sizeof(g_fl.info));
     if (x4) memcpy(x4, g_fl.x4, sizeof(g_fl.x4));
     return 0;
@@ -471,20 +458,16 @@ int dkmc_get_flow_info(long long *info16, double *x4)
 int dkmc_copy_flow_strands(int capacity, int *h_first_site, int *h_last_site, int *h_length, int *h_offset, int *h_left_seed, int *h_right_seed,
                            int *h_cut_left_site, int *h_cut_left_pos, int *h_cut_right_site, int *h_cut_right_pos, int *rows_out)
 {
-    if (!g_fl.valid) return dkmc_fail(3, "dkmc_copy_flow_strands: no finished dkmc_find_flow call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_fl.col[0].size(), rows_out);
-    int *const out[FL_COLS] = {h_first_site, h_last_site, h_length, h_offset, h_left_seed, h_right_seed, h_cut_left_site, h_cut_left_pos, h_cut_right_site,
-                               h_cut_right_pos};
-    for (int c = 0; r && c < FL_COLS; ++c)
-        if (out[c]) memcpy(out[c], g_fl.col[c].data(), r * sizeof(int));
+    NEED_FINISHED(g_fl.valid, "dkmc_copy_flow_strands", "dkmc_find_flow");
+    g_fl.strands.copy_out(capacity, rows_out, {h_first_site, h_last_site, h_length, h_offset, h_left_seed, h_right_seed, h_cut_left_site, h_cut_left_pos,
+                                               h_cut_right_site, h_cut_right_pos});
     return 0;
 }
 
 int dkmc_copy_flow_strand_sites(int capacity, int *h_site, int *rows_out)
 {
-    if (!g_fl.valid) return dkmc_fail(3, "dkmc_copy_flow_strand_sites: no finished dkmc_find_flow call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_fl.site.size(), rows_out);
-    if (r && h_site) memcpy(h_site, g_fl.site.data(), r * sizeof(int));
+    NEED_FINISHED(g_fl.valid, "dkmc_copy_flow_strand_sites", "dkmc_find_flow");
+    g_fl.sites.copy_out(capacity, rows_out, {h_site});
     return 0;
 }
 

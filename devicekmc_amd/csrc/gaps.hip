@@ -39,12 +39,20 @@ struct GpCtrl {
     unsigned long long pairs;        // distance tests made
     unsigned long long direct_key, direct_pair;
 };
+enum { E_A, E_B, E_RA, E_RB };      // the int columns of the edge table
 struct GapState {
     int valid = 0;
-    long long info[8] = {0, 0, 0, 0, 0, 0, -1, -1};
-    double d2x2[2] = {INFINITY, INFINITY};
-    std::vector<int> e_a, e_b, e_ra, e_rb, c_from, c_to;
-    std::vector<double> e_d2, c_d2;
+    long long info[8];
+    double d2x2[2];
+    ResultTable<4, 1> edges;         // site_a, site_b, root_a, root_b; d2
+    ResultTable<2, 1> chain;         // from, to; d2
+    void reset()
+    {
+        const long long z[8] = {0, 0, 0, 0, 1, 0, -1, -1};
+        memcpy(info, z, sizeof(z));
+        d2x2[0] = d2x2[1] = INFINITY;
+        edges.clear(); chain.clear();
+    }
 } g_gap;
 int g_gap_cell_skip = 1;
 
@@ -289,15 +297,6 @@ __global__ __launch_bounds__(GP_NT) void k_gp_edge_rows(int E, const unsigned lo
     row4[4 * e] = ra; row4[4 * e + 1] = rb; row4[4 * e + 2] = cflags[ra] & 3; row4[4 * e + 3] = cflags[rb] & 3;
 }
 
-void gap_reset()
-{
-    g_gap.info[0] = g_gap.info[1] = g_gap.info[2] = g_gap.info[3] = g_gap.info[5] = 0;
-    g_gap.info[4] = 1; g_gap.info[6] = g_gap.info[7] = -1;
-    g_gap.d2x2[0] = g_gap.d2x2[1] = INFINITY;
-    for (auto *v : {&g_gap.e_a, &g_gap.e_b, &g_gap.e_ra, &g_gap.e_rb, &g_gap.c_from, &g_gap.c_to}) v->clear();
-    g_gap.e_d2.clear(); g_gap.c_d2.clear();
-}
-
 // cells along an extent at edge h; -1 where they would be too many
 int gp_cells(double ext, double h)
 {
@@ -331,19 +330,25 @@ void gap_chain(const std::vector<int> &na, const std::vector<int> &nb)
         }
     }
     if (via[R] == -2) return;
-    double worst = 0.0;
-    for (int v = R; v != L;) {                                // R back to L, reversed below
+    std::vector<int> hop, a_first;                            // R back to L: the edge of a hop, and whether its end a is the one nearer to L
+    for (int v = R; v != L;) {
         const int e = via[v];
         const bool a_near_l = at(nb[e]) == v;                  // the hop arrives at v: its other end is the one nearer to L
-        g_gap.c_from.push_back(a_near_l ? g_gap.e_a[e] : g_gap.e_b[e]);
-        g_gap.c_to.push_back(a_near_l ? g_gap.e_b[e] : g_gap.e_a[e]);
-        g_gap.c_d2.push_back(g_gap.e_d2[e]);
-        worst = fmax(worst, g_gap.e_d2[e]);
+        hop.push_back(e); a_first.push_back(a_near_l);
         v = a_near_l ? at(na[e]) : at(nb[e]);
     }
-    std::reverse(g_gap.c_from.begin(), g_gap.c_from.end()); std::reverse(g_gap.c_to.begin(), g_gap.c_to.end());
-    std::reverse(g_gap.c_d2.begin(), g_gap.c_d2.end());
-    g_gap.info[2] = 1; g_gap.info[3] = (long long)g_gap.c_d2.size(); g_gap.d2x2[0] = worst;
+    const ResultTable<4, 1> &T = g_gap.edges;
+    const size_t hops = hop.size();
+    g_gap.chain.resize(hops);
+    double worst = 0.0;
+    for (size_t k = 0; k < hops; ++k) {                       // the rows run from L to R
+        const int e = hop[hops - 1 - k];
+        g_gap.chain.i[0][k] = T.i[a_first[hops - 1 - k] ? E_A : E_B][e];
+        g_gap.chain.i[1][k] = T.i[a_first[hops - 1 - k] ? E_B : E_A][e];
+        g_gap.chain.d[0][k] = T.d[0][e];
+        worst = fmax(worst, T.d[0][e]);
+    }
+    g_gap.info[2] = 1; g_gap.info[3] = (long long)hops; g_gap.d2x2[0] = worst;
 }
 
 }   // namespace
@@ -360,7 +365,7 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
         || (pbc && (!h_lattice || !(h_lattice[1] > 0.0) || !(h_lattice[2] > 0.0) || !isfinite(h_lattice[1]) || !isfinite(h_lattice[2]))))
         return dkmc_fail(3, "dkmc_find_gaps: bad arguments (N >= 0, device arrays of N sites, r_max finite and > 0, a positive lattice with pbc)", __FILE__, __LINE__);
     clamp_seeds(N, n_left_sites, n_right_sites);
-    gap_reset();
+    g_gap.reset();
     if (N == 0) { g_gap.valid = 1; return 0; }
     hipStream_t st = eng().stream;
     const size_t n = (size_t)N, nnode = n + 2;
@@ -506,12 +511,14 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
     std::sort(order.begin(), order.end(), [&](int p, int q) { return h_key[p] != h_key[q] ? h_key[p] < h_key[q] : h_pair[p] < h_pair[q]; });
     std::vector<int> node_a((size_t)E), node_b((size_t)E);
     auto node_of = [&](int root, int f) { return f == 0 ? root : ((f & 1) || bridged ? -1 : -2); };
+    ResultTable<4, 1> &T = g_gap.edges;
+    T.resize((size_t)E);
     for (int k = 0; k < E; ++k) {
         const int e = order[k];
-        g_gap.e_a.push_back((int)(h_pair[e] >> 32)); g_gap.e_b.push_back((int)(h_pair[e] & 0xffffffffull));
-        g_gap.e_d2.push_back(key_dbl(h_key[e]));
+        T.i[E_A][k] = (int)(h_pair[e] >> 32); T.i[E_B][k] = (int)(h_pair[e] & 0xffffffffull);
+        T.d[0][k] = key_dbl(h_key[e]);
         node_a[k] = node_of(h_row[4 * e], h_row[4 * e + 2]); node_b[k] = node_of(h_row[4 * e + 1], h_row[4 * e + 3]);
-        g_gap.e_ra.push_back(h_row[4 * e]); g_gap.e_rb.push_back(h_row[4 * e + 1]);
+        T.i[E_RA][k] = h_row[4 * e]; T.i[E_RB][k] = h_row[4 * e + 1];
     }
     g_gap.info[0] = h_ctrl.n_components; g_gap.info[1] = E; g_gap.info[4] = rounds; g_gap.info[5] = (long long)h_ctrl.pairs;
     if (bridged) { g_gap.info[2] = 2; g_gap.d2x2[0] = 0.0; }
@@ -528,33 +535,23 @@ int dkmc_find_gaps(int N, const double *d_x, const double *d_y, const double *d_
 
 int dkmc_get_gap_info(long long *info8, double *d2x2)
 {
-    if (!g_gap.valid) return dkmc_fail(3, "dkmc_get_gap_info: no finished dkmc_find_gaps call", __FILE__, __LINE__);
+    NEED_FINISHED(g_gap.valid, "dkmc_get_gap_info", "dkmc_find_gaps");
     if (info8) memcpy(info8, g_gap.info, sizeof(g_gap.info));
-    if (d2x2) { d2x2[0] = g_gap.d2x2[0]; d2x2[1] = g_gap.d2x2[1]; }
+    if (d2x2) memcpy(d2x2, g_gap.d2x2, sizeof(g_gap.d2x2));
     return 0;
 }
 
 int dkmc_copy_gap_edges(int capacity, int *h_site_a, int *h_site_b, int *h_root_a, int *h_root_b, double *h_d2, int *rows_out)
 {
-    if (!g_gap.valid) return dkmc_fail(3, "dkmc_copy_gap_edges: no finished dkmc_find_gaps call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_gap.e_a.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_site_a) memcpy(h_site_a, g_gap.e_a.data(), r * sizeof(int));
-    if (h_site_b) memcpy(h_site_b, g_gap.e_b.data(), r * sizeof(int));
-    if (h_root_a) memcpy(h_root_a, g_gap.e_ra.data(), r * sizeof(int));
-    if (h_root_b) memcpy(h_root_b, g_gap.e_rb.data(), r * sizeof(int));
-    if (h_d2) memcpy(h_d2, g_gap.e_d2.data(), r * sizeof(double));
+    NEED_FINISHED(g_gap.valid, "dkmc_copy_gap_edges", "dkmc_find_gaps");
+    g_gap.edges.copy_out(capacity, rows_out, {h_site_a, h_site_b, h_root_a, h_root_b}, {h_d2});
     return 0;
 }
 
 int dkmc_copy_gap_chain(int capacity, int *h_from, int *h_to, double *h_d2, int *rows_out)
 {
-    if (!g_gap.valid) return dkmc_fail(3, "dkmc_copy_gap_chain: no finished dkmc_find_gaps call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_gap.c_from.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_from) memcpy(h_from, g_gap.c_from.data(), r * sizeof(int));
-    if (h_to) memcpy(h_to, g_gap.c_to.data(), r * sizeof(int));
-    if (h_d2) memcpy(h_d2, g_gap.c_d2.data(), r * sizeof(double));
+    NEED_FINISHED(g_gap.valid, "dkmc_copy_gap_chain", "dkmc_find_gaps");
+    g_gap.chain.copy_out(capacity, rows_out, {h_from, h_to}, {h_d2});
     return 0;
 }
 

@@ -33,11 +33,18 @@ namespace {
 struct PtStat { int H, end, reached_left, reached_right; };
 struct PathState {
     int valid = 0;
-    long long info[8] = {0, -1, 0, 0, 0, 0, -1, 0};
-    std::vector<int> site, count;
-    std::vector<double> xmin, xmax;
-    double ms_label = 0.0, ms_sum = 0.0;
+    long long info[8];
+    ResultTable<1> path;             // site
+    ResultTable<1, 2> profile;       // count; xmin, xmax
+    double ms[2];
     PhaseTimer<2> timer;
+    void reset()
+    {
+        const long long z[8] = {0, -1, 0, 0, 0, 0, -1, 0};
+        memcpy(info, z, sizeof(z));
+        path.clear(); profile.clear();
+        ms[0] = ms[1] = 0.0;
+    }
 } g_pt;
 int g_pt_round_cap = PT_CAP_MAX;
 
@@ -196,24 +203,16 @@ __global__ void k_pt_walk(int N, int R, const PtStat *stat, const int *__restric
     }
 }
 
-void path_reset()
-{
-    const long long z[8] = {0, -1, 0, 0, 0, 0, -1, 0};
-    memcpy(g_pt.info, z, sizeof(z));
-    g_pt.site.clear(); g_pt.count.clear(); g_pt.xmin.clear(); g_pt.xmax.clear();
-    g_pt.ms_label = g_pt.ms_sum = 0.0;
-}
-
 }   // namespace
 
 extern "C" {
 
-void dkmc_debug_set_path_round_cap(int cap) { g_pt_round_cap = cap <= 0 ? PT_CAP_MAX : (cap > PT_CAP_MAX ? PT_CAP_MAX : cap); }
+void dkmc_debug_set_path_round_cap(int cap) { g_pt_round_cap = clamp_round_cap(cap, PT_CAP_MAX); }
 
 int dkmc_debug_get_path_times(double *ms2)
 {
-    if (!g_pt.valid) return dkmc_fail(3, "dkmc_debug_get_path_times: no finished dkmc_find_paths call", __FILE__, __LINE__);
-    if (ms2) { ms2[0] = g_pt.ms_label; ms2[1] = g_pt.ms_sum; }
+    NEED_FINISHED(g_pt.valid, "dkmc_debug_get_path_times", "dkmc_find_paths");
+    if (ms2) memcpy(ms2, g_pt.ms, sizeof(g_pt.ms));
     return 0;
 }
 
@@ -224,7 +223,7 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
     if (N < 0 || nn < 1 || slack < 0 || slack > PT_SLACK_MAX || (N > 0 && (!d_index || !d_label || !d_hops_left || !d_hops_right)))
         return dkmc_fail(3, "dkmc_find_paths: bad arguments (N >= 0, nn >= 1, 0 <= slack <= 65536, device arrays of N sites)", __FILE__, __LINE__);
     clamp_seeds(N, n_left_sites, n_right_sites);
-    path_reset();
+    g_pt.reset();
     if (N == 0) { g_pt.valid = 1; return 0; }
     hipStream_t st = eng().stream;
     const int cap = g_pt_round_cap;
@@ -246,13 +245,9 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
     if (int rc = run_rounds(st, ctrl, cap, ROUND_BATCH, &rounds,
                             [&](int r) { LAUNCH_LPR(lpr, k_pt_round, dim3(row_blocks), dim3(PT_NT), st, N, nn, d_index, hop, ctrl, r); })) return rc;
     if (!rounds) {
-        // not finished: no partial hop counts go out as valid
-        HIPCHK(hipMemsetAsync(d_hops_left, 0xff, n * sizeof(int), st));
-        HIPCHK(hipMemsetAsync(d_hops_right, 0xff, n * sizeof(int), st));
-        HIPCHK(hipStreamSynchronize(st));
         char msg[200];
         snprintf(msg, sizeof(msg), "dkmc_find_paths: labelling not finished after %d rounds (the cap: dkmc_debug_set_path_round_cap); hops set to -1", cap);
-        return dkmc_fail(4, msg, __FILE__, __LINE__);
+        return abandon(st, n, {d_hops_left, d_hops_right}, msg, __FILE__, __LINE__);
     }
     HIPCHK(g_pt.timer.mark(1, st));
     // summaries.  H <= rounds - 1, so R = rounds + slack rows hold every level of the profile
@@ -284,55 +279,48 @@ int dkmc_find_paths(int N, int nn, const int *d_index, const int *d_label, const
         if (H < 0 || H >= rounds) return dkmc_fail(4, "dkmc_find_paths: H outside the rounds run", __FILE__, __LINE__);
         const size_t np = (size_t)H + slack + 1;
         std::vector<unsigned long long> h_min(np), h_max(np);
-        g_pt.count.resize(np); g_pt.site.resize((size_t)H + 1);
-        HIPCHK(hipMemcpyAsync(g_pt.count.data(), cnt, np * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (int rc = fetch_columns(st, g_pt.profile, np, {cnt})) return rc;
         HIPCHK(hipMemcpyAsync(h_min.data(), kmin, np * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(h_max.data(), kmax, np * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(g_pt.site.data(), path, ((size_t)H + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (int rc = fetch_columns(st, g_pt.path, (size_t)H + 1, {path})) return rc;
         HIPCHK(hipStreamSynchronize(st));
-        g_pt.xmin.resize(np); g_pt.xmax.resize(np);
+        const std::vector<int> &count = g_pt.profile.i[0];
         long long corridor = 0;
         int level = 0;
         for (size_t k = 0; k < np; ++k) {
-            const bool has = d_site_x && g_pt.count[k] > 0;
-            g_pt.xmin[k] = has ? key_dbl(h_min[k]) : INFINITY; g_pt.xmax[k] = has ? key_dbl(h_max[k]) : -INFINITY;
-            corridor += g_pt.count[k];
-            if (k <= (size_t)H && g_pt.count[k] < g_pt.count[level]) level = (int)k;
+            key_range(d_site_x && count[k] > 0, h_min[k], h_max[k], &g_pt.profile.d[0][k], &g_pt.profile.d[1][k]);     // an empty row: +inf, -inf
+            corridor += count[k];
+            if (k <= (size_t)H && count[k] < count[level]) level = (int)k;
         }
-        for (int s : g_pt.site)
-            if (s < 0 || s >= N) { path_reset(); return dkmc_fail(4, "dkmc_find_paths: the path walk left the members", __FILE__, __LINE__); }
-        g_pt.info[0] = 1; g_pt.info[1] = H; g_pt.info[5] = corridor; g_pt.info[6] = level; g_pt.info[7] = g_pt.count[level];
+        for (int s : g_pt.path.i[0])
+            if (s < 0 || s >= N) return dkmc_fail(4, "dkmc_find_paths: the path walk left the members", __FILE__, __LINE__);
+        g_pt.info[0] = 1; g_pt.info[1] = H; g_pt.info[5] = corridor; g_pt.info[6] = level; g_pt.info[7] = count[level];
     }
     float ms[2] = {0.f, 0.f};
     HIPCHK(g_pt.timer.read(ms));
-    g_pt.ms_label = ms[0]; g_pt.ms_sum = ms[1];
+    g_pt.ms[0] = ms[0]; g_pt.ms[1] = ms[1];
     g_pt.valid = 1;
     return 0;
 }
 
 int dkmc_get_path_info(long long *info8)
 {
-    if (!g_pt.valid) return dkmc_fail(3, "dkmc_get_path_info: no finished dkmc_find_paths call", __FILE__, __LINE__);
+    NEED_FINISHED(g_pt.valid, "dkmc_get_path_info", "dkmc_find_paths");
     if (info8) memcpy(info8, g_pt.info, sizeof(g_pt.info));
     return 0;
 }
 
 int dkmc_copy_path_sites(int capacity, int *h_site, int *rows_out)
 {
-    if (!g_pt.valid) return dkmc_fail(3, "dkmc_copy_path_sites: no finished dkmc_find_paths call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_pt.site.size(), rows_out);
-    if (r && h_site) memcpy(h_site, g_pt.site.data(), r * sizeof(int));
+    NEED_FINISHED(g_pt.valid, "dkmc_copy_path_sites", "dkmc_find_paths");
+    g_pt.path.copy_out(capacity, rows_out, {h_site});
     return 0;
 }
 
 int dkmc_copy_path_profile(int capacity, int *h_count, double *h_xmin, double *h_xmax, int *rows_out)
 {
-    if (!g_pt.valid) return dkmc_fail(3, "dkmc_copy_path_profile: no finished dkmc_find_paths call", __FILE__, __LINE__);
-    const size_t r = clamp_rows(capacity, (long long)g_pt.count.size(), rows_out);
-    if (r == 0) return 0;
-    if (h_count) memcpy(h_count, g_pt.count.data(), r * sizeof(int));
-    if (h_xmin) memcpy(h_xmin, g_pt.xmin.data(), r * sizeof(double));
-    if (h_xmax) memcpy(h_xmax, g_pt.xmax.data(), r * sizeof(double));
+    NEED_FINISHED(g_pt.valid, "dkmc_copy_path_profile", "dkmc_find_paths");
+    g_pt.profile.copy_out(capacity, rows_out, {h_count}, {h_xmin, h_xmax});
     return 0;
 }
 

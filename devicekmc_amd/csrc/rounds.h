@@ -1,6 +1,8 @@
 // rounds.h -- what the filament analyses share (clusters.hip, gaps.hip, paths.hip, track.hip, cuts.hip, flow.hip): the min-hooking + compression labelling,
-// the host loop that runs rounds until one changes nothing, the lanes-per-row rule of the row kernels, the phase timer of the debug splits and the
-// row clamp of the copy-out entry points.  Kernels with internal linkage and inline host helpers, as in cellgrid.h: no symbol of its own.
+// the host loop that runs rounds until one changes nothing, the lanes-per-row rule of the row kernels, the phase timer of the debug splits, and what
+// happens after the kernels have run: the guard of the get / copy entry points, the end of a call that cannot deliver, the clamp of the debug round
+// caps, the fetch of device columns into a result table (result_table.h: the table, its copy-out body and clamp_rows) and the x range of a pair of
+// dbl_key words.  Kernels with internal linkage and inline host helpers, as in cellgrid.h: no symbol of its own.
 //
 // Labelling: min-hooking + compression in rounds, the kernel boundary is the only synchronisation point.
 //   root[] (the caller's array) holds, between rounds, the ROOT of every member's tree (-1: not a member); it is read-only inside a hook launch.
@@ -15,6 +17,7 @@
 //   pass anyway); a member row is read by LPR lanes, 16 up to 128 entries per row and the whole wave above.
 #pragma once
 #include "common.h"
+#include "result_table.h"
 
 #define ROUND_NT 256                 // threads of a workgroup in the kernels below
 #define ROUND_BATCH 8                // rounds enqueued per read-back; a round after the one that changed nothing returns at once
@@ -144,11 +147,36 @@ struct PhaseTimer {
     }
 };
 
-// ---- rows of a copy-out entry point: min(have, capacity), not below 0, reported in *rows_out ---
-inline size_t clamp_rows(int capacity, long long have, int *rows_out)
+// ---- after the kernels -------------------------------------------------------------------------
+// the guard of a get / copy entry point: nothing is handed out unless the last find call finished
+#define NEED_FINISHED(valid, entry, call) \
+    do { if (!(valid)) return dkmc_fail(3, entry ": no finished " call " call", __FILE__, __LINE__); } while (0)
+
+// a call that cannot deliver: no partial result goes out as valid.  The call's N-site outputs are set to -1 and msg is the error (code 4)
+template <int K>
+inline int abandon(hipStream_t st, size_t n, int *const (&outs)[K], const char *msg, const char *file, int line)
 {
-    long long rows = have < capacity ? have : capacity;
-    if (rows < 0) rows = 0;
-    if (rows_out) *rows_out = (int)rows;
-    return (size_t)rows;
+    for (int *out : outs) HIPCHK(hipMemsetAsync(out, 0xff, n * sizeof(int), st));
+    HIPCHK(hipStreamSynchronize(st));
+    return dkmc_fail(4, msg, file, line);
+}
+
+// a dkmc_debug_set_*_round_cap argument: 0 or less restores the default, nothing goes above the change words of run_rounds
+inline int clamp_round_cap(int cap, int dflt) { return cap <= 0 ? dflt : (cap > ROUND_CAP_MAX ? ROUND_CAP_MAX : cap); }
+
+// `rows` rows of T from the device: one copy per int column src[c], enqueued on st and not waited for; no copy at 0 rows.  The double columns are
+// sized and left to the caller.
+template <int NI, int ND>
+inline int fetch_columns(hipStream_t st, ResultTable<NI, ND> &T, size_t rows, const int *const (&src)[NI])
+{
+    T.resize(rows);
+    for (int c = 0; c < NI && rows; ++c) HIPCHK(hipMemcpyAsync(T.i[c].data(), src[c], rows * sizeof(int), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// the minimum and maximum of x over some sites from their dbl_key words; has = 0 (no x given, or no such site): the empty range +inf, -inf
+inline void key_range(bool has, unsigned long long kmin, unsigned long long kmax, double *lo, double *hi)
+{
+    *lo = has ? key_dbl(kmin) : INFINITY;
+    *hi = has ? key_dbl(kmax) : -INFINITY;
 }

@@ -40,11 +40,21 @@ struct TrSide {
 };
 struct TrackState {
     int valid = 0;
-    long long info[16] = {0};
-    double x2[2] = {INFINITY, -INFINITY};
-    std::vector<int> pairs[4], now[6], prev[6], critical;
-    double ms_pairs = 0.0, ms_rest = 0.0;
+    long long info[16];
+    double x2[2];
+    ResultTable<4> pairs;            // the columns of dkmc_copy_track_pairs, _now, _prev and _critical, in their order
+    ResultTable<6> now, prev;
+    ResultTable<1> critical;
+    double ms[2];
     PhaseTimer<2> timer;
+    void reset()
+    {
+        const long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, -1, -1, 0, 0, 0, 0, 0, 0};
+        memcpy(info, z, sizeof(z));
+        x2[0] = INFINITY; x2[1] = -INFINITY;
+        pairs.clear(); now.clear(); prev.clear(); critical.clear();
+        ms[0] = ms[1] = 0.0;
+    }
 } g_tr;
 int g_tr_hash = 0;
 
@@ -219,18 +229,6 @@ __global__ __launch_bounds__(TR_NT) void k_tr_scatter(int N, const int *lp, cons
     if (flags4[3 * n + i]) R.crit[pos4[3 * n + i]] = i;
 }
 
-void track_reset()
-{
-    const long long z[16] = {0, 0, 0, 0, 0, 0, 0, 0, -1, -1, 0, 0, 0, 0, 0, 0};
-    memcpy(g_tr.info, z, sizeof(z));
-    g_tr.x2[0] = INFINITY; g_tr.x2[1] = -INFINITY;
-    for (auto &v : g_tr.pairs) v.clear();
-    for (auto &v : g_tr.now) v.clear();
-    for (auto &v : g_tr.prev) v.clear();
-    g_tr.critical.clear();
-    g_tr.ms_pairs = g_tr.ms_rest = 0.0;
-}
-
 TrSide side_of(char *base, size_t n)
 {
     TrSide s;
@@ -239,17 +237,13 @@ TrSide side_of(char *base, size_t n)
     return s;
 }
 
-int copy_rows(const char *who, const std::vector<int> *cols, int ncols, int capacity, int *const *out, int *rows_out)
+// `rows` rows of T from the packed columns at src (the layout of rows_of); the end of what was read
+template <int NI>
+const int *unpack(ResultTable<NI> &T, size_t rows, const int *src)
 {
-    if (!g_tr.valid) {
-        char msg[120];
-        snprintf(msg, sizeof(msg), "%s: no finished dkmc_track_clusters call", who);
-        return dkmc_fail(3, msg, __FILE__, __LINE__);
-    }
-    const size_t rows = clamp_rows(capacity, (long long)cols[0].size(), rows_out);
-    for (int c = 0; c < ncols && rows; ++c)
-        if (out[c]) memcpy(out[c], cols[c].data(), rows * sizeof(int));
-    return 0;
+    T.resize(rows);
+    for (int c = 0; c < NI && rows; ++c) memcpy(T.i[c].data(), src + c * rows, rows * sizeof(int));
+    return src + NI * rows;
 }
 
 }   // namespace
@@ -260,8 +254,8 @@ void dkmc_debug_set_track_hash(int mode) { g_tr_hash = mode == 1 ? 1 : 0; }
 
 int dkmc_debug_get_track_times(double *ms2)
 {
-    if (!g_tr.valid) return dkmc_fail(3, "dkmc_debug_get_track_times: no finished dkmc_track_clusters call", __FILE__, __LINE__);
-    if (ms2) { ms2[0] = g_tr.ms_pairs; ms2[1] = g_tr.ms_rest; }
+    NEED_FINISHED(g_tr.valid, "dkmc_debug_get_track_times", "dkmc_track_clusters");
+    if (ms2) memcpy(ms2, g_tr.ms, sizeof(g_tr.ms));
     return 0;
 }
 
@@ -272,7 +266,7 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
     if (N < 0 || N > TR_NMAX || (N > 0 && (!d_label_prev || !d_label_now || !d_site_change)))
         return dkmc_fail(3, "dkmc_track_clusters: bad arguments (0 <= N <= 2^30, device arrays of N sites: label_prev, label_now, site_change)", __FILE__, __LINE__);
     clamp_seeds(N, n_left_sites, n_right_sites);
-    track_reset();
+    g_tr.reset();
     if (N == 0) { g_tr.valid = 1; return 0; }
     hipStream_t st = eng().stream;
     const size_t n = (size_t)N;
@@ -328,52 +322,56 @@ int dkmc_track_clusters(int N, const int *d_label_prev, const int *d_label_now, 
         HIPCHK(hipStreamSynchronize(st));
     }
     else if (timed) { HIPCHK(g_tr.timer.mark(2, st)); HIPCHK(hipStreamSynchronize(st)); }
-    const TrRows R = rows_of(rows.data(), np, nn, nv, nc);
-    for (int c = 0; c < 4; ++c) g_tr.pairs[c].assign(R.pairs + c * np, R.pairs + (c + 1) * np);
-    for (int c = 0; c < 6; ++c) { g_tr.now[c].assign(R.now + c * nn, R.now + (c + 1) * nn); g_tr.prev[c].assign(R.prev + c * nv, R.prev + (c + 1) * nv); }
-    g_tr.critical.assign(R.crit, R.crit + nc);
+    const int *src = unpack(g_tr.pairs, np, rows.data());
+    src = unpack(g_tr.now, nn, src);
+    src = unpack(g_tr.prev, nv, src);
+    unpack(g_tr.critical, nc, src);
     const int bp = (int)h.bridge_prev, bn = (int)h.bridge_now;          // all ones = -1: none
     const long long info[16] = {h.n_prev, h.n_now, h.n_pairs, (long long)h.mainline + h.regrouped, h.joined, h.left, h.regrouped,
                                 (bp >= 0 ? 2 : 0) | (bn >= 0 ? 1 : 0), bp, bn, h.born, h.died, h.merged, h.split, h.n_crit, 0};
     memcpy(g_tr.info, info, sizeof(info));
-    if (d_site_x && h.n_crit > 0) { g_tr.x2[0] = key_dbl(h.kmin); g_tr.x2[1] = key_dbl(h.kmax); }
+    key_range(d_site_x && h.n_crit > 0, h.kmin, h.kmax, &g_tr.x2[0], &g_tr.x2[1]);      // else the empty range of the reset
     float ms[2] = {0.f, 0.f};
     HIPCHK(g_tr.timer.read(ms));
-    g_tr.ms_pairs = ms[0]; g_tr.ms_rest = ms[1];
+    g_tr.ms[0] = ms[0]; g_tr.ms[1] = ms[1];
     g_tr.valid = 1;
     return 0;
 }
 
 int dkmc_get_track_info(long long *info16, double *x2)
 {
-    if (!g_tr.valid) return dkmc_fail(3, "dkmc_get_track_info: no finished dkmc_track_clusters call", __FILE__, __LINE__);
+    NEED_FINISHED(g_tr.valid, "dkmc_get_track_info", "dkmc_track_clusters");
     if (info16) memcpy(info16, g_tr.info, sizeof(g_tr.info));
-    if (x2) { x2[0] = g_tr.x2[0]; x2[1] = g_tr.x2[1]; }
+    if (x2) memcpy(x2, g_tr.x2, sizeof(g_tr.x2));
     return 0;
 }
 
 int dkmc_copy_track_pairs(int capacity, int *h_prev, int *h_now, int *h_count, int *h_first_site, int *rows_out)
 {
-    int *const out[4] = {h_prev, h_now, h_count, h_first_site};
-    return copy_rows("dkmc_copy_track_pairs", g_tr.pairs, 4, capacity, out, rows_out);
+    NEED_FINISHED(g_tr.valid, "dkmc_copy_track_pairs", "dkmc_track_clusters");
+    g_tr.pairs.copy_out(capacity, rows_out, {h_prev, h_now, h_count, h_first_site});
+    return 0;
 }
 
 int dkmc_copy_track_now(int capacity, int *h_root, int *h_size, int *h_joined, int *h_n_parents, int *h_main_parent, int *h_flags, int *rows_out)
 {
-    int *const out[6] = {h_root, h_size, h_joined, h_n_parents, h_main_parent, h_flags};
-    return copy_rows("dkmc_copy_track_now", g_tr.now, 6, capacity, out, rows_out);
+    NEED_FINISHED(g_tr.valid, "dkmc_copy_track_now", "dkmc_track_clusters");
+    g_tr.now.copy_out(capacity, rows_out, {h_root, h_size, h_joined, h_n_parents, h_main_parent, h_flags});
+    return 0;
 }
 
 int dkmc_copy_track_prev(int capacity, int *h_root, int *h_size, int *h_left, int *h_n_children, int *h_main_child, int *h_flags, int *rows_out)
 {
-    int *const out[6] = {h_root, h_size, h_left, h_n_children, h_main_child, h_flags};
-    return copy_rows("dkmc_copy_track_prev", g_tr.prev, 6, capacity, out, rows_out);
+    NEED_FINISHED(g_tr.valid, "dkmc_copy_track_prev", "dkmc_track_clusters");
+    g_tr.prev.copy_out(capacity, rows_out, {h_root, h_size, h_left, h_n_children, h_main_child, h_flags});
+    return 0;
 }
 
 int dkmc_copy_track_critical(int capacity, int *h_site, int *rows_out)
 {
-    int *const out[1] = {h_site};
-    return copy_rows("dkmc_copy_track_critical", &g_tr.critical, 1, capacity, out, rows_out);
+    NEED_FINISHED(g_tr.valid, "dkmc_copy_track_critical", "dkmc_track_clusters");
+    g_tr.critical.copy_out(capacity, rows_out, {h_site});
+    return 0;
 }
 
 }   // extern "C"

@@ -463,7 +463,7 @@ class Device:
         n_right: sites of the contact seeds, by default get_num_in_contacts(num_atoms_first_layer) on either side.  Changes nothing in gpubuf.
         Returns (labels: host int32 array, table, info) and keeps them as site_cluster, cluster_table, cluster_info."""
         n_left, n_right = self.contact_seeds(n_left, n_right)
-        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        index, nn = self._links(gpubuf, link_index)
         label, table, info = find_clusters(index, nn, gpubuf.site_element, gpubuf.site_charge, gpubuf.site_x, gpubuf.metal_types, members,
                                            n_left, n_right, capacity)
         self._cluster_label_prev = getattr(self, "_cluster_label", None)       # the tensor this call replaces (a reference), for track_clusters
@@ -502,13 +502,22 @@ class Device:
             otherwise()
         return self._cluster_label
 
+    def _labels_and_seeds(self, label, otherwise, n_left, n_right):
+        """(label, n_left, n_right) of an analysis: the labels by _labels_or -- first, with n_left / n_right as given --, then contact_seeds."""
+        label = self._labels_or(label, otherwise)
+        return (label,) + self.contact_seeds(n_left, n_right)
+
+    @staticmethod
+    def _links(gpubuf, link_index):
+        """(index, nn) an analysis walks: link_index = (int32 device tensor of N * nn, nn) if given, else gpubuf's neighbour index."""
+        return (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+
     def find_gaps(self, gpubuf: GPUBuffers, r_max=10.0, label=None, n_left=None, n_right=None):
         """Gap analysis on the device (dkmc_find_gaps; definitions: include/devicekmc_hip.h) over the labels of the last find_clusters -- one with
         the default members is run if there is none -- or over label (int32 device tensor of N): the island graph within r_max, the tunnelling
         chain between the contact clusters with its bottleneck hop, and the direct tip-to-tip gap, with this device's pbc and lattice and the
         contact seeds of find_clusters.  Changes nothing in gpubuf.  Returns (edges, chain, info) and keeps them as gap_edges, gap_chain, gap_info."""
-        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
-        n_left, n_right = self.contact_seeds(n_left, n_right)
+        label, n_left, n_right = self._labels_and_seeds(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right), n_left, n_right)
         self.gap_edges, self.gap_chain, self.gap_info = find_gaps(label, gpubuf.site_x, gpubuf.site_y, gpubuf.site_z, self.lattice, self.pbc,
                                                                   n_left, n_right, r_max)
         return self.gap_edges, self.gap_chain, self.gap_info
@@ -520,9 +529,8 @@ class Device:
         path, the level profile of the corridor of the walks at most slack links longer and its constriction, with the contact seeds of
         find_clusters.  Changes nothing in gpubuf.  Returns (hops_left, hops_right: host int32 arrays, path, profile, info) and keeps them as
         site_hops_left, site_hops_right, path_sites, path_profile, path_info."""
-        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
-        n_left, n_right = self.contact_seeds(n_left, n_right)
-        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        label, n_left, n_right = self._labels_and_seeds(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right), n_left, n_right)
+        index, nn = self._links(gpubuf, link_index)
         hl, hr, path, profile, info = find_paths(index, nn, label, gpubuf.site_x, n_left, n_right, slack)
         self.site_hops_left, self.site_hops_right = hl.cpu().numpy(), hr.cpu().numpy()
         self.path_sites, self.path_profile, self.path_info = path, profile, info
@@ -535,13 +543,13 @@ class Device:
         gpubuf.neigh_idx or link_index = (int32 device tensor of N * nn, nn) -- the index the path was found on -- with the contact seeds of
         find_clusters.  Changes nothing in gpubuf.  Returns (site_role, site_bypass: host int32 arrays, path_table, bypasses, necks, info) and
         keeps them as site_role, site_bypass, cut_path, cut_bypasses, cut_necks, cut_info."""
-        label = self._labels_or(label, ValueError("find_cuts runs on the labels of a find_clusters call: none was made on this Device (or pass label)"))
+        label, n_left, n_right = self._labels_and_seeds(
+            label, ValueError("find_cuts runs on the labels of a find_clusters call: none was made on this Device (or pass label)"), n_left, n_right)
         if path is None:
             path = getattr(self, "path_sites", None)
             if path is None:
                 raise ValueError("find_cuts takes a left-to-right path: no find_paths call was made on this Device (or pass path)")
-        n_left, n_right = self.contact_seeds(n_left, n_right)
-        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        index, nn = self._links(gpubuf, link_index)
         role, bypass, table, bypasses, necks, info = find_cuts(index, nn, label, gpubuf.site_x, n_left, n_right, path)
         self.site_role, self.site_bypass = role.cpu().numpy(), bypass.cpu().numpy()
         self.cut_path, self.cut_bypasses, self.cut_necks, self.cut_info = table, bypasses, necks, info
@@ -554,9 +562,8 @@ class Device:
         strands, over gpubuf.neigh_idx or link_index = (int32 device tensor of N * nn, nn), with the contact seeds of find_clusters.  Changes
         nothing in gpubuf.  Returns (site_zone, site_strand: host int32 arrays, strands, strand_sites, info) and keeps them as site_zone,
         site_strand, flow_strands, flow_strand_sites, flow_info."""
-        label = self._labels_or(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right))
-        n_left, n_right = self.contact_seeds(n_left, n_right)
-        index, nn = (gpubuf.neigh_idx, gpubuf.nn_) if link_index is None else link_index
+        label, n_left, n_right = self._labels_and_seeds(label, lambda: self.find_clusters(gpubuf, n_left=n_left, n_right=n_right), n_left, n_right)
+        index, nn = self._links(gpubuf, link_index)
         zone, strand, strands, sites, info = find_flow(index, nn, label, gpubuf.site_x, n_left, n_right, max_strands)
         self.site_zone, self.site_strand = zone.cpu().numpy(), strand.cpu().numpy()
         self.flow_strands, self.flow_strand_sites, self.flow_info = strands, sites, info

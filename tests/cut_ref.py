@@ -186,3 +186,20 @@ def assert_equal(role, bypass, table, bypasses, necks, info, ref, rows=None):
             assert np.array_equal(got[k], want[k][:n]), k
     for k in INFO:
         assert info[k] == r_info[k], (k, info[k], r_info[k])
+
+
+# ---- pinned cases (tests/test_cut_ref.py, tests/test_gpu_cuts.py, tests/test_flow_ref.py) --------------------------------------------------
+# the figures of the planted filaments of the 2.5 nm golden device: the reference and the device are pinned to the same ones.  radius: path_len, the cut positions, necks,
+# longest neck, its first position, bypass components
+PINNED_2P5 = {3.0: (48, [], 0, 0, -1, 1), 2.6: (48, [12], 1, 1, 12, 3), 2.4: (48, [12, 13, 14], 1, 3, 12, 4),
+              2.2: (48, [12, 13, 14, 19, 25, 26, 31], 4, 3, 12, 8)}
+PINNED_2P5_WIDE_BYPASS = (0, 3483, -1, 48)                                  # r = 3.0: the one bypass component's root, size, lo, hi
+
+
+def planted_2p5(s, p, el, neigh, r):
+    from analysis_support import _contacts
+    el2, _ = cr.plant_filament(el, s.x, s.y, s.z, r)
+    nl, nr = _contacts(el2, p.num_atoms_first_layer)
+    label = np.where(cr.member_mask(el2, None, list(p.metals), cr.METAL | cr.VACANCY_BIT), 0, -1).astype(np.int32)
+    path = pr.analyse(neigh, label, s.x, nl, nr, 0)[2]
+    return label, nl, nr, path

@@ -260,3 +260,21 @@ def assert_equal(zone, strand, table, sites, info, ref, rows=None):
         assert info[k] == r_info[k], (k, info[k], r_info[k])
     for k in X4:
         assert np.array_equal(np.float64(info[k]), np.float64(r_info[k])), (k, info[k], r_info[k])
+
+
+# ---- pinned cases and their graphs (tests/test_flow_ref.py, tests/test_gpu_flow.py) -------------------------------------------------------
+def rails(k, length, rng=None):
+    """k rails of `length` sites with a rung between neighbouring rails at every level: site k i + j is rail j at level i; with rng the sites of
+    every level are renumbered at random, so that the rails swap site numbers"""
+    site = np.arange(k * length).reshape(length, k)
+    if rng is not None:
+        site = np.stack([rng.permutation(row) for row in site])
+    links = [(site[i, j], site[i + 1, j]) for i in range(length - 1) for j in range(k)]
+    links += [(site[i, j], site[i, j + 1]) for i in range(length) for j in range(k - 1)]
+    return links
+
+
+# radius: W, the left-most minimum cut, the right-most one of the planted filaments of the 2.5 nm golden device
+PINNED_2P5 = {3.0: (2, [2792, 2864], [2972, 3014]), 2.6: (1, [1776], [1776]), 2.4: (1, [1776], [2010]), 2.2: (1, [1776], [4414]),
+              4.5: (6, [1337, 1375, 1468, 1469, 1492, 1511], [4354, 4380, 4401, 4414, 4464, 4517])}
+PINNED_2P5_ROUNDS = {3.0: (4, 296), 2.6: (3, 195), 2.4: (3, 193), 2.2: (3, 155), 4.5: (8, 610)}            # searches, rounds

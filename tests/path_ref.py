@@ -117,3 +117,9 @@ def assert_equal(hops_left, hops_right, path, profile, info, ref):
         assert np.array_equal(profile[k], rprof[k]), k
     for k in INFO:
         assert info[k] == rinfo[k], (k, info[k], rinfo[k])
+
+
+# ---- pinned cases (tests/test_path_ref.py, tests/test_gpu_paths.py) ----------------------------------------------------------------------
+# the figures of the planted filaments of the two golden devices: the reference and the device are pinned to the same ones
+PINNED_2P5_BRIDGED = {0: (2315, 19, 2), 2: (3123, 13, 3), 4: (3495, 13, 3)}            # slack: corridor sites, constriction level, width
+PINNED_7P5_BRIDGED = {0: (3727, 13, 2), 2: (6849, 18, 2)}

@@ -4,21 +4,10 @@ import numpy as np
 import pytest
 
 import cluster_ref as cr
+from analysis_support import _contacts, _random_case
 from conftest import params_7p5
 
 METALS = [4, 5, 6, 7, 8]
-
-
-def _random_case(rng, N, nn, p_member, p_pad, one_way):
-    """index with padding anywhere in a row; one_way: every link is entered in one of its two rows only"""
-    index = rng.integers(0, N, size=(N, nn)).astype(np.int32)
-    index[rng.random((N, nn)) < p_pad] = -1
-    if one_way:
-        rows = np.arange(N)[:, None]
-        index[(index >= 0) & (index < rows)] = -1                       # row u keeps only v >= u
-    element = np.where(rng.random(N) < p_member, rng.choice([2, 6], N), 3).astype(np.int32)
-    charge = rng.integers(0, 2, N).astype(np.int32) * 2
-    return index, element, charge, rng.normal(size=N) * 10.0
 
 
 @pytest.mark.parametrize("one_way", [False, True])
@@ -73,11 +62,6 @@ def device_2p5(cell_2p5):
     p = params.KMCParameters()
     el, neigh, nn, _ = structure.prepare_device(cell_2p5, p, None)
     return cell_2p5, p, el, neigh, nn
-
-
-def _contacts(el, n):
-    nondef = np.flatnonzero(el != 0)
-    return int(nondef[n - 1]) + 1, len(el) - int(nondef[len(nondef) - n])
 
 
 def test_pinned_counts_2p5(device_2p5):

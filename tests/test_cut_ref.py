@@ -7,7 +7,9 @@ import pytest
 import cluster_ref as cr
 import cut_ref as cu
 import path_ref as pr
-from test_cluster_ref import _contacts, _random_case
+from analysis_support import _random_case, index_of, ladder
+from analysis_support import ordered_chain as _chain
+from cut_ref import PINNED_2P5, PINNED_2P5_WIDE_BYPASS, planted_2p5
 
 CASES = [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1)]
 TRIALS = 6
@@ -124,25 +126,6 @@ def test_invalid_paths_are_named():
 
 
 # ---- hand cases ---------------------------------------------------------------------------------------------------------------------------
-def _chain(n):
-    return np.stack([np.arange(n) - 1, np.r_[np.arange(1, n), -1]], axis=1).astype(np.int32)
-
-
-def ladder(length, first=0):
-    """the links of two rails of `length` sites with a rung at every level: sites first + 2 i, first + 2 i + 1 are level i"""
-    a = first + 2 * np.arange(length)
-    return [(a[i], a[i + 1]) for i in range(length - 1)] + [(a[i] + 1, a[i + 1] + 1) for i in range(length - 1)] + [(a[i], a[i] + 1) for i in range(length)]
-
-
-def index_of(links, n, nn=4):
-    """each link entered once, in the row of its first end"""
-    index = np.full((n, nn), -1, dtype=np.int32)
-    fill = np.zeros(n, dtype=np.int64)
-    for u, v in links:
-        index[u, fill[u]] = v; fill[u] += 1
-    return index
-
-
 def test_ordered_chain_is_one_neck():
     n = 30
     x = np.arange(n) * 0.5
@@ -208,21 +191,6 @@ def device_2p5(cell_2p5):
     p = params.KMCParameters()
     el, neigh, nn, _ = structure.prepare_device(cell_2p5, p, None)
     return cell_2p5, p, el, neigh, nn
-
-
-# the figures of the planted filaments (tests/test_gpu_cuts.py pins the device to the same ones).  radius: path_len, the cut positions, necks,
-# longest neck, its first position, bypass components
-PINNED_2P5 = {3.0: (48, [], 0, 0, -1, 1), 2.6: (48, [12], 1, 1, 12, 3), 2.4: (48, [12, 13, 14], 1, 3, 12, 4),
-              2.2: (48, [12, 13, 14, 19, 25, 26, 31], 4, 3, 12, 8)}
-PINNED_2P5_WIDE_BYPASS = (0, 3483, -1, 48)                                  # r = 3.0: the one bypass component's root, size, lo, hi
-
-
-def planted_2p5(s, p, el, neigh, r):
-    el2, _ = cr.plant_filament(el, s.x, s.y, s.z, r)
-    nl, nr = _contacts(el2, p.num_atoms_first_layer)
-    label = np.where(cr.member_mask(el2, None, list(p.metals), cr.METAL | cr.VACANCY_BIT), 0, -1).astype(np.int32)
-    path = pr.analyse(neigh, label, s.x, nl, nr, 0)[2]
-    return label, nl, nr, path
 
 
 @pytest.mark.parametrize("r", [3.0, 2.6, 2.4, 2.2])

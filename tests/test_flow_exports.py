@@ -6,24 +6,11 @@ import os
 import re
 
 import numpy as np
+from analysis_support import _args, _code, _raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("dkmc_find_flow", "dkmc_get_flow_info", "dkmc_copy_flow_strands", "dkmc_copy_flow_strand_sites")
 DEBUG = ("dkmc_debug_set_flow_round_cap", "dkmc_debug_get_flow_times")
-
-
-def _raw(name):
-    return open(os.path.join(ROOT, "include", name)).read()
-
-
-def _code(name):
-    return re.sub(r"/\*.*?\*/", " ", _raw(name), flags=re.S)
-
-
-def _args(src, name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_headers_declare_the_calls():

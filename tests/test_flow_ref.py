@@ -7,7 +7,10 @@ import pytest
 import cluster_ref as cr
 import cut_ref as cu
 import flow_ref as fl
-from test_cut_ref import _chain, index_of, ladder, planted_2p5
+from analysis_support import _contacts, index_of, ladder
+from analysis_support import ordered_chain as _chain
+from cut_ref import planted_2p5
+from flow_ref import PINNED_2P5, PINNED_2P5_ROUNDS, rails
 
 # (interior sites, seeds per side, entries per row, link probability, one-way entries)
 CASES = [(3, 1, 2, 0.5, False), (6, 2, 3, 0.4, True), (9, 3, 3, 0.35, False), (12, 4, 4, 0.3, True), (14, 5, 5, 0.3, False), (14, 5, 6, 0.45, True),
@@ -189,17 +192,6 @@ def test_ladder():
     assert _zone_sets(res[0]) == ([0, 1], [2, 3], [n - 4, n - 3], [n - 2, n - 1])
 
 
-def rails(k, length, rng=None):
-    """k rails of `length` sites with a rung between neighbouring rails at every level: site k i + j is rail j at level i; with rng the sites of
-    every level are renumbered at random, so that the rails swap site numbers"""
-    site = np.arange(k * length).reshape(length, k)
-    if rng is not None:
-        site = np.stack([rng.permutation(row) for row in site])
-    links = [(site[i, j], site[i + 1, j]) for i in range(length - 1) for j in range(k)]
-    links += [(site[i, j], site[i, j + 1]) for i in range(length) for j in range(k - 1)]
-    return links
-
-
 @pytest.mark.parametrize("k,length", [(3, 7), (6, 5)])
 def test_rails_and_grid(k, length):
     n = k * length
@@ -285,15 +277,8 @@ def device_2p5(cell_2p5):
     return cell_2p5, p, el, neigh, nn
 
 
-# radius: W, the left-most minimum cut, the right-most one (tests/test_gpu_flow.py pins the device to the same figures)
-PINNED_2P5 = {3.0: (2, [2792, 2864], [2972, 3014]), 2.6: (1, [1776], [1776]), 2.4: (1, [1776], [2010]), 2.2: (1, [1776], [4414]),
-              4.5: (6, [1337, 1375, 1468, 1469, 1492, 1511], [4354, 4380, 4401, 4414, 4464, 4517])}
-PINNED_2P5_ROUNDS = {3.0: (4, 296), 2.6: (3, 195), 2.4: (3, 193), 2.2: (3, 155), 4.5: (8, 610)}            # searches, rounds
-
-
 def test_pristine_2p5(device_2p5):
     s, p, el, neigh, nn = device_2p5
-    from test_cluster_ref import _contacts
     nl, nr = _contacts(el, p.num_atoms_first_layer)
     label = np.where(cr.member_mask(el, None, list(p.metals), cr.METAL | cr.VACANCY_BIT), 0, -1).astype(np.int32)
     res = fl.analyse(neigh, label, s.x, nl, nr)

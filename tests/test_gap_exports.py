@@ -3,23 +3,10 @@ lib.py; the uniform-cell skip is a debug aid; dkmc_stats keeps its layout.  No G
 import ctypes
 import os
 import re
+from analysis_support import _args, _code, _raw
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CALLS = ("dkmc_find_gaps", "dkmc_get_gap_info", "dkmc_copy_gap_edges", "dkmc_copy_gap_chain")
-
-
-def _raw(name):
-    return open(os.path.join(ROOT, "include", name)).read()
-
-
-def _code(name):
-    return re.sub(r"/\*.*?\*/", " ", _raw(name), flags=re.S)
-
-
-def _args(src, name):
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, src)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_headers_declare_the_calls():

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cluster_ref as cr
+from analysis_support import _chain, _dev, hip  # noqa: F401
 from conftest import params_7p5
 
 pytestmark = pytest.mark.gpu
@@ -13,25 +14,10 @@ pytestmark = pytest.mark.gpu
 BOTH = cr.METAL | cr.VACANCY_BIT
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
-
-
 @pytest.fixture(autouse=True)
 def _default_cap(hip):
     yield
     hip[1].dkmc_debug_set_cluster_round_cap(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, index, element, charge, x, metals, members, n_left, n_right, capacity=None):

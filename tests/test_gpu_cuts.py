@@ -8,32 +8,17 @@ import pytest
 import cluster_ref as cr
 import cut_ref as cu
 import path_ref as pr
+from analysis_support import SHAPES, _chain, _dev, _random_case, hip, index_of, ladder  # noqa: F401
 from conftest import params_7p5
-from test_cluster_ref import _random_case
-from test_cut_ref import PINNED_2P5, PINNED_2P5_WIDE_BYPASS, index_of, ladder
+from cut_ref import PINNED_2P5, PINNED_2P5_WIDE_BYPASS
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
 
 
 @pytest.fixture(autouse=True)
 def _default_cap(hip):
     yield
     hip[1].dkmc_debug_set_cut_round_cap(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, index, label, x, n_left, n_right, path):
@@ -60,9 +45,7 @@ def _bytes(res):
 
 # ---- random graphs: workgroup and wave edges, every row-lane template, the whole-wave row ---------------------------------------------------
 @pytest.mark.parametrize("one_way", [False, True])
-@pytest.mark.parametrize("N,nn,p_member,p_pad", [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1),
-                                                 (255, 3, 0.7, 0.3), (256, 16, 0.5, 0.85), (257, 17, 0.6, 0.9), (1000, 1, 0.9, 0.1),
-                                                 (1000, 128, 0.5, 0.985), (1000, 130, 0.6, 0.99)])
+@pytest.mark.parametrize("N,nn,p_member,p_pad", SHAPES)
 def test_random_graphs(hip, N, nn, p_member, p_pad, one_way):
     rng = np.random.default_rng(1000 * N + nn + one_way)
     nl = nr = max(1, (2 * N) // 5)
@@ -85,14 +68,6 @@ def test_random_graphs(hip, N, nn, p_member, p_pad, one_way):
 
 
 # ---- chains and ladders -------------------------------------------------------------------------------------------------------------------
-def _chain(order):
-    """the sites of order linked in a row, both directions entered"""
-    n = len(order)
-    index = np.full((n, 2), -1, dtype=np.int32)
-    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
-    return index
-
-
 def test_ordered_chain(hip):
     n = 300
     x = np.arange(n) * 0.5

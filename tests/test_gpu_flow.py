@@ -8,33 +8,17 @@ import pytest
 
 import cluster_ref as cr
 import flow_ref as fl
+from analysis_support import SHAPES, _chain, _dev, _random_case, hip, index_of, ladder  # noqa: F401
 from conftest import params_7p5
-from test_cluster_ref import _random_case
-from test_cut_ref import index_of, ladder
-from test_flow_ref import PINNED_2P5, PINNED_2P5_ROUNDS, rails
+from flow_ref import PINNED_2P5, PINNED_2P5_ROUNDS, rails
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
 
 
 @pytest.fixture(autouse=True)
 def _default_cap(hip):
     yield
     hip[1].dkmc_debug_set_flow_round_cap(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, index, label, x, n_left, n_right, max_strands=64):
@@ -60,8 +44,7 @@ def _bytes(res):
 
 
 # ---- random graphs: workgroup and wave edges, every row-lane template, the whole-wave row ---------------------------------------------------
-RANDOM = [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1), (255, 3, 0.7, 0.3), (256, 16, 0.5, 0.85),
-          (257, 17, 0.6, 0.9), (1000, 1, 0.9, 0.1), (1000, 128, 0.5, 0.985), (1000, 130, 0.6, 0.99)]
+RANDOM = SHAPES
 
 
 def random_inputs(N, nn, p_member, p_pad, one_way):
@@ -105,14 +88,6 @@ def test_random_graphs_cover_the_statuses():
 
 
 # ---- chains, ladders, rails -----------------------------------------------------------------------------------------------------------------
-def _chain(order):
-    """the sites of order linked in a row, both directions entered"""
-    n = len(order)
-    index = np.full((n, 2), -1, dtype=np.int32)
-    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
-    return index
-
-
 def test_ordered_chain(hip):
     n = 300
     x = np.arange(n) * 0.5

@@ -10,6 +10,7 @@ import pytest
 
 import cluster_ref as cr
 import gap_ref as gr
+from analysis_support import _dev, hip  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOX = (50.0, 20.0, 20.0)
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
-
-
 @pytest.fixture(autouse=True)
 def _default_skip(hip):
     yield
     hip[1].dkmc_debug_set_gap_cell_skip(1)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, label, x, y, z, lattice, pbc, n_left, n_right, r_max):

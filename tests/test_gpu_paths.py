@@ -9,32 +9,17 @@ import pytest
 
 import cluster_ref as cr
 import path_ref as pr
+from analysis_support import SHAPES, _chain, _dev, _random_case, hip  # noqa: F401
 from conftest import params_7p5
-from test_cluster_ref import _random_case
-from test_path_ref import PINNED_2P5_BRIDGED, PINNED_7P5_BRIDGED
+from path_ref import PINNED_2P5_BRIDGED, PINNED_7P5_BRIDGED
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
 
 
 @pytest.fixture(autouse=True)
 def _default_cap(hip):
     yield
     hip[1].dkmc_debug_set_path_round_cap(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, index, label, x, n_left, n_right, slack):
@@ -65,9 +50,7 @@ def _bytes(res):
 
 # ---- random graphs: workgroup and wave edges, both row-lane templates, the whole-wave row ------------------------------------------------------
 @pytest.mark.parametrize("one_way", [False, True])
-@pytest.mark.parametrize("N,nn,p_member,p_pad", [(1, 1, 1.0, 0.0), (7, 2, 0.8, 0.3), (40, 3, 0.5, 0.5), (63, 2, 0.9, 0.2), (150, 4, 0.3, 0.1),
-                                                 (255, 3, 0.7, 0.3), (256, 16, 0.5, 0.85), (257, 17, 0.6, 0.9), (1000, 1, 0.9, 0.1),
-                                                 (1000, 128, 0.5, 0.985), (1000, 130, 0.6, 0.99)])
+@pytest.mark.parametrize("N,nn,p_member,p_pad", SHAPES)
 def test_random_graphs(hip, N, nn, p_member, p_pad, one_way):
     rng = np.random.default_rng(1000 * N + nn + one_way)
     connected = 0
@@ -107,14 +90,6 @@ def test_n_zero(hip):
 
 
 # ---- chains and ladders -------------------------------------------------------------------------------------------------------------------------
-def _chain(order):
-    """the sites of order linked in a row, both directions entered"""
-    n = len(order)
-    index = np.full((n, 2), -1, dtype=np.int32)
-    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
-    return index
-
-
 def test_ordered_chain_spans_many_batches(hip):
     n = 300
     index = _chain(np.arange(n))

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cluster_ref as cr
+from analysis_support import _chain, _dev, hip  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -12,26 +13,11 @@ VACANCY, OXYGEN = 2, 3                            # a member / a non-member with
 ROUND_BATCH = 8                                   # rounds the driver enqueues per read-back (csrc/rounds.h)
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
-
-
 @pytest.fixture(autouse=True)
 def _default_caps(hip):
     yield
     hip[1].dkmc_debug_set_cluster_round_cap(0)
     hip[1].dkmc_debug_set_cut_round_cap(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def _both(hip, index, mask):
@@ -62,14 +48,6 @@ def test_random_graphs(hip, N, nn, one_way):
     if one_way:
         index[(index >= 0) & (index < np.arange(N)[:, None])] = -1
     _both(hip, index, rng.random(N) < 0.7)
-
-
-def _chain(order):
-    """the sites of order linked in a row, both directions entered"""
-    n = len(order)
-    index = np.full((n, 2), -1, dtype=np.int32)
-    index[order[:-1], 0] = order[1:]; index[order[1:], 1] = order[:-1]
-    return index
 
 
 def _scrambled_chains(n=200):

@@ -11,33 +11,19 @@ import pytest
 
 import cluster_ref as cr
 import track_ref as tr
+from analysis_support import _dev, hip  # noqa: F401
 from conftest import params_7p5
-from test_track_ref import PINNED_2P5, PLANTINGS, check_pinned_2p5, random_pair
+from track_ref import PINNED_2P5, PLANTINGS, check_pinned_2p5, random_pair
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1, 7, 63, 64, 65, 255, 256, 257, 1000, 5000)
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import torch
-    import __graft_entry__ as g
-    g.build()
-    from devicekmc_amd import host, lib
-    assert torch.cuda.is_available()
-    return host, lib.load()
-
-
 @pytest.fixture(autouse=True)
 def _default_hash(hip):
     yield
     hip[1].dkmc_debug_set_track_hash(0)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype).reshape(-1)).to("cuda:0")
 
 
 def run_raw(hip, label_prev, label_now, x, n_left, n_right):

@@ -9,7 +9,8 @@ import pytest
 import cluster_ref as cr
 import path_ref as pr
 from conftest import params_7p5
-from test_cluster_ref import _contacts, _random_case
+from path_ref import PINNED_2P5_BRIDGED, PINNED_7P5_BRIDGED
+from analysis_support import _contacts, _random_case
 
 
 def _brute(index, label, x, n_left, n_right, slack):
@@ -119,11 +120,6 @@ def _planted(s, p, el, neigh, r, skip, slack):
     nl, nr = _contacts(el2, p.num_atoms_first_layer)
     label = np.where(cr.member_mask(el2, None, list(p.metals), cr.METAL | cr.VACANCY_BIT), 0, -1).astype(np.int32)
     return pr.analyse(neigh, label, s.x, nl, nr, slack)
-
-
-# the figures of the planted filaments (tests/test_gpu_paths.py pins the device to the same ones)
-PINNED_2P5_BRIDGED = {0: (2315, 19, 2), 2: (3123, 13, 3), 4: (3495, 13, 3)}            # slack: corridor sites, constriction level, width
-PINNED_7P5_BRIDGED = {0: (3727, 13, 2), 2: (6849, 18, 2)}
 
 
 @pytest.mark.parametrize("slack", [0, 2, 4])

@@ -176,3 +176,53 @@ def assert_equal(change, pairs, now, prev, critical, info, ref):
     assert np.asarray(critical).dtype == np.int32 and np.array_equal(critical, rcrit)
     for k in INFO + ("critical_xmin", "critical_xmax"):
         assert info[k] == rinfo[k], (k, info[k], rinfo[k])
+
+
+# ---- cases (tests/test_track_ref.py, tests/test_gpu_track.py) ---------------------------------------------------------------------------
+def random_pair(rng, N, k_prev, k_now, p_member=0.7):
+    """two label arrays of N sites with at most k_prev / k_now distinct ids (drawn from 0 ... N - 1) and non-member values of every kind"""
+    out = []
+    for k in (k_prev, k_now):
+        ids = rng.choice(N, size=min(k, N), replace=False)
+        lab = ids[rng.integers(0, len(ids), N)].astype(np.int64)
+        non = np.array([-1, N, N + 7, 2 ** 31 - 1, -2 ** 31], dtype=np.int64)
+        out.append(np.where(rng.random(N) < p_member, lab, non[rng.integers(0, len(non), N)]).astype(np.int32))
+    x = np.round(rng.normal(size=N) * 4.0) / 4.0                           # repeated values
+    return out[0], out[1], x
+
+
+def _rows(table, root):
+    j = int(np.flatnonzero(table["root"] == root)[0])
+    return {k: int(v[j]) for k, v in table.items()}
+
+
+# ---- the 2.5 nm device: pristine, planted open (the filament without 25 < x < 40), planted full ---------------------------------------------
+# per transition: info entries that are pinned
+PINNED_2P5 = {
+    ("pristine", "open"): dict(n_prev=79, n_now=70, n_pairs=81, stayed=3521, joined=60, left=0, merged=2, transition=0),
+    ("open", "full"): dict(n_prev=70, n_now=65, n_pairs=71, joined=25, left=0, transition=1, bridge_prev=-1, bridge_now=0, n_critical=25),
+    ("full", "open"): dict(n_prev=65, n_now=70, n_pairs=71, joined=0, left=25, transition=2, bridge_prev=0, bridge_now=-1, n_critical=25),
+    ("open", "open"): dict(n_prev=70, n_now=70, n_pairs=70, joined=0, left=0, regrouped=0, merged=0, split=0, transition=0, n_critical=0),
+}
+PINNED_MEMBERS = dict(pristine=3521, open=3581, full=3606)
+PLANTINGS = dict(pristine=None, open=(3.0, (25.0, 40.0)), full=(3.0, None))
+
+
+def check_pinned_2p5(key, res):
+    """the pinned figures of one transition on a result (change, pairs, now, prev, critical, info)"""
+    change, pairs, now, prev, critical, info = res
+    for k, v in PINNED_2P5[key].items():
+        assert info[k] == v, (key, k, info[k], v)
+    assert info["stayed"] + info["joined"] == PINNED_MEMBERS[key[1]] and info["stayed"] + info["left"] == PINNED_MEMBERS[key[0]], \
+        (key, info["stayed"], info["joined"], info["left"], PINNED_MEMBERS)
+    if key == ("open", "full"):
+        assert _rows(now, 0)["n_parents"] == 6, (key, _rows(now, 0))
+        assert abs(info["critical_xmin"] - 26.0348) <= 5e-5 and abs(info["critical_xmax"] - 39.945499) <= 5e-7, \
+            (key, info["critical_xmin"], info["critical_xmax"])      # the printed digits
+    if key == ("full", "open"):
+        assert _rows(prev, 0)["n_children"] == 6, (key, _rows(prev, 0))
+        assert abs(info["critical_xmin"] - 26.0348) <= 5e-5 and abs(info["critical_xmax"] - 39.945499) <= 5e-7, \
+            (key, info["critical_xmin"], info["critical_xmax"])
+    if key == ("open", "open"):
+        assert not ((now["flags"] & MERGED) | (prev["flags"] & SPLIT)).any() and (change[change != 0] == STAYED).all(), \
+            (key, now["flags"], prev["flags"], np.unique(change))
