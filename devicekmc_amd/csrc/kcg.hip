@@ -1040,26 +1040,17 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
 {
     Engine &e = eng(); hipStream_t st = e.stream;
     const int nv = emu ? nr : 1;
-    std::vector<void *> owned;
-    struct Free { std::vector<void *> &v; hipStream_t st; ~Free() { if (!v.empty()) (void)hipStreamSynchronize(st); for (void *p : v) (void)hipFree(p); } } freer{owned, st};
-    int fail = 0;
-    auto salloc = [&](int iv, int slot, size_t bytes) -> void * {
-        if (iv == 0) { void *p = scratch(slot, bytes); if (!p) fail = e.err_code ? e.err_code : 2; return p; }
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); fail = dkmc_fail(2, "K-CG slab emulation: out of device memory", __FILE__, __LINE__); return nullptr; }
-        owned.push_back(p);
-        return p;
-    };
+    SlabArena arena{st, "K-CG slab emulation: out of device memory"};
     if (nr < 1 || nr > XS_MAXR) return dkmc_fail(43, "slab-distributed K-CG: 1 ... 32 ranks", __FILE__, __LINE__);
     // ---- ownership (slab.h): slabs along the wider lateral axis, balanced by row count ----
-    int *itab = (int *)scratch(S_KS_TAB, (size_t)(XS_BINS + XS_MAXR + 2 + XS_MAXR * (XS_MAXR + 2)) * 4);
-    int *owner = (int *)scratch(S_KS_OWNER, (size_t)m * 4 * 2);
+    void *itab = scratch(S_KS_TAB, slab_tab_bytes());
+    void *owner = scratch(S_KS_OWNER, slab_owner_bytes(m));
     int *rows_by_owner = (int *)scratch(S_KS_LISTS, ((size_t)m + XS_MAXR + 8) * 4);
-    int *flag = (int *)scratch(S_KS_FLAG, (size_t)(m + 8) * 4 * 2);
+    void *flag = scratch(S_KS_FLAG, slab_flag_bytes(m));
     double *mm = (double *)scratch(S_KS_BOX, 64);
     if (!itab || !owner || !rows_by_owner || !flag || !mm) return e.err_code;
-    unsigned *mask = (unsigned *)(owner + m);
-    int *hist = itab, *cuts = itab + XS_BINS, *tab = itab + XS_BINS + XS_MAXR + 2, *pos = flag + m + 8, *rowoff_d = rows_by_owner + m;
+    const SlabWork W = slab_work(itab, owner, flag, m);
+    int *rowoff_d = rows_by_owner + m;
     // extent of the two lateral coordinates (host: one pass over 2 x m doubles per solve would cost more than it saves to do on the device -- the
     // extents are those of the site arrays and do not change: cached per coordinate pointer)
     static const double *ext_key = nullptr; static int ext_m = 0; static double ext[4];
@@ -1075,43 +1066,29 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
     const bool use_z = ext[3] - ext[2] > ext[1] - ext[0];
     const double *coord = use_z ? coord_z : coord_y;
     const double lo = use_z ? ext[2] : ext[0], hi = use_z ? ext[3] : ext[1];
-    const int nbk = (m + 255) / 256;
-    HIPCHK(hipMemsetAsync(itab, 0, (size_t)(XS_BINS + XS_MAXR + 2 + XS_MAXR * (XS_MAXR + 2)) * 4, st));
-    hipLaunchKernelGGL(k_slab_hist, dim3(nbk), dim3(256), 0, st, m, 0, coord, lo, hi, hist);
-    hipLaunchKernelGGL(k_slab_cuts, dim3(1), dim3(1), 0, st, nr, m, (const int *)hist, cuts);
-    hipLaunchKernelGGL(k_slab_owner, dim3(nbk), dim3(256), 0, st, m, 0, coord, lo, hi, nr, (const int *)cuts, owner);
-    hipLaunchKernelGGL((k_slab_mask<int>), dim3(nbk), dim3(256), 0, st, m, 0, rp, cf, (const int *)owner, mask);
-    hipLaunchKernelGGL(k_slab_count, dim3(std::min(nbk, 512)), dim3(256), 0, st, m, 0, nr, (const int *)owner, (const unsigned *)mask, (const int *)nullptr, tab);
-    std::vector<int> htab((size_t)nr * (nr + 2));
-    HIPCHK(hipMemcpyAsync(htab.data(), tab, htab.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int *nown = htab.data(), *hal = htab.data() + 2 * nr;
-    std::vector<int> rowoff((size_t)nr + 1, 0);
-    int maxown = 1;
-    for (int r = 0; r < nr; ++r) { rowoff[r + 1] = rowoff[r] + nown[r]; maxown = std::max(maxown, nown[r]); }
-    if (rowoff[nr] != m) return dkmc_fail(13, "slab-distributed K-CG: the slabs do not cover the rows", __FILE__, __LINE__);
-    HIPCHK(hipMemcpyAsync(rowoff_d, rowoff.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, st));
-    for (int r = 0; r < nr; ++r) {
-        hipLaunchKernelGGL(k_slab_flag_rows, dim3(nbk), dim3(256), 0, st, m, 0, (const int *)owner, r, flag);
-        int rc = dkmc_exclusive_scan_i32(flag, pos, m, nullptr); if (rc) return rc;
-        hipLaunchKernelGGL(k_slab_scatter_rows, dim3(nbk), dim3(256), 0, st, m, (const int *)flag, (const int *)pos, rowoff[r], rows_by_owner);
-    }
+    if (int rc = slab_partition(st, m, 0, rp, cf, coord, lo, hi, nr, (const int *)nullptr, W)) return rc;
+    std::vector<int> htab;
+    if (int rc = slab_download_tab(st, W, nr, htab)) return rc;
+    const SlabPlan P(htab.data(), nr);
+    const int *rowoff = P.rowoff, maxown = std::max(1, P.maxown);
+    if (!P.covers(m, 0)) return dkmc_fail(13, "slab-distributed K-CG: the slabs do not cover the rows", __FILE__, __LINE__);
+    HIPCHK(hipMemcpyAsync(rowoff_d, rowoff, (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, st));
+    for (int r = 0; r < nr; ++r) if (int rc = slab_rows_of_owner(st, m, 0, W, P, r, rows_by_owner)) return rc;
     std::vector<long long> cnt3((size_t)nr * nr);
-    long long halo_max = 0;
-    for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) cnt3[(size_t)a * nr + d] = a == d ? 0 : hal[a * nr + d];
-    for (int d = 0; d < nr; ++d) { long long t_ = 0; for (int a = 0; a < nr; ++a) t_ += cnt3[(size_t)a * nr + d]; halo_max = std::max(halo_max, t_); }
-    g_ks_halo[0] = halo_max; g_ks_halo[1] = maxown;
+    for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) cnt3[(size_t)a * nr + d] = a == d ? 0 : P.hal(a, d);
+    g_ks_halo[0] = slab_recv_max(cnt3.data(), nr); g_ks_halo[1] = maxown;
     // ---- per (virtual) rank: lists, vectors, exchange buffers ----
     std::vector<KsRank> RK((size_t)nv);
     for (int iv = 0; iv < nv; ++iv) {
-        KsRank &K = RK[iv]; const int v = emu ? iv : me0; K.v = v; K.n_own = nown[v];
-        for (int d = 0; d < nr; ++d) { if (d == v) continue; K.nhs += hal[v * nr + d]; K.nhr += hal[d * nr + v]; }
-        int *li = (int *)salloc(iv, S_KS_RLISTS, ((size_t)K.nhs + K.nhr + 8) * 4);
-        double *vec = iv == 0 ? nullptr : (double *)salloc(iv, 0, (size_t)m * 8 * 5);
-        K.xa = (double *)salloc(iv, S_KS_XA, (size_t)nr * KC_NPA * 8); K.xb = (double *)salloc(iv, S_KS_XB, (size_t)nr * KC_NP * 8);
-        K.send = (double *)salloc(iv, S_KS_SEND, (size_t)(K.nhs + 8) * 8); K.recv = (double *)salloc(iv, S_KS_RECV, (size_t)(K.nhr + 8) * 8);
-        K.ybuf = (double *)salloc(iv, S_KS_YBUF, (size_t)nr * maxown * 8);
-        K.ctrl = iv == 0 ? (KCtrl *)scratch(S_CG_CTRL, sizeof(KCtrl)) : (KCtrl *)salloc(iv, 0, sizeof(KCtrl));
+        KsRank &K = RK[iv]; const int v = emu ? iv : me0; K.v = v; K.n_own = P.nown()[v];
+        const SlabHalo H(P, v);
+        K.nhs = H.hsoff[nr]; K.nhr = H.hroff[nr];
+        int *li = (int *)arena.get(iv, S_KS_RLISTS, ((size_t)K.nhs + K.nhr + 8) * 4);
+        double *vec = iv == 0 ? nullptr : (double *)arena.get(iv, 0, (size_t)m * 8 * 5);
+        K.xa = (double *)arena.get(iv, S_KS_XA, (size_t)nr * KC_NPA * 8); K.xb = (double *)arena.get(iv, S_KS_XB, (size_t)nr * KC_NP * 8);
+        K.send = (double *)arena.get(iv, S_KS_SEND, (size_t)(K.nhs + 8) * 8); K.recv = (double *)arena.get(iv, S_KS_RECV, (size_t)(K.nhr + 8) * 8);
+        K.ybuf = (double *)arena.get(iv, S_KS_YBUF, (size_t)nr * maxown * 8);
+        K.ctrl = iv == 0 ? (KCtrl *)scratch(S_CG_CTRL, sizeof(KCtrl)) : (KCtrl *)arena.get(iv, 0, sizeof(KCtrl));
         if (iv == 0) {
             K.y = y; K.q = q0;
             K.r = (double *)scratch(S_CG_R, (size_t)m * 8); K.p = (double *)scratch(S_CG_P, (size_t)m * 8); K.t = (double *)scratch(S_CG_T, (size_t)m * 8);
@@ -1121,26 +1098,9 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
             HIPCHK(hipMemcpyAsync(K.y, y, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
             HIPCHK(hipMemcpyAsync(K.q, q0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
         }
-        if (fail || !K.ctrl) return fail ? fail : e.err_code;
+        if (arena.fail || !K.ctrl) return arena.fail ? arena.fail : e.err_code;
         K.own = rows_by_owner + rowoff[v]; K.hsend = li; K.hrecv = li + K.nhs;
-        int so_ = 0, ro_ = 0;
-        for (int d = 0; d < nr; ++d) {
-            if (d == v) continue;
-            const int j0 = rowoff[v], j1 = rowoff[v + 1];
-            if (j1 > j0 && hal[v * nr + d] > 0) {
-                hipLaunchKernelGGL(k_slab_flag_halo, dim3((j1 - j0 + 255) / 256), dim3(256), 0, st, j0, j1, (const int *)rows_by_owner, (const unsigned *)mask, d, flag);
-                int rc = dkmc_exclusive_scan_i32(flag, pos, j1 - j0, nullptr); if (rc) return rc;
-                hipLaunchKernelGGL(k_slab_scatter_halo, dim3((j1 - j0 + 255) / 256), dim3(256), 0, st, j0, j1, (const int *)rows_by_owner, (const int *)flag, (const int *)pos, so_, K.hsend);
-            }
-            so_ += hal[v * nr + d];
-            const int i0 = rowoff[d], i1 = rowoff[d + 1];
-            if (i1 > i0 && hal[d * nr + v] > 0) {
-                hipLaunchKernelGGL(k_slab_flag_halo, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, i0, i1, (const int *)rows_by_owner, (const unsigned *)mask, v, flag);
-                int rc = dkmc_exclusive_scan_i32(flag, pos, i1 - i0, nullptr); if (rc) return rc;
-                hipLaunchKernelGGL(k_slab_scatter_halo, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, i0, i1, (const int *)rows_by_owner, (const int *)flag, (const int *)pos, ro_, K.hrecv);
-            }
-            ro_ += hal[d * nr + v];
-        }
+        if (int rc = slab_halo_lists(st, W, P, H, v, rows_by_owner, K.hsend, K.hrecv)) return rc;
         HIPCHK(hipMemsetAsync(K.ctrl, 0, sizeof(KCtrl), st));
         HIPCHK(hipMemsetAsync(K.xa, 0, (size_t)nr * KC_NPA * 8, st));
         HIPCHK(hipMemsetAsync(K.xb, 0, (size_t)nr * KC_NP * 8, st));
@@ -1155,37 +1115,19 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
             if (which == 3) return comm_alltoallv_f64(K.send, K.recv, cnt3.data());
             return comm_allgather_f64(K.ybuf, (size_t)maxown);
         }
-        if (which != 3) {
-            const size_t n = which == 1 ? KC_NPA : (which == 2 ? KC_NP : (size_t)maxown);
-            for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) {
-                if (a == d) continue;
-                double *src = (which == 1 ? RK[a].xa : which == 2 ? RK[a].xb : RK[a].ybuf) + (size_t)a * n;
-                double *dst = (which == 1 ? RK[d].xa : which == 2 ? RK[d].xb : RK[d].ybuf) + (size_t)a * n;
-                HIPCHK(hipMemcpyAsync(dst, src, n * 8, hipMemcpyDeviceToDevice, st));
-            }
-            return 0;
-        }
-        for (int a = 0; a < nr; ++a) {
-            long long so_ = 0;
-            for (int d = 0; d < nr; ++d) {
-                const long long n = cnt3[(size_t)a * nr + d];
-                long long ro = 0; for (int a2 = 0; a2 < a; ++a2) ro += cnt3[(size_t)a2 * nr + d];
-                if (n > 0) HIPCHK(hipMemcpyAsync(RK[d].recv + ro, RK[a].send + so_, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-                so_ += n;
-            }
-        }
-        return 0;
+        if (which == 1) return slab_emu_allgather(st, nr, (size_t)KC_NPA, [&](int r) { return RK[r].xa; });
+        if (which == 2) return slab_emu_allgather(st, nr, (size_t)KC_NP, [&](int r) { return RK[r].xb; });
+        if (which == 3) return slab_emu_alltoallv(st, nr, cnt3.data(), [&](int r) { return RK[r].send; }, [&](int r) { return RK[r].recv; });
+        return slab_emu_allgather(st, nr, (size_t)maxown, [&](int r) { return RK[r].ybuf; });
     };
     const bool timing = emu && time_rank >= 0 && time_rank < nr;
-    hipEvent_t tev[2] = {nullptr, nullptr};
-    if (timing) { HIPCHK(hipEventCreate(&tev[0])); HIPCHK(hipEventCreate(&tev[1])); }
-    struct EvFree { hipEvent_t *ev; ~EvFree() { for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evfree{tev};
+    SlabTimer timer{st};
+    if (timing) if (int rc = timer.create()) return rc;
     double tsum[4] = {0, 0, 0, 0}; int tcount = 0;
     auto timed = [&](int iv, int cls, bool on, const std::function<void()> &launch) -> int {
-        if (timing && on && RK[iv].v == time_rank) {
-            HIPCHK(hipEventRecord(tev[0], st)); launch(); HIPCHK(hipEventRecord(tev[1], st)); HIPCHK(hipEventSynchronize(tev[1]));
-            float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, tev[0], tev[1])); tsum[cls] += ms;
-        } else launch();
+        float ms = 0.f;
+        if (int rc = timer.run(timing && on && RK[iv].v == time_rank, launch, &ms)) return rc;
+        tsum[cls] += ms;
         return 0;
     };
     auto halo = [&](bool on) -> int {
@@ -1254,15 +1196,8 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
         if (int rcx = xchg(4)) return rcx;
         for (int iv = 0; iv < nv; ++iv) { KsRank &K = RK[iv]; hipLaunchKernelGGL(k_ks_scatter_all, dim3(std::min((maxown + 255) / 256, 256), nr), dim3(256), 0, st, nr, K.v, maxown, (const int *)rows_by_owner, (const int *)rowoff_d, (const double *)K.ybuf, K.y); }
     }
-    if (emu && nv > 1) {
-        std::vector<double> y0_((size_t)m), yv_((size_t)m);
-        HIPCHK(hipMemcpyAsync(y0_.data(), RK[0].y, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int iv = 1; iv < nv; ++iv) {
-            HIPCHK(hipMemcpy(yv_.data(), RK[iv].y, (size_t)m * 8, hipMemcpyDeviceToHost));
-            if (memcmp(y0_.data(), yv_.data(), (size_t)m * 8) != 0) return dkmc_fail(13, "K-CG slab emulation: the virtual ranks hold different solutions", __FILE__, __LINE__);
-        }
-    }
+    if (emu && nv > 1)
+        if (int rc = slab_same_bits(st, nv, (size_t)m, [&](int iv) { return RK[iv].y; }, "K-CG slab emulation: the virtual ranks hold different solutions")) return rc;
     KCHK();
     HIPCHK(hipStreamSynchronize(st));
     if (timing) for (int c = 0; c < 4; ++c) g_ks_times[c] = tcount ? tsum[c] * 1e3 / tcount : 0.0;
@@ -1274,3 +1209,46 @@ static int kcg_slab_loop(int m, const int *rp, const int *cf, const double *diag
 // doubles received per iteration in the halo exchange (largest over the ranks), rows of the largest slab, kernel times of the timed virtual rank
 void kcg_slab_report(double *times_us, long long *halo_rows) { for (int c = 0; c < 4; ++c) if (times_us) times_us[c] = g_ks_times[c]; if (halo_rows) { halo_rows[0] = g_ks_halo[0]; halo_rows[1] = g_ks_halo[1]; } }
 void kcg_slab_iter_cap(int cap) { g_ks_iter_cap = cap; }
+
+// Test aid (devicekmc_hip_debug.h): slab.h's host functions as the two loops call them, on a caller-given pattern and on buffers of its own
+extern "C" int dkmc_debug_slab_plan(int m, int first, const int *rp, const int *ci, const double *coord, double lo, double hi, int nr, const int *mark, int v,
+                                    int *owner_out, unsigned *mask_out, int *tab_out, int *rows_by_owner_out, int *hsend_out, int *hrecv_out)
+{
+    Engine &e = eng(); hipStream_t st = e.stream;
+    if (m < 1 || first < 0 || first >= m || !rp || !ci || !coord || nr < 1 || nr > XS_MAXR || v < 0 || v >= nr || !owner_out || !mask_out || !tab_out || !rows_by_owner_out)
+        return dkmc_fail(13, "debug_slab_plan: bad arguments", __FILE__, __LINE__);
+    for (int i = 0; i < m; ++i) if (rp[i] < 0 || rp[i + 1] < rp[i]) return dkmc_fail(13, "debug_slab_plan: bad row pointers", __FILE__, __LINE__);
+    for (int p = 0; p < rp[m]; ++p) if ((ci[p] & 0x7fffffff) >= m) return dkmc_fail(13, "debug_slab_plan: column out of range", __FILE__, __LINE__);
+    SlabArena arena{st, "debug_slab_plan: out of device memory"};
+    const int nnz = rp[m], nd = m - first;
+    int *d_rp = (int *)arena.get(1, 0, (size_t)(m + 1) * 4), *d_ci = (int *)arena.get(1, 0, (size_t)nnz * 4), *d_mark = mark ? (int *)arena.get(1, 0, (size_t)m * 4) : nullptr;
+    double *d_coord = (double *)arena.get(1, 0, (size_t)nd * 8);
+    int *rows_by_owner = (int *)arena.get(1, 0, (size_t)m * 4);
+    const SlabWork W = slab_work(arena.get(1, 0, slab_tab_bytes()), arena.get(1, 0, slab_owner_bytes(m)), arena.get(1, 0, slab_flag_bytes(m)), m);
+    if (arena.fail) return arena.fail;
+    HIPCHK(hipMemcpyAsync(d_rp, rp, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ci, ci, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_coord, coord, (size_t)nd * 8, hipMemcpyHostToDevice, st));
+    if (mark) HIPCHK(hipMemcpyAsync(d_mark, mark, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    if (int rc = slab_partition(st, m, first, (const int *)d_rp, (const int *)d_ci, (const double *)d_coord, lo, hi, nr, (const int *)d_mark, W)) return rc;
+    std::vector<int> htab;
+    if (int rc = slab_download_tab(st, W, nr, htab)) return rc;
+    const SlabPlan P(htab.data(), nr);
+    if (P.rowoff[nr] != nd) return dkmc_fail(13, "debug_slab_plan: the slabs do not cover the rows", __FILE__, __LINE__);
+    for (int r = 0; r < nr; ++r) if (int rc = slab_rows_of_owner(st, m, first, W, P, r, rows_by_owner)) return rc;
+    const SlabHalo H(P, v);
+    int *li = (int *)arena.get(1, 0, ((size_t)H.hsoff[nr] + H.hroff[nr] + 8) * 4);
+    if (arena.fail) return arena.fail;
+    if (hsend_out && hrecv_out) {
+        if (int rc = slab_halo_lists(st, W, P, H, v, rows_by_owner, li, li + H.hsoff[nr])) return rc;
+        HIPCHK(hipMemcpyAsync(hsend_out, li, (size_t)H.hsoff[nr] * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hrecv_out, li + H.hsoff[nr], (size_t)H.hroff[nr] * 4, hipMemcpyDeviceToHost, st));
+    }
+    KCHK();
+    HIPCHK(hipMemcpyAsync(owner_out, W.owner, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(mask_out, W.mask, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rows_by_owner_out, rows_by_owner, (size_t)nd * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    memcpy(tab_out, htab.data(), htab.size() * 4);
+    return e.err_code;
+}

@@ -24,7 +24,7 @@
 // The same host loop runs N VIRTUAL ranks inside one process (emulation on one GPU: dkmc_xtb_emulate_slabs) -- every virtual rank with its own
 // panels, lists and exchange buffers, the exchanges as device copies -- which is how the partition, the lists and the rank-order sums are
 // tested for N = 2, 5, 8 on the one-GPU development box, and how the per-rank kernel times of the strong-scaling model are measured.
-// XS_MAXR (32): ranks -- owner masks are 32 bit (defined in front of xtb_cg)
+// Partition, halo lists, virtual ranks' buffers and emulated exchanges: slab.h, shared with the K loop; the offsets (SlabMeta): slab_plan.h
 #define XS_DRV (2 * XB_SP)                           // the two driver rows' partial sums in a piece of exchange 1
 #define XS_GSTR (XB_NG * 256 + 2)                    // one rank's block of exchange 2: partial Gram matrices, spare, abort word
 
@@ -335,31 +335,22 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     const int m = A.m, s = A.s, so = 4 * ((s + 3) / 4), ns = A.ns;
     const size_t pan = (size_t)m * XB_SP;
     const long long ncell = (long long)A.nK * A.nW;
-    std::vector<void *> owned;                       // hipMalloc'ed for virtual ranks > 0 (emulation); freed on every exit path
-    struct Free { std::vector<void *> &v; hipStream_t st; ~Free() { if (!v.empty()) (void)hipStreamSynchronize(st); for (void *p : v) (void)hipFree(p); } } freer{owned, st};
-    int fail = 0;
-    auto salloc = [&](int iv, int slot, size_t bytes) -> void * {
-        if (iv == 0) { void *p = scratch(slot, bytes); if (!p) fail = e.err_code ? e.err_code : 2; return p; }
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 8) != hipSuccess) { (void)hipGetLastError(); fail = dkmc_fail(2, "slab emulation: out of device memory", __FILE__, __LINE__); return nullptr; }
-        owned.push_back(p);
-        return p;
-    };
+    SlabArena arena{st, "slab emulation: out of device memory"};
     if (nr < 1 || nr > XS_MAXR) return dkmc_fail(43, "slab-distributed solve: 1 ... 32 ranks", __FILE__, __LINE__);
     if (!A.ay || !A.az) return dkmc_fail(43, "slab-distributed solve: needs the atom positions", __FILE__, __LINE__);
 
     // ---- ownership: slabs along the wider lateral axis, cuts balanced by row count (every rank computes the same from replicated data) ----
     XbAux *box = (XbAux *)scratch(S_XTB_SLAB_BOX, sizeof(XbAux));
-    int *itab = (int *)scratch(S_XTB_SLAB_TAB, (size_t)(XS_BINS + XS_MAXR + 2 + XS_MAXR * (XS_MAXR + 2)) * 4);
-    int *owner = (int *)scratch(S_XTB_SLAB_OWNER, (size_t)m * 4 * 2);
+    void *itab = scratch(S_XTB_SLAB_TAB, slab_tab_bytes());
+    void *owner_mask = scratch(S_XTB_SLAB_OWNER, slab_owner_bytes(m));
     int *lists = (int *)scratch(S_XTB_SLAB_LISTS, ((size_t)m + ns + 8) * 4);
     long long *sdst = (long long *)scratch(S_XTB_SLAB_SDST, (size_t)(ns + 1) * 8);
-    int *flag = (int *)scratch(S_XTB_SLAB_FLAG, (size_t)(m + 8) * 4 * 2);
-    if (!box || !itab || !owner || !lists || !sdst || !flag) return e.err_code;
-    unsigned *mask = (unsigned *)(owner + m);
-    int *hist = itab, *cuts = itab + XS_BINS, *tab = itab + XS_BINS + XS_MAXR + 2;
+    void *flag_pos = scratch(S_XTB_SLAB_FLAG, slab_flag_bytes(m));
+    if (!box || !itab || !owner_mask || !lists || !sdst || !flag_pos) return e.err_code;
+    const SlabWork W = slab_work(itab, owner_mask, flag_pos, m);
+    int *const owner = W.owner, *const flag = W.flag, *const pos = W.pos;
     int *rows_by_owner = lists, *S_by_owner = lists + m;
-    int *pos = flag + m + 8;
+    std::vector<int> htab;
     {
         XbAux h0{};
         if (int rc = xtb_box_modes(box, h0, A, 0, st)) return rc;
@@ -370,41 +361,27 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         // of tiles: slabs across it leave all contact rows of S on one rank (2x the exchange-1 payload at 8 ranks).  Both axes are tried (wider
         // first) and the one whose largest S share is smaller is kept.
         const int wide = (h0.hi[2] - h0.lo[2] > h0.hi[1] - h0.lo[1]) ? 2 : 1;
-        const int nb = (m + 255) / 256;
-        std::vector<int> htry((size_t)nr * (nr + 2));
         int best_axis = wide; long long best_max = -1;
         for (int pass = 0; pass < 3; ++pass) {
             const int axis = pass == 0 ? wide : (pass == 1 ? 3 - wide : best_axis);
             if (pass == 2 && axis == 3 - wide) break;                         // the second try is the one kept: everything is in place
-            const double *coord = axis == 2 ? A.az : A.ay;
-            const double lo = h0.lo[axis], hi = h0.hi[axis];
-            HIPCHK(hipMemsetAsync(itab, 0, (size_t)(XS_BINS + XS_MAXR + 2 + XS_MAXR * (XS_MAXR + 2)) * 4, st));
-            hipLaunchKernelGGL(k_slab_hist, dim3(nb), dim3(256), 0, st, m, 2, coord, lo, hi, hist);
-            hipLaunchKernelGGL(k_slab_cuts, dim3(1), dim3(1), 0, st, nr, m - 2, (const int *)hist, cuts);
-            hipLaunchKernelGGL(k_slab_owner, dim3(nb), dim3(256), 0, st, m, 2, coord, lo, hi, nr, (const int *)cuts, owner);
-            hipLaunchKernelGGL((k_slab_mask<xrp_t>), dim3(nb), dim3(256), 0, st, m, 2, A.rp, A.ci, (const int *)owner, mask);
-            hipLaunchKernelGGL(k_slab_count, dim3(std::min(nb, 512)), dim3(256), 0, st, m, 2, nr, (const int *)owner, (const unsigned *)mask, A.nsrank, tab);
+            if (int rc = slab_partition(st, m, 2, A.rp, A.ci, axis == 2 ? A.az : A.ay, h0.lo[axis], h0.hi[axis], nr, A.nsrank, W)) return rc;
             if (nr == 1) break;
-            HIPCHK(hipMemcpyAsync(htry.data(), tab, htry.size() * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            long long mx = 0; for (int r = 0; r < nr; ++r) mx = std::max<long long>(mx, htry[nr + r]);
+            if (int rc = slab_download_tab(st, W, nr, htab)) return rc;
+            long long mx = 0; for (int r = 0; r < nr; ++r) mx = std::max<long long>(mx, htab[nr + r]);
             if (pass == 2) break;
             if (best_max < 0 || mx < best_max - best_max / 16) { best_max = mx; best_axis = axis; }      // (the narrower axis must be clearly better)
         }
     }
-    std::vector<int> htab((size_t)nr * (nr + 2));
-    HIPCHK(hipMemcpyAsync(htab.data(), tab, htab.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int *nown = htab.data(), *nSr = htab.data() + nr, *hal = htab.data() + 2 * nr;      // hal[s * nr + d]
+    if (int rc = slab_download_tab(st, W, nr, htab)) return rc;
+    const SlabPlan P(htab.data(), nr);
+    const int *nown = P.nown(), *nSr = P.nmark();
     SlabMeta M0{}; M0.nr = nr;
-    M0.soffs[0] = M0.rowoff[0] = 0;
-    for (int r = 0; r < nr; ++r) { M0.soffs[r + 1] = M0.soffs[r] + nSr[r]; M0.rowoff[r + 1] = M0.rowoff[r] + nown[r]; }
-    if (M0.rowoff[nr] != m - 2 || M0.soffs[nr] != ns) return dkmc_fail(13, "slab-distributed solve: the slabs do not cover the rows", __FILE__, __LINE__);
+    for (int r = 0; r <= nr; ++r) { M0.soffs[r] = P.markoff[r]; M0.rowoff[r] = P.rowoff[r]; }
+    if (!P.covers(m - 2, ns)) return dkmc_fail(13, "slab-distributed solve: the slabs do not cover the rows", __FILE__, __LINE__);
     // rows and S ranks grouped by owner (ascending inside a group)
     for (int r = 0; r < nr; ++r) {
-        hipLaunchKernelGGL(k_slab_flag_rows, dim3((m + 255) / 256), dim3(256), 0, st, m, 2, (const int *)owner, r, flag);
-        int rc = dkmc_exclusive_scan_i32(flag, pos, m, nullptr); if (rc) return rc;
-        hipLaunchKernelGGL(k_slab_scatter_rows, dim3((m + 255) / 256), dim3(256), 0, st, m, (const int *)flag, (const int *)pos, M0.rowoff[r], rows_by_owner);
+        int rc = slab_rows_of_owner(st, m, 2, W, P, r, rows_by_owner); if (rc) return rc;
         hipLaunchKernelGGL(k_slab_flag_S, dim3((ns + 255) / 256), dim3(256), 0, st, ns, A.srow, (const int *)owner, r, flag);
         rc = dkmc_exclusive_scan_i32(flag, pos, ns, nullptr); if (rc) return rc;
         hipLaunchKernelGGL(k_slab_scatter_S, dim3((ns + 255) / 256), dim3(256), 0, st, ns, (const int *)flag, (const int *)pos, M0.soffs[r], r, so, S_by_owner, sdst);
@@ -430,10 +407,10 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
     std::vector<long long> cnt1((size_t)nr * nr), cnt3((size_t)nr * nr), cnt4((size_t)nr * nr), cnt5((size_t)nr * nr), cntH((size_t)nr * nr);
     for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d) {
         cnt1[(size_t)a * nr + d] = (long long)nSr[d] * so + XS_DRV + 2;
-        cnt3[(size_t)a * nr + d] = a == d ? 0 : ((long long)nSr[a] + hal[a * nr + d]) * XB_SP;
+        cnt3[(size_t)a * nr + d] = a == d ? 0 : ((long long)nSr[a] + P.hal(a, d)) * XB_SP;
         cnt4[(size_t)a * nr + d] = a == d ? 0 : nown[a];
         cnt5[(size_t)a * nr + d] = a == d ? 0 : (long long)nown[a] * XB_SP;
-        cntH[(size_t)a * nr + d] = a == d ? 0 : (long long)hal[a * nr + d] * XB_SP;      // halo exchange (preconditioned loop): the halo part of exchange 3
+        cntH[(size_t)a * nr + d] = a == d ? 0 : (long long)P.hal(a, d) * XB_SP;      // halo exchange (preconditioned loop): the halo part of exchange 3
     }
     for (int iv = 0; iv < nv; ++iv) {
         SlabRank &K = RK[iv]; const int v = emu ? iv : me0; K.v = v;
@@ -441,36 +418,33 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         else { K.items = A.items; K.item_n = A.item_n; K.w_lo = A.w_lo; K.w_hi = A.w_hi; K.sub_base = A.sub_base; K.nitem_w = A.nitem_w; K.nrecords = A.nrecords; }
         K.n_own = nown[v]; K.nS = nSr[v];
         SlabMeta &M = K.M; M = M0; M.me = v;
-        M.hsoff[0] = M.hroff[0] = 0; M.p3s[0] = M.p3r[0] = 0;
-        for (int r = 0; r < nr; ++r) {
-            M.hsoff[r + 1] = M.hsoff[r] + (r == v ? 0 : hal[v * nr + r]);
-            M.hroff[r + 1] = M.hroff[r] + (r == v ? 0 : hal[r * nr + v]);
-            M.p3s[r + 1] = M.p3s[r] + cnt3[(size_t)v * nr + r];
-            M.p3r[r + 1] = M.p3r[r] + cnt3[(size_t)r * nr + v];
+        const SlabHalo H(P, v);
+        for (int r = 0; r <= nr; ++r) {
+            M.hsoff[r] = H.hsoff[r]; M.hroff[r] = H.hroff[r];
+            M.p3s[r] = slab_send_off(cnt3.data(), nr, v, r); M.p3r[r] = slab_recv_off(cnt3.data(), nr, r, v);
         }
-        K.n1s = 0; K.n1r = 0;
-        for (int r = 0; r < nr; ++r) { K.n1s += cnt1[(size_t)v * nr + r]; K.n1r += cnt1[(size_t)r * nr + v]; }
+        K.n1s = slab_send_off(cnt1.data(), nr, v, nr); K.n1r = slab_recv_off(cnt1.data(), nr, nr, v);
         K.n3s = M.p3s[nr]; K.n3r = M.p3r[nr];
-        int *li = (int *)salloc(iv, S_XTB_SLAB_RLISTS, ((size_t)K.n_own + 2 + M.hsoff[nr] + M.hroff[nr] + ndrv + 8) * 4);
-        double *panels = (double *)salloc(iv, S_XTB_PANELS, (pan * 3 + m + 16) * 8);
-        K.QS = (double *)salloc(iv, S_XTB_QS, (size_t)A.ns_pad * XB_SP * 8);
-        K.rowpartB = (double *)salloc(iv, S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
-        K.colpartB = (double *)salloc(iv, S_XTB_COLPART, (size_t)(K.nrecords + 1) * XT_C * so * 8);
-        K.gpart = (double *)salloc(iv, S_XTB_GRAM, (size_t)ng * XB_NG * 256 * 8);
-        double *small = (double *)salloc(iv, S_XTB_SMALL, (size_t)(4 * 256 + 2 * XB_DSPLIT * XB_SP + XB_NG * 256) * 8);
-        K.gx = (double *)salloc(iv, S_XTB_SLAB_GX, (size_t)nr * XS_GSTR * 8);
-        if (keep_aux) K.Ypanel = (double *)salloc(iv, S_XTB_YPANEL, pan * 8);
+        int *li = (int *)arena.get(iv, S_XTB_SLAB_RLISTS, ((size_t)K.n_own + 2 + M.hsoff[nr] + M.hroff[nr] + ndrv + 8) * 4);
+        double *panels = (double *)arena.get(iv, S_XTB_PANELS, (pan * 3 + m + 16) * 8);
+        K.QS = (double *)arena.get(iv, S_XTB_QS, (size_t)A.ns_pad * XB_SP * 8);
+        K.rowpartB = (double *)arena.get(iv, S_XTB_ROWPART, (size_t)(ncell + 1) * XT_R * so * 8);
+        K.colpartB = (double *)arena.get(iv, S_XTB_COLPART, (size_t)(K.nrecords + 1) * XT_C * so * 8);
+        K.gpart = (double *)arena.get(iv, S_XTB_GRAM, (size_t)ng * XB_NG * 256 * 8);
+        double *small = (double *)arena.get(iv, S_XTB_SMALL, (size_t)(4 * 256 + 2 * XB_DSPLIT * XB_SP + XB_NG * 256) * 8);
+        K.gx = (double *)arena.get(iv, S_XTB_SLAB_GX, (size_t)nr * XS_GSTR * 8);
+        if (keep_aux) K.Ypanel = (double *)arena.get(iv, S_XTB_YPANEL, pan * 8);
         if (pd > 0) {
-            K.Vp = (double *)salloc(iv, S_XTB_PRE_V, (pan + m + 16) * 8); K.W1 = (double *)salloc(iv, S_XTB_PRE_W1, pan * 8);
-            K.W2 = (double *)salloc(iv, S_XTB_PRE_W2, pan * 8); K.Zp = (double *)salloc(iv, S_XTB_PRE_Z, pan * 8);
+            K.Vp = (double *)arena.get(iv, S_XTB_PRE_V, (pan + m + 16) * 8); K.W1 = (double *)arena.get(iv, S_XTB_PRE_W1, pan * 8);
+            K.W2 = (double *)arena.get(iv, S_XTB_PRE_W2, pan * 8); K.Zp = (double *)arena.get(iv, S_XTB_PRE_Z, pan * 8);
         }
         const size_t n4 = ((size_t)std::max<long long>((long long)(nr - 1) * K.n_own, (long long)(m - 2 - K.n_own)) + 8) * (keep_aux ? XB_SP : 1);
-        K.send1 = (double *)salloc(iv, S_XTB_SLAB_S1, (size_t)std::max<long long>(K.n1s, (long long)n4) * 8);
-        K.recv1 = (double *)salloc(iv, S_CG_XCHG, (size_t)std::max<long long>(K.n1r, (long long)n4) * 8);
-        K.send3 = (double *)salloc(iv, S_XTB_SLAB_S3, (size_t)(K.n3s + 8) * 8);
-        K.recv3 = (double *)salloc(iv, S_XTB_SLAB_R3, (size_t)(K.n3r + 8) * 8);
-        K.ctrl = iv == 0 ? A.ctrl : (XCtrl *)salloc(iv, 0, sizeof(XCtrl));
-        if (fail) return fail;
+        K.send1 = (double *)arena.get(iv, S_XTB_SLAB_S1, (size_t)std::max<long long>(K.n1s, (long long)n4) * 8);
+        K.recv1 = (double *)arena.get(iv, S_CG_XCHG, (size_t)std::max<long long>(K.n1r, (long long)n4) * 8);
+        K.send3 = (double *)arena.get(iv, S_XTB_SLAB_S3, (size_t)(K.n3s + 8) * 8);
+        K.recv3 = (double *)arena.get(iv, S_XTB_SLAB_R3, (size_t)(K.n3r + 8) * 8);
+        K.ctrl = iv == 0 ? A.ctrl : (XCtrl *)arena.get(iv, 0, sizeof(XCtrl));
+        if (arena.fail) return arena.fail;
         K.R = panels; K.P = panels + pan; K.T = panels + 2 * pan; K.y0 = panels + 3 * pan;
         K.mats = small; K.drvpart = small + 4 * 256;
         K.steplist = li; K.hsend = li + K.n_own + 2; K.hrecv = K.hsend + M.hsoff[nr]; K.dlist = K.hrecv + M.hroff[nr];
@@ -486,21 +460,7 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
         }
         hipLaunchKernelGGL(k_slab_steplist, dim3((K.n_own + 2 + 255) / 256), dim3(256), 0, st, K.n_own, (const int *)rows_by_owner + M0.rowoff[v], K.steplist);
         // halo lists: what I send to d (my rows with bit d), what I receive from s (the rows of s with my bit)
-        for (int d = 0; d < nr; ++d) {
-            if (d == v) continue;
-            const int j0 = M0.rowoff[v], j1 = M0.rowoff[v + 1];
-            if (j1 > j0 && hal[v * nr + d] > 0) {
-                hipLaunchKernelGGL(k_slab_flag_halo, dim3((j1 - j0 + 255) / 256), dim3(256), 0, st, j0, j1, (const int *)rows_by_owner, (const unsigned *)mask, d, flag);
-                int rc = dkmc_exclusive_scan_i32(flag, pos, j1 - j0, nullptr); if (rc) return rc;
-                hipLaunchKernelGGL(k_slab_scatter_halo, dim3((j1 - j0 + 255) / 256), dim3(256), 0, st, j0, j1, (const int *)rows_by_owner, (const int *)flag, (const int *)pos, M.hsoff[d], K.hsend);
-            }
-            const int i0 = M0.rowoff[d], i1 = M0.rowoff[d + 1];
-            if (i1 > i0 && hal[d * nr + v] > 0) {
-                hipLaunchKernelGGL(k_slab_flag_halo, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, i0, i1, (const int *)rows_by_owner, (const unsigned *)mask, v, flag);
-                int rc = dkmc_exclusive_scan_i32(flag, pos, i1 - i0, nullptr); if (rc) return rc;
-                hipLaunchKernelGGL(k_slab_scatter_halo, dim3((i1 - i0 + 255) / 256), dim3(256), 0, st, i0, i1, (const int *)rows_by_owner, (const int *)flag, (const int *)pos, M.hroff[d], K.hrecv);
-            }
-        }
+        if (int rc = slab_halo_lists(st, W, P, H, v, rows_by_owner, K.hsend, K.hrecv)) return rc;
         HIPCHK(hipMemsetAsync(K.QS, 0, (size_t)A.ns_pad * XB_SP * 8, st));
         HIPCHK(hipMemsetAsync(K.rowpartB, 0, (size_t)(ncell + 1) * XT_R * so * 8, st));
         HIPCHK(hipMemsetAsync(K.colpartB, 0, (size_t)(K.nrecords + 1) * XT_C * so * 8, st));
@@ -513,22 +473,16 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             HIPCHK(hipMemsetAsync(K.W1, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.W2, 0, pan * 8, st)); HIPCHK(hipMemsetAsync(K.Zp, 0, pan * 8, st));
             // N packed over the list rows (dkmc_set_x_nmul_form(1)): slices of four list entries, the one-GPU slots per row
             if (e.x_nmul_form == 1)
-                if (int rc = xtb_npack(A, K.n_own + 2, K.steplist, [&](int slot, size_t bytes) { return salloc(iv, slot, bytes); }, 64, &K.npk)) return rc;
+                if (int rc = xtb_npack(A, K.n_own + 2, K.steplist, [&](int slot, size_t bytes) { return arena.get(iv, slot, bytes); }, 64, &K.npk)) return rc;
         }
     }
     KCHK();
-    g_slab_xbytes[0] = g_slab_xbytes[1] = g_slab_xbytes[2] = 0;
-    for (int v = 0; v < nr; ++v) {
-        long long r1 = 0, r3 = 0;
-        for (int a = 0; a < nr; ++a) { if (a != v) { r1 += cnt1[(size_t)a * nr + v]; r3 += cnt3[(size_t)a * nr + v]; } }
-        g_slab_xbytes[0] = std::max(g_slab_xbytes[0], r1); g_slab_xbytes[2] = std::max(g_slab_xbytes[2], r3);
-    }
+    g_slab_xbytes[0] = slab_recv_max(cnt1.data(), nr); g_slab_xbytes[2] = slab_recv_max(cnt3.data(), nr);
     g_slab_xbytes[1] = (long long)(nr - 1) * XS_GSTR;
     e.stats.comm_count_per_rank = g_slab_xbytes[0] + g_slab_xbytes[1] + g_slab_xbytes[2];
     // preconditioned loop: exchange 3 carries QS + the halo of Vp; 2 d halo exchanges (P or Zp, then the Horner intermediates) are added per sweep
     g_slab_last.exchanges = nr > 1 ? (pd > 0 ? 2 * pd + 3 : 3) : 2;
-    g_slab_last.halo_doubles = 0; g_slab_last.nmul_us = 0.0;
-    for (int v = 0; v < nr; ++v) { long long rh = 0; for (int a = 0; a < nr; ++a) rh += cntH[(size_t)a * nr + v]; g_slab_last.halo_doubles = std::max(g_slab_last.halo_doubles, rh); }
+    g_slab_last.halo_doubles = slab_recv_max(cntH.data(), nr); g_slab_last.nmul_us = 0.0;
     if (pd > 0 && nr > 1) e.stats.comm_count_per_rank += 2LL * pd * g_slab_last.halo_doubles;
 
     // smooth auxiliary columns (as in xtb_cg)
@@ -549,40 +503,23 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             if (which == 7) return comm_allgather_f64(K.gx, 1);
             return comm_allgather_f64(K.gx, (size_t)XS_GSTR);
         }
-        if (which == 2 || which == 7) {
-            const size_t n = which == 2 ? (size_t)XS_GSTR : 1;
-            for (int a = 0; a < nr; ++a) for (int d = 0; d < nr; ++d)
-                if (a != d) HIPCHK(hipMemcpyAsync(RK[d].gx + (size_t)a * n, RK[a].gx + (size_t)a * n, n * 8, hipMemcpyDeviceToDevice, st));
-            return 0;
-        }
+        if (which == 2 || which == 7) return slab_emu_allgather(st, nr, which == 2 ? (size_t)XS_GSTR : 1, [&](int r) { return RK[r].gx; });
         const std::vector<long long> &cnt = which == 1 ? cnt1 : (which == 3 ? cnt3 : (which == 4 ? cnt4 : (which == 5 ? cnt5 : cntH)));
         const bool b3 = which == 3 || which == 6;
-        for (int a = 0; a < nr; ++a) {
-            long long so_ = 0;
-            for (int d = 0; d < nr; ++d) {
-                const long long n = cnt[(size_t)a * nr + d];
-                long long ro = 0; for (int a2 = 0; a2 < a; ++a2) ro += cnt[(size_t)a2 * nr + d];
-                const double *src = (b3 ? RK[a].send3 : RK[a].send1) + so_;
-                double *dst = (b3 ? RK[d].recv3 : RK[d].recv1) + ro;
-                if (n > 0) HIPCHK(hipMemcpyAsync(dst, src, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-                so_ += n;
-            }
-        }
-        return 0;
+        return slab_emu_alltoallv(st, nr, cnt.data(), [&](int r) { return b3 ? RK[r].send3 : RK[r].send1; }, [&](int r) { return b3 ? RK[r].recv3 : RK[r].recv1; });
     };
     // ---- timing of one virtual rank's kernels (emulation) ----
     SlabTimes &TM = g_slab_times;
     const bool timing = emu && time_rank >= 0 && time_rank < nr;
-    hipEvent_t tev[2] = {nullptr, nullptr};
-    if (timing) { TM = SlabTimes(); HIPCHK(hipEventCreate(&tev[0])); HIPCHK(hipEventCreate(&tev[1])); }
-    struct EvFree { hipEvent_t *ev; ~EvFree() { for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evfree{tev};
+    SlabTimer timer{st};
+    if (timing) { TM = SlabTimes(); if (int rc = timer.create()) return rc; }
     std::vector<std::pair<int, float>> tsamples;
     int tphase = 0;      // sweeps timed so far
     auto timed = [&](int iv, int cls, bool on, const std::function<void()> &launch) -> int {
-        if (timing && on && RK[iv].v == time_rank) {
-            HIPCHK(hipEventRecord(tev[0], st)); launch(); HIPCHK(hipEventRecord(tev[1], st)); HIPCHK(hipEventSynchronize(tev[1]));
-            float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, tev[0], tev[1])); tsamples.push_back({cls, ms});
-        } else launch();
+        const bool t = timing && on && RK[iv].v == time_rank;
+        float ms = 0.f;
+        if (int rc = timer.run(t, launch, &ms)) return rc;
+        if (t) tsamples.push_back({cls, ms});
         return 0;
     };
     const int nnb_of = 2 * XB_DSPLIT;
@@ -816,15 +753,8 @@ static int xtb_cg_slab(const XtbArgs &A, int nr, int me0, const XShare *emu_shar
             }
         }
     }
-    if (emu) {                                                              // ... and all of them must hold the same bits
-        std::vector<double> y_0((size_t)m), y_v((size_t)m);
-        HIPCHK(hipMemcpyAsync(y_0.data(), RK[0].y0, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int iv = 1; iv < nv; ++iv) {
-            HIPCHK(hipMemcpy(y_v.data(), RK[iv].y0, (size_t)m * 8, hipMemcpyDeviceToHost));
-            if (memcmp(y_0.data(), y_v.data(), (size_t)m * 8) != 0) return dkmc_fail(13, "slab emulation: the virtual ranks hold different solutions", __FILE__, __LINE__);
-        }
-    }
+    if (emu)                                                                // ... and all of them must hold the same bits
+        if (int rc = slab_same_bits(st, nv, (size_t)m, [&](int iv) { return RK[iv].y0; }, "slab emulation: the virtual ranks hold different solutions")) return rc;
     HIPCHK(hipMemcpyAsync(A.y, RK[0].y0, (size_t)m * 8, hipMemcpyDeviceToDevice, st));
     if (keep_aux) hipLaunchKernelGGL(k_xtb_yaux_out, dim3((unsigned)((pan + 255) / 256)), dim3(256), 0, st, m, (const int *)nullptr, (const double *)RK[0].Ypanel, A.sc, A.yaux);
     bool again = false;

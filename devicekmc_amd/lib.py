@@ -140,6 +140,7 @@ SYMBOLS = {
     "dkmc_kcg_form_info": (_I, [C.POINTER(dkmc_gpubuf), C.POINTER(C.c_longlong)]),
     "dkmc_kcg_form_words": (_I, [C.POINTER(dkmc_gpubuf), C.POINTER(C.c_longlong)]),
     "dkmc_debug_k_system": (_I, [C.POINTER(dkmc_gpubuf), _I, _I, _I, _I, _D, _D, _D, _D, _I, vp, vp, vp, vp]),
+    "dkmc_debug_slab_plan": (_I, [_I, _I, vp, vp, vp, _D, _D, _I, vp, _I, vp, vp, vp, vp, vp, vp]),
     "dkmc_debug_kbw_halfword_pos": (_I, [_I, _I]),
     "dkmc_debug_kbw_segment_cap": (None, [_I]),
     "dkmc_set_pair_cutoff": (None, [_D]),

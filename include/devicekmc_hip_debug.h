@@ -221,6 +221,19 @@ int dkmc_xtb_slab_last(int *exchanges_per_sweep, long long *halo_doubles_per_exc
 int dkmc_kcg_emulate_slabs(dkmc_gpubuf *buf, int N, int N_left, int N_right, double Vd, double high_G, double low_G, int num_metals, int nranks, int time_rank,
                            int iter_cap, double *max_abs_diff, int *iters_slab, int *iters_ref, double *times_us, long long *halo_rows);
 
+/* Test aid: the slab partition both distributed loops share (csrc/slab.h, csrc/slab_plan.h), on a pattern the caller supplies -- the host functions
+ * of slab.h exactly as the loops call them (one partition step, the count table to the host, rows_by_owner, the halo lists of rank v), with K's row
+ * pointer type (X's instantiation differs in that type only), on buffers of its own: nothing a solve reads is touched.  All arrays are host arrays.
+ * In: m rows with the CSR pattern rp[m + 1] / ci[rp[m]] (columns in [0, m); bit 31 of a column word is ignored, as in K), of which rows >= first
+ * are distributed; coord[m - first] the lateral coordinate of row first + i, binned over lo ... hi; nr ranks (1 ... 32); mark[m] (may be null):
+ * rows with mark >= 0 are counted per owner; v the rank whose lists are wanted.
+ * Out: owner[m] (0 for rows < first), mask[m] (bit d: the row has an entry in a row of owner d != its own; 0 for rows < first), tab[nr * (nr + 2)] =
+ * rows per owner | marked rows per owner | hal[s * nr + d] rows of s that d reads, rows_by_owner[m - first] (grouped by owner, ascending inside a
+ * group), hsend = the rows v sends, pieces in destination order (sum over d != v of hal[v][d] entries), hrecv = the rows v receives, pieces in
+ * source order (sum over s != v of hal[s][v]).  hsend and hrecv may both be null: the table and the per-row outputs only. */
+int dkmc_debug_slab_plan(int m, int first, const int *rp, const int *ci, const double *coord, double lo, double hi, int nr, const int *mark, int v,
+                         int *owner, unsigned *mask, int *tab, int *rows_by_owner, int *hsend, int *hrecv);
+
 /* Measurement aid: the form the K solve of this buffer's pattern runs on (built by initialize_sparsity) and its window statistics.  info[9]: form
  * (0 CSR positions, 1 blocked, 2 windowed blocked), rows, rows per block, blocks, doubles of the largest window, doubles of all windows, segments of
  * the most fragmented window, segments of all windows, stored column ints. */
